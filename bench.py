@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: exact-GP fits/sec (and predict points/sec) at N=4096, d=8, fp64 on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = every one of the rank's CELLS_PER_STEP independent cells fitted once (F1) at fixed
@@ -15,13 +15,17 @@ cells but the inputs x.  Inputs are resident in HBM when the timed region starts
 section 8e: no data-path collective) and one RCCL all_gather collects the results at the end; the
 reported value is all ranks' fits divided by the slowest rank's time ("weak" scaling).
 
-Rank 0 prints ONE JSON line.  Besides the driver's fields it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and reports the headline (value, ms_per_step);
+--dump-outputs DIR then writes what the last timed step returned (per cell: the loss and the status) as .npy files.  Everything
+else is measured only with --full, which adds to the line
   roofline      -- the dominant kernel (the Cholesky trailing-update GEMM) against the fp64 MFMA peak,
                    per-launch durations taken with HIP events on the launch stream in an instrumented
                    pass over the same workload;
   cpu_baseline  -- the numpy/scipy oracle (a restatement, "port": the reference cannot be imported here)
                    timed on this box's host cores on a bounded sample;
-  extra         -- F2 (objective + gradient), F3 (50 L-BFGS-B iterations, Matern-5/2 ARD) and predict rates.
+  extra         -- F2 (objective + gradient), F3 (50 L-BFGS-B iterations, Matern-5/2 ARD) and predict rates;
+  C4, stages_ms, single_cell_ms_per_fit, kernel_build_hbm, parity_at_bench_size.
+--no-extras, --batched-only and --only-c4 narrow what --full runs.
 """
 
 from __future__ import annotations
@@ -67,13 +71,20 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--cells", type=int, default=CELLS_PER_STEP, help="independent cells per GPU per step")
-    ap.add_argument("--no-extras", action="store_true", help="skip F2/F3/predict/cpu legs (profiling runs)")
-    ap.add_argument("--batched-only", action="store_true", help="profiling runs: no single-cell calls either, so every launch in a trace belongs to a batched step")
+    ap.add_argument("--full", action="store_true", help="after the headline also run the secondary legs (roofline, C4, extras, CPU baseline, parity)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned (per-cell losses and status) as DIR/<name>.npy")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip F2/F3/predict/cpu legs (profiling runs)")
+    ap.add_argument("--batched-only", action="store_true", help="with --full: no single-cell calls either, so every launch in a trace belongs to a batched step")
     ap.add_argument("--only-sparse", action="store_true", help="run only the sparse-model legs (sparse_section) and print their JSON")
-    ap.add_argument("--only-c4", action="store_true", help="of the secondary legs run only configs[3] (C4: every rank predicts its share, one gather to rank 0)")
+    ap.add_argument("--only-c4", action="store_true", help="with --full: of the secondary legs run only configs[3] (C4: every rank predicts its share, one gather to rank 0)")
     ap.add_argument("--c4-cells", type=int, default=1250, help="cells per rank in the C4 leg (configs[3]: 10 000 cells over 8 GPUs)")
     ap.add_argument("--c4-points", type=int, default=N_TEST, help="test points per cell in the C4 leg")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.only_c4 and not args.full:
+        ap.error("--only-c4 selects among the secondary legs: give --full as well")
+    return args
 
 
 def worst_code(codes):
@@ -300,9 +311,11 @@ def main():
     from gpras_amd._lib import DeviceBuffer, check, ptr
     from gpras_amd.synth import make_regression
 
-    with open(os.path.join(ROOT, ".bench_build.lock"), "w") as lock:  # one rank builds (normally nothing to do), the others wait
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        _build.build()
+    # a built tree is only read: it may belong to another user.  A stale one is rebuilt in place by one rank while the others wait.
+    if _build.needs_build():
+        with open(os.path.join(ROOT, ".bench_build.lock"), "w") as lock:
+            fcntl.flock(lock, fcntl.LOCK_EX)
+            _build.build()
     lib = _lib.load()
     device = local_rank if distributed else 0
     if distributed:
@@ -411,6 +424,8 @@ def main():
             dist.all_gather(gathered, mine)
     sync_all()
     elapsed = time.perf_counter() - t0
+    # what the caller of the timed path received from its last step (the --full legs below run more steps into the same arrays)
+    step_outputs = {"losses": losses.copy(), "status": status.astype(np.float64)}
     if distributed:
         all_losses = d_all.to_array((world, cells)) if comm is not None else np.stack(fx_parts) if fx is not None else torch.stack(gathered).cpu().numpy()
         assert np.array_equal(all_losses[rank], losses) and np.all(np.isfinite(all_losses))
@@ -459,13 +474,19 @@ def main():
         },
     }
 
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        suffix = f"_rank{rank}" if world > 1 else ""
+        for name, arr in step_outputs.items():
+            np.save(os.path.join(args.dump_outputs, f"{name}{suffix}.npy"), arr)
+
     # ---- BASELINE configs[3] (C4), MEASURED at one GPU's full share: `--c4-cells` (1250 = 10 000 / 8) independent cells, each fitted and
     # predicted (mean + variance, noise included) at the shared `--c4-points` (100 000) test points through gprx_predict_batch_dev into ONE
     # device block [means (cells, N*) | variances (cells, N*)] (2.0 GB), in chunks that fit the free HBM next to the factors (L and L^-1 of a
     # chunk's cells: gprx_cell_bytes); then the ONE collective north_star names: gprx_comm_gather of every rank's block to rank 0 over RCCL
     # (reference loop: gpr.py:336-341).  Every rank runs it (so that a launch with N ranks measures N shares and the real gather).
     c4 = None
-    if (not args.no_extras and not args.batched_only) or args.only_c4:
+    if args.full and ((not args.no_extras and not args.batched_only) or args.only_c4):
         try:
             n_c4, ns4 = max(1, args.c4_cells), max(1, min(args.c4_points, N_TEST))
             xs4 = np.ascontiguousarray(xs[:ns4])
@@ -547,7 +568,7 @@ def main():
         if c4 is not None:
             result["C4"] = c4
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel: instrumented pass over the same batched step, HIP events around every launch ----
         check(lib.gprx_set_profiling(h, 1), h)
         prof = (C.c_double * 8)()
@@ -590,7 +611,7 @@ def main():
             "cholesky_flops_per_step": cells * N_TRAIN**3 / 3,
             "whole_step_tflops": cells * N_TRAIN**3 / 3 / (elapsed / args.steps) / 1e12,
         }
-    if rank == 0 and not args.batched_only:
+    if rank == 0 and args.full and not args.batched_only:
         fit_one()
         ms = (C.c_double * 4)()
         lib.gprx_last_timings(h, ms)
@@ -614,7 +635,7 @@ def main():
             "stage_ms_with_parameter_upload": ms[0], "stage_GBps": kmat_bytes / (ms[0] * 1e-3) / 1e9}
 
     x1 = y1 = x5 = y5 = xs5 = gpu_mean1 = gpu_mean5 = None
-    if rank == 0 and not args.no_extras and not args.batched_only and not args.only_c4:
+    if rank == 0 and args.full and not args.no_extras and not args.batched_only and not args.only_c4:
         # (the secondary measurements must never cost the headline line: a failure is reported, not raised)
         try:
             extra = {}

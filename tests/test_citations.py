@@ -1,31 +1,25 @@
 """The boundary documents cite the reference by file:line; this checks the citations of ``gpr.py`` in ``include/gprx.h`` and
-``INTEGRATION.md`` against the reference's source (build container only: /root/reference does not travel to the GPU box).
+``INTEGRATION.md`` against the definitions of the reference's ``gpr.py`` (line count and the line span of every function and class,
+recorded in ``tests/golden/gpr_definitions.json`` by ``tests/golden/make_golden_citations.py``).
 
 Rule: a ``gpr.py:A-B`` (or ``gpr.py:A``) citation must lie inside the file, and when the text within two lines of it names a function
 or class that the reference's ``gpr.py`` defines, at least one of the ranges cited there must overlap that definition.
 """
 
-import ast
+import json
 import os
 import re
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/gpras/gpr.py"
-
-pytestmark = pytest.mark.skipif(not os.path.exists(REF), reason="/root/reference is only present in the build container")
+DEFINITIONS = os.path.join(ROOT, "tests", "golden", "gpr_definitions.json")
 
 
 def _definitions():
-    with open(REF) as f:
-        src = f.read()
-    tree = ast.parse(src)
-    spans = {}
-    for node in ast.walk(tree):
-        if isinstance(node, (ast.FunctionDef, ast.ClassDef)):
-            spans.setdefault(node.name, []).append((node.lineno, node.end_lineno))
-    return spans, src.count("\n") + 1
+    with open(DEFINITIONS) as f:
+        rec = json.load(f)
+    return {name: [tuple(span) for span in spans] for name, spans in rec["definitions"].items()}, rec["n_lines"]
 
 
 def _citations(text):

@@ -140,8 +140,8 @@ def test_bench_line_of_a_launched_world_of_one():
     import json
 
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29533")
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--cells", "8", "--no-extras",
-                          "--batched-only"], capture_output=True, text=True, timeout=900, env=env)
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--cells", "8", "--full",
+                          "--no-extras", "--batched-only"], capture_output=True, text=True, timeout=900, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1
@@ -152,6 +152,29 @@ def test_bench_line_of_a_launched_world_of_one():
     assert out["config"]["rccl_ranks_seen"] == {"ncclCommCount": 1, "distinct_ranks_gathered": 1}
 
 
+def test_plain_bench_run_reports_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain run times the steps and reports the headline only (the secondary legs need --full); --dump-outputs writes the per-cell
+    losses and status of the last timed step, the same from run to run whatever the step counts."""
+    import json
+
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
+    outs = []
+    for steps, warmup, tag in (("2", "1", "a"), ("3", "0", "b")):
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", steps, "--warmup", warmup, "--cells", "8",
+                              "--dump-outputs", str(tmp_path / tag)], capture_output=True, text=True, timeout=900, env=env)
+        assert res.returncode == 0, res.stderr[-3000:]
+        lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1
+        out = json.loads(lines[0])
+        assert out["metric"] == "gp_fits_per_sec" and out["value"] > 0 and out["steps"] == int(steps) and out["ms_per_step"] > 0
+        assert not {"roofline", "C4", "extra", "cpu_baseline", "stages_ms", "parity_at_bench_size"} & set(out)
+        outs.append({name: np.load(tmp_path / tag / f"{name}.npy") for name in ("losses", "status")})
+    for got in outs:
+        assert got["losses"].shape == (8,) and got["losses"].dtype == np.float64 and np.all(np.isfinite(got["losses"]))
+        assert got["status"].shape == (8,) and np.all(got["status"] == 0)
+    assert np.array_equal(outs[0]["losses"], outs[1]["losses"])
+
+
 def test_bench_c4_leg_of_a_launched_world_of_one():
     """the C4 leg of bench.py -- every rank predicts its share into ONE device block through gprx_predict_batch_dev in
     chunks, then ONE gprx_comm_gather of the blocks to rank 0, timed by itself -- as a launched world of one at a reduced size (the same
@@ -159,8 +182,8 @@ def test_bench_c4_leg_of_a_launched_world_of_one():
     import json
 
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29535")
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--cells", "4", "--only-c4",
-                          "--c4-cells", "10", "--c4-points", "3000"], capture_output=True, text=True, timeout=900, env=env)
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--cells", "4", "--full",
+                          "--only-c4", "--c4-cells", "10", "--c4-points", "3000"], capture_output=True, text=True, timeout=900, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
     out = json.loads([ln for ln in res.stdout.splitlines() if ln.strip()][-1])
     c4 = out["C4"]
