@@ -26,6 +26,7 @@
 #include "kmeans.h"
 #include "metrics.h"
 #include "pca.h"
+#include "pca_fit.h"
 #include "potrf.h"
 #include "potrf_cell.h"
 #include "potrf_dag.h"
@@ -2843,6 +2844,292 @@ int gprx_pca_reverse(gprx_pca_handle p, const double* mean, const double* var, i
 }
 
 const char* gprx_pca_last_error(gprx_pca_handle p) { return p ? p->err.c_str() : g_err.c_str(); }
+
+// ---- fitting the EOF preprocessor (PreProcessor.fit, gpras/preprocess.py:947-1007) ---------------------------------------
+struct gprx_pcafit_ctx {
+  int device = 0, mode = 0;
+  hipStream_t stream = nullptr;
+  int64_t rows = 0, rows_p = 0, cells = 0, n_wet = 0, ldc = 0;  // ldc: leading dimension of the compacted matrices (multiple of 16)
+  double *xc1 = nullptr, *xc2 = nullptr, *ws = nullptr, *A = nullptr, *E = nullptr, *Z = nullptr;
+  size_t ws_bytes = 0;
+  std::vector<unsigned char> cls;    // wetness class per cell
+  std::vector<double> mean, gram;    // input_mean over the wet cells, G (rows, rows)
+  hipEvent_t ev[8] = {};
+  double ms[6] = {0, 0, 0, 0, 0, 0};  // upload, stats, centring, Gram, components, projection
+  std::string err;
+};
+
+namespace {
+int ffail(gprx_pcafit_handle f, int code, const std::string& msg) {
+  if (f) f->err = msg;
+  g_err = msg;
+  return code;
+}
+#define FITCHK(f, expr)                                                                                              \
+  do {                                                                                                               \
+    hipError_t e_ = (expr);                                                                                          \
+    if (e_ != hipSuccess)                                                                                            \
+      return ffail(f, e_ == hipErrorOutOfMemory ? GPRX_ENOMEM : GPRX_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+
+// split-K plan of a product with `tiles` output tiles of 64 x 64 and K = kdim: a few thousand workgroups, slabs capped at 256 MiB
+int pcafit_kchunk(int64_t tiles, int64_t kdim, int64_t slab_doubles) {
+  int64_t nsplit = std::max<int64_t>(1, 2048 / std::max<int64_t>(tiles, 1));
+  nsplit = std::min<int64_t>(nsplit, std::max<int64_t>(1, ((int64_t)1 << 25) / std::max<int64_t>(slab_doubles, 1)));
+  int64_t kchunk = round_up((kdim + nsplit - 1) / nsplit, 16);
+  return (int)std::max<int64_t>(kchunk, 256);
+}
+
+int pcafit_ensure_ws(gprx_pcafit_handle f, size_t bytes) {
+  if (f->ws_bytes >= bytes) return GPRX_OK;
+  if (f->ws) FITCHK(f, hipFree(f->ws));
+  f->ws = nullptr;
+  f->ws_bytes = 0;
+  FITCHK(f, hipMalloc((void**)&f->ws, bytes));
+  f->ws_bytes = bytes;
+  return GPRX_OK;
+}
+
+float pcafit_elapsed(hipEvent_t a, hipEvent_t b) {
+  float ms = 0.f;
+  hipEventElapsedTime(&ms, a, b);
+  return ms;
+}
+
+// steps 1-3: upload, column statistics + classes, compaction + both centrings, Gram matrix
+int pcafit_run(gprx_pcafit_handle f, const double* x, const double* elevations, const double* weights, double thr) {
+  const int64_t rows = f->rows, cells = f->cells;
+  const size_t xb = sizeof(double) * (size_t)rows * cells;
+  hipStream_t st = f->stream;
+  // device memory of the whole fit, before anything is allocated: x, per-cell vectors, both compacted matrices, Gram slabs
+  {
+    const int64_t ldc_max = round_up(cells, 16);
+    const int64_t tiles = (rows + 63) / 64, ltiles = tiles * (tiles + 1) / 2;
+    const int64_t nsplit = (ldc_max + pcafit_kchunk(ltiles, ldc_max, rows * rows) - 1) / pcafit_kchunk(ltiles, ldc_max, rows * rows);
+    const double need = (double)xb + 8.0 * (4.0 * cells + (double)(rows + f->rows_p) * ldc_max + (double)(nsplit + 1) * rows * rows) + cells;
+    size_t fr = 0, tot = 0;
+    FITCHK(f, hipMemGetInfo(&fr, &tot));
+    if (need > 0.95 * (double)fr)
+      return ffail(f, GPRX_ENOMEM, "the fit needs " + std::to_string((long long)(need / 1048576.0)) + " MiB of device memory, " +
+                                       std::to_string((long long)(fr / 1048576)) + " MiB are free");
+  }
+  double *X = nullptr, *elev = nullptr, *w = nullptr, *mu = nullptr, *m2 = nullptr;
+  unsigned char* cls = nullptr;
+  int64_t* idx = nullptr;
+  int2* ops = nullptr;
+  auto release = [&] {
+    for (void* q : {(void*)X, (void*)elev, (void*)w, (void*)mu, (void*)m2, (void*)cls, (void*)idx, (void*)ops})
+      if (q) hipFree(q);
+  };
+  std::vector<int2> ops_h;
+  int depth = 0;
+  pcafit_pairwise_ops(0, (int)rows, 0, ops_h, depth);
+  if (depth > PCAFIT_STACK) return ffail(f, GPRX_EINVAL, "too many samples for the pairwise column sums");
+  const int nops = (int)ops_h.size();
+  auto run = [&]() -> int {
+    FITCHK(f, hipMalloc((void**)&ops, sizeof(int2) * ops_h.size()));
+    FITCHK(f, hipMemcpyAsync(ops, ops_h.data(), sizeof(int2) * ops_h.size(), hipMemcpyHostToDevice, st));
+    FITCHK(f, hipMalloc((void**)&X, xb));
+    FITCHK(f, hipMalloc((void**)&mu, sizeof(double) * cells));
+    FITCHK(f, hipMalloc((void**)&cls, (size_t)cells));
+    if (f->mode != PCAFIT_VELOCITY) {
+      FITCHK(f, hipMalloc((void**)&elev, sizeof(double) * cells));
+      FITCHK(f, hipMemcpyAsync(elev, elevations, sizeof(double) * cells, hipMemcpyHostToDevice, st));
+    }
+    if (weights) {
+      FITCHK(f, hipMalloc((void**)&w, sizeof(double) * cells));
+      FITCHK(f, hipMemcpyAsync(w, weights, sizeof(double) * cells, hipMemcpyHostToDevice, st));
+    }
+    // 1. x goes up once; one pass gives the classes and the column means
+    FITCHK(f, hipEventRecord(f->ev[0], st));
+    FITCHK(f, hipMemcpyAsync(X, x, xb, hipMemcpyHostToDevice, st));
+    FITCHK(f, hipEventRecord(f->ev[1], st));
+    hipLaunchKernelGGL(pcafit_colstats_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, (const double*)X, rows, cells,
+                       (const double*)elev, f->mode, thr, (const int2*)ops, nops, cls, mu);
+    FITCHK(f, hipGetLastError());
+    FITCHK(f, hipEventRecord(f->ev[2], st));
+    std::vector<double> mu_h((size_t)cells);
+    f->cls.resize((size_t)cells);
+    FITCHK(f, hipMemcpyAsync(f->cls.data(), cls, (size_t)cells, hipMemcpyDeviceToHost, st));
+    FITCHK(f, hipMemcpyAsync(mu_h.data(), mu, sizeof(double) * cells, hipMemcpyDeviceToHost, st));
+    FITCHK(f, hipStreamSynchronize(st));
+    // wet cells (class != AD) in ascending order: x[:, ~dry_indices]
+    std::vector<int64_t> idx_h;
+    idx_h.reserve((size_t)cells);
+    for (int64_t c = 0; c < cells; ++c)
+      if (f->cls[c] != 1) idx_h.push_back(c);
+    f->n_wet = (int64_t)idx_h.size();
+    if (f->n_wet < rows)
+      return ffail(f, GPRX_EINVAL, "the fit needs at least as many wet cells as samples: " + std::to_string((long long)f->n_wet) + " wet cells, " +
+                                       std::to_string((long long)rows) + " samples");
+    f->mean.resize((size_t)f->n_wet);
+    for (int64_t j = 0; j < f->n_wet; ++j) f->mean[j] = mu_h[idx_h[j]];
+    f->ldc = round_up(f->n_wet, 16);
+    const int64_t ldc = f->ldc;
+    // 2. compaction, centring, weighting, then IncrementalPCA's centring; xc2 has rows_p rows (zero beyond `rows`: the K padding
+    //    of the components GEMM)
+    FITCHK(f, hipMalloc((void**)&idx, sizeof(int64_t) * f->n_wet));
+    FITCHK(f, hipMalloc((void**)&m2, sizeof(double) * ldc));
+    FITCHK(f, hipMalloc((void**)&f->xc1, sizeof(double) * rows * ldc));
+    FITCHK(f, hipMalloc((void**)&f->xc2, sizeof(double) * f->rows_p * ldc));
+    FITCHK(f, hipMemcpyAsync(idx, idx_h.data(), sizeof(int64_t) * f->n_wet, hipMemcpyHostToDevice, st));
+    if (f->rows_p > rows) FITCHK(f, hipMemsetAsync(f->xc2 + rows * ldc, 0, sizeof(double) * (f->rows_p - rows) * ldc, st));
+    FITCHK(f, hipEventRecord(f->ev[3], st));
+    hipLaunchKernelGGL(pcafit_compact_kernel, dim3((unsigned)((ldc + 255) / 256)), dim3(256), 0, st, (const double*)X, rows, cells,
+                       (const int64_t*)idx, f->n_wet, ldc, (const double*)elev, f->mode, (const double*)mu, (const double*)w,
+                       (const int2*)ops, nops, f->xc1, f->xc2, m2);
+    FITCHK(f, hipGetLastError());
+    FITCHK(f, hipEventRecord(f->ev[4], st));
+    // 3. G = Xc2 Xc2^T: lower-triangle tiles, split-K slabs summed in a fixed order
+    const int n = (int)rows;
+    const int64_t tiles = (rows + 63) / 64, ltiles = tiles * (tiles + 1) / 2;
+    const int kchunk = pcafit_kchunk(ltiles, ldc, rows * rows);
+    const int nsplit = (int)((ldc + kchunk - 1) / kchunk);
+    int rc;
+    if ((rc = pcafit_ensure_ws(f, sizeof(double) * ((size_t)nsplit * rows * rows + (size_t)rows * rows)))) return rc;
+    double* G = f->ws + (size_t)nsplit * rows * rows;
+    GemmArgs p{f->xc2, f->xc2, f->ws, ldc, ldc, (int64_t)n, n, n, (int)ldc, 1.0, 0.0, GEMM_C_LOWER, 0, 0, 0, 0, 0, 0, kchunk, (int64_t)n * n};
+    FITCHK(f, (launch_gemm_t<0, 1, 64, 64>(st, p, 1, nsplit)));
+    hipLaunchKernelGGL(pcafit_gram_reduce_kernel, dim3((unsigned)(((int64_t)n * n + 255) / 256)), dim3(256), 0, st, (const double*)f->ws, nsplit, n, G);
+    FITCHK(f, hipGetLastError());
+    FITCHK(f, hipEventRecord(f->ev[5], st));
+    f->gram.resize((size_t)rows * rows);
+    FITCHK(f, hipMemcpyAsync(f->gram.data(), G, sizeof(double) * rows * rows, hipMemcpyDeviceToHost, st));
+    FITCHK(f, hipStreamSynchronize(st));
+    f->ms[0] = pcafit_elapsed(f->ev[0], f->ev[1]);
+    f->ms[1] = pcafit_elapsed(f->ev[1], f->ev[2]);
+    f->ms[2] = pcafit_elapsed(f->ev[3], f->ev[4]);
+    f->ms[3] = pcafit_elapsed(f->ev[4], f->ev[5]);
+    return GPRX_OK;
+  };
+  const int rc = run();
+  hipStreamSynchronize(st);  // nothing in flight reads a buffer released below
+  release();
+  return rc;
+}
+
+int pcafit_components(gprx_pcafit_handle f, int k, const double* u, const double* lam, double* eofs, double* z) {
+  const int64_t rows = f->rows, rp = f->rows_p, ldc = f->ldc;
+  hipStream_t st = f->stream;
+  // A = diag(lambda^-1/2) U_k^T, K padded to rows_p with zeros
+  std::vector<double> a((size_t)k * rp, 0.0);
+  for (int i = 0; i < k; ++i) {
+    const double s = 1.0 / std::sqrt(lam[i]);
+    for (int64_t t = 0; t < rows; ++t) a[(size_t)i * rp + t] = u[(size_t)t * k + i] * s;
+  }
+  if (f->A) FITCHK(f, hipFree(f->A));
+  if (f->E) FITCHK(f, hipFree(f->E));
+  if (f->Z) FITCHK(f, hipFree(f->Z));
+  f->A = f->E = f->Z = nullptr;
+  FITCHK(f, hipMalloc((void**)&f->A, sizeof(double) * a.size()));
+  FITCHK(f, hipMalloc((void**)&f->E, sizeof(double) * (size_t)k * ldc));
+  FITCHK(f, hipMalloc((void**)&f->Z, sizeof(double) * (size_t)rows * k));
+  FITCHK(f, hipMemcpyAsync(f->A, a.data(), sizeof(double) * a.size(), hipMemcpyHostToDevice, st));
+  const int tiles_m = (int)((rows + 63) / 64);
+  const int kchunk = pcafit_kchunk(tiles_m * ((k + 63) / 64), ldc, rows * k);
+  const int nsplit = (int)((ldc + kchunk - 1) / kchunk);
+  int rc;
+  if ((rc = pcafit_ensure_ws(f, sizeof(double) * (size_t)nsplit * rows * k))) return rc;
+  // 5. E = A Xc2 (NN, K = rows_p), then svd_flip on its rows
+  FITCHK(f, hipEventRecord(f->ev[5], st));
+  FITCHK(f, launch_gemm(st, 0, 0, k, (int)ldc, (int)rp, 1.0, f->A, rp, f->xc2, ldc, 0.0, f->E, ldc, 0));
+  hipLaunchKernelGGL(pcafit_sign_flip_kernel, dim3((unsigned)k), dim3(256), 0, st, f->E, ldc, f->n_wet);
+  FITCHK(f, hipGetLastError());
+  FITCHK(f, hipEventRecord(f->ev[6], st));
+  // 6. Z = Xc1 E^T (split-K NT; the padding columns of both operands are zero)
+  FITCHK(f, launch_gemm_splitk(st, 0, 1, (int)rows, k, (int)ldc, 1.0, f->xc1, ldc, f->E, ldc, 0.0, f->Z, k, f->ws, kchunk));
+  FITCHK(f, hipEventRecord(f->ev[7], st));
+  FITCHK(f, hipMemcpy2DAsync(eofs, sizeof(double) * f->n_wet, f->E, sizeof(double) * ldc, sizeof(double) * f->n_wet, (size_t)k,
+                             hipMemcpyDeviceToHost, st));
+  FITCHK(f, hipMemcpyAsync(z, f->Z, sizeof(double) * rows * k, hipMemcpyDeviceToHost, st));
+  FITCHK(f, hipStreamSynchronize(st));
+  f->ms[4] = pcafit_elapsed(f->ev[5], f->ev[6]);
+  f->ms[5] = pcafit_elapsed(f->ev[6], f->ev[7]);
+  return GPRX_OK;
+}
+}  // namespace
+
+int gprx_pcafit_destroy(gprx_pcafit_handle f) {
+  if (!f) return GPRX_OK;
+  hipSetDevice(f->device);
+  if (f->stream) hipStreamSynchronize(f->stream);
+  for (double* q : {f->xc1, f->xc2, f->ws, f->A, f->E, f->Z})
+    if (q) hipFree(q);
+  for (hipEvent_t e : f->ev)
+    if (e) hipEventDestroy(e);
+  if (f->stream) hipStreamDestroy(f->stream);
+  delete f;
+  return GPRX_OK;
+}
+
+int gprx_pcafit_create(int device, const double* x, int64_t n_samples, int64_t n_cells, const double* elevations, const double* weights,
+                       int mode, double wet_threshold, gprx_pcafit_handle* out) {
+  if (!out) return ffail(nullptr, GPRX_EINVAL, "out is null");
+  *out = nullptr;
+  if (!x) return ffail(nullptr, GPRX_EINVAL, "x is null");
+  if (mode < PCAFIT_WSE || mode > PCAFIT_VELOCITY) return ffail(nullptr, GPRX_EINVAL, "mode must be 0 (wse), 1 (depth) or 2 (velocity)");
+  if (mode != PCAFIT_VELOCITY && !elevations) return ffail(nullptr, GPRX_EINVAL, "wse and depth need the cell elevations");
+  if (n_samples < 2 || n_cells < n_samples || n_samples > 16384)
+    return ffail(nullptr, GPRX_EINVAL, "need 2 <= n_samples <= min(n_cells, 16384)");
+  gprx_pcafit_handle f = nullptr;
+  try {
+    FITCHK(nullptr, hipSetDevice(device));
+    f = new gprx_pcafit_ctx();
+    f->device = device;
+    f->mode = mode;
+    f->rows = n_samples;
+    f->rows_p = round_up(n_samples, 16);
+    f->cells = n_cells;
+    int rc = GPRX_OK;
+    hipError_t e = hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking);
+    for (hipEvent_t& ev : f->ev)
+      if (e == hipSuccess) e = hipEventCreate(&ev);
+    if (e != hipSuccess) rc = ffail(nullptr, GPRX_EHIP, std::string("hipStreamCreate / hipEventCreate: ") + hipGetErrorString(e));
+    if (!rc) rc = pcafit_run(f, x, elevations, weights, wet_threshold);
+    if (rc) {
+      gprx_pcafit_destroy(f);
+      return rc;
+    }
+  } catch (const std::bad_alloc&) {
+    gprx_pcafit_destroy(f);
+    return ffail(nullptr, GPRX_ENOMEM, "host allocation failed");
+  }
+  *out = f;
+  return GPRX_OK;
+}
+
+int gprx_pcafit_gram(gprx_pcafit_handle f, unsigned char* classes, double* input_mean, double* gram, int64_t* n_wet) {
+  if (!f) return ffail(f, GPRX_EINVAL, "null handle");
+  if (!classes || !input_mean || !gram || !n_wet) return ffail(f, GPRX_EINVAL, "null argument");
+  std::memcpy(classes, f->cls.data(), f->cls.size());
+  std::memcpy(input_mean, f->mean.data(), sizeof(double) * f->mean.size());
+  std::memcpy(gram, f->gram.data(), sizeof(double) * f->gram.size());
+  *n_wet = f->n_wet;
+  return GPRX_OK;
+}
+
+int gprx_pcafit_components(gprx_pcafit_handle f, int k, const double* u, const double* lam, double* eofs, double* z) {
+  if (!f) return ffail(f, GPRX_EINVAL, "null handle");
+  if (k < 0 || k >= f->rows) return ffail(f, GPRX_EINVAL, "need 0 <= k < n_samples (centring removes one direction)");
+  if (k == 0) return GPRX_OK;
+  if (!u || !lam || !eofs || !z) return ffail(f, GPRX_EINVAL, "null argument");
+  for (int i = 0; i < k; ++i)
+    if (!(lam[i] > 0.0)) return ffail(f, GPRX_EINVAL, "retained eigenvalues must be positive");
+  try {
+    FITCHK(f, hipSetDevice(f->device));
+    return pcafit_components(f, k, u, lam, eofs, z);
+  } catch (const std::bad_alloc&) {
+    return ffail(f, GPRX_ENOMEM, "host allocation failed");
+  }
+}
+
+int gprx_pcafit_timings(gprx_pcafit_handle f, double* ms) {
+  if (!f || !ms) return ffail(f, GPRX_EINVAL, "null argument");
+  for (int i = 0; i < 6; ++i) ms[i] = f->ms[i];
+  return GPRX_OK;
+}
+
+const char* gprx_pcafit_last_error(gprx_pcafit_handle f) { return f ? f->err.c_str() : g_err.c_str(); }
 
 // ---- fused error metrics over reconstructed fields ----------------------------
 int gprx_metrics_dev(int device, const double* x_dev, const double* y_dev, const double* conf_dev, int64_t rows, int64_t cells, int t_tol,

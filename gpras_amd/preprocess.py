@@ -1,9 +1,12 @@
-"""EOF (PCA) projection either side of the GP path on the GPU -- the next row after the GP path itself
-(SURVEY.md section 8(f) N1): ``transform`` / ``reverse_transform`` of the reference's ``PreProcessor``
-(``/root/reference/gpras/preprocess.py:1009-1038, 1052-1094``) with the same names, arguments and return shapes.
+"""EOF (PCA) preprocessing either side of the GP path on the GPU: the reference's ``PreProcessor``
+(``gpras/preprocess.py:866-1162``) with the same names, arguments, attributes and pickle format, and ``compute_norths_rule``
+(:1323-1353).
 
-``EOFProjector`` holds the fitted state (it does not fit the PCA: the reference does that once with scikit-learn's
-``IncrementalPCA`` on the host, preprocess.py:947-1007) and runs the two projections through ``libgprx.so``.
+``PreProcessor.fit`` runs the fit on the device (``gprx_pcafit_*``: wetness classes, input mean, compaction, both centrings
+and the Gram matrix of the single-batch ``IncrementalPCA``, then the EOFs and the training projection); only the
+eigendecomposition of the small (n_samples x n_samples) Gram matrix and North's rule run on the host.
+``EOFProjector`` holds a fitted state and runs the two projections through ``libgprx.so``; ``PreProcessor`` keeps one for
+``transform`` / ``reverse_transform``.
 Difference from the reference: a ``PreProcessor`` fitted WITHOUT weights keeps ``weights = np.empty(0)``
 (preprocess.py:917), so its ``transform`` fails on the broadcast at :1031; here missing or empty weights mean "unweighted".
 """
@@ -11,6 +14,8 @@ Difference from the reference: a ``PreProcessor`` fitted WITHOUT weights keeps `
 from __future__ import annotations
 
 import ctypes as C
+import pickle
+from dataclasses import dataclass
 from typing import Any
 
 import numpy as np
@@ -97,3 +102,231 @@ class EOFProjector:
     @property
     def handle(self):
         return self._h
+
+
+# ---- fitting (preprocess.py:947-1007) -------------------------------------------------------------------------------------
+MODES = ("wse", "depth", "velocity")
+CLASS_NAMES = np.array(["", "AD", "TF", "AF"], dtype="<U2")  # gprx_pcafit_gram class codes -> _classify_depths strings
+
+
+@dataclass
+class PCAFit:
+    """What ``PreProcessor.fit`` keeps of its PCA: the fields of a fitted single-batch ``IncrementalPCA`` that the fit and
+    ``compute_norths_rule`` read.  ``components_`` holds the retained rows only (the reference slices ``[:k]`` at :1000)."""
+
+    explained_variance_: np.ndarray
+    n_samples_seen_: int
+    components_: np.ndarray | None = None
+
+
+def compute_norths_rule(pca: Any) -> int:
+    """Number of significant EOF modes by North's rule (preprocess.py:1323-1353).  Duck-typed: a fitted ``PCA``
+    (``n_samples_``), ``IncrementalPCA`` or ``PCAFit`` (``n_samples_seen_``); anything else gives 0, as in the reference."""
+    if not hasattr(pca, "explained_variance_"):
+        return 0
+    if hasattr(pca, "n_samples_"):
+        n = pca.n_samples_
+    elif hasattr(pca, "n_samples_seen_"):
+        n = pca.n_samples_seen_
+    else:
+        return 0
+    eigenvalues = np.asarray(pca.explained_variance_)
+    eigenvalues = eigenvalues[eigenvalues > 1]  # Kaiser rule
+    if len(eigenvalues) == 0:
+        return 0
+    d_eigen = np.abs(np.diff(eigenvalues))
+    d_error = np.sqrt(2 / n) * eigenvalues[:-1]
+    ind = np.argmax(d_eigen <= d_error)
+    if ind == 0:
+        return int(len(eigenvalues))
+    return int(ind)
+
+
+def check_fit_args(x, elevations, weights, spatial_mode_count, hydraulic_parameter):
+    """The domain of the device fit, checked before any device work: float64 (cast here), 2 <= n_samples <= n_cells (the
+    fit itself also needs n_samples <= n_wet: one IncrementalPCA batch), k <= n_samples - 1 (the rank left after centring).
+    Returns the cast (x, elevations, weights)."""
+    if hydraulic_parameter not in MODES:
+        raise ValueError(f"unknown hydraulic_parameter {hydraulic_parameter!r}")
+    x = as_f64(x)
+    if x.ndim != 2:
+        raise ValueError("x must be (samples, cells)")
+    n_s, n_cells = x.shape
+    if n_s < 2 or n_s > n_cells:
+        raise ValueError(f"the fit needs 2 <= samples <= cells (one IncrementalPCA batch); x is {x.shape}")
+    if elevations is None or np.size(elevations) == 0:
+        if hydraulic_parameter != "velocity":
+            raise ValueError(f"hydraulic_parameter {hydraulic_parameter!r} needs the cell elevations")
+        elevations = None
+    else:
+        elevations = as_f64(elevations)
+        if elevations.shape != (n_cells,):
+            raise ValueError(f"elevations must be ({n_cells},)")
+    if weights is not None:
+        weights = as_f64(weights)
+        if weights.shape != (n_cells,):
+            raise ValueError(f"weights must be ({n_cells},)")
+    if spatial_mode_count is not None:
+        if int(spatial_mode_count) != spatial_mode_count or not 0 <= spatial_mode_count <= n_s - 1:
+            raise ValueError(f"spatial_mode_count must be an integer in [0, {n_s - 1}] (centring leaves rank samples - 1)")
+    return x, elevations, weights
+
+
+class PreProcessor:
+    """The reference's ``PreProcessor`` (preprocess.py:866-1162): same constructor, attributes, ``to_dict`` / pickle
+    format; ``fit``, ``transform``, ``reverse_transform`` and ``wse_2_depth`` on the device."""
+
+    device = 0
+
+    def __init__(self, spatial_mode_count: int = 0, input_mean=None, wet_threshold: float = 0.03, elevations=None,
+                 hydraulic_parameter: str = "wse", wetness_classes=None, weights=None, eofs=None, eigenvalues=None,
+                 n_samples_fit: float = 0, x_mean=None, x_std=None):
+        self.spatial_mode_count = spatial_mode_count
+        self.input_mean = input_mean if input_mean is not None else np.empty(0, dtype=float)
+        self.wet_threshold = wet_threshold
+        self.elevations = elevations if elevations is not None else np.empty(0, dtype=float)
+        self.hydraulic_parameter = hydraulic_parameter
+        self.wetness_classes = wetness_classes if wetness_classes is not None else np.empty(0, dtype=np.str_)
+        self.weights = weights if weights is not None else np.empty(0, dtype=float)
+        self.eofs = eofs if eofs is not None else np.empty(0, dtype=float)
+        self.eigenvalues = eigenvalues if eigenvalues is not None else np.empty(0, dtype=float)
+        self.n_samples_fit = n_samples_fit
+        self.x_mean = x_mean if x_mean is not None else np.empty(0, dtype=float)
+        self.x_std = x_std if x_std is not None else np.empty(0, dtype=float)
+        self._proj = None
+        self.pca_ = None
+
+    @property
+    def dry_indices(self) -> np.ndarray:
+        if self.wetness_classes is None:
+            raise ValueError("wetness_classes must be numpy array to access dry_indices")
+        return np.equal(self.wetness_classes, "AD")
+
+    @property
+    def eof(self) -> np.ndarray:
+        if self.eofs is None:
+            raise ValueError("EOFs have not been computed")
+        return self.eofs
+
+    def fit(self, x, elevations, weights=None, spatial_mode_count: int | None = None) -> None:
+        """PreProcessor.fit (preprocess.py:947-1007) on the device; North's rule picks the mode count when it is None."""
+        x, elev, w = check_fit_args(x, elevations, weights, spatial_mode_count, self.hydraulic_parameter)
+        n_s, n_cells = x.shape
+        lib = _lib.load()
+        mode = MODES.index(self.hydraulic_parameter)
+        h = C.c_void_p()
+        check(lib.gprx_pcafit_create(self.device, ptr(x), n_s, n_cells, None if elev is None else ptr(elev), None if w is None else ptr(w),
+                                     mode, float(self.wet_threshold), C.byref(h)))
+        try:
+            codes = np.empty(n_cells, dtype=np.uint8)
+            mean = np.empty(n_cells)
+            gram = np.empty((n_s, n_s))
+            n_wet = C.c_int64()
+            check(lib.gprx_pcafit_gram(h, ptr(codes), ptr(mean), ptr(gram), C.byref(n_wet)))
+            n_wet = n_wet.value
+            # the SVD of the twice-centred matrix from the eigendecomposition of its Gram matrix, largest first
+            lam, u = np.linalg.eigh(gram)
+            lam, u = np.maximum(lam[::-1], 0.0), u[:, ::-1]
+            pca = PCAFit(explained_variance_=lam / (n_s - 1), n_samples_seen_=n_s)
+            k = compute_norths_rule(pca) if spatial_mode_count is None else int(spatial_mode_count)
+            if k > n_s - 1 or (k > 0 and not lam[k - 1] > 0.0):
+                raise ValueError(f"{k} modes exceed the numerical rank of the centred data ({n_s} samples)")
+            eofs = np.empty((k, n_wet))
+            z = np.empty((n_s, k))
+            u_k = np.ascontiguousarray(u[:, :k])
+            lam_k = np.ascontiguousarray(lam[:k])
+            check(lib.gprx_pcafit_components(h, k, ptr(u_k), ptr(lam_k), ptr(eofs), ptr(z)))
+            self.last_timings_ms = self._timings(lib, h)
+        finally:
+            lib.gprx_pcafit_destroy(h)
+        self.elevations = elevations if elev is None else elev
+        self.wetness_classes = CLASS_NAMES[codes]
+        self.input_mean = mean[:n_wet].copy()
+        if w is not None:
+            self.weights = w[~self.dry_indices]
+        pca.components_ = eofs
+        self.pca_ = pca
+        self.spatial_mode_count = k
+        self.eofs = eofs
+        self.eigenvalues = pca.explained_variance_
+        self.n_samples_fit = pca.n_samples_seen_
+        self.x_mean = z.mean(axis=0)
+        self.x_std = z.std(axis=0)
+        self._close_projector()
+
+    @staticmethod
+    def _timings(lib, h) -> dict:
+        ms = np.zeros(6)
+        check(lib.gprx_pcafit_timings(h, ms.ctypes.data_as(C.POINTER(C.c_double))))
+        return dict(zip(("upload", "stats", "centring", "gram", "components", "projection"), ms.tolist()))
+
+    # ---- projections through one cached EOFProjector ----------------------------------------------------------------------
+    def _projector(self) -> EOFProjector:
+        if self._proj is None:
+            if self._n_modes() == 0:
+                raise ValueError("no spatial modes: fit first (a fit whose North's rule kept 0 modes has nothing to project)")
+            self._proj = EOFProjector.from_preprocessor(self, device=self.device)
+        return self._proj
+
+    def _n_modes(self) -> int:
+        return int(np.shape(self.eofs)[0]) if np.ndim(self.eofs) == 2 else 0
+
+    def _close_projector(self):
+        if self._proj is not None:
+            self._proj.close()
+            self._proj = None
+
+    def transform(self, x):
+        """(samples, cells) -> EOF space (samples, spatial_mode_count)  (preprocess.py:1009-1038)."""
+        if np.ndim(self.eofs) == 2 and self._n_modes() == 0:
+            x = as_f64(x)
+            return np.empty((x.shape[0], 0))  # x @ eofs.T of the reference with no modes
+        return self._projector().transform(x)
+
+    def reverse_transform(self, mean, var=None):
+        """EOF space -> (samples, cells) [, propagated variance]  (preprocess.py:1052-1085)."""
+        return self._projector().reverse_transform(mean, var)
+
+    def wse_2_depth(self, x):
+        """max(x - elevations, 0) on the device (preprocess.py:1041-1045)."""
+        proj = self._projector()
+        x = as_f64(x)
+        if x.ndim != 2 or x.shape[1] != proj.n_cells:
+            raise ValueError(f"x must be (samples, {proj.n_cells})")
+        if proj.elevations is None:
+            raise ValueError("wse_2_depth needs the cell elevations")
+        lib = _lib.load()
+        buf = _lib.DeviceBuffer.from_array(x, self.device)
+        try:
+            check(lib.gprx_pca_to_depth_dev(proj.handle, buf.ptr, x.shape[0], 0))
+            check(lib.gprx_pca_synchronize(proj.handle))
+            return buf.to_array(x.shape)
+        finally:
+            buf.free()
+
+    # ---- serialisation (preprocess.py:1135-1162) ----------------------------------------------------------------------
+    def to_dict(self) -> dict[str, Any]:
+        return {
+            "spatial_mode_count": self.spatial_mode_count,
+            "wet_threshold": self.wet_threshold,
+            "hydraulic_parameter": self.hydraulic_parameter,
+            "elevations": self.elevations,
+            "wetness_classes": self.wetness_classes,
+            "input_mean": self.input_mean,
+            "weights": self.weights,
+            "eofs": self.eofs,
+            "eigenvalues": self.eigenvalues,
+            "n_samples_fit": self.n_samples_fit,
+            "x_mean": self.x_mean,
+            "x_std": self.x_std,
+        }
+
+    def to_file(self, out_path) -> None:
+        with open(out_path, mode="wb") as f:
+            pickle.dump(self.to_dict(), f)
+
+    @classmethod
+    def from_file(cls, in_path) -> "PreProcessor":
+        with open(in_path, mode="rb") as f:
+            d = pickle.load(f)
+        return cls(**d)

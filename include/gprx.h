@@ -61,6 +61,7 @@ extern "C" {
 
 typedef struct gprx_ctx* gprx_handle;
 typedef struct gprx_pca_ctx* gprx_pca_handle;
+typedef struct gprx_pcafit_ctx* gprx_pcafit_handle;
 typedef struct gprx_comm_ctx* gprx_comm;
 
 /* ---- library / device -------------------------------------------------------------- */
@@ -331,6 +332,34 @@ int gprx_pca_synchronize(gprx_pca_handle p);
 int gprx_pca_to_depth_dev(gprx_pca_handle p, double* field_dev, int64_t rows, int add_elevations_first);
 int gprx_pca_sqrt_dev(gprx_pca_handle p, double* field_dev, int64_t count);
 int gprx_pca_transpose_dev(gprx_pca_handle p, const double* src_dev, int64_t rows, int64_t cols, double* dst_dev);
+
+/* ---- fitting the EOF preprocessor: PreProcessor.fit (gpras/preprocess.py:947-1007) --------------------------------------- */
+/* The fitted state gprx_pca_create takes, computed on the device.  Single-batch IncrementalPCA (sklearn partial_fit, first
+ * batch): 2 <= n_samples <= n_wet.  North's rule (preprocess.py:1323-1353) runs on the host between the two calls, as does
+ * the eigendecomposition of the small Gram matrix.
+ *
+ * create: uploads x (n_samples, n_cells) once and runs
+ *   - the wetness classes and the input mean: wse_2_depth (:1041-1045) for mode 1, classify_wetness_wse / _depth
+ *     (:1096-1126) with _classify_depths (:1128-1133) for modes 0 / 1, every cell TF for mode 2 (:969-977); the mean of the
+ *     PCA input over the wet cells (:977-980) in numpy's pairwise order over each column and one division (bit-identical to the reference's mean);
+ *   - the compaction, centring and weighting (:977-986: subtract, then weight; weights: n_cells values, or NULL = none)
+ *     and IncrementalPCA's own centring of that matrix (partial_fit: X -= col_mean);
+ *   - the Gram matrix G = Xc Xc^T of the twice-centred matrix (fp64 MFMA, split-K slabs summed in a fixed order).
+ *   mode: 0 = wse, 1 = depth, 2 = velocity (elevations may then be NULL).  Fewer wet cells than samples: GPRX_EINVAL.  Not
+ *   enough device memory for x, the two compacted copies and the Gram slabs: GPRX_ENOMEM before anything is allocated. */
+int gprx_pcafit_create(int device, const double* x, int64_t n_samples, int64_t n_cells, const double* elevations, const double* weights,
+                       int mode, double wet_threshold, gprx_pcafit_handle* out);
+/* classes (n_cells): 0 = "" (maximum exactly at the threshold, or NaN), 1 = AD, 2 = TF, 3 = AF (:1128-1133);
+ * input_mean (room for n_cells, the first n_wet are written: :980); gram (n_samples, n_samples); n_wet. */
+int gprx_pcafit_gram(gprx_pcafit_handle f, unsigned char* classes, double* input_mean, double* gram, int64_t* n_wet);
+/* u (n_samples, k) row-major: the eigenvectors of G of the k largest eigenvalues lambda (k), all > 0, 0 <= k < n_samples.
+ * eofs (k, n_wet) = diag(lambda^-1/2) u^T Xc with svd_flip(u_based_decision=False) applied (pca.components_[:k], :1000);
+ * z (n_samples, k) = Xc_once eofs^T, the training projection whose column mean / std are x_mean / x_std (:1004-1007). */
+int gprx_pcafit_components(gprx_pcafit_handle f, int k, const double* u, const double* lam, double* eofs, double* z);
+/* device milliseconds of the last create / components: upload of x, statistics, centring, Gram, components, projection */
+int gprx_pcafit_timings(gprx_pcafit_handle f, double* ms);
+int gprx_pcafit_destroy(gprx_pcafit_handle f);
+const char* gprx_pcafit_last_error(gprx_pcafit_handle f);
 
 /* ---- fused error metrics over two fields: SURVEY.md section 8(f) row N3 (gpras/metrics.py:85-318) ---------- */
 /* Two streaming passes over x (truth), y (prediction) and conf (may be NULL), each (rows, cells) row-major, yield every
