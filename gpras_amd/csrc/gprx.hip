@@ -1641,11 +1641,18 @@ int sgpr_adam_resident(gprx_handle h, int count, const int* units, double* theta
   hipStream_t st = h->stream;
   const int nt = h->ntheta;
   const int64_t nz = h->m * h->d, gw = nt + nz;
-  // ---- device state: doubles first, then ints ----
-  const size_t n_dbl = (size_t)count * nt + 2 * (size_t)count * gw + 2 * (size_t)count + (size_t)max_iter + 1 + (size_t)h->n_units;
+  static const int check_every = [] {
+    const char* e = getenv("GPRX_ADAM_CHECK_EVERY");
+    const int v = e ? atoi(e) : 0;
+    return v > 0 ? v : 25;
+  }();
+  // ---- device state: doubles first, then ints; the alpha table holds one window of check_every steps (not max_iter: a call "until
+  // the early stop" passes max_iter = 2^31 - 1) ----
+  const size_t n_dbl = (size_t)count * nt + 2 * (size_t)count * gw + 2 * (size_t)count + (size_t)check_every + (size_t)h->n_units;
   const size_t n_int = 5 * (size_t)count + gprx_ctx::SF_MAX_GROUPS;  // (one error word per group of cells)
   if ((rc = ensure(h, h->adam_dev, sizeof(double) * n_dbl + sizeof(int) * n_int))) return rc;
-  const size_t pin_need = sizeof(int) * ((size_t)count + gprx_ctx::SF_MAX_GROUPS);
+  // pinned: the window's alpha values, then the stop flags of the cells and the error words
+  const size_t pin_need = sizeof(double) * (size_t)check_every + sizeof(int) * ((size_t)count + gprx_ctx::SF_MAX_GROUPS);
   if (h->adam_pin_bytes < pin_need) {
     if (h->adam_pin) HIPCHK(h, hipHostFree(h->adam_pin));
     h->adam_pin = nullptr;
@@ -1659,7 +1666,7 @@ int sgpr_adam_resident(gprx_handle h, int count, const int* units, double* theta
   ad.vel = dp;                   dp += (size_t)count * gw;
   ad.best = dp;                  dp += count;
   ad.loss = dp;                  dp += count;
-  double* d_alpha = dp;          dp += (size_t)max_iter + 1;
+  double* d_alpha = dp;          dp += check_every;
   double* d_yy = dp;             dp += h->n_units;
   int* ip = reinterpret_cast<int*>(dp);
   ad.stale = ip;                 ip += count;
@@ -1669,7 +1676,7 @@ int sgpr_adam_resident(gprx_handle h, int count, const int* units, double* theta
   int* d_units = ip;             ip += count;
   ad.error = ip;
   ad.units = d_units;
-  ad.alpha = d_alpha;
+  ad.alpha = nullptr;  // (set per window)
   ad.yy = d_yy;
   ad.nt = nt;
   ad.nlen = h->nlen;
@@ -1683,9 +1690,6 @@ int sgpr_adam_resident(gprx_handle h, int count, const int* units, double* theta
   {
     double* hbest = hd.data() + (ad.best - h->adam_dev.p);
     for (int c = 0; c < count; ++c) hbest[c] = std::numeric_limits<double>::infinity();
-    double* halpha = hd.data() + (d_alpha - h->adam_dev.p);
-    for (int t = 1; t <= max_iter; ++t)
-      halpha[t] = ADAM_LR * std::sqrt(1.0 - std::pow(ADAM_BETA2, (double)t)) / (1.0 - std::pow(ADAM_BETA1, (double)t));  // gprx_adam_batch's expression
     std::memcpy(hd.data() + (d_yy - h->adam_dev.p), h->yy.data(), sizeof(double) * h->n_units);
     for (int c = 0; c < count; ++c) {
       hi[(size_t)count + c] = 1;          // active
@@ -1701,12 +1705,8 @@ int sgpr_adam_resident(gprx_handle h, int count, const int* units, double* theta
   p.active = ad.active;
   p.store_factors = 0;  // (nobody predicts from the cell blocks of a running optimisation)
   const int iso = (h->ard || h->dist_form) ? 0 : 1;
-  static const int check_every = [] {
-    const char* e = getenv("GPRX_ADAM_CHECK_EVERY");
-    const int v = e ? atoi(e) : 0;
-    return v > 0 ? v : 25;
-  }();
-  int* flags = reinterpret_cast<int*>(h->adam_pin);
+  double* halpha = h->adam_pin;
+  int* flags = reinterpret_cast<int*>(h->adam_pin + check_every);
   int error_cell = 0;
   h->factorized = false;  // the cell blocks are overwritten
   h->sparse_view = false;
@@ -1742,6 +1742,21 @@ int sgpr_adam_resident(gprx_handle h, int count, const int* units, double* theta
     HIPCHK(h, sf_launch_prep(sg_[g], h->kid, h->dist_form, pg[g], cells_g[g], nullptr, nullptr, h->cellpar.p + (size_t)cell0_g[g] * CELL_PAR, &adg[g]));  // opens step 1
   for (int done = 0; done < max_iter;) {
     const int k = std::min(check_every, max_iter - done);
+    // this window's alpha values (steps done + 1 .. done + k; every active cell is at the same step): the pinned block is free, the
+    // previous window's upload has completed before its stop flags were read
+    for (int i = 0; i < k; ++i) {
+      const double t = (double)done + 1.0 + i;
+      halpha[i] = ADAM_LR * std::sqrt(1.0 - std::pow(ADAM_BETA2, t)) / (1.0 - std::pow(ADAM_BETA1, t));  // gprx_adam_batch's expression
+    }
+    HIPCHK(h, hipMemcpyAsync(d_alpha, halpha, sizeof(double) * (size_t)k, hipMemcpyHostToDevice, st));
+    if (ngroups > 1) {
+      HIPCHK(h, hipEventRecord(h->sf_evs[0], st));
+      for (int g = 1; g < ngroups; ++g) HIPCHK(h, hipStreamWaitEvent(sg_[g], h->sf_evs[0], 0));
+    }
+    for (int g = 0; g < ngroups; ++g) {
+      adg[g].alpha = d_alpha;
+      adg[g].alpha_t1 = done + 1;
+    }
     for (int i = 0; i < k; ++i) {
       for (int g = 0; g < ngroups; ++g) {
         // (a group starts one launch behind the group before it; groups that start together stay in lock step and gain nothing)
@@ -2097,7 +2112,7 @@ int gprx_factorize_many(int count, gprx_handle* handles, const int* units, const
   return first_error;
 }
 
-int gprx_adam_batch(gprx_handle h, int count, const int* units, double* theta, double* z, int mask, int max_iter, int* n_evals, int* batches) {
+static int adam_batch(gprx_handle h, int count, const int* units, double* theta, double* z, int mask, int max_iter, int* n_evals, int* batches) {
 #pragma clang fp contract(off)
   int rc;
   if ((rc = check_handle(h))) return rc;
@@ -2163,6 +2178,14 @@ int gprx_adam_batch(gprx_handle h, int count, const int* units, double* theta, d
     active.swap(next);
   }
   return GPRX_OK;
+}
+
+int gprx_adam_batch(gprx_handle h, int count, const int* units, double* theta, double* z, int mask, int max_iter, int* n_evals, int* batches) {
+  try {
+    return adam_batch(h, count, units, theta, z, mask, max_iter, n_evals, batches);
+  } catch (const std::bad_alloc&) {  // (no C++ exception may cross the C ABI)
+    return fail(h, GPRX_ENOMEM, "host allocation failed");
+  }
 }
 
 int gprx_factorize_batch(gprx_handle h, int count, const int* units, const double* thetas, int mask, double* losses, int* status) {

@@ -135,13 +135,15 @@ __device__ __forceinline__ void sf_adam_body(const SfParams& p, const SfAdam& ad
   double* A = p.arena + (int64_t)cell * p.ss;
   const double* P2 = A + p.oP2;
   const int width = 2 + p.d, nt = ad.nt, nz = p.m * p.d, gw = nt + nz;
+  // (the step and its alpha are read before the barrier: thread 255 stores tstep[cell] = t below, and a wave that reached this
+  // read after that store would take the next step's alpha -- at the end of a window one entry past it)
+  const int t = ad.tstep[cell] + 1;
+  const double alpha = ad.alpha[t - ad.alpha_t1];
   if (tid < 4) sred[tid] = A[p.oRed + tid];
   sf_reduce_sums<ISO>(p, P2, ls, tid, &sred[4], shs);
   __syncthreads();
   const double variance = par[0], noise = par[1];
   const double nn = (double)p.n;
-  const int t = ad.tstep[cell] + 1;
-  const double alpha = ad.alpha[t];
   double* th = ad.theta + (int64_t)cell * nt;
   double* mom = ad.mom + (int64_t)cell * gw;
   double* vel = ad.vel + (int64_t)cell * gw;

@@ -66,10 +66,12 @@ struct SfAdam {
   int* n_evals;       // (cells) evaluations taken part in
   int* tstep;         // (cells) steps done
   const int* units;   // (cells) output column of each cell
-  const double* alpha;  // [0 .. max_iter]: lr sqrt(1 - beta2^t) / (1 - beta1^t), formed on the host (pow)
+  const double* alpha;  // [t - alpha_t1]: lr sqrt(1 - beta2^t) / (1 - beta1^t), formed on the host (pow), for the steps t of the current
+                        // window of stop-flag checks only (the host uploads each window's values before enqueuing its steps)
   const double* yy;   // (units) y.y
   int* error;         // [0]: 0, or 1 + the first cell whose Kuu or B stopped being positive definite
   int nt, nlen, ard, mask, max_iter;
+  int alpha_t1;       // the first step of the current window: alpha[0] belongs to it
 };
 
 constexpr int SF_STAMP_WORDS = 5 * 32;  // prep | pass 1 | mid | pass 2 | final, 32 words each ([31] of each block: s_memrealtime at entry, 100 MHz)
