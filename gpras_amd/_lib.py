@@ -98,6 +98,14 @@ PROTOTYPES = {
     "gprx_pcafit_timings": (C.c_int, [_vp, _dp]),
     "gprx_pcafit_destroy": (C.c_int, [_vp]),
     "gprx_pcafit_last_error": (C.c_char_p, [_vp]),
+    "gprx_hms_create": (C.c_int, [C.c_int, _vp, _i64, _i64, _i64, C.c_int, _vp, _i64, _vp, _i64, _vp, C.POINTER(_vp)]),
+    "gprx_hms_cov": (C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_int)]),
+    "gprx_hms_components": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
+    "gprx_hms_features": (C.c_int, [_vp, C.c_int, _vp, _vp, _i64, _vp, _i64, _vp, _vp, C.c_int, _vp]),
+    "gprx_hms_timings": (C.c_int, [_vp, _dp]),
+    "gprx_hms_destroy": (C.c_int, [_vp]),
+    "gprx_hms_last_error": (C.c_char_p, [_vp]),
+    "gprx_api": (C.c_int, [C.c_int, _vp, _i64, _vp, _i64, _i64, _vp]),
     "gprx_metrics": (C.c_int, [C.c_int, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_double, _vp, _vp, _vp, C.POINTER(C.c_uint64)]),
     "gprx_metrics_dev": (C.c_int, [C.c_int, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_double, _vp, _vp, _vp, C.POINTER(C.c_uint64)]),
     "gprx_kmeans_pp": (C.c_int, [C.c_int, _vp, _i64, C.c_int, _vp, C.c_int, C.c_int, _i64, _vp, _vp]),

@@ -22,6 +22,7 @@
 #include "gemm_f64.h"
 #include "gprx_common.h"
 #include "grad.h"
+#include "hms.h"
 #include "kmat.h"
 #include "kmeans.h"
 #include "metrics.h"
@@ -3153,6 +3154,415 @@ int gprx_pcafit_timings(gprx_pcafit_handle f, double* ms) {
 }
 
 const char* gprx_pcafit_last_error(gprx_pcafit_handle f) { return f ? f->err.c_str() : g_err.c_str(); }
+
+// ---- HmsPreProcessor (gpras/preprocess.py:1165-1320): the precip EOF fit, the features and the API ---------------------------
+struct gprx_hms_ctx {
+  int device = 0, route = -1;
+  hipStream_t stream = nullptr;
+  int64_t rows = 0, nfeat = 0, n_bc = 0, p = 0, ld2 = 0;
+  double *X = nullptr, *mu = nullptr, *X2 = nullptr, *ws = nullptr;  // X: x column-major (rows, nfeat), ldx = rows
+  int64_t *bc = nullptr, *pc = nullptr;
+  size_t ws_bytes = 0;
+  std::vector<int64_t> bc_h, pc_h;
+  std::vector<double> mu_h;  // input_mean (nfeat)
+  hipEvent_t ev[8] = {};
+  double ms[7] = {0, 0, 0, 0, 0, 0, 0};  // upload, column pass, covariance / Gram, components, projection, API, statistics / standardise
+  std::string err;
+};
+
+namespace {
+int hfail(gprx_hms_handle h, int code, const std::string& msg) {
+  if (h) h->err = msg;
+  g_err = msg;
+  return code;
+}
+#define HMSCHK(h, expr)                                                                                              \
+  do {                                                                                                               \
+    hipError_t e_ = (expr);                                                                                          \
+    if (e_ != hipSuccess)                                                                                            \
+      return hfail(h, e_ == hipErrorOutOfMemory ? GPRX_ENOMEM : GPRX_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+
+// the next allocations need `bytes` of device memory: GPRX_ENOMEM before any of them is made
+int hms_need(gprx_hms_handle h, double bytes, const char* what) {
+  size_t fr = 0, tot = 0;
+  HMSCHK(h, hipMemGetInfo(&fr, &tot));
+  if (bytes > 0.95 * (double)fr)
+    return hfail(h, GPRX_ENOMEM, std::string(what) + " needs " + std::to_string((long long)(bytes / 1048576.0)) + " MiB of device memory, " +
+                                     std::to_string((long long)(fr / 1048576)) + " MiB are free");
+  return GPRX_OK;
+}
+
+int hms_ws(gprx_hms_handle h, size_t bytes) {
+  if (h->ws_bytes >= bytes) return GPRX_OK;
+  if (h->ws) HMSCHK(h, hipFree(h->ws));
+  h->ws = nullptr;
+  h->ws_bytes = 0;
+  HMSCHK(h, hipMalloc((void**)&h->ws, bytes));
+  h->ws_bytes = bytes;
+  return GPRX_OK;
+}
+
+// split-K plan of the lower-triangle product of n x n with K = kdim (as the Gram of pcafit_run)
+void hms_split(int64_t n, int64_t kdim, int& kchunk, int& nsplit) {
+  const int64_t tiles = (n + 63) / 64, ltiles = tiles * (tiles + 1) / 2;
+  kchunk = pcafit_kchunk(ltiles, kdim, n * n);
+  nsplit = (int)((kdim + kchunk - 1) / kchunk);
+}
+
+// x goes up once and is kept column-major: an F-order x is copied as it is, a C-order x in row chunks through a staging buffer
+int hms_upload(gprx_hms_handle h, const double* x, int64_t ld, int fortran) {
+  const int64_t rows = h->rows, nf = h->nfeat;
+  hipStream_t st = h->stream;
+  HMSCHK(h, hipEventRecord(h->ev[0], st));
+  if (fortran) {
+    HMSCHK(h, hipMemcpy2DAsync(h->X, sizeof(double) * rows, x, sizeof(double) * ld, sizeof(double) * rows, (size_t)nf, hipMemcpyHostToDevice, st));
+  } else {
+    const int64_t chunk = std::min<int64_t>(rows, std::max<int64_t>(32, ((int64_t)1 << 22) / nf));  // <= 32 MiB staged
+    double* S = nullptr;
+    HMSCHK(h, hipMalloc((void**)&S, sizeof(double) * (size_t)chunk * nf));
+    int rc = GPRX_OK;
+    for (int64_t t0 = 0; t0 < rows && !rc; t0 += chunk) {
+      const int64_t tc = std::min(chunk, rows - t0);
+      hipError_t e = hipMemcpy2DAsync(S, sizeof(double) * nf, x + t0 * ld, sizeof(double) * ld, sizeof(double) * nf, (size_t)tc, hipMemcpyHostToDevice, st);
+      if (e == hipSuccess) {
+        hipLaunchKernelGGL(hms_transpose_kernel, dim3((unsigned)((tc + 31) / 32), (unsigned)((nf + 31) / 32)), dim3(256), 0, st, (const double*)S, tc, nf,
+                           h->X + t0, rows);
+        e = hipGetLastError();
+      }
+      if (e != hipSuccess) rc = hfail(h, GPRX_EHIP, std::string("upload of x: ") + hipGetErrorString(e));
+    }
+    hipStreamSynchronize(st);  // the staging buffer is no longer read
+    hipFree(S);
+    if (rc) return rc;
+  }
+  HMSCHK(h, hipEventRecord(h->ev[1], st));
+  return GPRX_OK;
+}
+
+// column pass and the covariance (route HMS_COV: C = X2^T X2, p x p) or Gram (HMS_GRAM: G = X2 X2^T, rows x rows) of the PCA input
+int hms_cov(gprx_hms_handle h, double* cov) {
+  const int64_t rows = h->rows, p = h->p;
+  hipStream_t st = h->stream;
+  const int route = rows >= p ? HMS_COV : HMS_GRAM;
+  const int64_t n = route == HMS_COV ? p : rows;
+  const int64_t ld2 = round_up(route == HMS_COV ? rows : p, 16), r2 = round_up(n, 16);
+  int kchunk = 0, nsplit = 0;
+  hms_split(n, ld2, kchunk, nsplit);
+  int rc;
+  if ((rc = hms_need(h, 8.0 * ((double)r2 * ld2 + (double)(nsplit + 1) * n * n + p), "the covariance"))) return rc;
+  double* m2 = nullptr;
+  HMSCHK(h, hipMalloc((void**)&m2, sizeof(double) * p));
+  auto run = [&]() -> int {
+    HMSCHK(h, hipMalloc((void**)&h->X2, sizeof(double) * (size_t)r2 * ld2));
+    h->ld2 = ld2;
+    h->route = route;
+    HMSCHK(h, hipEventRecord(h->ev[2], st));
+    hipLaunchKernelGGL(hms_colmean_kernel, dim3((unsigned)h->nfeat), dim3(256), 0, st, (const double*)h->X, rows, rows, (const int64_t*)nullptr,
+                       (const double*)nullptr, h->mu);
+    hipLaunchKernelGGL(hms_colmean_kernel, dim3((unsigned)p), dim3(256), 0, st, (const double*)h->X, rows, rows, (const int64_t*)h->pc,
+                       (const double*)h->mu, m2);
+    if (r2 > n) HMSCHK(h, hipMemsetAsync(h->X2 + n * ld2, 0, sizeof(double) * (size_t)(r2 - n) * ld2, st));
+    hipLaunchKernelGGL(hms_centre2_kernel, dim3((unsigned)((ld2 + 255) / 256), (unsigned)(route == HMS_COV ? p : rows)), dim3(256), 0, st,
+                       (const double*)h->X, rows, rows, (const int64_t*)h->pc, p, (const double*)h->mu, (const double*)m2, route, h->X2, ld2);
+    HMSCHK(h, hipGetLastError());
+    HMSCHK(h, hipEventRecord(h->ev[3], st));
+    if ((rc = hms_ws(h, sizeof(double) * ((size_t)nsplit * n * n + (size_t)n * n)))) return rc;
+    double* C = h->ws + (size_t)nsplit * n * n;
+    GemmArgs g{h->X2, h->X2, h->ws, ld2, ld2, n, (int)n, (int)n, (int)ld2, 1.0, 0.0, GEMM_C_LOWER, 0, 0, 0, 0, 0, 0, kchunk, n * n};
+    HMSCHK(h, (launch_gemm_t<0, 1, 64, 64>(st, g, 1, nsplit)));
+    hipLaunchKernelGGL(pcafit_gram_reduce_kernel, dim3((unsigned)((n * n + 255) / 256)), dim3(256), 0, st, (const double*)h->ws, nsplit, (int)n, C);
+    HMSCHK(h, hipGetLastError());
+    HMSCHK(h, hipEventRecord(h->ev[4], st));
+    h->mu_h.resize((size_t)h->nfeat);
+    HMSCHK(h, hipMemcpyAsync(h->mu_h.data(), h->mu, sizeof(double) * h->nfeat, hipMemcpyDeviceToHost, st));
+    HMSCHK(h, hipMemcpyAsync(cov, C, sizeof(double) * n * n, hipMemcpyDeviceToHost, st));
+    HMSCHK(h, hipStreamSynchronize(st));
+    h->ms[1] = pcafit_elapsed(h->ev[2], h->ev[3]);
+    h->ms[2] = pcafit_elapsed(h->ev[3], h->ev[4]);
+    return GPRX_OK;
+  };
+  rc = run();
+  hipStreamSynchronize(st);
+  hipFree(m2);
+  return rc;
+}
+
+// Gram route: E = diag(lambda^-1/2) U_k^T X2 (GEMM, K = rows padded to 16), svd_flip on its rows (pcafit_sign_flip_kernel)
+int hms_components(gprx_hms_handle h, int k, const double* u, const double* lam, double* eofs) {
+  const int64_t rows = h->rows, rp = round_up(rows, 16), ld2 = h->ld2;
+  hipStream_t st = h->stream;
+  std::vector<double> a((size_t)k * rp, 0.0);
+  for (int i = 0; i < k; ++i) {
+    const double s = 1.0 / std::sqrt(lam[i]);
+    for (int64_t t = 0; t < rows; ++t) a[(size_t)i * rp + t] = u[(size_t)t * k + i] * s;
+  }
+  int rc;
+  if ((rc = hms_need(h, 8.0 * ((double)a.size() + (double)k * ld2), "the components"))) return rc;
+  double *A = nullptr, *E = nullptr;
+  auto run = [&]() -> int {
+    HMSCHK(h, hipMalloc((void**)&A, sizeof(double) * a.size()));
+    HMSCHK(h, hipMalloc((void**)&E, sizeof(double) * (size_t)k * ld2));
+    HMSCHK(h, hipMemcpyAsync(A, a.data(), sizeof(double) * a.size(), hipMemcpyHostToDevice, st));
+    HMSCHK(h, hipEventRecord(h->ev[4], st));
+    HMSCHK(h, launch_gemm(st, 0, 0, k, (int)ld2, (int)rp, 1.0, A, rp, h->X2, ld2, 0.0, E, ld2, 0));
+    hipLaunchKernelGGL(pcafit_sign_flip_kernel, dim3((unsigned)k), dim3(256), 0, st, E, ld2, h->p);
+    HMSCHK(h, hipGetLastError());
+    HMSCHK(h, hipEventRecord(h->ev[5], st));
+    HMSCHK(h, hipMemcpy2DAsync(eofs, sizeof(double) * h->p, E, sizeof(double) * ld2, sizeof(double) * h->p, (size_t)k, hipMemcpyDeviceToHost, st));
+    HMSCHK(h, hipStreamSynchronize(st));
+    h->ms[3] = pcafit_elapsed(h->ev[4], h->ev[5]);
+    return GPRX_OK;
+  };
+  rc = run();
+  hipStreamSynchronize(st);
+  if (A) hipFree(A);
+  if (E) hipFree(E);
+  return rc;
+}
+
+// API on device vectors: lags = how many lags are summed (>= n_w: the weights beyond n_w are zeros)
+hipError_t hms_api_launch(hipStream_t st, const double* a, int64_t n, const double* w, int64_t n_w, int64_t lags, double* out) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(hms_api_kernel, dim3((unsigned)((n + HMS_API_BT - 1) / HMS_API_BT)), dim3(HMS_API_NT), 0, st, a, n, w, n_w, lags, out);
+  return hipGetLastError();
+}
+
+// features [x_bc, x_precip eofs^T, avg_precip, api_1, api_2] (:1251-1257, :1271-1277); fit: x_mean / x_std out; transform: out
+int hms_features(gprx_hms_handle h, int ke, const double* eofs, const double* w1, int64_t n1, const double* w2, int64_t n2, double* x_mean,
+                 double* x_std, int fit, double* out) {
+  const int64_t rows = h->rows, p = h->p, n_bc = h->n_bc, nf = n_bc + ke + 3;
+  hipStream_t st = h->stream;
+  const int nmb = std::max(1, (ke + HMS_MB - 1) / HMS_MB);
+  const int64_t ke_pad = (int64_t)nmb * HMS_MB;
+  std::vector<double> et((size_t)p * ke_pad, 0.0), mup((size_t)p), mub((size_t)std::max<int64_t>(n_bc, 1), 0.0);
+  for (int i = 0; i < ke; ++i)
+    for (int64_t j = 0; j < p; ++j) et[(size_t)j * ke_pad + i] = eofs[(size_t)i * p + j];
+  for (int64_t j = 0; j < p; ++j) mup[j] = h->mu_h[h->pc_h[j]];
+  for (int64_t b = 0; b < n_bc; ++b) mub[b] = h->mu_h[h->bc_h[b]];
+  int rc;
+  if ((rc = hms_need(h, 8.0 * ((double)et.size() + p + n_bc + n1 + n2 + 2.0 * nf + (double)nf * rows * (fit ? 1 : 2)) + 64, "the features")))
+    return rc;
+  double *Et = nullptr, *Mp = nullptr, *Mb = nullptr, *W1 = nullptr, *W2 = nullptr, *F = nullptr, *S = nullptr, *O = nullptr;
+  int* flag = nullptr;
+  auto run = [&]() -> int {
+    HMSCHK(h, hipMalloc((void**)&Et, sizeof(double) * et.size()));
+    HMSCHK(h, hipMalloc((void**)&Mp, sizeof(double) * p));
+    HMSCHK(h, hipMalloc((void**)&Mb, sizeof(double) * mub.size()));
+    HMSCHK(h, hipMalloc((void**)&W1, sizeof(double) * std::max<int64_t>(n1, 1)));
+    HMSCHK(h, hipMalloc((void**)&W2, sizeof(double) * std::max<int64_t>(n2, 1)));
+    HMSCHK(h, hipMalloc((void**)&F, sizeof(double) * (size_t)nf * rows));
+    HMSCHK(h, hipMalloc((void**)&S, sizeof(double) * 2 * nf));
+    HMSCHK(h, hipMalloc((void**)&flag, sizeof(int)));
+    HMSCHK(h, hipMemcpyAsync(Et, et.data(), sizeof(double) * et.size(), hipMemcpyHostToDevice, st));
+    HMSCHK(h, hipMemcpyAsync(Mp, mup.data(), sizeof(double) * p, hipMemcpyHostToDevice, st));
+    HMSCHK(h, hipMemcpyAsync(Mb, mub.data(), sizeof(double) * mub.size(), hipMemcpyHostToDevice, st));
+    if (n1) HMSCHK(h, hipMemcpyAsync(W1, w1, sizeof(double) * n1, hipMemcpyHostToDevice, st));
+    if (n2) HMSCHK(h, hipMemcpyAsync(W2, w2, sizeof(double) * n2, hipMemcpyHostToDevice, st));
+    HMSCHK(h, hipMemsetAsync(flag, 0, sizeof(int), st));
+    HMSCHK(h, hipEventRecord(h->ev[5], st));
+    hipLaunchKernelGGL(hms_project_kernel, dim3((unsigned)((rows + 255) / 256), (unsigned)nmb), dim3(256), 0, st, (const double*)h->X, rows, rows,
+                       (const int64_t*)h->pc, (const double*)Mp, p, (const double*)Et, ke_pad, ke, (const int64_t*)h->bc, (const double*)Mb, n_bc, F,
+                       rows, flag);
+    HMSCHK(h, hipGetLastError());
+    HMSCHK(h, hipEventRecord(h->ev[6], st));
+    int nonfinite = 0;
+    HMSCHK(h, hipMemcpyAsync(&nonfinite, flag, sizeof(int), hipMemcpyDeviceToHost, st));
+    HMSCHK(h, hipStreamSynchronize(st));
+    // the exactly-zero tail of the weights is cut only when avg_precip is finite (0 * inf or 0 * NaN would be NaN)
+    const double* a = F + (n_bc + ke) * rows;
+    HMSCHK(h, hms_api_launch(st, a, rows, W1, n1, nonfinite ? rows : std::min(n1, rows), F + (n_bc + ke + 1) * rows));
+    HMSCHK(h, hms_api_launch(st, a, rows, W2, n2, nonfinite ? rows : std::min(n2, rows), F + (n_bc + ke + 2) * rows));
+    HMSCHK(h, hipEventRecord(h->ev[7], st));
+    if (fit) {
+      hipLaunchKernelGGL(hms_colstats_kernel, dim3((unsigned)nf), dim3(256), 0, st, (const double*)F, rows, rows, S, S + nf);
+      HMSCHK(h, hipGetLastError());
+      HMSCHK(h, hipEventRecord(h->ev[0], st));
+      HMSCHK(h, hipMemcpyAsync(x_mean, S, sizeof(double) * nf, hipMemcpyDeviceToHost, st));
+      HMSCHK(h, hipMemcpyAsync(x_std, S + nf, sizeof(double) * nf, hipMemcpyDeviceToHost, st));
+    } else {
+      HMSCHK(h, hipMalloc((void**)&O, sizeof(double) * (size_t)nf * rows));
+      HMSCHK(h, hipMemcpyAsync(S, x_mean, sizeof(double) * nf, hipMemcpyHostToDevice, st));
+      HMSCHK(h, hipMemcpyAsync(S + nf, x_std, sizeof(double) * nf, hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL(hms_standardise_kernel, dim3((unsigned)((nf * rows + 255) / 256)), dim3(256), 0, st, (const double*)F, rows, rows, nf,
+                         (const double*)S, (const double*)(S + nf), O);
+      HMSCHK(h, hipGetLastError());
+      HMSCHK(h, hipEventRecord(h->ev[0], st));
+      HMSCHK(h, hipMemcpyAsync(out, O, sizeof(double) * nf * rows, hipMemcpyDeviceToHost, st));
+    }
+    HMSCHK(h, hipStreamSynchronize(st));
+    h->ms[4] = pcafit_elapsed(h->ev[5], h->ev[6]);
+    h->ms[5] = pcafit_elapsed(h->ev[6], h->ev[7]);
+    h->ms[6] = pcafit_elapsed(h->ev[7], h->ev[0]);
+    return GPRX_OK;
+  };
+  rc = run();
+  hipStreamSynchronize(st);
+  for (void* q : {(void*)Et, (void*)Mp, (void*)Mb, (void*)W1, (void*)W2, (void*)F, (void*)S, (void*)O, (void*)flag})
+    if (q) hipFree(q);
+  return rc;
+}
+}  // namespace
+
+int gprx_hms_destroy(gprx_hms_handle h) {
+  if (!h) return GPRX_OK;
+  hipSetDevice(h->device);
+  if (h->stream) hipStreamSynchronize(h->stream);
+  for (void* q : {(void*)h->X, (void*)h->mu, (void*)h->X2, (void*)h->ws, (void*)h->bc, (void*)h->pc})
+    if (q) hipFree(q);
+  for (hipEvent_t e : h->ev)
+    if (e) hipEventDestroy(e);
+  if (h->stream) hipStreamDestroy(h->stream);
+  delete h;
+  return GPRX_OK;
+}
+
+int gprx_hms_create(int device, const double* x, int64_t rows, int64_t ld, int64_t n_features, int fortran, const int64_t* bc_idx, int64_t n_bc,
+                    const int64_t* precip_idx, int64_t n_precip, const double* input_mean, gprx_hms_handle* out) {
+  if (!out) return hfail(nullptr, GPRX_EINVAL, "out is null");
+  *out = nullptr;
+  if (!x || !precip_idx || (n_bc > 0 && !bc_idx)) return hfail(nullptr, GPRX_EINVAL, "null argument");
+  if (rows < 1 || n_features < 1 || n_bc < 0 || n_precip < 1) return hfail(nullptr, GPRX_EINVAL, "need rows >= 1 and at least one precip column");
+  if (ld < (fortran ? rows : n_features)) return hfail(nullptr, GPRX_EINVAL, "ld is smaller than the contiguous dimension of x");
+  if (rows > ((int64_t)1 << 31) - 1024 || n_features > 65535 * 32) return hfail(nullptr, GPRX_EINVAL, "x is too large");
+  for (int64_t j = 0; j < n_precip; ++j)
+    if (precip_idx[j] < 0 || precip_idx[j] >= n_features) return hfail(nullptr, GPRX_EINVAL, "precip column out of range");
+  for (int64_t j = 0; j < n_bc; ++j)
+    if (bc_idx[j] < 0 || bc_idx[j] >= n_features) return hfail(nullptr, GPRX_EINVAL, "bc column out of range");
+  if (std::min(rows, n_precip) > 16384) return hfail(nullptr, GPRX_EINVAL, "min(rows, precip columns) must be <= 16384 (host eigh)");
+  gprx_hms_handle h = nullptr;
+  try {
+    HMSCHK(nullptr, hipSetDevice(device));
+    h = new gprx_hms_ctx();
+    h->device = device;
+    h->rows = rows;
+    h->nfeat = n_features;
+    h->n_bc = n_bc;
+    h->p = n_precip;
+    h->bc_h.assign(bc_idx, bc_idx + n_bc);
+    h->pc_h.assign(precip_idx, precip_idx + n_precip);
+    int rc = GPRX_OK;
+    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+    for (hipEvent_t& ev : h->ev)
+      if (e == hipSuccess) e = hipEventCreate(&ev);
+    if (e != hipSuccess) rc = hfail(nullptr, GPRX_EHIP, std::string("hipStreamCreate / hipEventCreate: ") + hipGetErrorString(e));
+    const double staged = fortran ? 0.0 : (double)std::min<int64_t>(rows, std::max<int64_t>(32, ((int64_t)1 << 22) / n_features)) * n_features;
+    if (!rc) rc = hms_need(h, 8.0 * ((double)rows * n_features + staged + n_features + n_bc + n_precip), "x");
+    auto setup = [&]() -> int {
+      HMSCHK(h, hipMalloc((void**)&h->X, sizeof(double) * (size_t)rows * n_features));
+      HMSCHK(h, hipMalloc((void**)&h->mu, sizeof(double) * n_features));
+      HMSCHK(h, hipMalloc((void**)&h->pc, sizeof(int64_t) * n_precip));
+      HMSCHK(h, hipMalloc((void**)&h->bc, sizeof(int64_t) * std::max<int64_t>(n_bc, 1)));
+      HMSCHK(h, hipMemcpyAsync(h->pc, precip_idx, sizeof(int64_t) * n_precip, hipMemcpyHostToDevice, h->stream));
+      if (n_bc) HMSCHK(h, hipMemcpyAsync(h->bc, bc_idx, sizeof(int64_t) * n_bc, hipMemcpyHostToDevice, h->stream));
+      if (input_mean) {
+        h->mu_h.assign(input_mean, input_mean + n_features);
+        HMSCHK(h, hipMemcpyAsync(h->mu, input_mean, sizeof(double) * n_features, hipMemcpyHostToDevice, h->stream));
+      }
+      int rc2 = hms_upload(h, x, ld, fortran);
+      if (rc2) return rc2;
+      HMSCHK(h, hipStreamSynchronize(h->stream));
+      h->ms[0] = pcafit_elapsed(h->ev[0], h->ev[1]);
+      return GPRX_OK;
+    };
+    if (!rc) rc = setup();
+    if (rc) {
+      gprx_hms_destroy(h);
+      return rc;
+    }
+  } catch (const std::bad_alloc&) {
+    gprx_hms_destroy(h);
+    return hfail(nullptr, GPRX_ENOMEM, "host allocation failed");
+  }
+  *out = h;
+  return GPRX_OK;
+}
+
+int gprx_hms_cov(gprx_hms_handle h, double* input_mean, double* cov, int* route) {
+  if (!h) return hfail(h, GPRX_EINVAL, "null handle");
+  if (!input_mean || !cov || !route) return hfail(h, GPRX_EINVAL, "null argument");
+  if (h->route >= 0 || !h->mu_h.empty()) return hfail(h, GPRX_ESTATE, "the covariance is computed once, by a handle created without input_mean");
+  if (h->rows < 2) return hfail(h, GPRX_EINVAL, "the fit needs rows >= 2");
+  try {
+    HMSCHK(h, hipSetDevice(h->device));
+    const int rc = hms_cov(h, cov);
+    if (rc) return rc;
+  } catch (const std::bad_alloc&) {
+    return hfail(h, GPRX_ENOMEM, "host allocation failed");
+  }
+  std::memcpy(input_mean, h->mu_h.data(), sizeof(double) * h->nfeat);
+  *route = h->route;
+  return GPRX_OK;
+}
+
+int gprx_hms_components(gprx_hms_handle h, int k, const double* u, const double* lam, double* eofs) {
+  if (!h) return hfail(h, GPRX_EINVAL, "null handle");
+  if (h->route != HMS_GRAM) return hfail(h, GPRX_ESTATE, "components are formed on the device only on the Gram route (rows < precip columns)");
+  if (k < 0 || k >= h->rows) return hfail(h, GPRX_EINVAL, "need 0 <= k < rows (centring removes one direction)");
+  if (k == 0) return GPRX_OK;
+  if (!u || !lam || !eofs) return hfail(h, GPRX_EINVAL, "null argument");
+  for (int i = 0; i < k; ++i)
+    if (!(lam[i] > 0.0)) return hfail(h, GPRX_EINVAL, "retained eigenvalues must be positive");
+  try {
+    HMSCHK(h, hipSetDevice(h->device));
+    return hms_components(h, k, u, lam, eofs);
+  } catch (const std::bad_alloc&) {
+    return hfail(h, GPRX_ENOMEM, "host allocation failed");
+  }
+}
+
+int gprx_hms_features(gprx_hms_handle h, int k, const double* eofs, const double* w1, int64_t n1, const double* w2, int64_t n2, double* x_mean,
+                      double* x_std, int fit, double* out) {
+  if (!h) return hfail(h, GPRX_EINVAL, "null handle");
+  if (k < 0 || n1 < 0 || n2 < 0 || (k > 0 && !eofs) || (n1 > 0 && !w1) || (n2 > 0 && !w2) || !x_mean || !x_std || (!fit && !out))
+    return hfail(h, GPRX_EINVAL, "null or negative argument");
+  if (h->mu_h.empty()) return hfail(h, GPRX_ESTATE, "input_mean is not known: run gprx_hms_cov first or pass it to gprx_hms_create");
+  try {
+    HMSCHK(h, hipSetDevice(h->device));
+    return hms_features(h, k, eofs, w1, n1, w2, n2, x_mean, x_std, fit, out);
+  } catch (const std::bad_alloc&) {
+    return hfail(h, GPRX_ENOMEM, "host allocation failed");
+  }
+}
+
+int gprx_hms_timings(gprx_hms_handle h, double* ms) {
+  if (!h || !ms) return hfail(h, GPRX_EINVAL, "null argument");
+  for (int i = 0; i < 7; ++i) ms[i] = h->ms[i];
+  return GPRX_OK;
+}
+
+int gprx_api(int device, const double* a, int64_t n, const double* w, int64_t n_w, int64_t window, double* out) {
+  if (n < 1 || window < 1) return hfail(nullptr, GPRX_EINVAL, "the series and the window must not be empty");
+  if (n_w < 0 || n_w > window || !a || !out || (n_w > 0 && !w)) return hfail(nullptr, GPRX_EINVAL, "need 0 <= n_w <= window and non-null arrays");
+  for (int64_t i = 0; i < n_w; ++i)
+    if (!std::isfinite(w[i])) return hfail(nullptr, GPRX_EINVAL, "the weights must be finite");
+  bool finite = true;
+  for (int64_t t = 0; t < n && finite; ++t) finite = std::isfinite(a[t]);
+  const int64_t lags = std::min(finite ? n_w : window, n);
+  HMSCHK(nullptr, hipSetDevice(device));
+  const int rc0 = hms_need(nullptr, 8.0 * (2.0 * n + std::max<int64_t>(n_w, 1)), "the API");
+  if (rc0) return rc0;
+  hipStream_t st = util_stream();
+  double *A = nullptr, *W = nullptr, *O = nullptr;
+  auto run = [&]() -> int {
+    HMSCHK(nullptr, hipMalloc((void**)&A, sizeof(double) * n));
+    HMSCHK(nullptr, hipMalloc((void**)&O, sizeof(double) * n));
+    HMSCHK(nullptr, hipMalloc((void**)&W, sizeof(double) * std::max<int64_t>(n_w, 1)));
+    HMSCHK(nullptr, hipMemcpyAsync(A, a, sizeof(double) * n, hipMemcpyHostToDevice, st));
+    if (n_w) HMSCHK(nullptr, hipMemcpyAsync(W, w, sizeof(double) * n_w, hipMemcpyHostToDevice, st));
+    HMSCHK(nullptr, hms_api_launch(st, A, n, W, n_w, lags, O));
+    HMSCHK(nullptr, hipMemcpyAsync(out, O, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    HMSCHK(nullptr, hipStreamSynchronize(st));
+    return GPRX_OK;
+  };
+  const int rc = run();
+  hipStreamSynchronize(st);
+  for (void* q : {(void*)A, (void*)W, (void*)O})
+    if (q) hipFree(q);
+  return rc;
+}
+
+const char* gprx_hms_last_error(gprx_hms_handle h) { return h ? h->err.c_str() : g_err.c_str(); }
 
 // ---- fused error metrics over reconstructed fields ----------------------------
 int gprx_metrics_dev(int device, const double* x_dev, const double* y_dev, const double* conf_dev, int64_t rows, int64_t cells, int t_tol,

@@ -1,6 +1,6 @@
 """EOF (PCA) preprocessing either side of the GP path on the GPU: the reference's ``PreProcessor``
-(``gpras/preprocess.py:866-1162``) with the same names, arguments, attributes and pickle format, and ``compute_norths_rule``
-(:1323-1353).
+(``gpras/preprocess.py:866-1162``) and ``HmsPreProcessor`` (:1165-1320) with the same names, arguments, attributes and pickle
+format, and ``compute_norths_rule`` (:1323-1353).
 
 ``PreProcessor.fit`` runs the fit on the device (``gprx_pcafit_*``: wetness classes, input mean, compaction, both centrings
 and the Gram matrix of the single-batch ``IncrementalPCA``, then the EOFs and the training projection); only the
@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import ctypes as C
 import pickle
+import time
 from dataclasses import dataclass
 from typing import Any
 
@@ -327,6 +328,232 @@ class PreProcessor:
 
     @classmethod
     def from_file(cls, in_path) -> "PreProcessor":
+        with open(in_path, mode="rb") as f:
+            d = pickle.load(f)
+        return cls(**d)
+
+
+# ---- HmsPreProcessor (preprocess.py:1165-1320) ------------------------------------------------------------------------------
+def _columns(mask, n_features: int, name: str) -> np.ndarray:
+    """np.arange(n_features)[mask] (:1231-1232): boolean masks and integer index arrays select as x[:, mask] does."""
+    m = np.asarray(mask)
+    if m.dtype == bool and m.shape != (n_features,):
+        raise ValueError(f"{name} has {m.size} entries, x has {n_features} features")
+    try:
+        return np.ascontiguousarray(np.arange(n_features)[m], dtype=np.int64).ravel()
+    except IndexError as e:
+        raise ValueError(f"{name}: {e}") from None
+
+
+def _device_x(x) -> tuple[np.ndarray, int, int]:
+    """x as float64, C or F order kept (DataFrame.values is usually F order): (x, ld, fortran)."""
+    x = np.asarray(x)
+    if x.ndim != 2:
+        raise ValueError("x must be (samples, features)")
+    if x.dtype != np.float64 or not (x.flags.c_contiguous or x.flags.f_contiguous):
+        x = np.ascontiguousarray(x, dtype=np.float64)
+    if x.flags.c_contiguous:
+        return x, x.shape[1], 0
+    return x, x.shape[0], 1
+
+
+_API_WEIGHTS: dict = {}
+
+
+def api_weights(k, window: int) -> np.ndarray:
+    """The reference's weights ``[k**i for i in range(window)]`` (:1293), same bits, without the exactly-zero tail: for
+    |k| < 1, k**i underflows to 0 and stays there (0.85**i beyond i = 4 580); k == 1 gives ones.  Cached per (k, window)."""
+    key = (type(k), k, int(window))
+    w = _API_WEIGHTS.get(key)
+    if w is None:
+        if k == 1:
+            w = np.ones(window)
+        elif abs(k) < 1:
+            vals = []
+            for i in range(window):
+                v = k**i
+                if v == 0:
+                    break
+                vals.append(v)
+            w = np.array(vals, dtype=np.float64)
+        else:
+            w = np.array([k**i for i in range(window)], dtype=np.float64)
+        w.setflags(write=False)
+        if len(_API_WEIGHTS) > 64:
+            _API_WEIGHTS.clear()
+        _API_WEIGHTS[key] = w
+    return w
+
+
+class HmsPreProcessor:
+    """The reference's ``HmsPreProcessor`` (preprocess.py:1165-1320): same constructor, attributes and ``to_dict`` / pickle
+    format; ``fit``, ``transform`` and ``calc_antecedent_precipitation_index`` run their arithmetic on the device
+    (``gprx_hms_*``, ``gprx_api``).  The host keeps the eigendecomposition of the small covariance
+    (p x p, or the T x T Gram matrix when T < p) and North's rule."""
+
+    device = 0
+
+    def __init__(self, precip_spatial_mode_count: int = 0, bc_mask=None, precip_mask=None, eofs=None, eigenvalues=None,
+                 n_samples_fit: float = 0, x_mean=None, x_std=None, input_mean=None):
+        self.precip_spatial_mode_count = precip_spatial_mode_count
+        self.bc_mask = bc_mask if bc_mask is not None else np.empty(0, dtype=float)
+        self.precip_mask = precip_mask if precip_mask is not None else np.empty(0, dtype=float)
+        self.eofs = eofs if eofs is not None else np.empty(0, dtype=float)
+        self.eigenvalues = eigenvalues if eigenvalues is not None else np.empty(0, dtype=float)
+        self.n_samples_fit = n_samples_fit
+        self.x_mean = x_mean if x_mean is not None else np.empty(0, dtype=float)
+        self.x_std = x_std if x_std is not None else np.empty(0, dtype=float)
+        self.input_mean = input_mean if input_mean is not None else np.empty(0, dtype=float)
+        self.pca_ = None
+        self.last_timings_ms: dict = {}
+
+    @staticmethod
+    def check_fit_args(x, bc_mask, precip_mask, precip_spatial_mode_count=None):
+        """The domain, checked before any device work: returns (x, ld, fortran, bc columns, precip columns)."""
+        x, ld, fortran = _device_x(x)
+        n_s, n_f = x.shape
+        bc = _columns(bc_mask, n_f, "bc_mask")
+        pc = _columns(precip_mask, n_f, "precip_mask")
+        if pc.size == 0:
+            raise ValueError("precip_mask selects no column")
+        if n_s < 2:
+            raise ValueError(f"the fit needs at least 2 samples; x is {x.shape}")
+        if min(n_s, pc.size) > 16384:
+            raise ValueError("min(samples, precip columns) must be <= 16384 (the host eigendecomposition)")
+        k = precip_spatial_mode_count
+        if k is not None and (int(k) != k or k < 0):
+            raise ValueError("precip_spatial_mode_count must be a non-negative integer")
+        return x, ld, fortran, bc, pc
+
+    def fit(self, x, bc_mask, precip_mask, precip_spatial_mode_count: int | None = None) -> None:
+        """HmsPreProcessor.fit (preprocess.py:1208-1261) on the device; North's rule picks the mode count when it is None."""
+        x, ld, fortran, bc, pc = self.check_fit_args(x, bc_mask, precip_mask, precip_spatial_mode_count)
+        n_s, n_f = x.shape
+        p = pc.size
+        lib = _lib.load()
+        h = C.c_void_p()
+        check(lib.gprx_hms_create(self.device, ptr(x), n_s, ld, n_f, fortran, ptr(bc), bc.size, ptr(pc), p, None, C.byref(h)))
+        try:
+            input_mean = np.empty(n_f)
+            route = C.c_int()
+            n_cov = p if n_s >= p else n_s
+            cov = np.empty((n_cov, n_cov))
+            check(lib.gprx_hms_cov(h, ptr(input_mean), ptr(cov), C.byref(route)))
+            t0 = time.perf_counter()
+            lam, v = np.linalg.eigh(cov)
+            lam, v = np.maximum(lam[::-1], 0.0), v[:, ::-1]
+            eigh_ms = (time.perf_counter() - t0) * 1e3
+            pca = PCAFit(explained_variance_=lam / (n_s - 1), n_samples_seen_=np.int64(n_s))
+            k = compute_norths_rule(pca) if precip_spatial_mode_count is None else int(precip_spatial_mode_count)
+            if route.value == 0:
+                # covariance route: the components are the eigenvectors, signed by svd_flip(u_based_decision=False)
+                comps = np.ascontiguousarray(v.T)
+                piv = comps[np.arange(p), np.argmax(np.abs(comps), axis=1)]
+                comps *= np.sign(piv)[:, None]
+                eofs = comps[:k]
+            else:
+                # Gram route: the components are X2^T u / sqrt(lambda), formed on the device
+                if k > n_s - 1 or (k > 0 and not lam[k - 1] > 0.0):
+                    raise ValueError(f"{k} modes exceed the numerical rank of the centred precip block ({n_s} samples)")
+                eofs = np.empty((k, p))
+                check(lib.gprx_hms_components(h, k, ptr(np.ascontiguousarray(v[:, :k])), ptr(np.ascontiguousarray(lam[:k])), ptr(eofs)))
+            ke = eofs.shape[0]
+            e_c = np.ascontiguousarray(eofs)
+            w1, w2 = api_weights(0.85, n_s), api_weights(1, n_s)
+            x_mean, x_std = np.empty(bc.size + ke + 3), np.empty(bc.size + ke + 3)
+            check(lib.gprx_hms_features(h, ke, ptr(e_c), ptr(w1), w1.size, ptr(w2), w2.size, ptr(x_mean), ptr(x_std), 1, None))
+            self.last_timings_ms = self._timings(lib, h)
+            self.last_timings_ms["host_eigh"] = eigh_ms
+        finally:
+            lib.gprx_hms_destroy(h)
+        self.input_mean = input_mean
+        self.bc_mask = bc_mask
+        self.precip_mask = precip_mask
+        pca.components_ = eofs
+        self.pca_ = pca
+        self.precip_spatial_mode_count = k
+        self.eofs = eofs
+        self.eigenvalues = pca.explained_variance_
+        self.n_samples_fit = pca.n_samples_seen_
+        self.x_mean = x_mean
+        self.x_std = x_std
+
+    @staticmethod
+    def _timings(lib, h) -> dict:
+        ms = np.zeros(7)
+        check(lib.gprx_hms_timings(h, ms.ctypes.data_as(C.POINTER(C.c_double))))
+        return dict(zip(("upload", "column_pass", "covariance", "components", "projection", "api", "features"), ms.tolist()))
+
+    def transform(self, x):
+        """(samples, features) -> standardised features (samples, n_bc + k + 3)  (preprocess.py:1263-1282)."""
+        x, ld, fortran = _device_x(x)
+        n_s, n_f = x.shape
+        mean = as_f64(self.input_mean)
+        if mean.shape != (n_f,):
+            raise ValueError(f"x has {n_f} features, input_mean {mean.size}: fit first")
+        bc = _columns(self.bc_mask, n_f, "bc_mask")
+        pc = _columns(self.precip_mask, n_f, "precip_mask")
+        if pc.size == 0:
+            raise ValueError("precip_mask selects no column")
+        eofs = as_f64(self.eofs)
+        if eofs.ndim != 2 or eofs.shape[1] != pc.size:
+            raise ValueError(f"eofs must be (k, {pc.size})")
+        ke = eofs.shape[0]
+        nf = bc.size + ke + 3
+        x_mean, x_std = as_f64(self.x_mean), as_f64(self.x_std)
+        if x_mean.shape != (nf,) or x_std.shape != (nf,):
+            raise ValueError(f"x_mean and x_std must be ({nf},)")
+        if n_s < 1:
+            raise ValueError("x has no rows")
+        lib = _lib.load()
+        h = C.c_void_p()
+        check(lib.gprx_hms_create(self.device, ptr(x), n_s, ld, n_f, fortran, ptr(bc), bc.size, ptr(pc), pc.size, ptr(mean), C.byref(h)))
+        try:
+            w1, w2 = api_weights(0.85, n_s), api_weights(1, n_s)
+            out = np.empty((n_s, nf))
+            check(lib.gprx_hms_features(h, ke, ptr(eofs), ptr(w1), w1.size, ptr(w2), w2.size, ptr(x_mean), ptr(x_std), 0, ptr(out)))
+            self.last_timings_ms = self._timings(lib, h)
+        finally:
+            lib.gprx_hms_destroy(h)
+        return out
+
+    def calc_antecedent_precipitation_index(self, x, k: float = 0.85, window: int | None = None):
+        """np.convolve(x, [k**i for i in range(window)], "full")[:len(x), None] (preprocess.py:1284-1294) on the device."""
+        a = np.asarray(x)
+        if a.ndim != 1:
+            raise ValueError("x must be one-dimensional")
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if window is None:
+            window = len(a)
+        if len(a) == 0 or window <= 0:
+            raise ValueError("the series and the window must not be empty")
+        w = api_weights(k, window)
+        if not np.all(np.isfinite(w)):
+            raise ValueError(f"the weights {k}**i overflow within the window")
+        out = np.empty((len(a), 1))
+        check(_lib.load().gprx_api(self.device, ptr(a), len(a), ptr(w), w.size, int(window), ptr(out)))
+        return out
+
+    # ---- serialisation (preprocess.py:1296-1320) --------------------------------------------------------------------------
+    def to_dict(self) -> dict[str, Any]:
+        return {
+            "precip_spatial_mode_count": self.precip_spatial_mode_count,
+            "bc_mask": self.bc_mask,
+            "precip_mask": self.precip_mask,
+            "eofs": self.eofs,
+            "eigenvalues": self.eigenvalues,
+            "n_samples_fit": self.n_samples_fit,
+            "x_mean": self.x_mean,
+            "x_std": self.x_std,
+            "input_mean": self.input_mean,
+        }
+
+    def to_file(self, out_path) -> None:
+        with open(out_path, mode="wb") as f:
+            pickle.dump(self.to_dict(), f)
+
+    @classmethod
+    def from_file(cls, in_path) -> "HmsPreProcessor":
         with open(in_path, mode="rb") as f:
             d = pickle.load(f)
         return cls(**d)

@@ -62,6 +62,7 @@ extern "C" {
 typedef struct gprx_ctx* gprx_handle;
 typedef struct gprx_pca_ctx* gprx_pca_handle;
 typedef struct gprx_pcafit_ctx* gprx_pcafit_handle;
+typedef struct gprx_hms_ctx* gprx_hms_handle;
 typedef struct gprx_comm_ctx* gprx_comm;
 
 /* ---- library / device -------------------------------------------------------------- */
@@ -360,6 +361,36 @@ int gprx_pcafit_components(gprx_pcafit_handle f, int k, const double* u, const d
 int gprx_pcafit_timings(gprx_pcafit_handle f, double* ms);
 int gprx_pcafit_destroy(gprx_pcafit_handle f);
 const char* gprx_pcafit_last_error(gprx_pcafit_handle f);
+
+/* ---- HmsPreProcessor: gpras/preprocess.py:1165-1320 ------------------------------------------------
+ * create: x (rows, n_features), C order (fortran = 0: x[t * ld + c]) or F order (fortran = 1: x[c * ld + t]), goes up once and
+ * stays on the device.  bc_idx / precip_idx: the columns of x[:, bc_mask] / x[:, precip_mask] (:1231-1232), in order, the host's
+ * np.arange(n_features)[mask].  input_mean (n_features): NULL for a fit (gprx_hms_cov computes it, :1226), the fitted one for a
+ * transform (:1266).  Needs rows >= 1 (a fit: 2), one precip column at least, min(rows, n_precip) <= 16384.  Not enough device memory:
+ * GPRX_ENOMEM before anything is allocated. */
+int gprx_hms_create(int device, const double* x, int64_t rows, int64_t ld, int64_t n_features, int fortran, const int64_t* bc_idx, int64_t n_bc,
+                    const int64_t* precip_idx, int64_t n_precip, const double* input_mean, gprx_hms_handle* out);
+/* The column pass and the product behind IncrementalPCA().fit(x_precip) (:1235-1236): input_mean (n_features) = x.mean(axis=0);
+ * X2 = the once-centred precip block centred again by its own column mean.  route 0 (rows >= n_precip): cov (n_precip, n_precip)
+ * = X2^T X2, whose eigenvectors are the components; route 1 (rows < n_precip): cov (rows, rows) = X2 X2^T, the Gram matrix. */
+int gprx_hms_cov(gprx_hms_handle h, double* input_mean, double* cov, int* route);
+/* Route 1 only: eofs (k, n_precip) = diag(lambda^-1/2) u^T X2 with svd_flip(u_based_decision=False) (pca.components_[:k], :1246);
+ * u (rows, k) row-major eigenvectors of the Gram matrix for its k largest eigenvalues lambda (all > 0), 0 <= k < rows. */
+int gprx_hms_components(gprx_hms_handle h, int k, const double* u, const double* lam, double* eofs);
+/* The features [x_bc, x_precip eofs^T, avg_precip, api(avg_precip, 0.85), api(avg_precip, 1)] (:1251-1257, :1271-1277) with
+ * eofs (k, n_precip); w1 / w2: the API weights k**i of the host (:1293), their first n1 / n2 entries (the rest, up to
+ * window = rows, are exact zeros).  fit = 1: x_mean / x_std (n_bc + k + 3) out -- the column mean and np.std of the entries that
+ * are not zero (:1260-1261); fit = 0: x_mean / x_std in, out (rows, n_bc + k + 3) = (features - x_mean) / x_std (:1280). */
+int gprx_hms_features(gprx_hms_handle h, int k, const double* eofs, const double* w1, int64_t n1, const double* w2, int64_t n2, double* x_mean,
+                      double* x_std, int fit, double* out);
+/* device milliseconds: upload of x, column pass, covariance / Gram, components, projection, API, statistics / standardisation */
+int gprx_hms_timings(gprx_hms_handle h, double* ms);
+int gprx_hms_destroy(gprx_hms_handle h);
+const char* gprx_hms_last_error(gprx_hms_handle h);
+/* calc_antecedent_precipitation_index (:1284-1294): out[t] = sum_{i=0}^{min(t, window-1)} w[i] a[t-i], t < n, on the device;
+ * w: the first n_w (<= window) weights, finite; the others are zeros (cut from the sum when a is finite).  n or window < 1:
+ * GPRX_EINVAL (np.convolve raises on an empty operand). */
+int gprx_api(int device, const double* a, int64_t n, const double* w, int64_t n_w, int64_t window, double* out);
 
 /* ---- fused error metrics over two fields: SURVEY.md section 8(f) row N3 (gpras/metrics.py:85-318) ---------- */
 /* Two streaming passes over x (truth), y (prediction) and conf (may be NULL), each (rows, cells) row-major, yield every
