@@ -106,6 +106,21 @@ PROTOTYPES = {
     "gprx_hms_destroy": (C.c_int, [_vp]),
     "gprx_hms_last_error": (C.c_char_p, [_vp]),
     "gprx_api": (C.c_int, [C.c_int, _vp, _i64, _vp, _i64, _i64, _vp]),
+    "gprx_spline_eval": (C.c_int, [C.c_int, _vp, C.c_int, _vp, _vp, _i64, _vp]),
+    "gprx_ps_create": (C.c_int, [C.c_int, _i64, _vp, _vp, _i64, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, C.POINTER(_vp)]),
+    "gprx_ps_destroy": (C.c_int, [_vp]),
+    "gprx_ps_last_error": (C.c_char_p, [_vp]),
+    "gprx_ps_set_weights": (C.c_int, [_vp, _vp]),
+    "gprx_ps_fit_centerline": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "gprx_ps_timings": (C.c_int, [_vp, _dp]),
+    "gprx_ps_rating": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    "gprx_ps_set_boundaries": (C.c_int, [_vp, _vp, _vp, _i64]),
+    "gprx_ps_centerline": (C.c_int, [_vp, _vp]),
+    "gprx_ps_gather": (C.c_int, [_vp, _vp, _i64, _vp]),
+    "gprx_ps_surface": (C.c_int, [_vp, _vp, _vp]),
+    "gprx_ps_surface_dev": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _vp, _i64]),
+    "gprx_ps_synchronize": (C.c_int, [_vp]),
+    "gprx_pca_slab_rows": (C.c_int, [_vp, C.POINTER(_i64)]),
     "gprx_metrics": (C.c_int, [C.c_int, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_double, _vp, _vp, _vp, C.POINTER(C.c_uint64)]),
     "gprx_metrics_dev": (C.c_int, [C.c_int, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_double, _vp, _vp, _vp, C.POINTER(C.c_uint64)]),
     "gprx_kmeans_pp": (C.c_int, [C.c_int, _vp, _i64, C.c_int, _vp, C.c_int, C.c_int, _i64, _vp, _vp]),

@@ -133,6 +133,23 @@ class DevicePipeline:
             var_t.free()
         return DeviceFields(full, conf, ns, cells)
 
+    def predict_mean_field_dev(self, x_test) -> tuple[DeviceBuffer, int]:
+        """``hf_reducer.reverse_transform(gpr.predict(x_test)[0])`` (the fluvial estimate of the pseudo-surface model,
+        preprocess.py:601-606) left on the device: a ``(T*, cells)`` buffer, and ``T*``.  The caller frees the buffer."""
+        mean_t, var_t, ns = self.predict_modes_dev(x_test)
+        var_t.free()
+        full = DeviceBuffer(8 * ns * self.projector.n_cells, self.device)
+        try:
+            ph = self.projector.handle
+            check(self._lib.gprx_pca_reverse_dev(ph, mean_t.ptr, None, ns, full.ptr, None))
+            check(self._lib.gprx_pca_synchronize(ph))
+        except Exception:
+            full.free()
+            raise
+        finally:
+            mean_t.free()
+        return full, ns
+
     def _require_elevations(self):
         if self.projector.elevations is None:
             raise ValueError("wse_2_depth needs the cell elevations (the projector was built without them)")

@@ -63,6 +63,7 @@ typedef struct gprx_ctx* gprx_handle;
 typedef struct gprx_pca_ctx* gprx_pca_handle;
 typedef struct gprx_pcafit_ctx* gprx_pcafit_handle;
 typedef struct gprx_hms_ctx* gprx_hms_handle;
+typedef struct gprx_ps_ctx* gprx_ps_handle;
 typedef struct gprx_comm_ctx* gprx_comm;
 
 /* ---- library / device -------------------------------------------------------------- */
@@ -391,6 +392,53 @@ const char* gprx_hms_last_error(gprx_hms_handle h);
  * w: the first n_w (<= window) weights, finite; the others are zeros (cut from the sum when a is finite).  n or window < 1:
  * GPRX_EINVAL (np.convolve raises on an empty operand). */
 int gprx_api(int device, const double* a, int64_t n, const double* w, int64_t n_w, int64_t window, double* out);
+
+/* ---- pseudo-surface low-fidelity model: gpras/preprocess.py:454-697 --------------------------------
+ * RatingCurve.predict (preprocess.py:511-513): out[i] = s(x[i]), i < n, for the cubic B-spline with FITPACK's knot vector
+ * knots[0..nt) (boundary knots repeated four times, 8 <= nt <= 72) and coefficients coef[0..nt-4), what
+ * LSQUnivariateSpline.get_knots / get_coeffs describe (:492-496).  Arguments outside [knots[3], knots[nt-4]] are evaluated with
+ * the end polynomial pieces (FITPACK's ext = 0).  NaN in, NaN out. */
+int gprx_spline_eval(int device, const double* knots, int nt, const double* coef, const double* x, int64_t n, double* out);
+/* The numeric state of PseudoSurfaceDataBuilder (preprocess.py:516-579): elev (n_cells) = cell_elevations, idx (n_cells) =
+ * cell_interpolater (:669-674), every value in [0, n_centerline) or GPRX_EINVAL; w (n_centerline) = cl_interpolater (:667) or NULL
+ * (then gprx_ps_fit_centerline / gprx_ps_set_weights before a surface); the two rating curves (:620-632) as for gprx_spline_eval,
+ * nt = 0 for a handle without curves.  Not enough device memory: GPRX_ENOMEM before anything is allocated. */
+int gprx_ps_create(int device, int64_t n_cells, const double* elev, const int32_t* idx, int64_t n_centerline, const double* w, const double* us_knots,
+                   int us_nt, const double* us_coef, const double* ds_knots, int ds_nt, const double* ds_coef, gprx_ps_handle* out);
+int gprx_ps_destroy(gprx_ps_handle h);
+const char* gprx_ps_last_error(gprx_ps_handle h);
+int gprx_ps_set_weights(gprx_ps_handle h, const double* w);
+/* _set_centerline_interpolater (preprocess.py:643-667): over the rows with us_q > 0 or ds_q > 0 (:657),
+ * w[c] = np.median((us_wse - centerline_wse[:, c]) / (us_wse - ds_wse)), c < n_centerline; centerline_wse (rows, n_centerline)
+ * row-major.  np.median's semantics: a NaN ratio makes the column NaN, infinities order as the ends, an even count gives
+ * (a + b) / 2.  The weights stay in the handle and come back in w.  No kept row: GPRX_EINVAL. */
+int gprx_ps_fit_centerline(gprx_ps_handle h, const double* us_wse, const double* ds_wse, const double* us_q, const double* ds_q,
+                           const double* centerline_wse, int64_t rows, double* w);
+/* device milliseconds (waits for the handle's stream): ms[0] the kernel of the last gprx_ps_fit_centerline, ms[1] the kernel of
+ * the last gprx_ps_surface_dev; 0 for what has not run */
+int gprx_ps_timings(gprx_ps_handle h, double* ms);
+/* get_lf_plan_data's first step (preprocess.py:587-589): the two rating curves turn the flows us_q / ds_q (T) into the boundary
+ * elevations, which stay in the handle as the boundary series of the calls below; us_wse / ds_wse (T) receive them unless NULL. */
+int gprx_ps_rating(gprx_ps_handle h, const double* us_q, const double* ds_q, int64_t T, double* us_wse, double* ds_wse);
+/* the boundary series given directly (T each) */
+int gprx_ps_set_boundaries(gprx_ps_handle h, const double* us_wse, const double* ds_wse, int64_t T);
+/* interpolate_centerline (preprocess.py:634-637): out (T, n_centerline) = us - outer(us - ds, w) */
+int gprx_ps_centerline(gprx_ps_handle h, double* out);
+/* interpolate_surface (preprocess.py:639-641): out (rows, n_cells) = centerline[:, idx], centerline (rows, n_centerline) */
+int gprx_ps_gather(gprx_ps_handle h, const double* centerline, int64_t rows, double* out);
+/* get_lf_plan_data (preprocess.py:591-597) for the boundary series of the handle:
+ * out[t, c] = np.maximum(np.maximum(us[t] - (us[t] - ds[t]) * w[idx[c]], elev[c]), fluvial[t, c]); fluvial (T, n_cells) is the
+ * result of get_lf_fluvial_est (:601-606), or NULL (that floor is skipped).  Host buffers, staged in row slabs. */
+int gprx_ps_surface(gprx_ps_handle h, const double* fluvial, double* out);
+/* The same for rows [t0, t0 + rows) of the boundary series on device buffers: fluvial_dev (rows, ldf) or NULL, out_dev (rows, ldo),
+ * ldf, ldo >= n_cells.  Columns [n_cells, ldo) of out are set to 0, so that out_dev can be the padded input of
+ * gprx_pca_transform_dev while fluvial_dev is the output of gprx_pca_reverse_dev (ldf = n_cells).  out_dev == fluvial_dev (in place)
+ * needs ldf == ldo.  Asynchronous on the handle's stream: gprx_ps_synchronize before another handle reads out_dev. */
+int gprx_ps_surface_dev(gprx_ps_handle h, int64_t t0, int64_t rows, const double* fluvial_dev, int64_t ldf, double* out_dev, int64_t ldo);
+int gprx_ps_synchronize(gprx_ps_handle h);
+/* rows per device pass of gprx_pca_transform (the split-K plan of gprx_pca_transform_dev depends on the rows of a call, so a
+ * caller of the _dev entry that wants the bits of gprx_pca_transform cuts its rows into the same slabs) */
+int gprx_pca_slab_rows(gprx_pca_handle p, int64_t* rows);
 
 /* ---- fused error metrics over two fields: SURVEY.md section 8(f) row N3 (gpras/metrics.py:85-318) ---------- */
 /* Two streaming passes over x (truth), y (prediction) and conf (may be NULL), each (rows, cells) row-major, yield every
