@@ -1,0 +1,824 @@
+// libgprx C ABI, EOF family: the projection either side of the GP path (gprx_pca_*), the fit of the preprocessor (gprx_pcafit_*)
+// and HmsPreProcessor with the antecedent precipitation index (gprx_hms_*, gprx_api).  They share the split-K Gram plan.
+#include "abi_common.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "gemm_f64.h"
+#include "gprx_common.h"
+#include "hms.h"
+#include "pca.h"
+#include "pca_fit.h"
+
+using namespace gprx;
+
+struct gprx_pca_ctx {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  int64_t cells = 0, cells_p = 0;  // cells_p: leading dimension of the device copies (multiple of 16, zero padded)
+  int k = 0, depth = 0;
+  Buf mu, wfwd, wrev, elev, E, base, xm, xs;  // per-cell parameters expanded to all cells; E: (k, cells_p)
+  Buf dX, dZ, ws, dMean, dVar, dFull, dVfull;
+  std::string err;
+};
+
+void gprx::launch_transpose_small(hipStream_t st, const double* src, int64_t rows, int64_t cols, double* dst) {
+  hipLaunchKernelGGL(transpose_small_kernel, dim3((unsigned)std::min<int64_t>((rows * cols + 255) / 256, 4096)), dim3(256), 0, st, src, rows, cols, dst);
+}
+
+extern "C" {
+
+// ---- EOF projection either side of the GP path ------------------------------
+namespace {
+int pupload(gprx_pca_handle p, Buf& b, const std::vector<double>& v) {
+  int rc = ensure(p, b, sizeof(double) * v.size());
+  if (rc) return rc;
+  HIPCHK(p, copy_sync(b.p, v.data(), sizeof(double) * v.size(), hipMemcpyHostToDevice));
+  return GPRX_OK;
+}
+}  // namespace
+
+int gprx_pca_create(int device, int64_t n_cells, int k, const unsigned char* dry, const double* elevations, const double* input_mean,
+                    const double* weights, const double* eofs, const double* x_mean, const double* x_std, int depth_mode,
+                    gprx_pca_handle* out) {
+  if (!out) return fail(nullptr, GPRX_EINVAL, "out is null");
+  *out = nullptr;
+  if (n_cells <= 0 || k <= 0 || k > 64) return fail(nullptr, GPRX_EINVAL, "n_cells must be positive and 1 <= k <= 64");
+  if (!input_mean || !eofs || !x_mean || !x_std) return fail(nullptr, GPRX_EINVAL, "input_mean, eofs, x_mean, x_std must be non-null");
+  int64_t n_dry = 0;
+  if (dry)
+    for (int64_t c = 0; c < n_cells; ++c) n_dry += dry[c] != 0;
+  if (depth_mode && !elevations) return fail(nullptr, GPRX_EINVAL, "depth mode needs the cell elevations");
+  if (!depth_mode && n_dry > 0 && !elevations) return fail(nullptr, GPRX_EINVAL, "always-dry cells are filled with their elevations: elevations is null");
+  HIPCHK(nullptr, hipSetDevice(device));
+  gprx_pca_handle p = new gprx_pca_ctx();
+  p->device = device;
+  p->cells = n_cells;
+  p->cells_p = round_up(n_cells, 16);
+  p->k = k;
+  p->depth = depth_mode ? 1 : 0;
+  const int64_t n_wet = n_cells - n_dry, cp = p->cells_p;
+  // expand the wet-cell parameters to the full cell axis: dry cells get weight 0 (forward) / 1 (reverse), E = 0 and the fill value
+  std::vector<double> mu(cp, 0.0), wf(cp, 0.0), wr(cp, 1.0), el(cp, 0.0), base(cp, 0.0), E((size_t)k * cp, 0.0);
+  int64_t j = 0;
+  for (int64_t c = 0; c < n_cells; ++c) {
+    if (elevations) el[c] = elevations[c];
+    if (dry && dry[c]) {
+      base[c] = depth_mode ? 0.0 : elevations[c];
+      continue;
+    }
+    mu[c] = input_mean[j];
+    wf[c] = weights ? weights[j] : 1.0;
+    wr[c] = wf[c];
+    base[c] = input_mean[j];
+    for (int kk = 0; kk < k; ++kk) E[(size_t)kk * cp + c] = eofs[(size_t)kk * n_wet + j];
+    ++j;
+  }
+  int rc = GPRX_OK;
+  hipError_t e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
+  if (e != hipSuccess) {
+    delete p;
+    return fail(nullptr, GPRX_EHIP, std::string("hipStreamCreate: ") + hipGetErrorString(e));
+  }
+  std::vector<double> xm(x_mean, x_mean + k), xs(x_std, x_std + k);
+  if ((rc = pupload(p, p->mu, mu)) || (rc = pupload(p, p->wfwd, wf)) || (rc = pupload(p, p->wrev, wr)) || (rc = pupload(p, p->elev, el)) ||
+      (rc = pupload(p, p->base, base)) || (rc = pupload(p, p->E, E)) || (rc = pupload(p, p->xm, xm)) || (rc = pupload(p, p->xs, xs))) {
+    gprx_pca_destroy(p);
+    return rc;
+  }
+  *out = p;
+  return GPRX_OK;
+}
+
+int gprx_pca_destroy(gprx_pca_handle p) {
+  if (!p) return GPRX_OK;
+  release_handle(p->device, p->stream, {p->mu.p, p->wfwd.p, p->wrev.p, p->elev.p, p->E.p, p->base.p, p->xm.p, p->xs.p, p->dX.p, p->dZ.p, p->ws.p, p->dMean.p, p->dVar.p,
+                                           p->dFull.p, p->dVfull.p});
+  delete p;
+  return GPRX_OK;
+}
+
+// x_dev: (rows, ld) with ld = cells_p (padding columns may hold anything finite: their weight is 0); z_dev: (rows, k)
+int gprx_pca_transform_dev(gprx_pca_handle p, const double* x_dev, int64_t rows, double* z_dev) {
+  if (!p) return fail(p, GPRX_EINVAL, "null handle");
+  if (rows < 0 || (rows > 0 && (!x_dev || !z_dev))) return fail(p, GPRX_EINVAL, "null argument");
+  if (rows == 0) return GPRX_OK;
+  if (rows > (1 << 30)) return fail(p, GPRX_EINVAL, "too many rows in one call");
+  HIPCHK(p, hipSetDevice(p->device));
+  hipStream_t st = p->stream;
+  const int64_t cp = p->cells_p;
+  // Z = ((g(X) - mu) w) E^T in ONE pass over X: the centring / weighting runs inside the GEMM's operand load
+  // (gemm_f64_kernel AXF); M = rows, N = k, K = cells_p cut into slices so that a few thousand workgroups exist
+  const int tiles_m = (int)((rows + 63) / 64);
+  int nsplit = std::max(1, 2048 / tiles_m);
+  int kchunk = (int)round_up((cp + nsplit - 1) / nsplit, 16);
+  if (kchunk < 256) kchunk = 256;
+  nsplit = (int)((cp + kchunk - 1) / kchunk);
+  int rc;
+  if ((rc = ensure(p, p->ws, sizeof(double) * (size_t)nsplit * rows * p->k))) return rc;
+  HIPCHK(p, launch_gemm_splitk_axf(st, (int)rows, p->k, (int)cp, x_dev, cp, p->E.p, cp, z_dev, p->k, p->ws.p, kchunk, p->mu.p, p->wfwd.p,
+                                   p->depth ? p->elev.p : nullptr));
+  hipLaunchKernelGGL(pca_standardize_kernel, dim3((unsigned)((rows * p->k + 255) / 256)), dim3(256), 0, st, z_dev, rows, p->k,
+                     (const double*)p->xm.p, (const double*)p->xs.p);
+  HIPCHK(p, hipGetLastError());
+  return GPRX_OK;
+}
+
+int gprx_pca_reverse_dev(gprx_pca_handle p, const double* mean_dev, const double* var_dev, int64_t rows, double* full_dev, double* vfull_dev) {
+  if (!p) return fail(p, GPRX_EINVAL, "null handle");
+  if (rows < 0 || (rows > 0 && (!mean_dev || !full_dev))) return fail(p, GPRX_EINVAL, "null argument");
+  if ((var_dev == nullptr) != (vfull_dev == nullptr)) return fail(p, GPRX_EINVAL, "var and var_full must both be given or both be null");
+  if (rows == 0) return GPRX_OK;
+  HIPCHK(p, hipSetDevice(p->device));
+  dim3 grid((unsigned)((p->cells + 255) / 256), (unsigned)std::min<int64_t>((rows + PCA_RB - 1) / PCA_RB, 64));
+  if (p->k <= 16)
+    hipLaunchKernelGGL(pca_reverse_kernel<16>, grid, dim3(256), 0, p->stream, mean_dev, var_dev, rows, p->k, p->cells, (const double*)p->E.p, p->cells_p,
+                       (const double*)p->wrev.p, (const double*)p->base.p, (const double*)p->xm.p, (const double*)p->xs.p, full_dev, vfull_dev);
+  else
+    hipLaunchKernelGGL(pca_reverse_kernel<64>, grid, dim3(256), 0, p->stream, mean_dev, var_dev, rows, p->k, p->cells, (const double*)p->E.p, p->cells_p,
+                       (const double*)p->wrev.p, (const double*)p->base.p, (const double*)p->xm.p, (const double*)p->xs.p, full_dev, vfull_dev);
+  HIPCHK(p, hipGetLastError());
+  return GPRX_OK;
+}
+
+int gprx_pca_to_depth_dev(gprx_pca_handle p, double* field_dev, int64_t rows, int add_elevations_first) {
+  if (!p) return fail(p, GPRX_EINVAL, "null handle");
+  if (rows < 0 || (rows > 0 && !field_dev)) return fail(p, GPRX_EINVAL, "null argument");
+  if (rows == 0) return GPRX_OK;
+  HIPCHK(p, hipSetDevice(p->device));
+  hipLaunchKernelGGL(field_to_depth_kernel, dim3(4096), dim3(256), 0, p->stream, field_dev, rows, p->cells, (const double*)p->elev.p,
+                     add_elevations_first ? 1 : 0);
+  HIPCHK(p, hipGetLastError());
+  return GPRX_OK;
+}
+
+int gprx_pca_sqrt_dev(gprx_pca_handle p, double* field_dev, int64_t count) {
+  if (!p) return fail(p, GPRX_EINVAL, "null handle");
+  if (count < 0 || (count > 0 && !field_dev)) return fail(p, GPRX_EINVAL, "null argument");
+  if (count == 0) return GPRX_OK;
+  HIPCHK(p, hipSetDevice(p->device));
+  hipLaunchKernelGGL(field_sqrt_kernel, dim3(4096), dim3(256), 0, p->stream, field_dev, count);
+  HIPCHK(p, hipGetLastError());
+  return GPRX_OK;
+}
+
+int gprx_pca_transpose_dev(gprx_pca_handle p, const double* src_dev, int64_t rows, int64_t cols, double* dst_dev) {
+  if (!p) return fail(p, GPRX_EINVAL, "null handle");
+  if (rows < 0 || cols < 0 || (rows * cols > 0 && (!src_dev || !dst_dev))) return fail(p, GPRX_EINVAL, "null argument");
+  if (rows * cols == 0) return GPRX_OK;
+  HIPCHK(p, hipSetDevice(p->device));
+  launch_transpose_small(p->stream, src_dev, rows, cols, dst_dev);
+  HIPCHK(p, hipGetLastError());
+  return GPRX_OK;
+}
+
+int gprx_pca_synchronize(gprx_pca_handle p) {
+  if (!p) return fail(p, GPRX_EINVAL, "null handle");
+  HIPCHK(p, hipStreamSynchronize(p->stream));
+  return GPRX_OK;
+}
+
+int gprx_pca_transform(gprx_pca_handle p, const double* x, int64_t rows, double* z) {
+  if (!p) return fail(p, GPRX_EINVAL, "null handle");
+  if (rows < 0 || (rows > 0 && (!x || !z))) return fail(p, GPRX_EINVAL, "null argument");
+  HIPCHK(p, hipSetDevice(p->device));
+  const int64_t cp = p->cells_p, chunk = std::max<int64_t>(64, pca_chunk_doubles() / cp);
+  int rc;
+  for (int64_t t0 = 0; t0 < rows; t0 += chunk) {
+    const int64_t nr = std::min(chunk, rows - t0);
+    if ((rc = ensure(p, p->dX, sizeof(double) * (size_t)nr * cp)) || (rc = ensure(p, p->dZ, sizeof(double) * (size_t)nr * p->k))) return rc;
+    if (cp > p->cells)  // padding columns must be finite (their weight is 0, and 0 * NaN is not)
+      HIPCHK(p, hipMemset2DAsync(p->dX.p + p->cells, sizeof(double) * cp, 0, sizeof(double) * (cp - p->cells), nr, p->stream));
+    HIPCHK(p, hipMemcpy2DAsync(p->dX.p, sizeof(double) * cp, x + t0 * p->cells, sizeof(double) * p->cells, sizeof(double) * p->cells, nr,
+                               hipMemcpyHostToDevice, p->stream));
+    if ((rc = gprx_pca_transform_dev(p, p->dX.p, nr, p->dZ.p))) return rc;
+    HIPCHK(p, hipMemcpyAsync(z + t0 * p->k, p->dZ.p, sizeof(double) * nr * p->k, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(p, hipStreamSynchronize(p->stream));
+  }
+  return GPRX_OK;
+}
+
+int gprx_pca_reverse(gprx_pca_handle p, const double* mean, const double* var, int64_t rows, double* full, double* var_full) {
+  if (!p) return fail(p, GPRX_EINVAL, "null handle");
+  if (rows < 0 || (rows > 0 && (!mean || !full))) return fail(p, GPRX_EINVAL, "null argument");
+  if ((var == nullptr) != (var_full == nullptr)) return fail(p, GPRX_EINVAL, "var and var_full must both be given or both be null");
+  HIPCHK(p, hipSetDevice(p->device));
+  const int64_t chunk = std::max<int64_t>(64, pca_chunk_doubles() / p->cells);
+  int rc;
+  for (int64_t t0 = 0; t0 < rows; t0 += chunk) {
+    const int64_t nr = std::min(chunk, rows - t0);
+    if ((rc = ensure(p, p->dMean, sizeof(double) * (size_t)nr * p->k)) || (rc = ensure(p, p->dFull, sizeof(double) * (size_t)nr * p->cells))) return rc;
+    HIPCHK(p, hipMemcpyAsync(p->dMean.p, mean + t0 * p->k, sizeof(double) * nr * p->k, hipMemcpyHostToDevice, p->stream));
+    if (var) {
+      if ((rc = ensure(p, p->dVar, sizeof(double) * (size_t)nr * p->k)) || (rc = ensure(p, p->dVfull, sizeof(double) * (size_t)nr * p->cells))) return rc;
+      HIPCHK(p, hipMemcpyAsync(p->dVar.p, var + t0 * p->k, sizeof(double) * nr * p->k, hipMemcpyHostToDevice, p->stream));
+    }
+    if ((rc = gprx_pca_reverse_dev(p, p->dMean.p, var ? p->dVar.p : nullptr, nr, p->dFull.p, var ? p->dVfull.p : nullptr))) return rc;
+    HIPCHK(p, hipMemcpyAsync(full + t0 * p->cells, p->dFull.p, sizeof(double) * nr * p->cells, hipMemcpyDeviceToHost, p->stream));
+    if (var) HIPCHK(p, hipMemcpyAsync(var_full + t0 * p->cells, p->dVfull.p, sizeof(double) * nr * p->cells, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(p, hipStreamSynchronize(p->stream));
+  }
+  return GPRX_OK;
+}
+
+int gprx_pca_slab_rows(gprx_pca_handle p, int64_t* rows) {
+  if (!p || !rows) return fail(p, GPRX_EINVAL, "null argument");
+  *rows = std::max<int64_t>(64, pca_chunk_doubles() / p->cells_p);
+  return GPRX_OK;
+}
+
+const char* gprx_pca_last_error(gprx_pca_handle p) { return p ? p->err.c_str() : last_error().c_str(); }
+
+// ---- fitting the EOF preprocessor (PreProcessor.fit, gpras/preprocess.py:947-1007) ---------------------------------------
+struct gprx_pcafit_ctx {
+  int device = 0, mode = 0;
+  hipStream_t stream = nullptr;
+  int64_t rows = 0, rows_p = 0, cells = 0, n_wet = 0, ldc = 0;  // ldc: leading dimension of the compacted matrices (multiple of 16)
+  double *xc1 = nullptr, *xc2 = nullptr, *A = nullptr, *E = nullptr, *Z = nullptr;
+  Buf ws;  // split-K slabs, then their sum
+  std::vector<unsigned char> cls;    // wetness class per cell
+  std::vector<double> mean, gram;    // input_mean over the wet cells, G (rows, rows)
+  hipEvent_t ev[8] = {};
+  double ms[6] = {0, 0, 0, 0, 0, 0};  // upload, stats, centring, Gram, components, projection
+  std::string err;
+};
+
+namespace {
+// split-K plan of a product with `tiles` output tiles of 64 x 64 and K = kdim: a few thousand workgroups, slabs capped at 256 MiB
+int pcafit_kchunk(int64_t tiles, int64_t kdim, int64_t slab_doubles) {
+  int64_t nsplit = std::max<int64_t>(1, 2048 / std::max<int64_t>(tiles, 1));
+  nsplit = std::min<int64_t>(nsplit, std::max<int64_t>(1, ((int64_t)1 << 25) / std::max<int64_t>(slab_doubles, 1)));
+  int64_t kchunk = round_up((kdim + nsplit - 1) / nsplit, 16);
+  return (int)std::max<int64_t>(kchunk, 256);
+}
+
+// steps 1-3: upload, column statistics + classes, compaction + both centrings, Gram matrix
+int pcafit_run(gprx_pcafit_handle f, const double* x, const double* elevations, const double* weights, double thr) {
+  const int64_t rows = f->rows, cells = f->cells;
+  const size_t xb = sizeof(double) * (size_t)rows * cells;
+  hipStream_t st = f->stream;
+  // device memory of the whole fit, before anything is allocated: x, per-cell vectors, both compacted matrices, Gram slabs
+  {
+    const int64_t ldc_max = round_up(cells, 16);
+    const int64_t tiles = (rows + 63) / 64, ltiles = tiles * (tiles + 1) / 2;
+    const int64_t nsplit = (ldc_max + pcafit_kchunk(ltiles, ldc_max, rows * rows) - 1) / pcafit_kchunk(ltiles, ldc_max, rows * rows);
+    const double need = (double)xb + 8.0 * (4.0 * cells + (double)(rows + f->rows_p) * ldc_max + (double)(nsplit + 1) * rows * rows) + cells;
+    int rc0;
+    if ((rc0 = need_device_bytes(f, need, "the fit"))) return rc0;
+  }
+  double *X = nullptr, *elev = nullptr, *w = nullptr, *mu = nullptr, *m2 = nullptr;
+  unsigned char* cls = nullptr;
+  int64_t* idx = nullptr;
+  int2* ops = nullptr;
+  DevTemps tmp(st, {(void**)&X, (void**)&elev, (void**)&w, (void**)&mu, (void**)&m2, (void**)&cls, (void**)&idx, (void**)&ops});
+  std::vector<int2> ops_h;
+  int depth = 0;
+  pcafit_pairwise_ops(0, (int)rows, 0, ops_h, depth);
+  if (depth > PCAFIT_STACK) return fail(f, GPRX_EINVAL, "too many samples for the pairwise column sums");
+  const int nops = (int)ops_h.size();
+  HIPCHK(f, hipMalloc((void**)&ops, sizeof(int2) * ops_h.size()));
+  HIPCHK(f, hipMemcpyAsync(ops, ops_h.data(), sizeof(int2) * ops_h.size(), hipMemcpyHostToDevice, st));
+  HIPCHK(f, hipMalloc((void**)&X, xb));
+  HIPCHK(f, hipMalloc((void**)&mu, sizeof(double) * cells));
+  HIPCHK(f, hipMalloc((void**)&cls, (size_t)cells));
+  if (f->mode != PCAFIT_VELOCITY) {
+    HIPCHK(f, hipMalloc((void**)&elev, sizeof(double) * cells));
+    HIPCHK(f, hipMemcpyAsync(elev, elevations, sizeof(double) * cells, hipMemcpyHostToDevice, st));
+  }
+  if (weights) {
+    HIPCHK(f, hipMalloc((void**)&w, sizeof(double) * cells));
+    HIPCHK(f, hipMemcpyAsync(w, weights, sizeof(double) * cells, hipMemcpyHostToDevice, st));
+  }
+  // 1. x goes up once; one pass gives the classes and the column means
+  HIPCHK(f, hipEventRecord(f->ev[0], st));
+  HIPCHK(f, hipMemcpyAsync(X, x, xb, hipMemcpyHostToDevice, st));
+  HIPCHK(f, hipEventRecord(f->ev[1], st));
+  hipLaunchKernelGGL(pcafit_colstats_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, (const double*)X, rows, cells,
+                     (const double*)elev, f->mode, thr, (const int2*)ops, nops, cls, mu);
+  HIPCHK(f, hipGetLastError());
+  HIPCHK(f, hipEventRecord(f->ev[2], st));
+  std::vector<double> mu_h((size_t)cells);
+  f->cls.resize((size_t)cells);
+  HIPCHK(f, hipMemcpyAsync(f->cls.data(), cls, (size_t)cells, hipMemcpyDeviceToHost, st));
+  HIPCHK(f, hipMemcpyAsync(mu_h.data(), mu, sizeof(double) * cells, hipMemcpyDeviceToHost, st));
+  HIPCHK(f, hipStreamSynchronize(st));
+  // wet cells (class != AD) in ascending order: x[:, ~dry_indices]
+  std::vector<int64_t> idx_h;
+  idx_h.reserve((size_t)cells);
+  for (int64_t c = 0; c < cells; ++c)
+    if (f->cls[c] != 1) idx_h.push_back(c);
+  f->n_wet = (int64_t)idx_h.size();
+  if (f->n_wet < rows)
+    return fail(f, GPRX_EINVAL, "the fit needs at least as many wet cells as samples: " + std::to_string((long long)f->n_wet) + " wet cells, " +
+                                     std::to_string((long long)rows) + " samples");
+  f->mean.resize((size_t)f->n_wet);
+  for (int64_t j = 0; j < f->n_wet; ++j) f->mean[j] = mu_h[idx_h[j]];
+  f->ldc = round_up(f->n_wet, 16);
+  const int64_t ldc = f->ldc;
+  // 2. compaction, centring, weighting, then IncrementalPCA's centring; xc2 has rows_p rows (zero beyond `rows`: the K padding
+  //    of the components GEMM)
+  HIPCHK(f, hipMalloc((void**)&idx, sizeof(int64_t) * f->n_wet));
+  HIPCHK(f, hipMalloc((void**)&m2, sizeof(double) * ldc));
+  HIPCHK(f, hipMalloc((void**)&f->xc1, sizeof(double) * rows * ldc));
+  HIPCHK(f, hipMalloc((void**)&f->xc2, sizeof(double) * f->rows_p * ldc));
+  HIPCHK(f, hipMemcpyAsync(idx, idx_h.data(), sizeof(int64_t) * f->n_wet, hipMemcpyHostToDevice, st));
+  if (f->rows_p > rows) HIPCHK(f, hipMemsetAsync(f->xc2 + rows * ldc, 0, sizeof(double) * (f->rows_p - rows) * ldc, st));
+  HIPCHK(f, hipEventRecord(f->ev[3], st));
+  hipLaunchKernelGGL(pcafit_compact_kernel, dim3((unsigned)((ldc + 255) / 256)), dim3(256), 0, st, (const double*)X, rows, cells,
+                     (const int64_t*)idx, f->n_wet, ldc, (const double*)elev, f->mode, (const double*)mu, (const double*)w,
+                     (const int2*)ops, nops, f->xc1, f->xc2, m2);
+  HIPCHK(f, hipGetLastError());
+  HIPCHK(f, hipEventRecord(f->ev[4], st));
+  // 3. G = Xc2 Xc2^T: lower-triangle tiles, split-K slabs summed in a fixed order
+  const int n = (int)rows;
+  const int64_t tiles = (rows + 63) / 64, ltiles = tiles * (tiles + 1) / 2;
+  const int kchunk = pcafit_kchunk(ltiles, ldc, rows * rows);
+  const int nsplit = (int)((ldc + kchunk - 1) / kchunk);
+  int rc;
+  if ((rc = ensure(f, f->ws, sizeof(double) * ((size_t)nsplit * rows * rows + (size_t)rows * rows)))) return rc;
+  double* G = f->ws.p + (size_t)nsplit * rows * rows;
+  GemmArgs p{f->xc2, f->xc2, f->ws.p, ldc, ldc, (int64_t)n, n, n, (int)ldc, 1.0, 0.0, GEMM_C_LOWER, 0, 0, 0, 0, 0, 0, kchunk, (int64_t)n * n};
+  HIPCHK(f, (launch_gemm_t<0, 1, 64, 64>(st, p, 1, nsplit)));
+  hipLaunchKernelGGL(pcafit_gram_reduce_kernel, dim3((unsigned)(((int64_t)n * n + 255) / 256)), dim3(256), 0, st, (const double*)f->ws.p, nsplit, n, G);
+  HIPCHK(f, hipGetLastError());
+  HIPCHK(f, hipEventRecord(f->ev[5], st));
+  f->gram.resize((size_t)rows * rows);
+  HIPCHK(f, hipMemcpyAsync(f->gram.data(), G, sizeof(double) * rows * rows, hipMemcpyDeviceToHost, st));
+  HIPCHK(f, hipStreamSynchronize(st));
+  f->ms[0] = elapsed_ms(f->ev[0], f->ev[1]);
+  f->ms[1] = elapsed_ms(f->ev[1], f->ev[2]);
+  f->ms[2] = elapsed_ms(f->ev[3], f->ev[4]);
+  f->ms[3] = elapsed_ms(f->ev[4], f->ev[5]);
+  return GPRX_OK;
+}
+
+int pcafit_components(gprx_pcafit_handle f, int k, const double* u, const double* lam, double* eofs, double* z) {
+  const int64_t rows = f->rows, rp = f->rows_p, ldc = f->ldc;
+  hipStream_t st = f->stream;
+  // A = diag(lambda^-1/2) U_k^T, K padded to rows_p with zeros
+  std::vector<double> a((size_t)k * rp, 0.0);
+  for (int i = 0; i < k; ++i) {
+    const double s = 1.0 / std::sqrt(lam[i]);
+    for (int64_t t = 0; t < rows; ++t) a[(size_t)i * rp + t] = u[(size_t)t * k + i] * s;
+  }
+  if (f->A) HIPCHK(f, hipFree(f->A));
+  if (f->E) HIPCHK(f, hipFree(f->E));
+  if (f->Z) HIPCHK(f, hipFree(f->Z));
+  f->A = f->E = f->Z = nullptr;
+  HIPCHK(f, hipMalloc((void**)&f->A, sizeof(double) * a.size()));
+  HIPCHK(f, hipMalloc((void**)&f->E, sizeof(double) * (size_t)k * ldc));
+  HIPCHK(f, hipMalloc((void**)&f->Z, sizeof(double) * (size_t)rows * k));
+  HIPCHK(f, hipMemcpyAsync(f->A, a.data(), sizeof(double) * a.size(), hipMemcpyHostToDevice, st));
+  const int tiles_m = (int)((rows + 63) / 64);
+  const int kchunk = pcafit_kchunk(tiles_m * ((k + 63) / 64), ldc, rows * k);
+  const int nsplit = (int)((ldc + kchunk - 1) / kchunk);
+  int rc;
+  if ((rc = ensure(f, f->ws, sizeof(double) * (size_t)nsplit * rows * k))) return rc;
+  // 5. E = A Xc2 (NN, K = rows_p), then svd_flip on its rows
+  HIPCHK(f, hipEventRecord(f->ev[5], st));
+  HIPCHK(f, launch_gemm(st, 0, 0, k, (int)ldc, (int)rp, 1.0, f->A, rp, f->xc2, ldc, 0.0, f->E, ldc, 0));
+  hipLaunchKernelGGL(pcafit_sign_flip_kernel, dim3((unsigned)k), dim3(256), 0, st, f->E, ldc, f->n_wet);
+  HIPCHK(f, hipGetLastError());
+  HIPCHK(f, hipEventRecord(f->ev[6], st));
+  // 6. Z = Xc1 E^T (split-K NT; the padding columns of both operands are zero)
+  HIPCHK(f, launch_gemm_splitk(st, 0, 1, (int)rows, k, (int)ldc, 1.0, f->xc1, ldc, f->E, ldc, 0.0, f->Z, k, f->ws.p, kchunk));
+  HIPCHK(f, hipEventRecord(f->ev[7], st));
+  HIPCHK(f, hipMemcpy2DAsync(eofs, sizeof(double) * f->n_wet, f->E, sizeof(double) * ldc, sizeof(double) * f->n_wet, (size_t)k,
+                             hipMemcpyDeviceToHost, st));
+  HIPCHK(f, hipMemcpyAsync(z, f->Z, sizeof(double) * rows * k, hipMemcpyDeviceToHost, st));
+  HIPCHK(f, hipStreamSynchronize(st));
+  f->ms[4] = elapsed_ms(f->ev[5], f->ev[6]);
+  f->ms[5] = elapsed_ms(f->ev[6], f->ev[7]);
+  return GPRX_OK;
+}
+}  // namespace
+
+int gprx_pcafit_destroy(gprx_pcafit_handle f) {
+  if (!f) return GPRX_OK;
+  release_handle(f->device, f->stream, {f->xc1, f->xc2, f->ws.p, f->A, f->E, f->Z}, f->ev, 8);
+  delete f;
+  return GPRX_OK;
+}
+
+int gprx_pcafit_create(int device, const double* x, int64_t n_samples, int64_t n_cells, const double* elevations, const double* weights,
+                       int mode, double wet_threshold, gprx_pcafit_handle* out) {
+  if (!out) return fail(nullptr, GPRX_EINVAL, "out is null");
+  *out = nullptr;
+  if (!x) return fail(nullptr, GPRX_EINVAL, "x is null");
+  if (mode < PCAFIT_WSE || mode > PCAFIT_VELOCITY) return fail(nullptr, GPRX_EINVAL, "mode must be 0 (wse), 1 (depth) or 2 (velocity)");
+  if (mode != PCAFIT_VELOCITY && !elevations) return fail(nullptr, GPRX_EINVAL, "wse and depth need the cell elevations");
+  if (n_samples < 2 || n_cells < n_samples || n_samples > 16384)
+    return fail(nullptr, GPRX_EINVAL, "need 2 <= n_samples <= min(n_cells, 16384)");
+  gprx_pcafit_handle f = nullptr;
+  try {
+    HIPCHK(nullptr, hipSetDevice(device));
+    f = new gprx_pcafit_ctx();
+    f->device = device;
+    f->mode = mode;
+    f->rows = n_samples;
+    f->rows_p = round_up(n_samples, 16);
+    f->cells = n_cells;
+    int rc = GPRX_OK;
+    hipError_t e = hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking);
+    for (hipEvent_t& ev : f->ev)
+      if (e == hipSuccess) e = hipEventCreate(&ev);
+    if (e != hipSuccess) rc = fail(nullptr, GPRX_EHIP, std::string("hipStreamCreate / hipEventCreate: ") + hipGetErrorString(e));
+    if (!rc) rc = pcafit_run(f, x, elevations, weights, wet_threshold);
+    if (rc) {
+      gprx_pcafit_destroy(f);
+      return rc;
+    }
+  } catch (const std::bad_alloc&) {
+    gprx_pcafit_destroy(f);
+    return fail(nullptr, GPRX_ENOMEM, "host allocation failed");
+  }
+  *out = f;
+  return GPRX_OK;
+}
+
+int gprx_pcafit_gram(gprx_pcafit_handle f, unsigned char* classes, double* input_mean, double* gram, int64_t* n_wet) {
+  if (!f) return fail(f, GPRX_EINVAL, "null handle");
+  if (!classes || !input_mean || !gram || !n_wet) return fail(f, GPRX_EINVAL, "null argument");
+  std::memcpy(classes, f->cls.data(), f->cls.size());
+  std::memcpy(input_mean, f->mean.data(), sizeof(double) * f->mean.size());
+  std::memcpy(gram, f->gram.data(), sizeof(double) * f->gram.size());
+  *n_wet = f->n_wet;
+  return GPRX_OK;
+}
+
+int gprx_pcafit_components(gprx_pcafit_handle f, int k, const double* u, const double* lam, double* eofs, double* z) {
+  if (!f) return fail(f, GPRX_EINVAL, "null handle");
+  if (k < 0 || k >= f->rows) return fail(f, GPRX_EINVAL, "need 0 <= k < n_samples (centring removes one direction)");
+  if (k == 0) return GPRX_OK;
+  if (!u || !lam || !eofs || !z) return fail(f, GPRX_EINVAL, "null argument");
+  for (int i = 0; i < k; ++i)
+    if (!(lam[i] > 0.0)) return fail(f, GPRX_EINVAL, "retained eigenvalues must be positive");
+  try {
+    HIPCHK(f, hipSetDevice(f->device));
+    return pcafit_components(f, k, u, lam, eofs, z);
+  } catch (const std::bad_alloc&) {
+    return fail(f, GPRX_ENOMEM, "host allocation failed");
+  }
+}
+
+int gprx_pcafit_timings(gprx_pcafit_handle f, double* ms) {
+  if (!f || !ms) return fail(f, GPRX_EINVAL, "null argument");
+  for (int i = 0; i < 6; ++i) ms[i] = f->ms[i];
+  return GPRX_OK;
+}
+
+const char* gprx_pcafit_last_error(gprx_pcafit_handle f) { return f ? f->err.c_str() : last_error().c_str(); }
+
+// ---- HmsPreProcessor (gpras/preprocess.py:1165-1320): the precip EOF fit, the features and the API ---------------------------
+struct gprx_hms_ctx {
+  int device = 0, route = -1;
+  hipStream_t stream = nullptr;
+  int64_t rows = 0, nfeat = 0, n_bc = 0, p = 0, ld2 = 0;
+  double *X = nullptr, *mu = nullptr, *X2 = nullptr;  // X: x column-major (rows, nfeat), ldx = rows
+  Buf ws;  // split-K slabs, then their sum
+  int64_t *bc = nullptr, *pc = nullptr;
+  std::vector<int64_t> bc_h, pc_h;
+  std::vector<double> mu_h;  // input_mean (nfeat)
+  hipEvent_t ev[8] = {};
+  double ms[7] = {0, 0, 0, 0, 0, 0, 0};  // upload, column pass, covariance / Gram, components, projection, API, statistics / standardise
+  std::string err;
+};
+
+namespace {
+// split-K plan of the lower-triangle product of n x n with K = kdim (as the Gram of pcafit_run)
+void hms_split(int64_t n, int64_t kdim, int& kchunk, int& nsplit) {
+  const int64_t tiles = (n + 63) / 64, ltiles = tiles * (tiles + 1) / 2;
+  kchunk = pcafit_kchunk(ltiles, kdim, n * n);
+  nsplit = (int)((kdim + kchunk - 1) / kchunk);
+}
+
+// x goes up once and is kept column-major: an F-order x is copied as it is, a C-order x in row chunks through a staging buffer
+int hms_upload(gprx_hms_handle h, const double* x, int64_t ld, int fortran) {
+  const int64_t rows = h->rows, nf = h->nfeat;
+  hipStream_t st = h->stream;
+  HIPCHK(h, hipEventRecord(h->ev[0], st));
+  if (fortran) {
+    HIPCHK(h, hipMemcpy2DAsync(h->X, sizeof(double) * rows, x, sizeof(double) * ld, sizeof(double) * rows, (size_t)nf, hipMemcpyHostToDevice, st));
+  } else {
+    const int64_t chunk = std::min<int64_t>(rows, std::max<int64_t>(32, ((int64_t)1 << 22) / nf));  // <= 32 MiB staged
+    double* S = nullptr;
+    HIPCHK(h, hipMalloc((void**)&S, sizeof(double) * (size_t)chunk * nf));
+    int rc = GPRX_OK;
+    for (int64_t t0 = 0; t0 < rows && !rc; t0 += chunk) {
+      const int64_t tc = std::min(chunk, rows - t0);
+      hipError_t e = hipMemcpy2DAsync(S, sizeof(double) * nf, x + t0 * ld, sizeof(double) * ld, sizeof(double) * nf, (size_t)tc, hipMemcpyHostToDevice, st);
+      if (e == hipSuccess) {
+        hipLaunchKernelGGL(hms_transpose_kernel, dim3((unsigned)((tc + 31) / 32), (unsigned)((nf + 31) / 32)), dim3(256), 0, st, (const double*)S, tc, nf,
+                           h->X + t0, rows);
+        e = hipGetLastError();
+      }
+      if (e != hipSuccess) rc = fail(h, GPRX_EHIP, std::string("upload of x: ") + hipGetErrorString(e));
+    }
+    hipStreamSynchronize(st);  // the staging buffer is no longer read
+    hipFree(S);
+    if (rc) return rc;
+  }
+  HIPCHK(h, hipEventRecord(h->ev[1], st));
+  return GPRX_OK;
+}
+
+// column pass and the covariance (route HMS_COV: C = X2^T X2, p x p) or Gram (HMS_GRAM: G = X2 X2^T, rows x rows) of the PCA input
+int hms_cov(gprx_hms_handle h, double* cov) {
+  const int64_t rows = h->rows, p = h->p;
+  hipStream_t st = h->stream;
+  const int route = rows >= p ? HMS_COV : HMS_GRAM;
+  const int64_t n = route == HMS_COV ? p : rows;
+  const int64_t ld2 = round_up(route == HMS_COV ? rows : p, 16), r2 = round_up(n, 16);
+  int kchunk = 0, nsplit = 0;
+  hms_split(n, ld2, kchunk, nsplit);
+  int rc;
+  if ((rc = need_device_bytes(h, 8.0 * ((double)r2 * ld2 + (double)(nsplit + 1) * n * n + p), "the covariance"))) return rc;
+  double* m2 = nullptr;
+  DevTemps tmp(st, {(void**)&m2});
+  HIPCHK(h, hipMalloc((void**)&m2, sizeof(double) * p));
+  HIPCHK(h, hipMalloc((void**)&h->X2, sizeof(double) * (size_t)r2 * ld2));
+  h->ld2 = ld2;
+  h->route = route;
+  HIPCHK(h, hipEventRecord(h->ev[2], st));
+  hipLaunchKernelGGL(hms_colmean_kernel, dim3((unsigned)h->nfeat), dim3(256), 0, st, (const double*)h->X, rows, rows, (const int64_t*)nullptr,
+                     (const double*)nullptr, h->mu);
+  hipLaunchKernelGGL(hms_colmean_kernel, dim3((unsigned)p), dim3(256), 0, st, (const double*)h->X, rows, rows, (const int64_t*)h->pc,
+                     (const double*)h->mu, m2);
+  if (r2 > n) HIPCHK(h, hipMemsetAsync(h->X2 + n * ld2, 0, sizeof(double) * (size_t)(r2 - n) * ld2, st));
+  hipLaunchKernelGGL(hms_centre2_kernel, dim3((unsigned)((ld2 + 255) / 256), (unsigned)(route == HMS_COV ? p : rows)), dim3(256), 0, st,
+                     (const double*)h->X, rows, rows, (const int64_t*)h->pc, p, (const double*)h->mu, (const double*)m2, route, h->X2, ld2);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipEventRecord(h->ev[3], st));
+  if ((rc = ensure(h, h->ws, sizeof(double) * ((size_t)nsplit * n * n + (size_t)n * n)))) return rc;
+  double* C = h->ws.p + (size_t)nsplit * n * n;
+  GemmArgs g{h->X2, h->X2, h->ws.p, ld2, ld2, n, (int)n, (int)n, (int)ld2, 1.0, 0.0, GEMM_C_LOWER, 0, 0, 0, 0, 0, 0, kchunk, n * n};
+  HIPCHK(h, (launch_gemm_t<0, 1, 64, 64>(st, g, 1, nsplit)));
+  hipLaunchKernelGGL(pcafit_gram_reduce_kernel, dim3((unsigned)((n * n + 255) / 256)), dim3(256), 0, st, (const double*)h->ws.p, nsplit, (int)n, C);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipEventRecord(h->ev[4], st));
+  h->mu_h.resize((size_t)h->nfeat);
+  HIPCHK(h, hipMemcpyAsync(h->mu_h.data(), h->mu, sizeof(double) * h->nfeat, hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipMemcpyAsync(cov, C, sizeof(double) * n * n, hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipStreamSynchronize(st));
+  h->ms[1] = elapsed_ms(h->ev[2], h->ev[3]);
+  h->ms[2] = elapsed_ms(h->ev[3], h->ev[4]);
+  return GPRX_OK;
+}
+
+// Gram route: E = diag(lambda^-1/2) U_k^T X2 (GEMM, K = rows padded to 16), svd_flip on its rows (pcafit_sign_flip_kernel)
+int hms_components(gprx_hms_handle h, int k, const double* u, const double* lam, double* eofs) {
+  const int64_t rows = h->rows, rp = round_up(rows, 16), ld2 = h->ld2;
+  hipStream_t st = h->stream;
+  std::vector<double> a((size_t)k * rp, 0.0);
+  for (int i = 0; i < k; ++i) {
+    const double s = 1.0 / std::sqrt(lam[i]);
+    for (int64_t t = 0; t < rows; ++t) a[(size_t)i * rp + t] = u[(size_t)t * k + i] * s;
+  }
+  int rc;
+  if ((rc = need_device_bytes(h, 8.0 * ((double)a.size() + (double)k * ld2), "the components"))) return rc;
+  double *A = nullptr, *E = nullptr;
+  DevTemps tmp(st, {(void**)&A, (void**)&E});
+  HIPCHK(h, hipMalloc((void**)&A, sizeof(double) * a.size()));
+  HIPCHK(h, hipMalloc((void**)&E, sizeof(double) * (size_t)k * ld2));
+  HIPCHK(h, hipMemcpyAsync(A, a.data(), sizeof(double) * a.size(), hipMemcpyHostToDevice, st));
+  HIPCHK(h, hipEventRecord(h->ev[4], st));
+  HIPCHK(h, launch_gemm(st, 0, 0, k, (int)ld2, (int)rp, 1.0, A, rp, h->X2, ld2, 0.0, E, ld2, 0));
+  hipLaunchKernelGGL(pcafit_sign_flip_kernel, dim3((unsigned)k), dim3(256), 0, st, E, ld2, h->p);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipEventRecord(h->ev[5], st));
+  HIPCHK(h, hipMemcpy2DAsync(eofs, sizeof(double) * h->p, E, sizeof(double) * ld2, sizeof(double) * h->p, (size_t)k, hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipStreamSynchronize(st));
+  h->ms[3] = elapsed_ms(h->ev[4], h->ev[5]);
+  return GPRX_OK;
+}
+
+// API on device vectors: lags = how many lags are summed (>= n_w: the weights beyond n_w are zeros)
+hipError_t hms_api_launch(hipStream_t st, const double* a, int64_t n, const double* w, int64_t n_w, int64_t lags, double* out) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(hms_api_kernel, dim3((unsigned)((n + HMS_API_BT - 1) / HMS_API_BT)), dim3(HMS_API_NT), 0, st, a, n, w, n_w, lags, out);
+  return hipGetLastError();
+}
+
+// features [x_bc, x_precip eofs^T, avg_precip, api_1, api_2] (:1251-1257, :1271-1277); fit: x_mean / x_std out; transform: out
+int hms_features(gprx_hms_handle h, int ke, const double* eofs, const double* w1, int64_t n1, const double* w2, int64_t n2, double* x_mean,
+                 double* x_std, int fit, double* out) {
+  const int64_t rows = h->rows, p = h->p, n_bc = h->n_bc, nf = n_bc + ke + 3;
+  hipStream_t st = h->stream;
+  const int nmb = std::max(1, (ke + HMS_MB - 1) / HMS_MB);
+  const int64_t ke_pad = (int64_t)nmb * HMS_MB;
+  std::vector<double> et((size_t)p * ke_pad, 0.0), mup((size_t)p), mub((size_t)std::max<int64_t>(n_bc, 1), 0.0);
+  for (int i = 0; i < ke; ++i)
+    for (int64_t j = 0; j < p; ++j) et[(size_t)j * ke_pad + i] = eofs[(size_t)i * p + j];
+  for (int64_t j = 0; j < p; ++j) mup[j] = h->mu_h[h->pc_h[j]];
+  for (int64_t b = 0; b < n_bc; ++b) mub[b] = h->mu_h[h->bc_h[b]];
+  int rc;
+  if ((rc = need_device_bytes(h, 8.0 * ((double)et.size() + p + n_bc + n1 + n2 + 2.0 * nf + (double)nf * rows * (fit ? 1 : 2)) + 64, "the features")))
+    return rc;
+  double *Et = nullptr, *Mp = nullptr, *Mb = nullptr, *W1 = nullptr, *W2 = nullptr, *F = nullptr, *S = nullptr, *O = nullptr;
+  int* flag = nullptr;
+  DevTemps tmp(st, {(void**)&Et, (void**)&Mp, (void**)&Mb, (void**)&W1, (void**)&W2, (void**)&F, (void**)&S, (void**)&O, (void**)&flag});
+  HIPCHK(h, hipMalloc((void**)&Et, sizeof(double) * et.size()));
+  HIPCHK(h, hipMalloc((void**)&Mp, sizeof(double) * p));
+  HIPCHK(h, hipMalloc((void**)&Mb, sizeof(double) * mub.size()));
+  HIPCHK(h, hipMalloc((void**)&W1, sizeof(double) * std::max<int64_t>(n1, 1)));
+  HIPCHK(h, hipMalloc((void**)&W2, sizeof(double) * std::max<int64_t>(n2, 1)));
+  HIPCHK(h, hipMalloc((void**)&F, sizeof(double) * (size_t)nf * rows));
+  HIPCHK(h, hipMalloc((void**)&S, sizeof(double) * 2 * nf));
+  HIPCHK(h, hipMalloc((void**)&flag, sizeof(int)));
+  HIPCHK(h, hipMemcpyAsync(Et, et.data(), sizeof(double) * et.size(), hipMemcpyHostToDevice, st));
+  HIPCHK(h, hipMemcpyAsync(Mp, mup.data(), sizeof(double) * p, hipMemcpyHostToDevice, st));
+  HIPCHK(h, hipMemcpyAsync(Mb, mub.data(), sizeof(double) * mub.size(), hipMemcpyHostToDevice, st));
+  if (n1) HIPCHK(h, hipMemcpyAsync(W1, w1, sizeof(double) * n1, hipMemcpyHostToDevice, st));
+  if (n2) HIPCHK(h, hipMemcpyAsync(W2, w2, sizeof(double) * n2, hipMemcpyHostToDevice, st));
+  HIPCHK(h, hipMemsetAsync(flag, 0, sizeof(int), st));
+  HIPCHK(h, hipEventRecord(h->ev[5], st));
+  hipLaunchKernelGGL(hms_project_kernel, dim3((unsigned)((rows + 255) / 256), (unsigned)nmb), dim3(256), 0, st, (const double*)h->X, rows, rows,
+                     (const int64_t*)h->pc, (const double*)Mp, p, (const double*)Et, ke_pad, ke, (const int64_t*)h->bc, (const double*)Mb, n_bc, F,
+                     rows, flag);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipEventRecord(h->ev[6], st));
+  int nonfinite = 0;
+  HIPCHK(h, hipMemcpyAsync(&nonfinite, flag, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipStreamSynchronize(st));
+  // the exactly-zero tail of the weights is cut only when avg_precip is finite (0 * inf or 0 * NaN would be NaN)
+  const double* a = F + (n_bc + ke) * rows;
+  HIPCHK(h, hms_api_launch(st, a, rows, W1, n1, nonfinite ? rows : std::min(n1, rows), F + (n_bc + ke + 1) * rows));
+  HIPCHK(h, hms_api_launch(st, a, rows, W2, n2, nonfinite ? rows : std::min(n2, rows), F + (n_bc + ke + 2) * rows));
+  HIPCHK(h, hipEventRecord(h->ev[7], st));
+  if (fit) {
+    hipLaunchKernelGGL(hms_colstats_kernel, dim3((unsigned)nf), dim3(256), 0, st, (const double*)F, rows, rows, S, S + nf);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->ev[0], st));
+    HIPCHK(h, hipMemcpyAsync(x_mean, S, sizeof(double) * nf, hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(x_std, S + nf, sizeof(double) * nf, hipMemcpyDeviceToHost, st));
+  } else {
+    HIPCHK(h, hipMalloc((void**)&O, sizeof(double) * (size_t)nf * rows));
+    HIPCHK(h, hipMemcpyAsync(S, x_mean, sizeof(double) * nf, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(S + nf, x_std, sizeof(double) * nf, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(hms_standardise_kernel, dim3((unsigned)((nf * rows + 255) / 256)), dim3(256), 0, st, (const double*)F, rows, rows, nf,
+                       (const double*)S, (const double*)(S + nf), O);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->ev[0], st));
+    HIPCHK(h, hipMemcpyAsync(out, O, sizeof(double) * nf * rows, hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(h, hipStreamSynchronize(st));
+  h->ms[4] = elapsed_ms(h->ev[5], h->ev[6]);
+  h->ms[5] = elapsed_ms(h->ev[6], h->ev[7]);
+  h->ms[6] = elapsed_ms(h->ev[7], h->ev[0]);
+  return GPRX_OK;
+}
+}  // namespace
+
+int gprx_hms_destroy(gprx_hms_handle h) {
+  if (!h) return GPRX_OK;
+  release_handle(h->device, h->stream, {h->X, h->mu, h->X2, h->ws.p, h->bc, h->pc}, h->ev, 8);
+  delete h;
+  return GPRX_OK;
+}
+
+int gprx_hms_create(int device, const double* x, int64_t rows, int64_t ld, int64_t n_features, int fortran, const int64_t* bc_idx, int64_t n_bc,
+                    const int64_t* precip_idx, int64_t n_precip, const double* input_mean, gprx_hms_handle* out) {
+  if (!out) return fail(nullptr, GPRX_EINVAL, "out is null");
+  *out = nullptr;
+  if (!x || !precip_idx || (n_bc > 0 && !bc_idx)) return fail(nullptr, GPRX_EINVAL, "null argument");
+  if (rows < 1 || n_features < 1 || n_bc < 0 || n_precip < 1) return fail(nullptr, GPRX_EINVAL, "need rows >= 1 and at least one precip column");
+  if (ld < (fortran ? rows : n_features)) return fail(nullptr, GPRX_EINVAL, "ld is smaller than the contiguous dimension of x");
+  if (rows > ((int64_t)1 << 31) - 1024 || n_features > 65535 * 32) return fail(nullptr, GPRX_EINVAL, "x is too large");
+  for (int64_t j = 0; j < n_precip; ++j)
+    if (precip_idx[j] < 0 || precip_idx[j] >= n_features) return fail(nullptr, GPRX_EINVAL, "precip column out of range");
+  for (int64_t j = 0; j < n_bc; ++j)
+    if (bc_idx[j] < 0 || bc_idx[j] >= n_features) return fail(nullptr, GPRX_EINVAL, "bc column out of range");
+  if (std::min(rows, n_precip) > 16384) return fail(nullptr, GPRX_EINVAL, "min(rows, precip columns) must be <= 16384 (host eigh)");
+  gprx_hms_handle h = nullptr;
+  try {
+    HIPCHK(nullptr, hipSetDevice(device));
+    h = new gprx_hms_ctx();
+    h->device = device;
+    h->rows = rows;
+    h->nfeat = n_features;
+    h->n_bc = n_bc;
+    h->p = n_precip;
+    h->bc_h.assign(bc_idx, bc_idx + n_bc);
+    h->pc_h.assign(precip_idx, precip_idx + n_precip);
+    int rc = GPRX_OK;
+    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+    for (hipEvent_t& ev : h->ev)
+      if (e == hipSuccess) e = hipEventCreate(&ev);
+    if (e != hipSuccess) rc = fail(nullptr, GPRX_EHIP, std::string("hipStreamCreate / hipEventCreate: ") + hipGetErrorString(e));
+    const double staged = fortran ? 0.0 : (double)std::min<int64_t>(rows, std::max<int64_t>(32, ((int64_t)1 << 22) / n_features)) * n_features;
+    if (!rc) rc = need_device_bytes(h, 8.0 * ((double)rows * n_features + staged + n_features + n_bc + n_precip), "x");
+    auto setup = [&]() -> int {
+      HIPCHK(h, hipMalloc((void**)&h->X, sizeof(double) * (size_t)rows * n_features));
+      HIPCHK(h, hipMalloc((void**)&h->mu, sizeof(double) * n_features));
+      HIPCHK(h, hipMalloc((void**)&h->pc, sizeof(int64_t) * n_precip));
+      HIPCHK(h, hipMalloc((void**)&h->bc, sizeof(int64_t) * std::max<int64_t>(n_bc, 1)));
+      HIPCHK(h, hipMemcpyAsync(h->pc, precip_idx, sizeof(int64_t) * n_precip, hipMemcpyHostToDevice, h->stream));
+      if (n_bc) HIPCHK(h, hipMemcpyAsync(h->bc, bc_idx, sizeof(int64_t) * n_bc, hipMemcpyHostToDevice, h->stream));
+      if (input_mean) {
+        h->mu_h.assign(input_mean, input_mean + n_features);
+        HIPCHK(h, hipMemcpyAsync(h->mu, input_mean, sizeof(double) * n_features, hipMemcpyHostToDevice, h->stream));
+      }
+      int rc2 = hms_upload(h, x, ld, fortran);
+      if (rc2) return rc2;
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+      h->ms[0] = elapsed_ms(h->ev[0], h->ev[1]);
+      return GPRX_OK;
+    };
+    if (!rc) rc = setup();
+    if (rc) {
+      gprx_hms_destroy(h);
+      return rc;
+    }
+  } catch (const std::bad_alloc&) {
+    gprx_hms_destroy(h);
+    return fail(nullptr, GPRX_ENOMEM, "host allocation failed");
+  }
+  *out = h;
+  return GPRX_OK;
+}
+
+int gprx_hms_cov(gprx_hms_handle h, double* input_mean, double* cov, int* route) {
+  if (!h) return fail(h, GPRX_EINVAL, "null handle");
+  if (!input_mean || !cov || !route) return fail(h, GPRX_EINVAL, "null argument");
+  if (h->route >= 0 || !h->mu_h.empty()) return fail(h, GPRX_ESTATE, "the covariance is computed once, by a handle created without input_mean");
+  if (h->rows < 2) return fail(h, GPRX_EINVAL, "the fit needs rows >= 2");
+  try {
+    HIPCHK(h, hipSetDevice(h->device));
+    const int rc = hms_cov(h, cov);
+    if (rc) return rc;
+  } catch (const std::bad_alloc&) {
+    return fail(h, GPRX_ENOMEM, "host allocation failed");
+  }
+  std::memcpy(input_mean, h->mu_h.data(), sizeof(double) * h->nfeat);
+  *route = h->route;
+  return GPRX_OK;
+}
+
+int gprx_hms_components(gprx_hms_handle h, int k, const double* u, const double* lam, double* eofs) {
+  if (!h) return fail(h, GPRX_EINVAL, "null handle");
+  if (h->route != HMS_GRAM) return fail(h, GPRX_ESTATE, "components are formed on the device only on the Gram route (rows < precip columns)");
+  if (k < 0 || k >= h->rows) return fail(h, GPRX_EINVAL, "need 0 <= k < rows (centring removes one direction)");
+  if (k == 0) return GPRX_OK;
+  if (!u || !lam || !eofs) return fail(h, GPRX_EINVAL, "null argument");
+  for (int i = 0; i < k; ++i)
+    if (!(lam[i] > 0.0)) return fail(h, GPRX_EINVAL, "retained eigenvalues must be positive");
+  try {
+    HIPCHK(h, hipSetDevice(h->device));
+    return hms_components(h, k, u, lam, eofs);
+  } catch (const std::bad_alloc&) {
+    return fail(h, GPRX_ENOMEM, "host allocation failed");
+  }
+}
+
+int gprx_hms_features(gprx_hms_handle h, int k, const double* eofs, const double* w1, int64_t n1, const double* w2, int64_t n2, double* x_mean,
+                      double* x_std, int fit, double* out) {
+  if (!h) return fail(h, GPRX_EINVAL, "null handle");
+  if (k < 0 || n1 < 0 || n2 < 0 || (k > 0 && !eofs) || (n1 > 0 && !w1) || (n2 > 0 && !w2) || !x_mean || !x_std || (!fit && !out))
+    return fail(h, GPRX_EINVAL, "null or negative argument");
+  if (h->mu_h.empty()) return fail(h, GPRX_ESTATE, "input_mean is not known: run gprx_hms_cov first or pass it to gprx_hms_create");
+  try {
+    HIPCHK(h, hipSetDevice(h->device));
+    return hms_features(h, k, eofs, w1, n1, w2, n2, x_mean, x_std, fit, out);
+  } catch (const std::bad_alloc&) {
+    return fail(h, GPRX_ENOMEM, "host allocation failed");
+  }
+}
+
+int gprx_hms_timings(gprx_hms_handle h, double* ms) {
+  if (!h || !ms) return fail(h, GPRX_EINVAL, "null argument");
+  for (int i = 0; i < 7; ++i) ms[i] = h->ms[i];
+  return GPRX_OK;
+}
+
+int gprx_api(int device, const double* a, int64_t n, const double* w, int64_t n_w, int64_t window, double* out) {
+  if (n < 1 || window < 1) return fail(nullptr, GPRX_EINVAL, "the series and the window must not be empty");
+  if (n_w < 0 || n_w > window || !a || !out || (n_w > 0 && !w)) return fail(nullptr, GPRX_EINVAL, "need 0 <= n_w <= window and non-null arrays");
+  for (int64_t i = 0; i < n_w; ++i)
+    if (!std::isfinite(w[i])) return fail(nullptr, GPRX_EINVAL, "the weights must be finite");
+  bool finite = true;
+  for (int64_t t = 0; t < n && finite; ++t) finite = std::isfinite(a[t]);
+  const int64_t lags = std::min(finite ? n_w : window, n);
+  HIPCHK(nullptr, hipSetDevice(device));
+  const int rc0 = need_device_bytes(nullptr, 8.0 * (2.0 * n + std::max<int64_t>(n_w, 1)), "the API");
+  if (rc0) return rc0;
+  hipStream_t st = util_stream();
+  double *A = nullptr, *W = nullptr, *O = nullptr;
+  DevTemps tmp(st, {(void**)&A, (void**)&W, (void**)&O});
+  HIPCHK(nullptr, hipMalloc((void**)&A, sizeof(double) * n));
+  HIPCHK(nullptr, hipMalloc((void**)&O, sizeof(double) * n));
+  HIPCHK(nullptr, hipMalloc((void**)&W, sizeof(double) * std::max<int64_t>(n_w, 1)));
+  HIPCHK(nullptr, hipMemcpyAsync(A, a, sizeof(double) * n, hipMemcpyHostToDevice, st));
+  if (n_w) HIPCHK(nullptr, hipMemcpyAsync(W, w, sizeof(double) * n_w, hipMemcpyHostToDevice, st));
+  HIPCHK(nullptr, hms_api_launch(st, A, n, W, n_w, lags, O));
+  HIPCHK(nullptr, hipMemcpyAsync(out, O, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+  HIPCHK(nullptr, hipStreamSynchronize(st));
+  return GPRX_OK;
+}
+
+const char* gprx_hms_last_error(gprx_hms_handle h) { return h ? h->err.c_str() : last_error().c_str(); }
+
+}  // extern "C"

@@ -666,7 +666,8 @@ inline hipError_t launch_gemm_t(hipStream_t st, GemmArgs p, int batch, int nspli
 constexpr int S64_LD = 64;  // LDS row stride (doubles), unpadded: 16-B chunk c of row `row` sits at chunk c ^ (row & 15) -- conflict-free
                             // for the four 16-lane groups of ds_read_b128 (the padded stride 66 cost two cycles per group)
 
-__global__ __launch_bounds__(256) void syrk_k64_kernel(const double* __restrict__ A, const double* __restrict__ B, double* __restrict__ C,
+// (static, like splitk_reduce_kernel: more than one translation unit of the library includes this header)
+static __global__ __launch_bounds__(256) void syrk_k64_kernel(const double* __restrict__ A, const double* __restrict__ B, double* __restrict__ C,
                                                        int64_t lda, int64_t ldc, int M, int N, int tiles_n, int64_t cs) {
   __shared__ __attribute__((aligned(16))) double sA[64 * S64_LD];
   __shared__ __attribute__((aligned(16))) double sB[64 * S64_LD];
@@ -834,7 +835,7 @@ inline hipError_t launch_gemm(hipStream_t st, int ta, int tb, int M, int N, int 
 
 // ---- split-K for skinny products (few output tiles, long K) -------------------------------------------
 // out[i][j] = beta * out[i][j] + sum_z slab_z[i][j]   (fixed summation order: deterministic)
-__global__ __launch_bounds__(256) void splitk_reduce_kernel(const double* __restrict__ ws, int nsplit, int M, int N, double beta,
+static __global__ __launch_bounds__(256) void splitk_reduce_kernel(const double* __restrict__ ws, int nsplit, int M, int N, double beta,
                                                             double* __restrict__ C, int64_t ldc, int64_t ws_cell = 0, int64_t c_cell = 0) {
   ws += (int64_t)blockIdx.y * ws_cell;  // blockIdx.y = cell
   C += (int64_t)blockIdx.y * c_cell;

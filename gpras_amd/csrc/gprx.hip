@@ -1,9 +1,7 @@
 // libgprx: C ABI (include/gprx.h) over the gfx950 kernels in this directory.
 // Host orchestration only: parameter transforms and priors (scalar math), buffer ownership,
 // launch sequences.  No CPU fallback exists for any device stage.
-#include "../../include/gprx.h"
-
-#include <hip/hip_runtime.h>
+#include "abi_common.h"
 
 #include <algorithm>
 #include <chrono>
@@ -18,20 +16,13 @@
 #include <thread>
 #include <vector>
 
-#include "comm.h"
 #include "gemm_f64.h"
 #include "gprx_common.h"
 #include "grad.h"
-#include "hms.h"
 #include "kmat.h"
-#include "kmeans.h"
-#include "metrics.h"
-#include "pca.h"
-#include "pca_fit.h"
 #include "potrf.h"
 #include "potrf_cell.h"
 #include "potrf_dag.h"
-#include "pseudo.h"
 #include "sgpr.h"
 #include "sgpr_asm.h"
 #include "sgpr_fused.h"
@@ -39,17 +30,29 @@
 
 using namespace gprx;
 
-namespace {
+namespace gprx {
 
-thread_local std::string g_err;
+std::string& last_error() {
+  thread_local std::string msg;
+  return msg;
+}
 
-struct Buf {
-  double* p = nullptr;
-  size_t bytes = 0;
-  bool borrowed = false;  // view into the batch arena (gprx_select_slot): never freed through this Buf
-};
+// (see abi_common.h: the one utility stream per device of the whole library)
+hipStream_t util_stream() {
+  static std::mutex m;
+  static std::map<int, hipStream_t> streams;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+  std::lock_guard<std::mutex> lock(m);
+  auto it = streams.find(dev);
+  if (it != streams.end()) return it->second;
+  hipStream_t st = nullptr;
+  if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) return nullptr;
+  streams.emplace(dev, st);
+  return st;
+}
 
-}  // namespace
+}  // namespace gprx
 
 struct Theta {
   double variance, noise;
@@ -132,25 +135,6 @@ struct gprx_ctx {
   hipEvent_t stagger_evt = nullptr;
 };
 
-struct gprx_comm_ctx {
-  int device = 0, rank = 0, world = 1;
-  ncclComm_t comm = nullptr;
-  hipStream_t stream = nullptr;
-  double* scratch = nullptr;  // device staging of the host-buffer entry points
-  size_t scratch_bytes = 0;
-  std::string err;
-};
-
-struct gprx_pca_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  int64_t cells = 0, cells_p = 0;  // cells_p: leading dimension of the device copies (multiple of 16, zero padded)
-  int k = 0, depth = 0;
-  Buf mu, wfwd, wrev, elev, E, base, xm, xs;  // per-cell parameters expanded to all cells; E: (k, cells_p)
-  Buf dX, dZ, ws, dMean, dVar, dFull, dVfull;
-  std::string err;
-};
-
 namespace {
 
 // kernel-matrix and trace launches evaluate r2 in the handle's distance form (gprx_set_distance_form)
@@ -160,65 +144,9 @@ Args with_form(Args a, gprx_handle h) {
   return a;
 }
 
-int fail(gprx_handle h, int code, const std::string& msg) {
-  if (h) h->err = msg;
-  g_err = msg;
-  return code;
-}
-
-#define HIPCHK(h, expr)                                                                            \
-  do {                                                                                             \
-    hipError_t e_ = (expr);                                                                        \
-    if (e_ != hipSuccess) {                                                                        \
-      return fail(h, e_ == hipErrorOutOfMemory ? GPRX_ENOMEM : GPRX_EHIP,                          \
-                  std::string(#expr) + ": " + hipGetErrorString(e_));                              \
-    }                                                                                              \
-  } while (0)
-
 int& predict_path_tuning() {
   static int v = 0;  // 0: choose, 1: always through L^-1, 2: always forward substitution
   return v;
-}
-
-// The legacy (NULL) stream is never used.  A legacy-stream call (hipMemcpy, hipMemset, a launch on stream 0, hipDeviceSynchronize)
-// from one host thread is refused while ANOTHER thread captures a graph ("operation would make the legacy stream depend on a
-// capturing blocking stream") and invalidates that capture -- in every capture mode of this runtime.  Synchronous copies and
-// the handle-less entry points go through one non-blocking utility stream per device instead.
-hipStream_t util_stream() {
-  static std::mutex m;
-  static std::map<int, hipStream_t> streams;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-  std::lock_guard<std::mutex> lock(m);
-  auto it = streams.find(dev);
-  if (it != streams.end()) return it->second;
-  hipStream_t st = nullptr;
-  if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) return nullptr;
-  streams.emplace(dev, st);
-  return st;
-}
-hipError_t copy_sync(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
-  hipStream_t st = util_stream();
-  if (!st) return hipErrorInvalidValue;
-  hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, st);
-  return e != hipSuccess ? e : hipStreamSynchronize(st);
-}
-hipError_t memset_sync(void* dst, int value, size_t bytes) {
-  hipStream_t st = util_stream();
-  if (!st) return hipErrorInvalidValue;
-  hipError_t e = hipMemsetAsync(dst, value, bytes, st);
-  return e != hipSuccess ? e : hipStreamSynchronize(st);
-}
-
-int ensure(gprx_handle h, Buf& b, size_t bytes) {
-  if (b.bytes >= bytes) return GPRX_OK;
-  if (b.p && !b.borrowed) HIPCHK(h, hipFree(b.p));
-  b.p = nullptr;
-  b.bytes = 0;
-  b.borrowed = false;
-  HIPCHK(h, hipMalloc((void**)&b.p, bytes));
-  b.bytes = bytes;
-  return GPRX_OK;
 }
 
 int ensure_zeroed(gprx_handle h, Buf& b, size_t bytes) {
@@ -1824,7 +1752,7 @@ extern "C" {
 
 int gprx_version(void) { return GPRX_VERSION; }
 
-const char* gprx_last_error(gprx_handle h) { return h ? h->err.c_str() : g_err.c_str(); }
+const char* gprx_last_error(gprx_handle h) { return h ? h->err.c_str() : last_error().c_str(); }
 
 int gprx_device_count(int* count) {
   if (!count) return fail(nullptr, GPRX_EINVAL, "count is null");
@@ -2626,9 +2554,8 @@ int gprx_predict_batch_t(gprx_handle h, int count, const int* units, const doubl
                                  include_noise)))
       return rc;
     if (ns > 0) {
-      const unsigned grid = (unsigned)std::min<int64_t>(((int64_t)cnt * ns + 255) / 256, 4096);
-      hipLaunchKernelGGL(transpose_small_kernel, dim3(grid), dim3(256), 0, h->stream, (const double*)dmean, (int64_t)cnt, ns, tmean);
-      hipLaunchKernelGGL(transpose_small_kernel, dim3(grid), dim3(256), 0, h->stream, (const double*)dvar, (int64_t)cnt, ns, tvar);
+      launch_transpose_small(h->stream, dmean, cnt, ns, tmean);
+      launch_transpose_small(h->stream, dvar, cnt, ns, tvar);
       HIPCHK(h, hipGetLastError());
       if (cnt == count) {
         HIPCHK(h, hipMemcpyAsync(means_t, tmean, sizeof(double) * ns * cnt, hipMemcpyDeviceToHost, h->stream));
@@ -2642,1545 +2569,6 @@ int gprx_predict_batch_t(gprx_handle h, int count, const int* units, const doubl
     }
     HIPCHK(h, wait_stream(h, h->stream));
   }
-  return GPRX_OK;
-}
-
-// ---- EOF projection either side of the GP path ------------------------------
-namespace {
-int pfail(gprx_pca_handle p, int code, const std::string& msg) {
-  if (p) p->err = msg;
-  g_err = msg;
-  return code;
-}
-#define PCACHK(p, expr)                                                                                              \
-  do {                                                                                                               \
-    hipError_t e_ = (expr);                                                                                          \
-    if (e_ != hipSuccess)                                                                                            \
-      return pfail(p, e_ == hipErrorOutOfMemory ? GPRX_ENOMEM : GPRX_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-int pensure(gprx_pca_handle p, Buf& b, size_t bytes) {
-  if (b.bytes >= bytes) return GPRX_OK;
-  if (b.p) PCACHK(p, hipFree(b.p));
-  b.p = nullptr;
-  b.bytes = 0;
-  PCACHK(p, hipMalloc((void**)&b.p, bytes));
-  b.bytes = bytes;
-  return GPRX_OK;
-}
-int pupload(gprx_pca_handle p, Buf& b, const std::vector<double>& v) {
-  int rc = pensure(p, b, sizeof(double) * v.size());
-  if (rc) return rc;
-  PCACHK(p, copy_sync(b.p, v.data(), sizeof(double) * v.size(), hipMemcpyHostToDevice));
-  return GPRX_OK;
-}
-// device staging per pass of the host-buffer entry points: 1 GiB of x / output (GPRX_PCA_CHUNK_DOUBLES overrides, for tests)
-int64_t pca_chunk_doubles() {
-  static const int64_t v = getenv("GPRX_PCA_CHUNK_DOUBLES") ? atoll(getenv("GPRX_PCA_CHUNK_DOUBLES")) : ((int64_t)1 << 27);
-  return v;
-}
-}  // namespace
-
-int gprx_pca_create(int device, int64_t n_cells, int k, const unsigned char* dry, const double* elevations, const double* input_mean,
-                    const double* weights, const double* eofs, const double* x_mean, const double* x_std, int depth_mode,
-                    gprx_pca_handle* out) {
-  if (!out) return pfail(nullptr, GPRX_EINVAL, "out is null");
-  *out = nullptr;
-  if (n_cells <= 0 || k <= 0 || k > 64) return pfail(nullptr, GPRX_EINVAL, "n_cells must be positive and 1 <= k <= 64");
-  if (!input_mean || !eofs || !x_mean || !x_std) return pfail(nullptr, GPRX_EINVAL, "input_mean, eofs, x_mean, x_std must be non-null");
-  int64_t n_dry = 0;
-  if (dry)
-    for (int64_t c = 0; c < n_cells; ++c) n_dry += dry[c] != 0;
-  if (depth_mode && !elevations) return pfail(nullptr, GPRX_EINVAL, "depth mode needs the cell elevations");
-  if (!depth_mode && n_dry > 0 && !elevations) return pfail(nullptr, GPRX_EINVAL, "always-dry cells are filled with their elevations: elevations is null");
-  PCACHK(nullptr, hipSetDevice(device));
-  gprx_pca_handle p = new gprx_pca_ctx();
-  p->device = device;
-  p->cells = n_cells;
-  p->cells_p = round_up(n_cells, 16);
-  p->k = k;
-  p->depth = depth_mode ? 1 : 0;
-  const int64_t n_wet = n_cells - n_dry, cp = p->cells_p;
-  // expand the wet-cell parameters to the full cell axis: dry cells get weight 0 (forward) / 1 (reverse), E = 0 and the fill value
-  std::vector<double> mu(cp, 0.0), wf(cp, 0.0), wr(cp, 1.0), el(cp, 0.0), base(cp, 0.0), E((size_t)k * cp, 0.0);
-  int64_t j = 0;
-  for (int64_t c = 0; c < n_cells; ++c) {
-    if (elevations) el[c] = elevations[c];
-    if (dry && dry[c]) {
-      base[c] = depth_mode ? 0.0 : elevations[c];
-      continue;
-    }
-    mu[c] = input_mean[j];
-    wf[c] = weights ? weights[j] : 1.0;
-    wr[c] = wf[c];
-    base[c] = input_mean[j];
-    for (int kk = 0; kk < k; ++kk) E[(size_t)kk * cp + c] = eofs[(size_t)kk * n_wet + j];
-    ++j;
-  }
-  int rc = GPRX_OK;
-  hipError_t e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
-  if (e != hipSuccess) {
-    delete p;
-    return pfail(nullptr, GPRX_EHIP, std::string("hipStreamCreate: ") + hipGetErrorString(e));
-  }
-  std::vector<double> xm(x_mean, x_mean + k), xs(x_std, x_std + k);
-  if ((rc = pupload(p, p->mu, mu)) || (rc = pupload(p, p->wfwd, wf)) || (rc = pupload(p, p->wrev, wr)) || (rc = pupload(p, p->elev, el)) ||
-      (rc = pupload(p, p->base, base)) || (rc = pupload(p, p->E, E)) || (rc = pupload(p, p->xm, xm)) || (rc = pupload(p, p->xs, xs))) {
-    gprx_pca_destroy(p);
-    return rc;
-  }
-  *out = p;
-  return GPRX_OK;
-}
-
-int gprx_pca_destroy(gprx_pca_handle p) {
-  if (!p) return GPRX_OK;
-  hipSetDevice(p->device);
-  if (p->stream) hipStreamSynchronize(p->stream);
-  for (Buf* b : {&p->mu, &p->wfwd, &p->wrev, &p->elev, &p->E, &p->base, &p->xm, &p->xs, &p->dX, &p->dZ, &p->ws, &p->dMean, &p->dVar, &p->dFull,
-                 &p->dVfull})
-    if (b->p) hipFree(b->p);
-  if (p->stream) hipStreamDestroy(p->stream);
-  delete p;
-  return GPRX_OK;
-}
-
-// x_dev: (rows, ld) with ld = cells_p (padding columns may hold anything finite: their weight is 0); z_dev: (rows, k)
-int gprx_pca_transform_dev(gprx_pca_handle p, const double* x_dev, int64_t rows, double* z_dev) {
-  if (!p) return pfail(p, GPRX_EINVAL, "null handle");
-  if (rows < 0 || (rows > 0 && (!x_dev || !z_dev))) return pfail(p, GPRX_EINVAL, "null argument");
-  if (rows == 0) return GPRX_OK;
-  if (rows > (1 << 30)) return pfail(p, GPRX_EINVAL, "too many rows in one call");
-  PCACHK(p, hipSetDevice(p->device));
-  hipStream_t st = p->stream;
-  const int64_t cp = p->cells_p;
-  // Z = ((g(X) - mu) w) E^T in ONE pass over X: the centring / weighting runs inside the GEMM's operand load
-  // (gemm_f64_kernel AXF); M = rows, N = k, K = cells_p cut into slices so that a few thousand workgroups exist
-  const int tiles_m = (int)((rows + 63) / 64);
-  int nsplit = std::max(1, 2048 / tiles_m);
-  int kchunk = (int)round_up((cp + nsplit - 1) / nsplit, 16);
-  if (kchunk < 256) kchunk = 256;
-  nsplit = (int)((cp + kchunk - 1) / kchunk);
-  int rc;
-  if ((rc = pensure(p, p->ws, sizeof(double) * (size_t)nsplit * rows * p->k))) return rc;
-  PCACHK(p, launch_gemm_splitk_axf(st, (int)rows, p->k, (int)cp, x_dev, cp, p->E.p, cp, z_dev, p->k, p->ws.p, kchunk, p->mu.p, p->wfwd.p,
-                                   p->depth ? p->elev.p : nullptr));
-  hipLaunchKernelGGL(pca_standardize_kernel, dim3((unsigned)((rows * p->k + 255) / 256)), dim3(256), 0, st, z_dev, rows, p->k,
-                     (const double*)p->xm.p, (const double*)p->xs.p);
-  PCACHK(p, hipGetLastError());
-  return GPRX_OK;
-}
-
-int gprx_pca_reverse_dev(gprx_pca_handle p, const double* mean_dev, const double* var_dev, int64_t rows, double* full_dev, double* vfull_dev) {
-  if (!p) return pfail(p, GPRX_EINVAL, "null handle");
-  if (rows < 0 || (rows > 0 && (!mean_dev || !full_dev))) return pfail(p, GPRX_EINVAL, "null argument");
-  if ((var_dev == nullptr) != (vfull_dev == nullptr)) return pfail(p, GPRX_EINVAL, "var and var_full must both be given or both be null");
-  if (rows == 0) return GPRX_OK;
-  PCACHK(p, hipSetDevice(p->device));
-  dim3 grid((unsigned)((p->cells + 255) / 256), (unsigned)std::min<int64_t>((rows + PCA_RB - 1) / PCA_RB, 64));
-  if (p->k <= 16)
-    hipLaunchKernelGGL(pca_reverse_kernel<16>, grid, dim3(256), 0, p->stream, mean_dev, var_dev, rows, p->k, p->cells, (const double*)p->E.p, p->cells_p,
-                       (const double*)p->wrev.p, (const double*)p->base.p, (const double*)p->xm.p, (const double*)p->xs.p, full_dev, vfull_dev);
-  else
-    hipLaunchKernelGGL(pca_reverse_kernel<64>, grid, dim3(256), 0, p->stream, mean_dev, var_dev, rows, p->k, p->cells, (const double*)p->E.p, p->cells_p,
-                       (const double*)p->wrev.p, (const double*)p->base.p, (const double*)p->xm.p, (const double*)p->xs.p, full_dev, vfull_dev);
-  PCACHK(p, hipGetLastError());
-  return GPRX_OK;
-}
-
-int gprx_pca_to_depth_dev(gprx_pca_handle p, double* field_dev, int64_t rows, int add_elevations_first) {
-  if (!p) return pfail(p, GPRX_EINVAL, "null handle");
-  if (rows < 0 || (rows > 0 && !field_dev)) return pfail(p, GPRX_EINVAL, "null argument");
-  if (rows == 0) return GPRX_OK;
-  PCACHK(p, hipSetDevice(p->device));
-  hipLaunchKernelGGL(field_to_depth_kernel, dim3(4096), dim3(256), 0, p->stream, field_dev, rows, p->cells, (const double*)p->elev.p,
-                     add_elevations_first ? 1 : 0);
-  PCACHK(p, hipGetLastError());
-  return GPRX_OK;
-}
-
-int gprx_pca_sqrt_dev(gprx_pca_handle p, double* field_dev, int64_t count) {
-  if (!p) return pfail(p, GPRX_EINVAL, "null handle");
-  if (count < 0 || (count > 0 && !field_dev)) return pfail(p, GPRX_EINVAL, "null argument");
-  if (count == 0) return GPRX_OK;
-  PCACHK(p, hipSetDevice(p->device));
-  hipLaunchKernelGGL(field_sqrt_kernel, dim3(4096), dim3(256), 0, p->stream, field_dev, count);
-  PCACHK(p, hipGetLastError());
-  return GPRX_OK;
-}
-
-int gprx_pca_transpose_dev(gprx_pca_handle p, const double* src_dev, int64_t rows, int64_t cols, double* dst_dev) {
-  if (!p) return pfail(p, GPRX_EINVAL, "null handle");
-  if (rows < 0 || cols < 0 || (rows * cols > 0 && (!src_dev || !dst_dev))) return pfail(p, GPRX_EINVAL, "null argument");
-  if (rows * cols == 0) return GPRX_OK;
-  PCACHK(p, hipSetDevice(p->device));
-  hipLaunchKernelGGL(transpose_small_kernel, dim3((unsigned)std::min<int64_t>((rows * cols + 255) / 256, 4096)), dim3(256), 0, p->stream, src_dev, rows,
-                     cols, dst_dev);
-  PCACHK(p, hipGetLastError());
-  return GPRX_OK;
-}
-
-int gprx_pca_synchronize(gprx_pca_handle p) {
-  if (!p) return pfail(p, GPRX_EINVAL, "null handle");
-  PCACHK(p, hipStreamSynchronize(p->stream));
-  return GPRX_OK;
-}
-
-int gprx_pca_transform(gprx_pca_handle p, const double* x, int64_t rows, double* z) {
-  if (!p) return pfail(p, GPRX_EINVAL, "null handle");
-  if (rows < 0 || (rows > 0 && (!x || !z))) return pfail(p, GPRX_EINVAL, "null argument");
-  PCACHK(p, hipSetDevice(p->device));
-  const int64_t cp = p->cells_p, chunk = std::max<int64_t>(64, pca_chunk_doubles() / cp);
-  int rc;
-  for (int64_t t0 = 0; t0 < rows; t0 += chunk) {
-    const int64_t nr = std::min(chunk, rows - t0);
-    if ((rc = pensure(p, p->dX, sizeof(double) * (size_t)nr * cp)) || (rc = pensure(p, p->dZ, sizeof(double) * (size_t)nr * p->k))) return rc;
-    if (cp > p->cells)  // padding columns must be finite (their weight is 0, and 0 * NaN is not)
-      PCACHK(p, hipMemset2DAsync(p->dX.p + p->cells, sizeof(double) * cp, 0, sizeof(double) * (cp - p->cells), nr, p->stream));
-    PCACHK(p, hipMemcpy2DAsync(p->dX.p, sizeof(double) * cp, x + t0 * p->cells, sizeof(double) * p->cells, sizeof(double) * p->cells, nr,
-                               hipMemcpyHostToDevice, p->stream));
-    if ((rc = gprx_pca_transform_dev(p, p->dX.p, nr, p->dZ.p))) return rc;
-    PCACHK(p, hipMemcpyAsync(z + t0 * p->k, p->dZ.p, sizeof(double) * nr * p->k, hipMemcpyDeviceToHost, p->stream));
-    PCACHK(p, hipStreamSynchronize(p->stream));
-  }
-  return GPRX_OK;
-}
-
-int gprx_pca_reverse(gprx_pca_handle p, const double* mean, const double* var, int64_t rows, double* full, double* var_full) {
-  if (!p) return pfail(p, GPRX_EINVAL, "null handle");
-  if (rows < 0 || (rows > 0 && (!mean || !full))) return pfail(p, GPRX_EINVAL, "null argument");
-  if ((var == nullptr) != (var_full == nullptr)) return pfail(p, GPRX_EINVAL, "var and var_full must both be given or both be null");
-  PCACHK(p, hipSetDevice(p->device));
-  const int64_t chunk = std::max<int64_t>(64, pca_chunk_doubles() / p->cells);
-  int rc;
-  for (int64_t t0 = 0; t0 < rows; t0 += chunk) {
-    const int64_t nr = std::min(chunk, rows - t0);
-    if ((rc = pensure(p, p->dMean, sizeof(double) * (size_t)nr * p->k)) || (rc = pensure(p, p->dFull, sizeof(double) * (size_t)nr * p->cells))) return rc;
-    PCACHK(p, hipMemcpyAsync(p->dMean.p, mean + t0 * p->k, sizeof(double) * nr * p->k, hipMemcpyHostToDevice, p->stream));
-    if (var) {
-      if ((rc = pensure(p, p->dVar, sizeof(double) * (size_t)nr * p->k)) || (rc = pensure(p, p->dVfull, sizeof(double) * (size_t)nr * p->cells))) return rc;
-      PCACHK(p, hipMemcpyAsync(p->dVar.p, var + t0 * p->k, sizeof(double) * nr * p->k, hipMemcpyHostToDevice, p->stream));
-    }
-    if ((rc = gprx_pca_reverse_dev(p, p->dMean.p, var ? p->dVar.p : nullptr, nr, p->dFull.p, var ? p->dVfull.p : nullptr))) return rc;
-    PCACHK(p, hipMemcpyAsync(full + t0 * p->cells, p->dFull.p, sizeof(double) * nr * p->cells, hipMemcpyDeviceToHost, p->stream));
-    if (var) PCACHK(p, hipMemcpyAsync(var_full + t0 * p->cells, p->dVfull.p, sizeof(double) * nr * p->cells, hipMemcpyDeviceToHost, p->stream));
-    PCACHK(p, hipStreamSynchronize(p->stream));
-  }
-  return GPRX_OK;
-}
-
-const char* gprx_pca_last_error(gprx_pca_handle p) { return p ? p->err.c_str() : g_err.c_str(); }
-
-// ---- fitting the EOF preprocessor (PreProcessor.fit, gpras/preprocess.py:947-1007) ---------------------------------------
-struct gprx_pcafit_ctx {
-  int device = 0, mode = 0;
-  hipStream_t stream = nullptr;
-  int64_t rows = 0, rows_p = 0, cells = 0, n_wet = 0, ldc = 0;  // ldc: leading dimension of the compacted matrices (multiple of 16)
-  double *xc1 = nullptr, *xc2 = nullptr, *ws = nullptr, *A = nullptr, *E = nullptr, *Z = nullptr;
-  size_t ws_bytes = 0;
-  std::vector<unsigned char> cls;    // wetness class per cell
-  std::vector<double> mean, gram;    // input_mean over the wet cells, G (rows, rows)
-  hipEvent_t ev[8] = {};
-  double ms[6] = {0, 0, 0, 0, 0, 0};  // upload, stats, centring, Gram, components, projection
-  std::string err;
-};
-
-namespace {
-int ffail(gprx_pcafit_handle f, int code, const std::string& msg) {
-  if (f) f->err = msg;
-  g_err = msg;
-  return code;
-}
-#define FITCHK(f, expr)                                                                                              \
-  do {                                                                                                               \
-    hipError_t e_ = (expr);                                                                                          \
-    if (e_ != hipSuccess)                                                                                            \
-      return ffail(f, e_ == hipErrorOutOfMemory ? GPRX_ENOMEM : GPRX_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-// split-K plan of a product with `tiles` output tiles of 64 x 64 and K = kdim: a few thousand workgroups, slabs capped at 256 MiB
-int pcafit_kchunk(int64_t tiles, int64_t kdim, int64_t slab_doubles) {
-  int64_t nsplit = std::max<int64_t>(1, 2048 / std::max<int64_t>(tiles, 1));
-  nsplit = std::min<int64_t>(nsplit, std::max<int64_t>(1, ((int64_t)1 << 25) / std::max<int64_t>(slab_doubles, 1)));
-  int64_t kchunk = round_up((kdim + nsplit - 1) / nsplit, 16);
-  return (int)std::max<int64_t>(kchunk, 256);
-}
-
-int pcafit_ensure_ws(gprx_pcafit_handle f, size_t bytes) {
-  if (f->ws_bytes >= bytes) return GPRX_OK;
-  if (f->ws) FITCHK(f, hipFree(f->ws));
-  f->ws = nullptr;
-  f->ws_bytes = 0;
-  FITCHK(f, hipMalloc((void**)&f->ws, bytes));
-  f->ws_bytes = bytes;
-  return GPRX_OK;
-}
-
-float pcafit_elapsed(hipEvent_t a, hipEvent_t b) {
-  float ms = 0.f;
-  hipEventElapsedTime(&ms, a, b);
-  return ms;
-}
-
-// steps 1-3: upload, column statistics + classes, compaction + both centrings, Gram matrix
-int pcafit_run(gprx_pcafit_handle f, const double* x, const double* elevations, const double* weights, double thr) {
-  const int64_t rows = f->rows, cells = f->cells;
-  const size_t xb = sizeof(double) * (size_t)rows * cells;
-  hipStream_t st = f->stream;
-  // device memory of the whole fit, before anything is allocated: x, per-cell vectors, both compacted matrices, Gram slabs
-  {
-    const int64_t ldc_max = round_up(cells, 16);
-    const int64_t tiles = (rows + 63) / 64, ltiles = tiles * (tiles + 1) / 2;
-    const int64_t nsplit = (ldc_max + pcafit_kchunk(ltiles, ldc_max, rows * rows) - 1) / pcafit_kchunk(ltiles, ldc_max, rows * rows);
-    const double need = (double)xb + 8.0 * (4.0 * cells + (double)(rows + f->rows_p) * ldc_max + (double)(nsplit + 1) * rows * rows) + cells;
-    size_t fr = 0, tot = 0;
-    FITCHK(f, hipMemGetInfo(&fr, &tot));
-    if (need > 0.95 * (double)fr)
-      return ffail(f, GPRX_ENOMEM, "the fit needs " + std::to_string((long long)(need / 1048576.0)) + " MiB of device memory, " +
-                                       std::to_string((long long)(fr / 1048576)) + " MiB are free");
-  }
-  double *X = nullptr, *elev = nullptr, *w = nullptr, *mu = nullptr, *m2 = nullptr;
-  unsigned char* cls = nullptr;
-  int64_t* idx = nullptr;
-  int2* ops = nullptr;
-  auto release = [&] {
-    for (void* q : {(void*)X, (void*)elev, (void*)w, (void*)mu, (void*)m2, (void*)cls, (void*)idx, (void*)ops})
-      if (q) hipFree(q);
-  };
-  std::vector<int2> ops_h;
-  int depth = 0;
-  pcafit_pairwise_ops(0, (int)rows, 0, ops_h, depth);
-  if (depth > PCAFIT_STACK) return ffail(f, GPRX_EINVAL, "too many samples for the pairwise column sums");
-  const int nops = (int)ops_h.size();
-  auto run = [&]() -> int {
-    FITCHK(f, hipMalloc((void**)&ops, sizeof(int2) * ops_h.size()));
-    FITCHK(f, hipMemcpyAsync(ops, ops_h.data(), sizeof(int2) * ops_h.size(), hipMemcpyHostToDevice, st));
-    FITCHK(f, hipMalloc((void**)&X, xb));
-    FITCHK(f, hipMalloc((void**)&mu, sizeof(double) * cells));
-    FITCHK(f, hipMalloc((void**)&cls, (size_t)cells));
-    if (f->mode != PCAFIT_VELOCITY) {
-      FITCHK(f, hipMalloc((void**)&elev, sizeof(double) * cells));
-      FITCHK(f, hipMemcpyAsync(elev, elevations, sizeof(double) * cells, hipMemcpyHostToDevice, st));
-    }
-    if (weights) {
-      FITCHK(f, hipMalloc((void**)&w, sizeof(double) * cells));
-      FITCHK(f, hipMemcpyAsync(w, weights, sizeof(double) * cells, hipMemcpyHostToDevice, st));
-    }
-    // 1. x goes up once; one pass gives the classes and the column means
-    FITCHK(f, hipEventRecord(f->ev[0], st));
-    FITCHK(f, hipMemcpyAsync(X, x, xb, hipMemcpyHostToDevice, st));
-    FITCHK(f, hipEventRecord(f->ev[1], st));
-    hipLaunchKernelGGL(pcafit_colstats_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, (const double*)X, rows, cells,
-                       (const double*)elev, f->mode, thr, (const int2*)ops, nops, cls, mu);
-    FITCHK(f, hipGetLastError());
-    FITCHK(f, hipEventRecord(f->ev[2], st));
-    std::vector<double> mu_h((size_t)cells);
-    f->cls.resize((size_t)cells);
-    FITCHK(f, hipMemcpyAsync(f->cls.data(), cls, (size_t)cells, hipMemcpyDeviceToHost, st));
-    FITCHK(f, hipMemcpyAsync(mu_h.data(), mu, sizeof(double) * cells, hipMemcpyDeviceToHost, st));
-    FITCHK(f, hipStreamSynchronize(st));
-    // wet cells (class != AD) in ascending order: x[:, ~dry_indices]
-    std::vector<int64_t> idx_h;
-    idx_h.reserve((size_t)cells);
-    for (int64_t c = 0; c < cells; ++c)
-      if (f->cls[c] != 1) idx_h.push_back(c);
-    f->n_wet = (int64_t)idx_h.size();
-    if (f->n_wet < rows)
-      return ffail(f, GPRX_EINVAL, "the fit needs at least as many wet cells as samples: " + std::to_string((long long)f->n_wet) + " wet cells, " +
-                                       std::to_string((long long)rows) + " samples");
-    f->mean.resize((size_t)f->n_wet);
-    for (int64_t j = 0; j < f->n_wet; ++j) f->mean[j] = mu_h[idx_h[j]];
-    f->ldc = round_up(f->n_wet, 16);
-    const int64_t ldc = f->ldc;
-    // 2. compaction, centring, weighting, then IncrementalPCA's centring; xc2 has rows_p rows (zero beyond `rows`: the K padding
-    //    of the components GEMM)
-    FITCHK(f, hipMalloc((void**)&idx, sizeof(int64_t) * f->n_wet));
-    FITCHK(f, hipMalloc((void**)&m2, sizeof(double) * ldc));
-    FITCHK(f, hipMalloc((void**)&f->xc1, sizeof(double) * rows * ldc));
-    FITCHK(f, hipMalloc((void**)&f->xc2, sizeof(double) * f->rows_p * ldc));
-    FITCHK(f, hipMemcpyAsync(idx, idx_h.data(), sizeof(int64_t) * f->n_wet, hipMemcpyHostToDevice, st));
-    if (f->rows_p > rows) FITCHK(f, hipMemsetAsync(f->xc2 + rows * ldc, 0, sizeof(double) * (f->rows_p - rows) * ldc, st));
-    FITCHK(f, hipEventRecord(f->ev[3], st));
-    hipLaunchKernelGGL(pcafit_compact_kernel, dim3((unsigned)((ldc + 255) / 256)), dim3(256), 0, st, (const double*)X, rows, cells,
-                       (const int64_t*)idx, f->n_wet, ldc, (const double*)elev, f->mode, (const double*)mu, (const double*)w,
-                       (const int2*)ops, nops, f->xc1, f->xc2, m2);
-    FITCHK(f, hipGetLastError());
-    FITCHK(f, hipEventRecord(f->ev[4], st));
-    // 3. G = Xc2 Xc2^T: lower-triangle tiles, split-K slabs summed in a fixed order
-    const int n = (int)rows;
-    const int64_t tiles = (rows + 63) / 64, ltiles = tiles * (tiles + 1) / 2;
-    const int kchunk = pcafit_kchunk(ltiles, ldc, rows * rows);
-    const int nsplit = (int)((ldc + kchunk - 1) / kchunk);
-    int rc;
-    if ((rc = pcafit_ensure_ws(f, sizeof(double) * ((size_t)nsplit * rows * rows + (size_t)rows * rows)))) return rc;
-    double* G = f->ws + (size_t)nsplit * rows * rows;
-    GemmArgs p{f->xc2, f->xc2, f->ws, ldc, ldc, (int64_t)n, n, n, (int)ldc, 1.0, 0.0, GEMM_C_LOWER, 0, 0, 0, 0, 0, 0, kchunk, (int64_t)n * n};
-    FITCHK(f, (launch_gemm_t<0, 1, 64, 64>(st, p, 1, nsplit)));
-    hipLaunchKernelGGL(pcafit_gram_reduce_kernel, dim3((unsigned)(((int64_t)n * n + 255) / 256)), dim3(256), 0, st, (const double*)f->ws, nsplit, n, G);
-    FITCHK(f, hipGetLastError());
-    FITCHK(f, hipEventRecord(f->ev[5], st));
-    f->gram.resize((size_t)rows * rows);
-    FITCHK(f, hipMemcpyAsync(f->gram.data(), G, sizeof(double) * rows * rows, hipMemcpyDeviceToHost, st));
-    FITCHK(f, hipStreamSynchronize(st));
-    f->ms[0] = pcafit_elapsed(f->ev[0], f->ev[1]);
-    f->ms[1] = pcafit_elapsed(f->ev[1], f->ev[2]);
-    f->ms[2] = pcafit_elapsed(f->ev[3], f->ev[4]);
-    f->ms[3] = pcafit_elapsed(f->ev[4], f->ev[5]);
-    return GPRX_OK;
-  };
-  const int rc = run();
-  hipStreamSynchronize(st);  // nothing in flight reads a buffer released below
-  release();
-  return rc;
-}
-
-int pcafit_components(gprx_pcafit_handle f, int k, const double* u, const double* lam, double* eofs, double* z) {
-  const int64_t rows = f->rows, rp = f->rows_p, ldc = f->ldc;
-  hipStream_t st = f->stream;
-  // A = diag(lambda^-1/2) U_k^T, K padded to rows_p with zeros
-  std::vector<double> a((size_t)k * rp, 0.0);
-  for (int i = 0; i < k; ++i) {
-    const double s = 1.0 / std::sqrt(lam[i]);
-    for (int64_t t = 0; t < rows; ++t) a[(size_t)i * rp + t] = u[(size_t)t * k + i] * s;
-  }
-  if (f->A) FITCHK(f, hipFree(f->A));
-  if (f->E) FITCHK(f, hipFree(f->E));
-  if (f->Z) FITCHK(f, hipFree(f->Z));
-  f->A = f->E = f->Z = nullptr;
-  FITCHK(f, hipMalloc((void**)&f->A, sizeof(double) * a.size()));
-  FITCHK(f, hipMalloc((void**)&f->E, sizeof(double) * (size_t)k * ldc));
-  FITCHK(f, hipMalloc((void**)&f->Z, sizeof(double) * (size_t)rows * k));
-  FITCHK(f, hipMemcpyAsync(f->A, a.data(), sizeof(double) * a.size(), hipMemcpyHostToDevice, st));
-  const int tiles_m = (int)((rows + 63) / 64);
-  const int kchunk = pcafit_kchunk(tiles_m * ((k + 63) / 64), ldc, rows * k);
-  const int nsplit = (int)((ldc + kchunk - 1) / kchunk);
-  int rc;
-  if ((rc = pcafit_ensure_ws(f, sizeof(double) * (size_t)nsplit * rows * k))) return rc;
-  // 5. E = A Xc2 (NN, K = rows_p), then svd_flip on its rows
-  FITCHK(f, hipEventRecord(f->ev[5], st));
-  FITCHK(f, launch_gemm(st, 0, 0, k, (int)ldc, (int)rp, 1.0, f->A, rp, f->xc2, ldc, 0.0, f->E, ldc, 0));
-  hipLaunchKernelGGL(pcafit_sign_flip_kernel, dim3((unsigned)k), dim3(256), 0, st, f->E, ldc, f->n_wet);
-  FITCHK(f, hipGetLastError());
-  FITCHK(f, hipEventRecord(f->ev[6], st));
-  // 6. Z = Xc1 E^T (split-K NT; the padding columns of both operands are zero)
-  FITCHK(f, launch_gemm_splitk(st, 0, 1, (int)rows, k, (int)ldc, 1.0, f->xc1, ldc, f->E, ldc, 0.0, f->Z, k, f->ws, kchunk));
-  FITCHK(f, hipEventRecord(f->ev[7], st));
-  FITCHK(f, hipMemcpy2DAsync(eofs, sizeof(double) * f->n_wet, f->E, sizeof(double) * ldc, sizeof(double) * f->n_wet, (size_t)k,
-                             hipMemcpyDeviceToHost, st));
-  FITCHK(f, hipMemcpyAsync(z, f->Z, sizeof(double) * rows * k, hipMemcpyDeviceToHost, st));
-  FITCHK(f, hipStreamSynchronize(st));
-  f->ms[4] = pcafit_elapsed(f->ev[5], f->ev[6]);
-  f->ms[5] = pcafit_elapsed(f->ev[6], f->ev[7]);
-  return GPRX_OK;
-}
-}  // namespace
-
-int gprx_pcafit_destroy(gprx_pcafit_handle f) {
-  if (!f) return GPRX_OK;
-  hipSetDevice(f->device);
-  if (f->stream) hipStreamSynchronize(f->stream);
-  for (double* q : {f->xc1, f->xc2, f->ws, f->A, f->E, f->Z})
-    if (q) hipFree(q);
-  for (hipEvent_t e : f->ev)
-    if (e) hipEventDestroy(e);
-  if (f->stream) hipStreamDestroy(f->stream);
-  delete f;
-  return GPRX_OK;
-}
-
-int gprx_pcafit_create(int device, const double* x, int64_t n_samples, int64_t n_cells, const double* elevations, const double* weights,
-                       int mode, double wet_threshold, gprx_pcafit_handle* out) {
-  if (!out) return ffail(nullptr, GPRX_EINVAL, "out is null");
-  *out = nullptr;
-  if (!x) return ffail(nullptr, GPRX_EINVAL, "x is null");
-  if (mode < PCAFIT_WSE || mode > PCAFIT_VELOCITY) return ffail(nullptr, GPRX_EINVAL, "mode must be 0 (wse), 1 (depth) or 2 (velocity)");
-  if (mode != PCAFIT_VELOCITY && !elevations) return ffail(nullptr, GPRX_EINVAL, "wse and depth need the cell elevations");
-  if (n_samples < 2 || n_cells < n_samples || n_samples > 16384)
-    return ffail(nullptr, GPRX_EINVAL, "need 2 <= n_samples <= min(n_cells, 16384)");
-  gprx_pcafit_handle f = nullptr;
-  try {
-    FITCHK(nullptr, hipSetDevice(device));
-    f = new gprx_pcafit_ctx();
-    f->device = device;
-    f->mode = mode;
-    f->rows = n_samples;
-    f->rows_p = round_up(n_samples, 16);
-    f->cells = n_cells;
-    int rc = GPRX_OK;
-    hipError_t e = hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking);
-    for (hipEvent_t& ev : f->ev)
-      if (e == hipSuccess) e = hipEventCreate(&ev);
-    if (e != hipSuccess) rc = ffail(nullptr, GPRX_EHIP, std::string("hipStreamCreate / hipEventCreate: ") + hipGetErrorString(e));
-    if (!rc) rc = pcafit_run(f, x, elevations, weights, wet_threshold);
-    if (rc) {
-      gprx_pcafit_destroy(f);
-      return rc;
-    }
-  } catch (const std::bad_alloc&) {
-    gprx_pcafit_destroy(f);
-    return ffail(nullptr, GPRX_ENOMEM, "host allocation failed");
-  }
-  *out = f;
-  return GPRX_OK;
-}
-
-int gprx_pcafit_gram(gprx_pcafit_handle f, unsigned char* classes, double* input_mean, double* gram, int64_t* n_wet) {
-  if (!f) return ffail(f, GPRX_EINVAL, "null handle");
-  if (!classes || !input_mean || !gram || !n_wet) return ffail(f, GPRX_EINVAL, "null argument");
-  std::memcpy(classes, f->cls.data(), f->cls.size());
-  std::memcpy(input_mean, f->mean.data(), sizeof(double) * f->mean.size());
-  std::memcpy(gram, f->gram.data(), sizeof(double) * f->gram.size());
-  *n_wet = f->n_wet;
-  return GPRX_OK;
-}
-
-int gprx_pcafit_components(gprx_pcafit_handle f, int k, const double* u, const double* lam, double* eofs, double* z) {
-  if (!f) return ffail(f, GPRX_EINVAL, "null handle");
-  if (k < 0 || k >= f->rows) return ffail(f, GPRX_EINVAL, "need 0 <= k < n_samples (centring removes one direction)");
-  if (k == 0) return GPRX_OK;
-  if (!u || !lam || !eofs || !z) return ffail(f, GPRX_EINVAL, "null argument");
-  for (int i = 0; i < k; ++i)
-    if (!(lam[i] > 0.0)) return ffail(f, GPRX_EINVAL, "retained eigenvalues must be positive");
-  try {
-    FITCHK(f, hipSetDevice(f->device));
-    return pcafit_components(f, k, u, lam, eofs, z);
-  } catch (const std::bad_alloc&) {
-    return ffail(f, GPRX_ENOMEM, "host allocation failed");
-  }
-}
-
-int gprx_pcafit_timings(gprx_pcafit_handle f, double* ms) {
-  if (!f || !ms) return ffail(f, GPRX_EINVAL, "null argument");
-  for (int i = 0; i < 6; ++i) ms[i] = f->ms[i];
-  return GPRX_OK;
-}
-
-const char* gprx_pcafit_last_error(gprx_pcafit_handle f) { return f ? f->err.c_str() : g_err.c_str(); }
-
-// ---- HmsPreProcessor (gpras/preprocess.py:1165-1320): the precip EOF fit, the features and the API ---------------------------
-struct gprx_hms_ctx {
-  int device = 0, route = -1;
-  hipStream_t stream = nullptr;
-  int64_t rows = 0, nfeat = 0, n_bc = 0, p = 0, ld2 = 0;
-  double *X = nullptr, *mu = nullptr, *X2 = nullptr, *ws = nullptr;  // X: x column-major (rows, nfeat), ldx = rows
-  int64_t *bc = nullptr, *pc = nullptr;
-  size_t ws_bytes = 0;
-  std::vector<int64_t> bc_h, pc_h;
-  std::vector<double> mu_h;  // input_mean (nfeat)
-  hipEvent_t ev[8] = {};
-  double ms[7] = {0, 0, 0, 0, 0, 0, 0};  // upload, column pass, covariance / Gram, components, projection, API, statistics / standardise
-  std::string err;
-};
-
-namespace {
-int hfail(gprx_hms_handle h, int code, const std::string& msg) {
-  if (h) h->err = msg;
-  g_err = msg;
-  return code;
-}
-#define HMSCHK(h, expr)                                                                                              \
-  do {                                                                                                               \
-    hipError_t e_ = (expr);                                                                                          \
-    if (e_ != hipSuccess)                                                                                            \
-      return hfail(h, e_ == hipErrorOutOfMemory ? GPRX_ENOMEM : GPRX_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-// the next allocations need `bytes` of device memory: GPRX_ENOMEM before any of them is made
-int hms_need(gprx_hms_handle h, double bytes, const char* what) {
-  size_t fr = 0, tot = 0;
-  HMSCHK(h, hipMemGetInfo(&fr, &tot));
-  if (bytes > 0.95 * (double)fr)
-    return hfail(h, GPRX_ENOMEM, std::string(what) + " needs " + std::to_string((long long)(bytes / 1048576.0)) + " MiB of device memory, " +
-                                     std::to_string((long long)(fr / 1048576)) + " MiB are free");
-  return GPRX_OK;
-}
-
-int hms_ws(gprx_hms_handle h, size_t bytes) {
-  if (h->ws_bytes >= bytes) return GPRX_OK;
-  if (h->ws) HMSCHK(h, hipFree(h->ws));
-  h->ws = nullptr;
-  h->ws_bytes = 0;
-  HMSCHK(h, hipMalloc((void**)&h->ws, bytes));
-  h->ws_bytes = bytes;
-  return GPRX_OK;
-}
-
-// split-K plan of the lower-triangle product of n x n with K = kdim (as the Gram of pcafit_run)
-void hms_split(int64_t n, int64_t kdim, int& kchunk, int& nsplit) {
-  const int64_t tiles = (n + 63) / 64, ltiles = tiles * (tiles + 1) / 2;
-  kchunk = pcafit_kchunk(ltiles, kdim, n * n);
-  nsplit = (int)((kdim + kchunk - 1) / kchunk);
-}
-
-// x goes up once and is kept column-major: an F-order x is copied as it is, a C-order x in row chunks through a staging buffer
-int hms_upload(gprx_hms_handle h, const double* x, int64_t ld, int fortran) {
-  const int64_t rows = h->rows, nf = h->nfeat;
-  hipStream_t st = h->stream;
-  HMSCHK(h, hipEventRecord(h->ev[0], st));
-  if (fortran) {
-    HMSCHK(h, hipMemcpy2DAsync(h->X, sizeof(double) * rows, x, sizeof(double) * ld, sizeof(double) * rows, (size_t)nf, hipMemcpyHostToDevice, st));
-  } else {
-    const int64_t chunk = std::min<int64_t>(rows, std::max<int64_t>(32, ((int64_t)1 << 22) / nf));  // <= 32 MiB staged
-    double* S = nullptr;
-    HMSCHK(h, hipMalloc((void**)&S, sizeof(double) * (size_t)chunk * nf));
-    int rc = GPRX_OK;
-    for (int64_t t0 = 0; t0 < rows && !rc; t0 += chunk) {
-      const int64_t tc = std::min(chunk, rows - t0);
-      hipError_t e = hipMemcpy2DAsync(S, sizeof(double) * nf, x + t0 * ld, sizeof(double) * ld, sizeof(double) * nf, (size_t)tc, hipMemcpyHostToDevice, st);
-      if (e == hipSuccess) {
-        hipLaunchKernelGGL(hms_transpose_kernel, dim3((unsigned)((tc + 31) / 32), (unsigned)((nf + 31) / 32)), dim3(256), 0, st, (const double*)S, tc, nf,
-                           h->X + t0, rows);
-        e = hipGetLastError();
-      }
-      if (e != hipSuccess) rc = hfail(h, GPRX_EHIP, std::string("upload of x: ") + hipGetErrorString(e));
-    }
-    hipStreamSynchronize(st);  // the staging buffer is no longer read
-    hipFree(S);
-    if (rc) return rc;
-  }
-  HMSCHK(h, hipEventRecord(h->ev[1], st));
-  return GPRX_OK;
-}
-
-// column pass and the covariance (route HMS_COV: C = X2^T X2, p x p) or Gram (HMS_GRAM: G = X2 X2^T, rows x rows) of the PCA input
-int hms_cov(gprx_hms_handle h, double* cov) {
-  const int64_t rows = h->rows, p = h->p;
-  hipStream_t st = h->stream;
-  const int route = rows >= p ? HMS_COV : HMS_GRAM;
-  const int64_t n = route == HMS_COV ? p : rows;
-  const int64_t ld2 = round_up(route == HMS_COV ? rows : p, 16), r2 = round_up(n, 16);
-  int kchunk = 0, nsplit = 0;
-  hms_split(n, ld2, kchunk, nsplit);
-  int rc;
-  if ((rc = hms_need(h, 8.0 * ((double)r2 * ld2 + (double)(nsplit + 1) * n * n + p), "the covariance"))) return rc;
-  double* m2 = nullptr;
-  HMSCHK(h, hipMalloc((void**)&m2, sizeof(double) * p));
-  auto run = [&]() -> int {
-    HMSCHK(h, hipMalloc((void**)&h->X2, sizeof(double) * (size_t)r2 * ld2));
-    h->ld2 = ld2;
-    h->route = route;
-    HMSCHK(h, hipEventRecord(h->ev[2], st));
-    hipLaunchKernelGGL(hms_colmean_kernel, dim3((unsigned)h->nfeat), dim3(256), 0, st, (const double*)h->X, rows, rows, (const int64_t*)nullptr,
-                       (const double*)nullptr, h->mu);
-    hipLaunchKernelGGL(hms_colmean_kernel, dim3((unsigned)p), dim3(256), 0, st, (const double*)h->X, rows, rows, (const int64_t*)h->pc,
-                       (const double*)h->mu, m2);
-    if (r2 > n) HMSCHK(h, hipMemsetAsync(h->X2 + n * ld2, 0, sizeof(double) * (size_t)(r2 - n) * ld2, st));
-    hipLaunchKernelGGL(hms_centre2_kernel, dim3((unsigned)((ld2 + 255) / 256), (unsigned)(route == HMS_COV ? p : rows)), dim3(256), 0, st,
-                       (const double*)h->X, rows, rows, (const int64_t*)h->pc, p, (const double*)h->mu, (const double*)m2, route, h->X2, ld2);
-    HMSCHK(h, hipGetLastError());
-    HMSCHK(h, hipEventRecord(h->ev[3], st));
-    if ((rc = hms_ws(h, sizeof(double) * ((size_t)nsplit * n * n + (size_t)n * n)))) return rc;
-    double* C = h->ws + (size_t)nsplit * n * n;
-    GemmArgs g{h->X2, h->X2, h->ws, ld2, ld2, n, (int)n, (int)n, (int)ld2, 1.0, 0.0, GEMM_C_LOWER, 0, 0, 0, 0, 0, 0, kchunk, n * n};
-    HMSCHK(h, (launch_gemm_t<0, 1, 64, 64>(st, g, 1, nsplit)));
-    hipLaunchKernelGGL(pcafit_gram_reduce_kernel, dim3((unsigned)((n * n + 255) / 256)), dim3(256), 0, st, (const double*)h->ws, nsplit, (int)n, C);
-    HMSCHK(h, hipGetLastError());
-    HMSCHK(h, hipEventRecord(h->ev[4], st));
-    h->mu_h.resize((size_t)h->nfeat);
-    HMSCHK(h, hipMemcpyAsync(h->mu_h.data(), h->mu, sizeof(double) * h->nfeat, hipMemcpyDeviceToHost, st));
-    HMSCHK(h, hipMemcpyAsync(cov, C, sizeof(double) * n * n, hipMemcpyDeviceToHost, st));
-    HMSCHK(h, hipStreamSynchronize(st));
-    h->ms[1] = pcafit_elapsed(h->ev[2], h->ev[3]);
-    h->ms[2] = pcafit_elapsed(h->ev[3], h->ev[4]);
-    return GPRX_OK;
-  };
-  rc = run();
-  hipStreamSynchronize(st);
-  hipFree(m2);
-  return rc;
-}
-
-// Gram route: E = diag(lambda^-1/2) U_k^T X2 (GEMM, K = rows padded to 16), svd_flip on its rows (pcafit_sign_flip_kernel)
-int hms_components(gprx_hms_handle h, int k, const double* u, const double* lam, double* eofs) {
-  const int64_t rows = h->rows, rp = round_up(rows, 16), ld2 = h->ld2;
-  hipStream_t st = h->stream;
-  std::vector<double> a((size_t)k * rp, 0.0);
-  for (int i = 0; i < k; ++i) {
-    const double s = 1.0 / std::sqrt(lam[i]);
-    for (int64_t t = 0; t < rows; ++t) a[(size_t)i * rp + t] = u[(size_t)t * k + i] * s;
-  }
-  int rc;
-  if ((rc = hms_need(h, 8.0 * ((double)a.size() + (double)k * ld2), "the components"))) return rc;
-  double *A = nullptr, *E = nullptr;
-  auto run = [&]() -> int {
-    HMSCHK(h, hipMalloc((void**)&A, sizeof(double) * a.size()));
-    HMSCHK(h, hipMalloc((void**)&E, sizeof(double) * (size_t)k * ld2));
-    HMSCHK(h, hipMemcpyAsync(A, a.data(), sizeof(double) * a.size(), hipMemcpyHostToDevice, st));
-    HMSCHK(h, hipEventRecord(h->ev[4], st));
-    HMSCHK(h, launch_gemm(st, 0, 0, k, (int)ld2, (int)rp, 1.0, A, rp, h->X2, ld2, 0.0, E, ld2, 0));
-    hipLaunchKernelGGL(pcafit_sign_flip_kernel, dim3((unsigned)k), dim3(256), 0, st, E, ld2, h->p);
-    HMSCHK(h, hipGetLastError());
-    HMSCHK(h, hipEventRecord(h->ev[5], st));
-    HMSCHK(h, hipMemcpy2DAsync(eofs, sizeof(double) * h->p, E, sizeof(double) * ld2, sizeof(double) * h->p, (size_t)k, hipMemcpyDeviceToHost, st));
-    HMSCHK(h, hipStreamSynchronize(st));
-    h->ms[3] = pcafit_elapsed(h->ev[4], h->ev[5]);
-    return GPRX_OK;
-  };
-  rc = run();
-  hipStreamSynchronize(st);
-  if (A) hipFree(A);
-  if (E) hipFree(E);
-  return rc;
-}
-
-// API on device vectors: lags = how many lags are summed (>= n_w: the weights beyond n_w are zeros)
-hipError_t hms_api_launch(hipStream_t st, const double* a, int64_t n, const double* w, int64_t n_w, int64_t lags, double* out) {
-  if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(hms_api_kernel, dim3((unsigned)((n + HMS_API_BT - 1) / HMS_API_BT)), dim3(HMS_API_NT), 0, st, a, n, w, n_w, lags, out);
-  return hipGetLastError();
-}
-
-// features [x_bc, x_precip eofs^T, avg_precip, api_1, api_2] (:1251-1257, :1271-1277); fit: x_mean / x_std out; transform: out
-int hms_features(gprx_hms_handle h, int ke, const double* eofs, const double* w1, int64_t n1, const double* w2, int64_t n2, double* x_mean,
-                 double* x_std, int fit, double* out) {
-  const int64_t rows = h->rows, p = h->p, n_bc = h->n_bc, nf = n_bc + ke + 3;
-  hipStream_t st = h->stream;
-  const int nmb = std::max(1, (ke + HMS_MB - 1) / HMS_MB);
-  const int64_t ke_pad = (int64_t)nmb * HMS_MB;
-  std::vector<double> et((size_t)p * ke_pad, 0.0), mup((size_t)p), mub((size_t)std::max<int64_t>(n_bc, 1), 0.0);
-  for (int i = 0; i < ke; ++i)
-    for (int64_t j = 0; j < p; ++j) et[(size_t)j * ke_pad + i] = eofs[(size_t)i * p + j];
-  for (int64_t j = 0; j < p; ++j) mup[j] = h->mu_h[h->pc_h[j]];
-  for (int64_t b = 0; b < n_bc; ++b) mub[b] = h->mu_h[h->bc_h[b]];
-  int rc;
-  if ((rc = hms_need(h, 8.0 * ((double)et.size() + p + n_bc + n1 + n2 + 2.0 * nf + (double)nf * rows * (fit ? 1 : 2)) + 64, "the features")))
-    return rc;
-  double *Et = nullptr, *Mp = nullptr, *Mb = nullptr, *W1 = nullptr, *W2 = nullptr, *F = nullptr, *S = nullptr, *O = nullptr;
-  int* flag = nullptr;
-  auto run = [&]() -> int {
-    HMSCHK(h, hipMalloc((void**)&Et, sizeof(double) * et.size()));
-    HMSCHK(h, hipMalloc((void**)&Mp, sizeof(double) * p));
-    HMSCHK(h, hipMalloc((void**)&Mb, sizeof(double) * mub.size()));
-    HMSCHK(h, hipMalloc((void**)&W1, sizeof(double) * std::max<int64_t>(n1, 1)));
-    HMSCHK(h, hipMalloc((void**)&W2, sizeof(double) * std::max<int64_t>(n2, 1)));
-    HMSCHK(h, hipMalloc((void**)&F, sizeof(double) * (size_t)nf * rows));
-    HMSCHK(h, hipMalloc((void**)&S, sizeof(double) * 2 * nf));
-    HMSCHK(h, hipMalloc((void**)&flag, sizeof(int)));
-    HMSCHK(h, hipMemcpyAsync(Et, et.data(), sizeof(double) * et.size(), hipMemcpyHostToDevice, st));
-    HMSCHK(h, hipMemcpyAsync(Mp, mup.data(), sizeof(double) * p, hipMemcpyHostToDevice, st));
-    HMSCHK(h, hipMemcpyAsync(Mb, mub.data(), sizeof(double) * mub.size(), hipMemcpyHostToDevice, st));
-    if (n1) HMSCHK(h, hipMemcpyAsync(W1, w1, sizeof(double) * n1, hipMemcpyHostToDevice, st));
-    if (n2) HMSCHK(h, hipMemcpyAsync(W2, w2, sizeof(double) * n2, hipMemcpyHostToDevice, st));
-    HMSCHK(h, hipMemsetAsync(flag, 0, sizeof(int), st));
-    HMSCHK(h, hipEventRecord(h->ev[5], st));
-    hipLaunchKernelGGL(hms_project_kernel, dim3((unsigned)((rows + 255) / 256), (unsigned)nmb), dim3(256), 0, st, (const double*)h->X, rows, rows,
-                       (const int64_t*)h->pc, (const double*)Mp, p, (const double*)Et, ke_pad, ke, (const int64_t*)h->bc, (const double*)Mb, n_bc, F,
-                       rows, flag);
-    HMSCHK(h, hipGetLastError());
-    HMSCHK(h, hipEventRecord(h->ev[6], st));
-    int nonfinite = 0;
-    HMSCHK(h, hipMemcpyAsync(&nonfinite, flag, sizeof(int), hipMemcpyDeviceToHost, st));
-    HMSCHK(h, hipStreamSynchronize(st));
-    // the exactly-zero tail of the weights is cut only when avg_precip is finite (0 * inf or 0 * NaN would be NaN)
-    const double* a = F + (n_bc + ke) * rows;
-    HMSCHK(h, hms_api_launch(st, a, rows, W1, n1, nonfinite ? rows : std::min(n1, rows), F + (n_bc + ke + 1) * rows));
-    HMSCHK(h, hms_api_launch(st, a, rows, W2, n2, nonfinite ? rows : std::min(n2, rows), F + (n_bc + ke + 2) * rows));
-    HMSCHK(h, hipEventRecord(h->ev[7], st));
-    if (fit) {
-      hipLaunchKernelGGL(hms_colstats_kernel, dim3((unsigned)nf), dim3(256), 0, st, (const double*)F, rows, rows, S, S + nf);
-      HMSCHK(h, hipGetLastError());
-      HMSCHK(h, hipEventRecord(h->ev[0], st));
-      HMSCHK(h, hipMemcpyAsync(x_mean, S, sizeof(double) * nf, hipMemcpyDeviceToHost, st));
-      HMSCHK(h, hipMemcpyAsync(x_std, S + nf, sizeof(double) * nf, hipMemcpyDeviceToHost, st));
-    } else {
-      HMSCHK(h, hipMalloc((void**)&O, sizeof(double) * (size_t)nf * rows));
-      HMSCHK(h, hipMemcpyAsync(S, x_mean, sizeof(double) * nf, hipMemcpyHostToDevice, st));
-      HMSCHK(h, hipMemcpyAsync(S + nf, x_std, sizeof(double) * nf, hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL(hms_standardise_kernel, dim3((unsigned)((nf * rows + 255) / 256)), dim3(256), 0, st, (const double*)F, rows, rows, nf,
-                         (const double*)S, (const double*)(S + nf), O);
-      HMSCHK(h, hipGetLastError());
-      HMSCHK(h, hipEventRecord(h->ev[0], st));
-      HMSCHK(h, hipMemcpyAsync(out, O, sizeof(double) * nf * rows, hipMemcpyDeviceToHost, st));
-    }
-    HMSCHK(h, hipStreamSynchronize(st));
-    h->ms[4] = pcafit_elapsed(h->ev[5], h->ev[6]);
-    h->ms[5] = pcafit_elapsed(h->ev[6], h->ev[7]);
-    h->ms[6] = pcafit_elapsed(h->ev[7], h->ev[0]);
-    return GPRX_OK;
-  };
-  rc = run();
-  hipStreamSynchronize(st);
-  for (void* q : {(void*)Et, (void*)Mp, (void*)Mb, (void*)W1, (void*)W2, (void*)F, (void*)S, (void*)O, (void*)flag})
-    if (q) hipFree(q);
-  return rc;
-}
-}  // namespace
-
-int gprx_hms_destroy(gprx_hms_handle h) {
-  if (!h) return GPRX_OK;
-  hipSetDevice(h->device);
-  if (h->stream) hipStreamSynchronize(h->stream);
-  for (void* q : {(void*)h->X, (void*)h->mu, (void*)h->X2, (void*)h->ws, (void*)h->bc, (void*)h->pc})
-    if (q) hipFree(q);
-  for (hipEvent_t e : h->ev)
-    if (e) hipEventDestroy(e);
-  if (h->stream) hipStreamDestroy(h->stream);
-  delete h;
-  return GPRX_OK;
-}
-
-int gprx_hms_create(int device, const double* x, int64_t rows, int64_t ld, int64_t n_features, int fortran, const int64_t* bc_idx, int64_t n_bc,
-                    const int64_t* precip_idx, int64_t n_precip, const double* input_mean, gprx_hms_handle* out) {
-  if (!out) return hfail(nullptr, GPRX_EINVAL, "out is null");
-  *out = nullptr;
-  if (!x || !precip_idx || (n_bc > 0 && !bc_idx)) return hfail(nullptr, GPRX_EINVAL, "null argument");
-  if (rows < 1 || n_features < 1 || n_bc < 0 || n_precip < 1) return hfail(nullptr, GPRX_EINVAL, "need rows >= 1 and at least one precip column");
-  if (ld < (fortran ? rows : n_features)) return hfail(nullptr, GPRX_EINVAL, "ld is smaller than the contiguous dimension of x");
-  if (rows > ((int64_t)1 << 31) - 1024 || n_features > 65535 * 32) return hfail(nullptr, GPRX_EINVAL, "x is too large");
-  for (int64_t j = 0; j < n_precip; ++j)
-    if (precip_idx[j] < 0 || precip_idx[j] >= n_features) return hfail(nullptr, GPRX_EINVAL, "precip column out of range");
-  for (int64_t j = 0; j < n_bc; ++j)
-    if (bc_idx[j] < 0 || bc_idx[j] >= n_features) return hfail(nullptr, GPRX_EINVAL, "bc column out of range");
-  if (std::min(rows, n_precip) > 16384) return hfail(nullptr, GPRX_EINVAL, "min(rows, precip columns) must be <= 16384 (host eigh)");
-  gprx_hms_handle h = nullptr;
-  try {
-    HMSCHK(nullptr, hipSetDevice(device));
-    h = new gprx_hms_ctx();
-    h->device = device;
-    h->rows = rows;
-    h->nfeat = n_features;
-    h->n_bc = n_bc;
-    h->p = n_precip;
-    h->bc_h.assign(bc_idx, bc_idx + n_bc);
-    h->pc_h.assign(precip_idx, precip_idx + n_precip);
-    int rc = GPRX_OK;
-    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    for (hipEvent_t& ev : h->ev)
-      if (e == hipSuccess) e = hipEventCreate(&ev);
-    if (e != hipSuccess) rc = hfail(nullptr, GPRX_EHIP, std::string("hipStreamCreate / hipEventCreate: ") + hipGetErrorString(e));
-    const double staged = fortran ? 0.0 : (double)std::min<int64_t>(rows, std::max<int64_t>(32, ((int64_t)1 << 22) / n_features)) * n_features;
-    if (!rc) rc = hms_need(h, 8.0 * ((double)rows * n_features + staged + n_features + n_bc + n_precip), "x");
-    auto setup = [&]() -> int {
-      HMSCHK(h, hipMalloc((void**)&h->X, sizeof(double) * (size_t)rows * n_features));
-      HMSCHK(h, hipMalloc((void**)&h->mu, sizeof(double) * n_features));
-      HMSCHK(h, hipMalloc((void**)&h->pc, sizeof(int64_t) * n_precip));
-      HMSCHK(h, hipMalloc((void**)&h->bc, sizeof(int64_t) * std::max<int64_t>(n_bc, 1)));
-      HMSCHK(h, hipMemcpyAsync(h->pc, precip_idx, sizeof(int64_t) * n_precip, hipMemcpyHostToDevice, h->stream));
-      if (n_bc) HMSCHK(h, hipMemcpyAsync(h->bc, bc_idx, sizeof(int64_t) * n_bc, hipMemcpyHostToDevice, h->stream));
-      if (input_mean) {
-        h->mu_h.assign(input_mean, input_mean + n_features);
-        HMSCHK(h, hipMemcpyAsync(h->mu, input_mean, sizeof(double) * n_features, hipMemcpyHostToDevice, h->stream));
-      }
-      int rc2 = hms_upload(h, x, ld, fortran);
-      if (rc2) return rc2;
-      HMSCHK(h, hipStreamSynchronize(h->stream));
-      h->ms[0] = pcafit_elapsed(h->ev[0], h->ev[1]);
-      return GPRX_OK;
-    };
-    if (!rc) rc = setup();
-    if (rc) {
-      gprx_hms_destroy(h);
-      return rc;
-    }
-  } catch (const std::bad_alloc&) {
-    gprx_hms_destroy(h);
-    return hfail(nullptr, GPRX_ENOMEM, "host allocation failed");
-  }
-  *out = h;
-  return GPRX_OK;
-}
-
-int gprx_hms_cov(gprx_hms_handle h, double* input_mean, double* cov, int* route) {
-  if (!h) return hfail(h, GPRX_EINVAL, "null handle");
-  if (!input_mean || !cov || !route) return hfail(h, GPRX_EINVAL, "null argument");
-  if (h->route >= 0 || !h->mu_h.empty()) return hfail(h, GPRX_ESTATE, "the covariance is computed once, by a handle created without input_mean");
-  if (h->rows < 2) return hfail(h, GPRX_EINVAL, "the fit needs rows >= 2");
-  try {
-    HMSCHK(h, hipSetDevice(h->device));
-    const int rc = hms_cov(h, cov);
-    if (rc) return rc;
-  } catch (const std::bad_alloc&) {
-    return hfail(h, GPRX_ENOMEM, "host allocation failed");
-  }
-  std::memcpy(input_mean, h->mu_h.data(), sizeof(double) * h->nfeat);
-  *route = h->route;
-  return GPRX_OK;
-}
-
-int gprx_hms_components(gprx_hms_handle h, int k, const double* u, const double* lam, double* eofs) {
-  if (!h) return hfail(h, GPRX_EINVAL, "null handle");
-  if (h->route != HMS_GRAM) return hfail(h, GPRX_ESTATE, "components are formed on the device only on the Gram route (rows < precip columns)");
-  if (k < 0 || k >= h->rows) return hfail(h, GPRX_EINVAL, "need 0 <= k < rows (centring removes one direction)");
-  if (k == 0) return GPRX_OK;
-  if (!u || !lam || !eofs) return hfail(h, GPRX_EINVAL, "null argument");
-  for (int i = 0; i < k; ++i)
-    if (!(lam[i] > 0.0)) return hfail(h, GPRX_EINVAL, "retained eigenvalues must be positive");
-  try {
-    HMSCHK(h, hipSetDevice(h->device));
-    return hms_components(h, k, u, lam, eofs);
-  } catch (const std::bad_alloc&) {
-    return hfail(h, GPRX_ENOMEM, "host allocation failed");
-  }
-}
-
-int gprx_hms_features(gprx_hms_handle h, int k, const double* eofs, const double* w1, int64_t n1, const double* w2, int64_t n2, double* x_mean,
-                      double* x_std, int fit, double* out) {
-  if (!h) return hfail(h, GPRX_EINVAL, "null handle");
-  if (k < 0 || n1 < 0 || n2 < 0 || (k > 0 && !eofs) || (n1 > 0 && !w1) || (n2 > 0 && !w2) || !x_mean || !x_std || (!fit && !out))
-    return hfail(h, GPRX_EINVAL, "null or negative argument");
-  if (h->mu_h.empty()) return hfail(h, GPRX_ESTATE, "input_mean is not known: run gprx_hms_cov first or pass it to gprx_hms_create");
-  try {
-    HMSCHK(h, hipSetDevice(h->device));
-    return hms_features(h, k, eofs, w1, n1, w2, n2, x_mean, x_std, fit, out);
-  } catch (const std::bad_alloc&) {
-    return hfail(h, GPRX_ENOMEM, "host allocation failed");
-  }
-}
-
-int gprx_hms_timings(gprx_hms_handle h, double* ms) {
-  if (!h || !ms) return hfail(h, GPRX_EINVAL, "null argument");
-  for (int i = 0; i < 7; ++i) ms[i] = h->ms[i];
-  return GPRX_OK;
-}
-
-int gprx_api(int device, const double* a, int64_t n, const double* w, int64_t n_w, int64_t window, double* out) {
-  if (n < 1 || window < 1) return hfail(nullptr, GPRX_EINVAL, "the series and the window must not be empty");
-  if (n_w < 0 || n_w > window || !a || !out || (n_w > 0 && !w)) return hfail(nullptr, GPRX_EINVAL, "need 0 <= n_w <= window and non-null arrays");
-  for (int64_t i = 0; i < n_w; ++i)
-    if (!std::isfinite(w[i])) return hfail(nullptr, GPRX_EINVAL, "the weights must be finite");
-  bool finite = true;
-  for (int64_t t = 0; t < n && finite; ++t) finite = std::isfinite(a[t]);
-  const int64_t lags = std::min(finite ? n_w : window, n);
-  HMSCHK(nullptr, hipSetDevice(device));
-  const int rc0 = hms_need(nullptr, 8.0 * (2.0 * n + std::max<int64_t>(n_w, 1)), "the API");
-  if (rc0) return rc0;
-  hipStream_t st = util_stream();
-  double *A = nullptr, *W = nullptr, *O = nullptr;
-  auto run = [&]() -> int {
-    HMSCHK(nullptr, hipMalloc((void**)&A, sizeof(double) * n));
-    HMSCHK(nullptr, hipMalloc((void**)&O, sizeof(double) * n));
-    HMSCHK(nullptr, hipMalloc((void**)&W, sizeof(double) * std::max<int64_t>(n_w, 1)));
-    HMSCHK(nullptr, hipMemcpyAsync(A, a, sizeof(double) * n, hipMemcpyHostToDevice, st));
-    if (n_w) HMSCHK(nullptr, hipMemcpyAsync(W, w, sizeof(double) * n_w, hipMemcpyHostToDevice, st));
-    HMSCHK(nullptr, hms_api_launch(st, A, n, W, n_w, lags, O));
-    HMSCHK(nullptr, hipMemcpyAsync(out, O, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-    HMSCHK(nullptr, hipStreamSynchronize(st));
-    return GPRX_OK;
-  };
-  const int rc = run();
-  hipStreamSynchronize(st);
-  for (void* q : {(void*)A, (void*)W, (void*)O})
-    if (q) hipFree(q);
-  return rc;
-}
-
-const char* gprx_hms_last_error(gprx_hms_handle h) { return h ? h->err.c_str() : g_err.c_str(); }
-
-// ---- pseudo-surface low-fidelity model (gpras/preprocess.py:454-697) ------------------------------------
-struct gprx_ps_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  int64_t cells = 0, C = 0, T = 0;
-  double *elev = nullptr, *w = nullptr, *us = nullptr, *ds = nullptr, *q = nullptr, *slab = nullptr, *cl = nullptr;
-  int* idx = nullptr;
-  double* spl[2] = {nullptr, nullptr};  // per curve: knots [0, PS_MAX_KNOTS), coefficients [PS_MAX_KNOTS, 2 PS_MAX_KNOTS)
-  int nt[2] = {0, 0};
-  size_t bnd_bytes = 0, q_bytes = 0, slab_bytes = 0, cl_bytes = 0;
-  bool have_w = false;
-  hipEvent_t ev[4] = {};  // around the last centerline fit kernel and the last surface launch
-  bool fit_timed = false, surface_timed = false;
-  std::string err;
-};
-
-namespace {
-int psfail(gprx_ps_handle h, int code, const std::string& msg) {
-  if (h) h->err = msg;
-  g_err = msg;
-  return code;
-}
-#define PSCHK(h, expr)                                                                                                \
-  do {                                                                                                                \
-    hipError_t e_ = (expr);                                                                                           \
-    if (e_ != hipSuccess)                                                                                             \
-      return psfail(h, e_ == hipErrorOutOfMemory ? GPRX_ENOMEM : GPRX_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-// the next allocations need `bytes` of device memory: GPRX_ENOMEM before any of them is made
-int ps_need(gprx_ps_handle h, double bytes, const char* what) {
-  size_t fr = 0, tot = 0;
-  PSCHK(h, hipMemGetInfo(&fr, &tot));
-  if (bytes > 0.95 * (double)fr)
-    return psfail(h, GPRX_ENOMEM, std::string(what) + " needs " + std::to_string((long long)(bytes / 1048576.0)) + " MiB of device memory, " +
-                                      std::to_string((long long)(fr / 1048576)) + " MiB are free");
-  return GPRX_OK;
-}
-
-int ps_ensure(gprx_ps_handle h, double*& p, size_t& have, size_t bytes, const char* what) {
-  if (have >= bytes) return GPRX_OK;
-  if (p) PSCHK(h, hipFree(p));
-  p = nullptr;
-  have = 0;
-  int rc = ps_need(h, (double)bytes, what);
-  if (rc) return rc;
-  PSCHK(h, hipMalloc((void**)&p, bytes));
-  have = bytes;
-  return GPRX_OK;
-}
-
-int ps_check_spline(gprx_ps_handle h, const double* t, int nt, const double* c) {
-  if (!t || !c) return psfail(h, GPRX_EINVAL, "null knots or coefficients");
-  if (nt < 8 || nt > PS_MAX_KNOTS) return psfail(h, GPRX_EINVAL, "a cubic spline needs 8 <= knots <= " + std::to_string(PS_MAX_KNOTS) + " (boundary knots included)");
-  for (int i = 0; i + 1 < nt; ++i)
-    if (!(t[i] <= t[i + 1])) return psfail(h, GPRX_EINVAL, "the knots must be finite and non-decreasing");
-  if (!(t[3] < t[nt - 4])) return psfail(h, GPRX_EINVAL, "the knots span an empty interval");
-  return GPRX_OK;
-}
-
-hipError_t ps_spline_launch(hipStream_t st, const double* x, int64_t n, const double* tc, int nt, double* out) {
-  const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 2048);
-  hipLaunchKernelGGL(ps_spline_kernel, dim3(grid), dim3(256), 0, st, x, n, tc, tc + PS_MAX_KNOTS, nt, out);
-  return hipGetLastError();
-}
-
-hipError_t ps_surface_launch(hipStream_t st, const PsSurfaceArgs& a) {
-  const int64_t pairs = (a.ldo + 1) / 2, tiles = ((pairs + PS_NT - 1) / PS_NT) * ((a.T + PS_RT - 1) / PS_RT);
-  const unsigned grid = (unsigned)std::min<int64_t>(tiles, 2048);
-  const size_t lds = a.w && a.C <= PS_W_LDS ? sizeof(double) * (size_t)a.C : 0;
-  const bool vf = a.fluvial && a.ldf % 2 == 0 && (uintptr_t)a.fluvial % 16 == 0;
-  const bool vo = a.ldo % 2 == 0 && (uintptr_t)a.out % 16 == 0;
-  if (vf && vo)
-    hipLaunchKernelGGL((ps_surface_kernel<true, true>), dim3(grid), dim3(PS_NT), lds, st, a);
-  else if (vo)
-    hipLaunchKernelGGL((ps_surface_kernel<false, true>), dim3(grid), dim3(PS_NT), lds, st, a);
-  else if (vf)
-    hipLaunchKernelGGL((ps_surface_kernel<true, false>), dim3(grid), dim3(PS_NT), lds, st, a);
-  else
-    hipLaunchKernelGGL((ps_surface_kernel<false, false>), dim3(grid), dim3(PS_NT), lds, st, a);
-  return hipGetLastError();
-}
-
-int ps_boundary_buffers(gprx_ps_handle h, int64_t T) {
-  if (T < 1 || T > ((int64_t)1 << 31) - 1024) return psfail(h, GPRX_EINVAL, "need 1 <= T < 2^31 rows");
-  const size_t bytes = sizeof(double) * 2 * (size_t)T;
-  if (h->bnd_bytes < bytes) {
-    int rc = ps_ensure(h, h->us, h->bnd_bytes, bytes, "the boundary series");
-    if (rc) return rc;
-    h->ds = h->us + T;
-  }
-  h->ds = h->us + T;
-  h->T = T;
-  return GPRX_OK;
-}
-}  // namespace
-
-int gprx_ps_destroy(gprx_ps_handle h) {
-  if (!h) return GPRX_OK;
-  hipSetDevice(h->device);
-  if (h->stream) hipStreamSynchronize(h->stream);
-  for (void* q : {(void*)h->elev, (void*)h->w, (void*)h->us, (void*)h->q, (void*)h->slab, (void*)h->cl, (void*)h->idx, (void*)h->spl[0], (void*)h->spl[1]})
-    if (q) hipFree(q);
-  for (hipEvent_t e : h->ev)
-    if (e) hipEventDestroy(e);
-  if (h->stream) hipStreamDestroy(h->stream);
-  delete h;
-  return GPRX_OK;
-}
-
-int gprx_ps_create(int device, int64_t n_cells, const double* elev, const int32_t* idx, int64_t n_centerline, const double* w, const double* us_knots,
-                   int us_nt, const double* us_coef, const double* ds_knots, int ds_nt, const double* ds_coef, gprx_ps_handle* out) {
-  if (!out) return psfail(nullptr, GPRX_EINVAL, "out is null");
-  *out = nullptr;
-  if (!elev || !idx) return psfail(nullptr, GPRX_EINVAL, "null argument");
-  if (n_cells < 1 || n_centerline < 1 || n_cells > ((int64_t)1 << 31) - 1024 || n_centerline > ((int64_t)1 << 31) - 1024)
-    return psfail(nullptr, GPRX_EINVAL, "need 1 <= n_cells, n_centerline < 2^31");
-  for (int64_t c = 0; c < n_cells; ++c)
-    if (idx[c] < 0 || idx[c] >= n_centerline) return psfail(nullptr, GPRX_EINVAL, "cell_interpolater holds an index outside [0, n_centerline)");
-  const double* kn[2] = {us_knots, ds_knots};
-  const double* co[2] = {us_coef, ds_coef};
-  const int nts[2] = {us_nt, ds_nt};
-  int rc = GPRX_OK;
-  for (int s = 0; s < 2; ++s)
-    if (nts[s] != 0 && (rc = ps_check_spline(nullptr, kn[s], nts[s], co[s]))) return rc;
-  gprx_ps_handle h = nullptr;
-  try {
-    PSCHK(nullptr, hipSetDevice(device));
-    h = new gprx_ps_ctx();
-    h->device = device;
-    h->cells = n_cells;
-    h->C = n_centerline;
-    const int64_t ce = round_up(n_cells, 2);  // the surface kernel reads idx and elev in pairs
-    std::vector<double> el(ce, 0.0);
-    std::vector<int> ix(ce, 0);
-    std::copy(elev, elev + n_cells, el.begin());
-    std::copy(idx, idx + n_cells, ix.begin());
-    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    for (hipEvent_t& ev : h->ev)
-      if (e == hipSuccess) e = hipEventCreate(&ev);
-    if (e != hipSuccess) rc = psfail(nullptr, GPRX_EHIP, std::string("hipStreamCreate / hipEventCreate: ") + hipGetErrorString(e));
-    if (!rc) rc = ps_need(h, 12.0 * ce + 8.0 * n_centerline + 32.0 * PS_MAX_KNOTS, "the pseudo-surface state");
-    std::vector<double> tc[2];  // staged until the stream is idle, on the failure path too (gprx_ps_destroy waits for it)
-    auto setup = [&]() -> int {
-      PSCHK(h, hipMalloc((void**)&h->elev, sizeof(double) * ce));
-      PSCHK(h, hipMalloc((void**)&h->idx, sizeof(int) * ce));
-      PSCHK(h, hipMalloc((void**)&h->w, sizeof(double) * n_centerline));
-      PSCHK(h, hipMemcpyAsync(h->elev, el.data(), sizeof(double) * ce, hipMemcpyHostToDevice, h->stream));
-      PSCHK(h, hipMemcpyAsync(h->idx, ix.data(), sizeof(int) * ce, hipMemcpyHostToDevice, h->stream));
-      if (w) {
-        PSCHK(h, hipMemcpyAsync(h->w, w, sizeof(double) * n_centerline, hipMemcpyHostToDevice, h->stream));
-        h->have_w = true;
-      }
-      for (int s = 0; s < 2; ++s) {
-        if (!nts[s]) continue;
-        tc[s].assign(2 * PS_MAX_KNOTS, 0.0);
-        std::copy(kn[s], kn[s] + nts[s], tc[s].begin());
-        std::copy(co[s], co[s] + nts[s] - 4, tc[s].begin() + PS_MAX_KNOTS);
-        PSCHK(h, hipMalloc((void**)&h->spl[s], sizeof(double) * 2 * PS_MAX_KNOTS));
-        PSCHK(h, hipMemcpyAsync(h->spl[s], tc[s].data(), sizeof(double) * 2 * PS_MAX_KNOTS, hipMemcpyHostToDevice, h->stream));
-        h->nt[s] = nts[s];
-      }
-      PSCHK(h, hipStreamSynchronize(h->stream));  // the host vectors above are read until here
-      return GPRX_OK;
-    };
-    if (!rc) rc = setup();
-    if (rc) {
-      gprx_ps_destroy(h);
-      return rc;
-    }
-  } catch (const std::bad_alloc&) {
-    gprx_ps_destroy(h);
-    return psfail(nullptr, GPRX_ENOMEM, "host allocation failed");
-  }
-  *out = h;
-  return GPRX_OK;
-}
-
-int gprx_spline_eval(int device, const double* knots, int nt, const double* coef, const double* x, int64_t n, double* out) {
-  int rc = ps_check_spline(nullptr, knots, nt, coef);
-  if (rc) return rc;
-  if (n < 0 || (n > 0 && (!x || !out))) return psfail(nullptr, GPRX_EINVAL, "null argument");
-  if (n == 0) return GPRX_OK;
-  PSCHK(nullptr, hipSetDevice(device));
-  if ((rc = ps_need(nullptr, 16.0 * n + 16.0 * PS_MAX_KNOTS, "the spline evaluation"))) return rc;
-  hipStream_t st = util_stream();
-  double *X = nullptr, *O = nullptr, *TC = nullptr;
-  std::vector<double> tc;  // read by the stream until the synchronisation below
-  auto run = [&]() -> int {
-    tc.assign(2 * PS_MAX_KNOTS, 0.0);
-    std::copy(knots, knots + nt, tc.begin());
-    std::copy(coef, coef + nt - 4, tc.begin() + PS_MAX_KNOTS);
-    PSCHK(nullptr, hipMalloc((void**)&X, sizeof(double) * n));
-    PSCHK(nullptr, hipMalloc((void**)&O, sizeof(double) * n));
-    PSCHK(nullptr, hipMalloc((void**)&TC, sizeof(double) * 2 * PS_MAX_KNOTS));
-    PSCHK(nullptr, hipMemcpyAsync(X, x, sizeof(double) * n, hipMemcpyHostToDevice, st));
-    PSCHK(nullptr, hipMemcpyAsync(TC, tc.data(), sizeof(double) * 2 * PS_MAX_KNOTS, hipMemcpyHostToDevice, st));
-    PSCHK(nullptr, ps_spline_launch(st, X, n, TC, nt, O));
-    PSCHK(nullptr, hipMemcpyAsync(out, O, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-    PSCHK(nullptr, hipStreamSynchronize(st));
-    return GPRX_OK;
-  };
-  try {
-    rc = run();
-  } catch (const std::bad_alloc&) {
-    rc = psfail(nullptr, GPRX_ENOMEM, "host allocation failed");
-  }
-  hipStreamSynchronize(st);
-  for (void* q : {(void*)X, (void*)O, (void*)TC})
-    if (q) hipFree(q);
-  return rc;
-}
-
-int gprx_ps_set_weights(gprx_ps_handle h, const double* w) {
-  if (!h) return psfail(h, GPRX_EINVAL, "null handle");
-  if (!w) return psfail(h, GPRX_EINVAL, "null argument");
-  PSCHK(h, hipSetDevice(h->device));
-  PSCHK(h, hipMemcpyAsync(h->w, w, sizeof(double) * h->C, hipMemcpyHostToDevice, h->stream));
-  PSCHK(h, hipStreamSynchronize(h->stream));
-  h->have_w = true;
-  return GPRX_OK;
-}
-
-int gprx_ps_fit_centerline(gprx_ps_handle h, const double* us_wse, const double* ds_wse, const double* us_q, const double* ds_q,
-                           const double* centerline_wse, int64_t rows, double* w) {
-  if (!h) return psfail(h, GPRX_EINVAL, "null handle");
-  if (!us_wse || !ds_wse || !us_q || !ds_q || !centerline_wse || !w) return psfail(h, GPRX_EINVAL, "null argument");
-  if (rows < 1 || rows > ((int64_t)1 << 31) - 1024) return psfail(h, GPRX_EINVAL, "need 1 <= rows < 2^31");
-  PSCHK(h, hipSetDevice(h->device));
-  double *W = nullptr, *B = nullptr;
-  unsigned char* K = nullptr;
-  const int64_t C = h->C;
-  std::vector<unsigned char> keep;  // read by the stream until the synchronisation below
-  auto run = [&]() -> int {
-    keep.assign(rows, 0);
-    int64_t n_keep = 0;
-    for (int64_t r = 0; r < rows; ++r) n_keep += (keep[r] = (us_q[r] > 0 || ds_q[r] > 0) ? 1 : 0);
-    if (n_keep == 0) return psfail(h, GPRX_EINVAL, "no row has a positive upstream or downstream flow: the median is over nothing");
-    int rc = ps_need(h, 8.0 * ((double)rows * C + 2.0 * rows) + rows, "the centerline fit");
-    if (rc) return rc;
-    PSCHK(h, hipMalloc((void**)&W, sizeof(double) * (size_t)rows * C));
-    PSCHK(h, hipMalloc((void**)&B, sizeof(double) * 2 * rows));
-    PSCHK(h, hipMalloc((void**)&K, rows));
-    PSCHK(h, hipMemcpyAsync(W, centerline_wse, sizeof(double) * (size_t)rows * C, hipMemcpyHostToDevice, h->stream));
-    PSCHK(h, hipMemcpyAsync(B, us_wse, sizeof(double) * rows, hipMemcpyHostToDevice, h->stream));
-    PSCHK(h, hipMemcpyAsync(B + rows, ds_wse, sizeof(double) * rows, hipMemcpyHostToDevice, h->stream));
-    PSCHK(h, hipMemcpyAsync(K, keep.data(), rows, hipMemcpyHostToDevice, h->stream));
-    PSCHK(h, hipEventRecord(h->ev[0], h->stream));
-    hipLaunchKernelGGL(ps_fit_kernel, dim3((unsigned)((C + PSF_COLS - 1) / PSF_COLS)), dim3(PSF_NT), 0, h->stream, (const double*)W, rows, C,
-                       (const double*)B, (const double*)(B + rows), (const unsigned char*)K, (unsigned)n_keep, h->w);
-    PSCHK(h, hipGetLastError());
-    PSCHK(h, hipEventRecord(h->ev[1], h->stream));
-    PSCHK(h, hipMemcpyAsync(w, h->w, sizeof(double) * C, hipMemcpyDeviceToHost, h->stream));
-    PSCHK(h, hipStreamSynchronize(h->stream));
-    h->fit_timed = true;
-    h->have_w = true;
-    return GPRX_OK;
-  };
-  int rc;
-  try {
-    rc = run();
-  } catch (const std::bad_alloc&) {
-    rc = psfail(h, GPRX_ENOMEM, "host allocation failed");
-  }
-  hipStreamSynchronize(h->stream);
-  for (void* q : {(void*)W, (void*)B, (void*)K})
-    if (q) hipFree(q);
-  return rc;
-}
-
-int gprx_ps_timings(gprx_ps_handle h, double* ms) {
-  if (!h || !ms) return psfail(h, GPRX_EINVAL, "null argument");
-  PSCHK(h, hipSetDevice(h->device));
-  PSCHK(h, hipStreamSynchronize(h->stream));
-  float v[2] = {0.f, 0.f};
-  if (h->fit_timed) PSCHK(h, hipEventElapsedTime(&v[0], h->ev[0], h->ev[1]));
-  if (h->surface_timed) PSCHK(h, hipEventElapsedTime(&v[1], h->ev[2], h->ev[3]));
-  ms[0] = v[0];
-  ms[1] = v[1];
-  return GPRX_OK;
-}
-
-int gprx_ps_rating(gprx_ps_handle h, const double* us_q, const double* ds_q, int64_t T, double* us_wse, double* ds_wse) {
-  if (!h) return psfail(h, GPRX_EINVAL, "null handle");
-  if (!us_q || !ds_q) return psfail(h, GPRX_EINVAL, "null argument");
-  if (!h->nt[0] || !h->nt[1]) return psfail(h, GPRX_ESTATE, "the handle was created without rating curves");
-  PSCHK(h, hipSetDevice(h->device));
-  int rc = ps_boundary_buffers(h, T);
-  if (rc) return rc;
-  if ((rc = ps_ensure(h, h->q, h->q_bytes, sizeof(double) * 2 * (size_t)T, "the flows"))) return rc;
-  PSCHK(h, hipMemcpyAsync(h->q, us_q, sizeof(double) * T, hipMemcpyHostToDevice, h->stream));
-  PSCHK(h, hipMemcpyAsync(h->q + T, ds_q, sizeof(double) * T, hipMemcpyHostToDevice, h->stream));
-  PSCHK(h, ps_spline_launch(h->stream, h->q, T, h->spl[0], h->nt[0], h->us));
-  PSCHK(h, ps_spline_launch(h->stream, h->q + T, T, h->spl[1], h->nt[1], h->ds));
-  if (us_wse) PSCHK(h, hipMemcpyAsync(us_wse, h->us, sizeof(double) * T, hipMemcpyDeviceToHost, h->stream));
-  if (ds_wse) PSCHK(h, hipMemcpyAsync(ds_wse, h->ds, sizeof(double) * T, hipMemcpyDeviceToHost, h->stream));
-  PSCHK(h, hipStreamSynchronize(h->stream));
-  return GPRX_OK;
-}
-
-int gprx_ps_set_boundaries(gprx_ps_handle h, const double* us_wse, const double* ds_wse, int64_t T) {
-  if (!h) return psfail(h, GPRX_EINVAL, "null handle");
-  if (!us_wse || !ds_wse) return psfail(h, GPRX_EINVAL, "null argument");
-  PSCHK(h, hipSetDevice(h->device));
-  int rc = ps_boundary_buffers(h, T);
-  if (rc) return rc;
-  PSCHK(h, hipMemcpyAsync(h->us, us_wse, sizeof(double) * T, hipMemcpyHostToDevice, h->stream));
-  PSCHK(h, hipMemcpyAsync(h->ds, ds_wse, sizeof(double) * T, hipMemcpyHostToDevice, h->stream));
-  PSCHK(h, hipStreamSynchronize(h->stream));
-  return GPRX_OK;
-}
-
-int gprx_ps_surface_dev(gprx_ps_handle h, int64_t t0, int64_t rows, const double* fluvial_dev, int64_t ldf, double* out_dev, int64_t ldo) {
-  if (!h) return psfail(h, GPRX_EINVAL, "null handle");
-  if (rows == 0) return GPRX_OK;
-  if (!out_dev) return psfail(h, GPRX_EINVAL, "null argument");
-  if (!h->have_w) return psfail(h, GPRX_ESTATE, "the centerline interpolater is not set: fit it or pass it to gprx_ps_create");
-  if (h->T == 0) return psfail(h, GPRX_ESTATE, "no boundary series: call gprx_ps_rating or gprx_ps_set_boundaries first");
-  if (t0 < 0 || rows < 0 || t0 + rows > h->T) return psfail(h, GPRX_EINVAL, "rows [t0, t0 + rows) lie outside the boundary series");
-  if (ldo < h->cells || (fluvial_dev && ldf < h->cells)) return psfail(h, GPRX_EINVAL, "a leading dimension is smaller than n_cells");
-  if (fluvial_dev == out_dev && ldf != ldo) return psfail(h, GPRX_EINVAL, "in place needs equal leading dimensions");
-  PSCHK(h, hipSetDevice(h->device));
-  PsSurfaceArgs a{h->us + t0, h->ds + t0, h->w, nullptr, h->idx, h->elev, fluvial_dev, out_dev, rows, h->cells, h->C, ldf, ldo};
-  PSCHK(h, hipEventRecord(h->ev[2], h->stream));
-  PSCHK(h, ps_surface_launch(h->stream, a));
-  PSCHK(h, hipEventRecord(h->ev[3], h->stream));
-  h->surface_timed = true;
-  return GPRX_OK;
-}
-
-int gprx_ps_synchronize(gprx_ps_handle h) {
-  if (!h) return psfail(h, GPRX_EINVAL, "null handle");
-  PSCHK(h, hipStreamSynchronize(h->stream));
-  return GPRX_OK;
-}
-
-int gprx_ps_surface(gprx_ps_handle h, const double* fluvial, double* out) {
-  if (!h) return psfail(h, GPRX_EINVAL, "null handle");
-  if (!out) return psfail(h, GPRX_EINVAL, "null argument");
-  if (h->T == 0) return psfail(h, GPRX_ESTATE, "no boundary series: call gprx_ps_rating or gprx_ps_set_boundaries first");
-  PSCHK(h, hipSetDevice(h->device));
-  const int64_t cells = h->cells, chunk = std::max<int64_t>(64, pca_chunk_doubles() / cells);
-  int rc;
-  for (int64_t t0 = 0; t0 < h->T; t0 += chunk) {
-    const int64_t nr = std::min(chunk, h->T - t0);
-    if ((rc = ps_ensure(h, h->slab, h->slab_bytes, sizeof(double) * (size_t)nr * cells, "a slab of the surface"))) return rc;
-    if (fluvial) PSCHK(h, hipMemcpyAsync(h->slab, fluvial + t0 * cells, sizeof(double) * nr * cells, hipMemcpyHostToDevice, h->stream));
-    if ((rc = gprx_ps_surface_dev(h, t0, nr, fluvial ? h->slab : nullptr, cells, h->slab, cells))) return rc;  // in place
-    PSCHK(h, hipMemcpyAsync(out + t0 * cells, h->slab, sizeof(double) * nr * cells, hipMemcpyDeviceToHost, h->stream));
-    PSCHK(h, hipStreamSynchronize(h->stream));
-  }
-  return GPRX_OK;
-}
-
-int gprx_ps_centerline(gprx_ps_handle h, double* out) {
-  if (!h) return psfail(h, GPRX_EINVAL, "null handle");
-  if (!out) return psfail(h, GPRX_EINVAL, "null argument");
-  if (!h->have_w) return psfail(h, GPRX_ESTATE, "the centerline interpolater is not set: fit it or pass it to gprx_ps_create");
-  if (h->T == 0) return psfail(h, GPRX_ESTATE, "no boundary series: call gprx_ps_rating or gprx_ps_set_boundaries first");
-  PSCHK(h, hipSetDevice(h->device));
-  const int64_t C = h->C, chunk = std::max<int64_t>(64, pca_chunk_doubles() / C);
-  int rc;
-  for (int64_t t0 = 0; t0 < h->T; t0 += chunk) {
-    const int64_t nr = std::min(chunk, h->T - t0);
-    if ((rc = ps_ensure(h, h->slab, h->slab_bytes, sizeof(double) * (size_t)nr * C, "a slab of the centerline"))) return rc;
-    PsSurfaceArgs a{h->us + t0, h->ds + t0, h->w, nullptr, nullptr, nullptr, nullptr, h->slab, nr, C, C, C, C};
-    PSCHK(h, ps_surface_launch(h->stream, a));
-    PSCHK(h, hipMemcpyAsync(out + t0 * C, h->slab, sizeof(double) * nr * C, hipMemcpyDeviceToHost, h->stream));
-    PSCHK(h, hipStreamSynchronize(h->stream));
-  }
-  return GPRX_OK;
-}
-
-int gprx_ps_gather(gprx_ps_handle h, const double* centerline, int64_t rows, double* out) {
-  if (!h) return psfail(h, GPRX_EINVAL, "null handle");
-  if (rows < 0 || (rows > 0 && (!centerline || !out))) return psfail(h, GPRX_EINVAL, "null argument");
-  PSCHK(h, hipSetDevice(h->device));
-  const int64_t C = h->C, cells = h->cells, chunk = std::max<int64_t>(64, pca_chunk_doubles() / cells);
-  int rc;
-  for (int64_t t0 = 0; t0 < rows; t0 += chunk) {
-    const int64_t nr = std::min(chunk, rows - t0);
-    if ((rc = ps_ensure(h, h->slab, h->slab_bytes, sizeof(double) * (size_t)nr * cells, "a slab of the surface")) ||
-        (rc = ps_ensure(h, h->cl, h->cl_bytes, sizeof(double) * (size_t)nr * C, "a slab of the centerline")))
-      return rc;
-    PSCHK(h, hipMemcpyAsync(h->cl, centerline + t0 * C, sizeof(double) * nr * C, hipMemcpyHostToDevice, h->stream));
-    PsSurfaceArgs a{nullptr, nullptr, nullptr, h->cl, h->idx, nullptr, nullptr, h->slab, nr, cells, C, cells, cells};
-    PSCHK(h, ps_surface_launch(h->stream, a));
-    PSCHK(h, hipMemcpyAsync(out + t0 * cells, h->slab, sizeof(double) * nr * cells, hipMemcpyDeviceToHost, h->stream));
-    PSCHK(h, hipStreamSynchronize(h->stream));
-  }
-  return GPRX_OK;
-}
-
-const char* gprx_ps_last_error(gprx_ps_handle h) { return h ? h->err.c_str() : g_err.c_str(); }
-
-int gprx_pca_slab_rows(gprx_pca_handle p, int64_t* rows) {
-  if (!p || !rows) return pfail(p, GPRX_EINVAL, "null argument");
-  *rows = std::max<int64_t>(64, pca_chunk_doubles() / p->cells_p);
-  return GPRX_OK;
-}
-
-// ---- fused error metrics over reconstructed fields ----------------------------
-int gprx_metrics_dev(int device, const double* x_dev, const double* y_dev, const double* conf_dev, int64_t rows, int64_t cells, int t_tol,
-                     double v_tol, double* row_sums_dev, double* cell_sums_dev, int* cell_arg_dev, unsigned long long* matches) {
-  if (!x_dev || !y_dev || !row_sums_dev || !cell_sums_dev || !cell_arg_dev || !matches) return fail(nullptr, GPRX_EINVAL, "null argument");
-  if (rows <= 0 || cells <= 0 || rows > (1 << 30)) return fail(nullptr, GPRX_EINVAL, "rows and cells must be positive");
-  if (t_tol < 0 || t_tol > MET_TMAX) return fail(nullptr, GPRX_EINVAL, "t_tol must be between 0 and 8");
-  HIPCHK(nullptr, hipSetDevice(device));
-  const int nwg = (int)((cells + 255) / 256);
-  unsigned long long* match_partial = nullptr;
-  HIPCHK(nullptr, hipMalloc((void**)&match_partial, sizeof(unsigned long long) * nwg));
-  MetricsArgs a{x_dev, y_dev, conf_dev, rows, cells, v_tol, t_tol, cell_sums_dev, cell_sums_dev + cells, cell_sums_dev + 2 * cells,
-                cell_sums_dev + 3 * cells, cell_sums_dev + 4 * cells, cell_arg_dev, cell_arg_dev + cells, match_partial};
-  hipLaunchKernelGGL(metrics_cells_kernel, dim3(nwg), dim3(256), 0, util_stream(), a);
-  hipLaunchKernelGGL(metrics_rows_kernel, dim3((unsigned)rows), dim3(256), 0, util_stream(), x_dev, y_dev, conf_dev, cells, row_sums_dev);
-  std::vector<unsigned long long> hm(nwg);
-  hipError_t e = copy_sync(hm.data(), match_partial, sizeof(unsigned long long) * nwg, hipMemcpyDeviceToHost);  // synchronises
-  hipFree(match_partial);
-  HIPCHK(nullptr, e);
-  unsigned long long total = 0;
-  for (auto v : hm) total += v;
-  *matches = total;
-  return GPRX_OK;
-}
-
-int gprx_metrics(int device, const double* x, const double* y, const double* conf, int64_t rows, int64_t cells, int t_tol, double v_tol,
-                 double* row_sums, double* cell_sums, int* cell_arg, unsigned long long* matches) {
-  if (!x || !y || !row_sums || !cell_sums || !cell_arg || !matches) return fail(nullptr, GPRX_EINVAL, "null argument");
-  if (rows <= 0 || cells <= 0) return fail(nullptr, GPRX_EINVAL, "rows and cells must be positive");
-  HIPCHK(nullptr, hipSetDevice(device));
-  const size_t fb = sizeof(double) * (size_t)rows * cells;
-  double *dx = nullptr, *dy = nullptr, *dc = nullptr, *drow = nullptr, *dcell = nullptr;
-  int* darg = nullptr;
-  auto cleanup = [&]() {
-    for (void* q : {(void*)dx, (void*)dy, (void*)dc, (void*)drow, (void*)dcell, (void*)darg})
-      if (q) hipFree(q);
-  };
-  hipError_t e = hipMalloc((void**)&dx, fb);
-  if (e == hipSuccess) e = hipMalloc((void**)&dy, fb);
-  if (e == hipSuccess && conf) e = hipMalloc((void**)&dc, fb);
-  if (e == hipSuccess) e = hipMalloc((void**)&drow, sizeof(double) * rows * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&dcell, sizeof(double) * cells * 5);
-  if (e == hipSuccess) e = hipMalloc((void**)&darg, sizeof(int) * cells * 2);
-  if (e == hipSuccess) e = copy_sync(dx, x, fb, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = copy_sync(dy, y, fb, hipMemcpyHostToDevice);
-  if (e == hipSuccess && conf) e = copy_sync(dc, conf, fb, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    cleanup();
-    return fail(nullptr, e == hipErrorOutOfMemory ? GPRX_ENOMEM : GPRX_EHIP, std::string("gprx_metrics staging: ") + hipGetErrorString(e));
-  }
-  int rc = gprx_metrics_dev(device, dx, dy, dc, rows, cells, t_tol, v_tol, drow, dcell, darg, matches);
-  if (rc == GPRX_OK) {
-    e = copy_sync(row_sums, drow, sizeof(double) * rows * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = copy_sync(cell_sums, dcell, sizeof(double) * cells * 5, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = copy_sync(cell_arg, darg, sizeof(int) * cells * 2, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = fail(nullptr, GPRX_EHIP, std::string("gprx_metrics copy back: ") + hipGetErrorString(e));
-  }
-  cleanup();
-  return rc;
-}
-
-// ---- k-means inducing-point initialisation: Lloyd iterations on the device ---------------
-int gprx_kmeans_lloyd(int device, const double* x, int64_t n, int d, double* centers, int m, double tol, int max_iter, int32_t* labels,
-                      int* n_iter, int* empty) {
-  if (!x || !centers || !labels || !n_iter || !empty) return fail(nullptr, GPRX_EINVAL, "null argument");
-  if (n <= 0 || d <= 0 || d > 64 || m <= 0 || m > n || max_iter <= 0 || n > (1 << 30)) return fail(nullptr, GPRX_EINVAL, "need 0 < m <= n, 0 < d <= 64, max_iter > 0");
-  HIPCHK(nullptr, hipSetDevice(device));
-  double *dx = nullptr, *dc[2] = {nullptr, nullptr}, *dstat = nullptr;
-  int* dlab = nullptr;
-  auto cleanup = [&]() {
-    for (void* q : {(void*)dx, (void*)dc[0], (void*)dc[1], (void*)dstat, (void*)dlab})
-      if (q) hipFree(q);
-  };
-  const size_t cb = sizeof(double) * (size_t)m * d;
-  hipError_t e = hipMalloc((void**)&dx, sizeof(double) * (size_t)n * d);
-  if (e == hipSuccess) e = hipMalloc((void**)&dc[0], cb);
-  if (e == hipSuccess) e = hipMalloc((void**)&dc[1], cb);
-  if (e == hipSuccess) e = hipMalloc((void**)&dstat, sizeof(double) * (2 + m));
-  if (e == hipSuccess) e = hipMalloc((void**)&dlab, sizeof(int) * n);
-  if (e == hipSuccess) e = copy_sync(dx, x, sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = copy_sync(dc[0], centers, cb, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = memset_sync(dlab, 0xff, sizeof(int) * n);  // labels_old = -1 (_kmeans_single_lloyd)
-  if (e != hipSuccess) {
-    cleanup();
-    return fail(nullptr, e == hipErrorOutOfMemory ? GPRX_ENOMEM : GPRX_EHIP, std::string("gprx_kmeans_lloyd staging: ") + hipGetErrorString(e));
-  }
-  std::vector<double> stat(2 + m);
-  const dim3 pgrid((unsigned)((n + 255) / 256));
-  int cur = 0, it = 0;
-  bool strict = false;
-  *empty = 0;
-  for (it = 0; it < max_iter; ++it) {
-    // one iteration of lloyd_iter_chunked_dense: labels from the current centres, then the new centres and their shifts
-    // the flags are cleared on the stream the two kernels run on (a non-blocking stream has no ordering with the legacy stream)
-    e = hipMemsetAsync(dstat, 0, sizeof(double) * 2, util_stream());
-    if (e != hipSuccess) break;
-    hipLaunchKernelGGL(kmeans_assign_kernel, pgrid, dim3(256), 0, util_stream(), (const double*)dx, (int)n, d, (const double*)dc[cur], m, dlab, dstat);
-    hipLaunchKernelGGL(kmeans_update_kernel, dim3(m), dim3(256), 0, util_stream(), (const double*)dx, (int)n, d, (const int*)dlab, (const double*)dc[cur],
-                       dc[cur ^ 1], dstat);
-    e = copy_sync(stat.data(), dstat, sizeof(double) * (2 + m), hipMemcpyDeviceToHost);  // synchronises
-    if (e != hipSuccess) break;
-    if (stat[1] != 0.0) {  // scikit-learn relocates empty clusters to far points; the caller falls back to it
-      *empty = 1;
-      break;
-    }
-    cur ^= 1;  // centers, centers_new = centers_new, centers
-    if (stat[0] == 0.0) {  // labels equal labels_old: strict convergence
-      strict = true;
-      ++it;
-      break;
-    }
-    double shift_tot = 0.0;
-    for (int j = 0; j < m; ++j) shift_tot += stat[2 + j];
-    if (shift_tot <= tol) {
-      ++it;
-      break;
-    }
-  }
-  if (e == hipSuccess && !*empty && !strict) {
-    // rerun the E-step so that the labels match the final centres
-    hipLaunchKernelGGL(kmeans_assign_kernel, pgrid, dim3(256), 0, util_stream(), (const double*)dx, (int)n, d, (const double*)dc[cur], m, dlab, dstat);
-  }
-  if (e == hipSuccess) e = copy_sync(centers, dc[cur], cb, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = copy_sync(labels, dlab, sizeof(int) * n, hipMemcpyDeviceToHost);
-  cleanup();
-  HIPCHK(nullptr, e);
-  *n_iter = it > max_iter ? max_iter : it;
-  return GPRX_OK;
-}
-
-// k-means++ seeding on the device (kmeans.h): x (n, d) host, centred as scikit-learn centres it; xsq = row_norms(x, squared=True);
-// first_id and uniforms ((m - 1) x trials) are the host's RandomState draws.  indices_out: m chosen point indices.
-int gprx_kmeans_pp(int device, const double* x, int64_t n, int d, const double* xsq, int m, int trials, int64_t first_id, const double* uniforms,
-                   int64_t* indices_out) {
-  if (!x || !xsq || !indices_out || (m > 1 && !uniforms)) return fail(nullptr, GPRX_EINVAL, "null argument");
-  if (n <= 0 || d <= 0 || d > 64 || m <= 0 || m > n || trials <= 0 || trials > KPP_MAX_TRIALS || first_id < 0 || first_id >= n || n > (1 << 30))
-    return fail(nullptr, GPRX_EINVAL, "need 0 < m <= n, 0 < d <= 64, 0 < trials <= 16, 0 <= first_id < n");
-  HIPCHK(nullptr, hipSetDevice(device));
-  hipStream_t us = util_stream();
-  if (!us) return fail(nullptr, GPRX_EHIP, "no utility stream");
-  const int nblocks = (int)((n + 255) / 256);
-  double *dx = nullptr, *dsq = nullptr, *dbuf = nullptr, *dpart = nullptr, *duni = nullptr;
-  KppState* dst = nullptr;
-  long long* didx = nullptr;
-  auto cleanup = [&]() {
-    for (void* q : {(void*)dx, (void*)dsq, (void*)dbuf, (void*)dpart, (void*)duni, (void*)dst, (void*)didx})
-      if (q) hipFree(q);
-  };
-  const size_t slab = sizeof(double) * (size_t)trials * n;  // one generation of candidate distance arrays
-  hipError_t e = hipMalloc((void**)&dx, sizeof(double) * (size_t)n * d);
-  if (e == hipSuccess) e = hipMalloc((void**)&dsq, sizeof(double) * n);
-  if (e == hipSuccess) e = hipMalloc((void**)&dbuf, 2 * slab);
-  if (e == hipSuccess) e = hipMalloc((void**)&dpart, sizeof(double) * (size_t)trials * nblocks);
-  if (e == hipSuccess) e = hipMalloc((void**)&duni, sizeof(double) * (size_t)std::max(1, (m - 1) * trials));
-  if (e == hipSuccess) e = hipMalloc((void**)&dst, 2 * sizeof(KppState));
-  if (e == hipSuccess) e = hipMalloc((void**)&didx, sizeof(long long) * m);
-  if (e == hipSuccess) e = hipMemcpyAsync(dx, x, sizeof(double) * (size_t)n * d, hipMemcpyHostToDevice, us);
-  if (e == hipSuccess) e = hipMemcpyAsync(dsq, xsq, sizeof(double) * n, hipMemcpyHostToDevice, us);
-  if (e == hipSuccess && m > 1) e = hipMemcpyAsync(duni, uniforms, sizeof(double) * (size_t)(m - 1) * trials, hipMemcpyHostToDevice, us);
-  if (e != hipSuccess) {
-    hipStreamSynchronize(us);
-    cleanup();
-    return fail(nullptr, e == hipErrorOutOfMemory ? GPRX_ENOMEM : GPRX_EHIP, std::string("gprx_kmeans_pp staging: ") + hipGetErrorString(e));
-  }
-  double* gen[2] = {dbuf, dbuf + (size_t)trials * n};
-  // distances to the first centre: generation 0, one "candidate"
-  hipLaunchKernelGGL(kpp_dist_kernel, dim3(nblocks, 1), dim3(256), 0, us, (const double*)dx, (int)n, d, (const double*)dsq, (const KppState*)nullptr,
-                     (const double*)nullptr, (int)first_id, gen[0], dpart, nblocks);
-  int cur = 0, prev_trials = 1;
-  for (int c = 1; c <= m; ++c) {
-    // choose among the candidates of centre c - 1 (c == 1: the first centre itself); c < m: candidates of centre c
-    const bool more = c < m;
-    hipLaunchKernelGGL(kpp_select_kernel, dim3(1), dim3(256), 0, us, (int)n, (const double*)gen[cur], (const double*)dpart, nblocks, prev_trials,
-                       c == 1 ? (const KppState*)nullptr : (const KppState*)(dst + ((c - 1) & 1)), (int)first_id, dst + (c & 1),
-                       more ? (const double*)(duni + (size_t)(c - 1) * trials) : (const double*)nullptr, trials, didx + (c - 1));
-    if (!more) break;
-    hipLaunchKernelGGL(kpp_dist_kernel, dim3(nblocks, trials), dim3(256), 0, us, (const double*)dx, (int)n, d, (const double*)dsq,
-                       (const KppState*)(dst + (c & 1)), (const double*)gen[cur], (int)first_id, gen[cur ^ 1], dpart, nblocks);
-    cur ^= 1;
-    prev_trials = trials;
-  }
-  std::vector<long long> idx(m);
-  e = hipMemcpyAsync(idx.data(), didx, sizeof(long long) * m, hipMemcpyDeviceToHost, us);
-  hipError_t e2 = hipStreamSynchronize(us);
-  cleanup();
-  HIPCHK(nullptr, e);
-  HIPCHK(nullptr, e2);
-  for (int c = 0; c < m; ++c) indices_out[c] = idx[c];
-  return GPRX_OK;
-}
-
-int gprx_gather_rows(int device, const double* field_dev, int64_t rows, int64_t cells, const int64_t* idx, double* out) {
-  if (!field_dev || !idx || !out) return fail(nullptr, GPRX_EINVAL, "null argument");
-  if (rows <= 0 || cells <= 0) return fail(nullptr, GPRX_EINVAL, "rows and cells must be positive");
-  std::vector<int64_t> wrapped(idx, idx + cells);
-  for (int64_t c = 0; c < cells; ++c) {
-    if (wrapped[c] < -rows || wrapped[c] >= rows) {
-      char msg[160];
-      snprintf(msg, sizeof msg, "index %lld is out of bounds for axis 0 with size %lld", (long long)idx[c], (long long)rows);
-      return fail(nullptr, GPRX_EINVAL, msg);
-    }
-    if (wrapped[c] < 0) wrapped[c] += rows;
-  }
-  HIPCHK(nullptr, hipSetDevice(device));
-  int64_t* didx = nullptr;
-  double* dout = nullptr;
-  hipError_t e = hipMalloc((void**)&didx, sizeof(int64_t) * cells);
-  if (e == hipSuccess) e = hipMalloc((void**)&dout, sizeof(double) * cells);
-  if (e == hipSuccess) e = copy_sync(didx, wrapped.data(), sizeof(int64_t) * cells, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, util_stream(), field_dev, cells, (const int64_t*)didx, dout);
-    e = copy_sync(out, dout, sizeof(double) * cells, hipMemcpyDeviceToHost);  // synchronises
-  }
-  if (didx) hipFree(didx);
-  if (dout) hipFree(dout);
-  HIPCHK(nullptr, e);
   return GPRX_OK;
 }
 
@@ -4204,187 +2592,6 @@ int gprx_cell_bytes(gprx_handle h, int with_gradient, int64_t* bytes) {
   int64_t doubles = round_up((np + NB) * np + np * NB + np * STAGE_LD + np, 64);  // arena cell (ensure_arena)
   if (with_gradient) doubles += 2 * np * np + (np / KM_T) * (np / KM_T) * (2 + h->d) + (2 + h->d);  // garena + trace partials
   *bytes = (int64_t)sizeof(double) * doubles;
-  return GPRX_OK;
-}
-
-// ---- the one collective of the path: RCCL over xGMI -----------------------------------------
-namespace {
-int cfail(gprx_comm c, int code, const std::string& msg) {
-  if (c) c->err = msg;
-  g_err = msg;
-  return code;
-}
-#define COMMHIP(c, expr)                                                                                               \
-  do {                                                                                                                 \
-    hipError_t e_ = (expr);                                                                                            \
-    if (e_ != hipSuccess) return cfail(c, e_ == hipErrorOutOfMemory ? GPRX_ENOMEM : GPRX_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-#define COMMNCCL(c, expr)                                                                                              \
-  do {                                                                                                                 \
-    ncclResult_t r_ = (expr);                                                                                          \
-    if (r_ != ncclSuccess) return cfail(c, GPRX_ERCCL, std::string(#expr) + ": " + rccl().GetErrorString(r_));         \
-  } while (0)
-int comm_scratch(gprx_comm c, size_t bytes) {
-  if (c->scratch_bytes >= bytes) return GPRX_OK;
-  if (c->scratch) COMMHIP(c, hipFree(c->scratch));
-  c->scratch = nullptr;
-  c->scratch_bytes = 0;
-  COMMHIP(c, hipMalloc((void**)&c->scratch, bytes));
-  c->scratch_bytes = bytes;
-  return GPRX_OK;
-}
-}  // namespace
-
-// RCCL is loaded only after this process has initialised HIP and seen its devices: loaded first (measured on the MI355X
-// box: ncclGetUniqueId before any HIP call) it left the process with "no ROCm-capable device is detected".
-static int comm_runtime_ready() {
-  int count = 0;
-  COMMHIP(nullptr, hipInit(0));
-  COMMHIP(nullptr, hipGetDeviceCount(&count));
-  if (count <= 0) return cfail(nullptr, GPRX_EHIP, "no device visible to this process");
-  COMMHIP(nullptr, hipFree(nullptr));  // forces the runtime (context of the current device) into existence
-  if (!rccl().load()) return cfail(nullptr, GPRX_ERCCL, rccl().error);
-  return GPRX_OK;
-}
-
-int gprx_comm_runtime_check(int device) {
-  COMMHIP(nullptr, hipSetDevice(device));
-  return comm_runtime_ready();
-}
-
-int gprx_comm_unique_id(unsigned char* id128) {
-  if (!id128) return cfail(nullptr, GPRX_EINVAL, "null argument");
-  int rc0;
-  if ((rc0 = comm_runtime_ready())) return rc0;
-  ncclUniqueId id;
-  COMMNCCL(nullptr, rccl().GetUniqueId(&id));
-  static_assert(sizeof(id) == GPRX_UNIQUE_ID_BYTES, "ncclUniqueId size");
-  std::memcpy(id128, &id, sizeof(id));
-  return GPRX_OK;
-}
-
-int gprx_comm_init(int device, int rank, int world, const unsigned char* id128, gprx_comm* out) {
-  if (!out) return cfail(nullptr, GPRX_EINVAL, "out is null");
-  *out = nullptr;
-  if (!id128 || world <= 0 || rank < 0 || rank >= world) return cfail(nullptr, GPRX_EINVAL, "bad rank / world / id");
-  COMMHIP(nullptr, hipSetDevice(device));
-  int rc0;
-  if ((rc0 = comm_runtime_ready())) return rc0;
-  gprx_comm c = new gprx_comm_ctx();
-  c->device = device;
-  c->rank = rank;
-  c->world = world;
-  hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-  if (e != hipSuccess) {
-    delete c;
-    return cfail(nullptr, GPRX_EHIP, std::string("hipStreamCreate: ") + hipGetErrorString(e));
-  }
-  ncclUniqueId id;
-  std::memcpy(&id, id128, sizeof(id));
-  ncclResult_t r = rccl().CommInitRank(&c->comm, world, id, rank);  // collective: every rank of the job calls it
-  if (r != ncclSuccess) {
-    const std::string msg = std::string("ncclCommInitRank: ") + rccl().GetErrorString(r);
-    hipStreamDestroy(c->stream);
-    delete c;
-    return cfail(nullptr, GPRX_ERCCL, msg);
-  }
-  *out = c;
-  return GPRX_OK;
-}
-
-int gprx_comm_destroy(gprx_comm c) {
-  if (!c) return GPRX_OK;
-  hipSetDevice(c->device);
-  if (c->stream) hipStreamSynchronize(c->stream);
-  if (c->comm) rccl().CommDestroy(c->comm);
-  if (c->scratch) hipFree(c->scratch);
-  if (c->stream) hipStreamDestroy(c->stream);
-  delete c;
-  return GPRX_OK;
-}
-
-const char* gprx_comm_last_error(gprx_comm c) { return c ? c->err.c_str() : g_err.c_str(); }
-
-int gprx_comm_rank(gprx_comm c, int* rank, int* world) {
-  if (!c || !rank || !world) return cfail(c, GPRX_EINVAL, "null argument");
-  *rank = c->rank;
-  *world = c->world;
-  // what RCCL itself reports for this communicator (ncclCommUserRank / ncclCommCount), so that "did RCCL see N ranks" does not rest
-  // on the numbers the caller passed to gprx_comm_init
-  if (rccl().CommUserRank) COMMNCCL(c, rccl().CommUserRank(c->comm, rank));
-  if (rccl().CommCount) COMMNCCL(c, rccl().CommCount(c->comm, world));
-  return GPRX_OK;
-}
-
-int gprx_comm_synchronize(gprx_comm c) {
-  if (!c) return cfail(c, GPRX_EINVAL, "null communicator");
-  COMMHIP(c, hipSetDevice(c->device));
-  COMMHIP(c, hipStreamSynchronize(c->stream));
-  return GPRX_OK;
-}
-
-int gprx_comm_all_gather(gprx_comm c, const double* send_dev, double* recv_dev, int64_t count) {
-  if (!c || count < 0 || (count > 0 && (!send_dev || !recv_dev))) return cfail(c, GPRX_EINVAL, "null argument");
-  if (count == 0) return GPRX_OK;
-  COMMHIP(c, hipSetDevice(c->device));
-  COMMNCCL(c, rccl().AllGather(send_dev, recv_dev, (size_t)count, ncclDouble, c->comm, c->stream));
-  return GPRX_OK;
-}
-
-int gprx_comm_gather(gprx_comm c, const double* send_dev, double* recv_dev, int64_t count, int root) {
-  if (!c || count < 0 || root < 0 || root >= c->world || (count > 0 && !send_dev)) return cfail(c, GPRX_EINVAL, "bad argument");
-  if (c->rank == root && count > 0 && !recv_dev) return cfail(c, GPRX_EINVAL, "recv_dev is null on the root");
-  if (count == 0) return GPRX_OK;
-  COMMHIP(c, hipSetDevice(c->device));
-  // one group: the root posts world - 1 receives (its own block is a device copy), every other rank one send; inside a
-  // node all inbound xGMI links of the root are busy at once
-  COMMNCCL(c, rccl().GroupStart());
-  ncclResult_t r = ncclSuccess;
-  if (c->rank == root) {
-    for (int p = 0; p < c->world && r == ncclSuccess; ++p)
-      if (p != root) r = rccl().Recv(recv_dev + (int64_t)p * count, (size_t)count, ncclDouble, p, c->comm, c->stream);
-  } else {
-    r = rccl().Send(send_dev, (size_t)count, ncclDouble, root, c->comm, c->stream);
-  }
-  const ncclResult_t r2 = rccl().GroupEnd();
-  COMMNCCL(c, r);
-  COMMNCCL(c, r2);
-  if (c->rank == root && recv_dev + (int64_t)root * count != send_dev)
-    COMMHIP(c, hipMemcpyAsync(recv_dev + (int64_t)root * count, send_dev, sizeof(double) * count, hipMemcpyDeviceToDevice, c->stream));
-  return GPRX_OK;
-}
-
-int gprx_comm_all_reduce_max(gprx_comm c, double* buf_dev, int64_t count) {
-  if (!c || count < 0 || (count > 0 && !buf_dev)) return cfail(c, GPRX_EINVAL, "null argument");
-  if (count == 0) return GPRX_OK;
-  COMMHIP(c, hipSetDevice(c->device));
-  COMMNCCL(c, rccl().AllReduce(buf_dev, buf_dev, (size_t)count, ncclDouble, ncclMax, c->comm, c->stream));
-  return GPRX_OK;
-}
-
-int gprx_comm_all_gather_host(gprx_comm c, const double* send, double* recv, int64_t count) {
-  if (!c || count < 0 || (count > 0 && (!send || !recv))) return cfail(c, GPRX_EINVAL, "null argument");
-  if (count == 0) return GPRX_OK;
-  COMMHIP(c, hipSetDevice(c->device));
-  int rc;
-  if ((rc = comm_scratch(c, sizeof(double) * (size_t)count * (c->world + 1)))) return rc;
-  double* dsend = c->scratch;
-  double* drecv = c->scratch + count;
-  COMMHIP(c, hipMemcpyAsync(dsend, send, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
-  if ((rc = gprx_comm_all_gather(c, dsend, drecv, count))) return rc;
-  COMMHIP(c, hipMemcpyAsync(recv, drecv, sizeof(double) * count * c->world, hipMemcpyDeviceToHost, c->stream));
-  COMMHIP(c, hipStreamSynchronize(c->stream));
-  return GPRX_OK;
-}
-
-int gprx_comm_barrier(gprx_comm c) {
-  if (!c) return cfail(c, GPRX_EINVAL, "null communicator");
-  int rc;
-  COMMHIP(c, hipSetDevice(c->device));
-  if ((rc = comm_scratch(c, sizeof(double) * (size_t)(c->world + 1)))) return rc;
-  COMMHIP(c, hipMemsetAsync(c->scratch, 0, sizeof(double), c->stream));
-  if ((rc = gprx_comm_all_reduce_max(c, c->scratch, 1))) return rc;
-  COMMHIP(c, hipStreamSynchronize(c->stream));
   return GPRX_OK;
 }
 

@@ -87,6 +87,15 @@ def test_library_loads_and_exports_every_declared_symbol():
             _lib.check(lib.gprx_create(0, 16, 4, 0, 0, 0, C.byref(h)))
 
 
+def test_last_error_is_one_string_for_every_handle_family():
+    """gprx_*_last_error(NULL) of any family reports the last failed call of any family on this thread: the library keeps one
+    thread-local message, whichever part of it an entry point lives in.  The failing call returns before any HIP call."""
+    lib = _lib.load()
+    assert lib.gprx_pcafit_create(0, None, 4, 8, None, None, 0, 0.0, None) == _lib.GPRX_EINVAL
+    for name in ("gprx_last_error", "gprx_ps_last_error", "gprx_comm_last_error"):
+        assert getattr(lib, name)(None) == b"out is null", name
+
+
 def test_missing_library_is_an_error_not_a_fallback(monkeypatch, tmp_path):
     monkeypatch.setattr(_lib, "_lib", None)
     monkeypatch.setattr(_lib, "LIB_PATH", tmp_path / "libgprx.so")

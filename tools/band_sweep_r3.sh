@@ -6,7 +6,7 @@ python3 -m gpras_amd._build --stale > /dev/null || exit 1
 export GPRX_NO_BUILD=1
 cp gpras_amd/libgprx.so /tmp/libgprx_keep.so
 for b in 2 4 8 16; do
-  hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -Wno-unused-value -DGPRX_BAND=$b -o gpras_amd/libgprx.so gpras_amd/csrc/gprx.hip || exit 1
+  export GPRX_EXTRA_FLAGS=-DGPRX_BAND=$b; GPRX_NO_BUILD= python3 -m gpras_amd._build --stale > /dev/null || exit 1
   v=$(timeout -k 10 150 python3 bench.py --steps 10 --warmup 2 --full --no-extras --batched-only 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['value'],1), round(d['roofline']['frac'],4))")
   rm -rf gpurun_out/band_f gpurun_out/band_w
   timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/band_f -o f -- python3 bench.py --steps 3 --warmup 1 --no-extras --batched-only > /dev/null 2>&1

@@ -7,7 +7,7 @@ python3 -m gpras_amd._build --stale > /dev/null || exit 1
 export GPRX_NO_BUILD=1
 cp gpras_amd/libgprx.so /tmp/libgprx_keep.so
 for v in NONE GPRX_KMAT_NOEXP GPRX_KMAT_NOSTORE; do
-  hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -Wno-unused-value -D$v -o gpras_amd/libgprx.so gpras_amd/csrc/gprx.hip || exit 1
+  export GPRX_EXTRA_FLAGS=-D$v; GPRX_NO_BUILD= python3 -m gpras_amd._build --stale > /dev/null || exit 1
   touch gpras_amd/libgprx.so
   rm -rf gpurun_out/kv_$v
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/kv_$v -o b -- python3 bench.py --steps 3 --warmup 1 --no-extras --batched-only > /dev/null 2> gpurun_out/kv_$v.log

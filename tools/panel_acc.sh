@@ -4,7 +4,7 @@
 # (TAIL on its own stream, concurrent) and without (no_lookahead: everything in stream order).
 cd $GRAFT_REPO_ROOT
 cp gpras_amd/libgprx.so /tmp/libgprx_keep.so
-hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -Wno-unused-value -DGPRX_PANEL_ACC -o gpras_amd/libgprx.so gpras_amd/csrc/gprx.hip || exit 1
+export GPRX_EXTRA_FLAGS=-DGPRX_PANEL_ACC; python3 -m gpras_amd._build --stale > /dev/null || exit 1
 for la in 0 1; do timeout -k 10 200 python3 tools/panel_acc.py 16384 12 $la || break; done
 # (the CU-mask variants recorded in profiles/r03_panel_phases_beside_tail.txt need tools/patches/r03_chain_cus_cu_mask_streams.patch)
 cp /tmp/libgprx_keep.so gpras_amd/libgprx.so
