@@ -47,7 +47,6 @@ struct GemmArgs {
   // per-cell alpha (two-level batches): alpha = alpha_tab[cell * alpha_stride] when alpha_tab is set
   const double* alpha_tab = nullptr;
   int alpha_stride = 0;
-  int persist_slots = 0;  // > 0 (NT, LDS-DMA eligible, no split-K): persistent grid of persist_slots x #CUs workgroups
   // rowsq != nullptr: C is NOT stored; instead rowsq[(2 tj + wn) * rowsq_ld + row] = sum over the 16 TN columns of this wave
   // of (alpha * acc)^2 -- the row sums of squares of the product in 2 * tiles_n partial slabs (summed by rowsq_final_kernel
   // in a fixed order).  The predictive variance needs only these sums of V^T = Ks^T L^-T, never V itself.
@@ -561,22 +560,6 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128) ? 2 : (((PF && !DMA) ||
   gemm_tile<TA, TB, BM, BN, PF, AXF, DMA>(p, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, smem);
 }
 
-// The same tiles from a PERSISTENT grid: workgroup b takes tiles b, b + gridDim.x, ... of the (nwg x batch) tile list.  A
-// launch of `slots` x 256 workgroups keeps at most `slots` workgroups of this kernel on a CU, so the wave slots, registers
-// and LDS of the remaining slot stay free for the small dependent kernels of the panel chain that runs beside the bulk
-// update on another stream (measured at N = 16384: behind an ordinary launch, whose workgroups fill every CU, those kernels
-// waited 20-170 us for a slot each).  gridDim.x must be a multiple of 8 (the tile -> XCD affinity of the remap survives).
-template <int BM, int BN, int PF>
-__global__ __launch_bounds__(256, (BM * BN >= 128 * 128) ? 2 : 4) void gemm_f64_nt_dma_persistent_kernel(GemmArgs p, int batch) {
-  __shared__ __attribute__((aligned(16))) double smem[GemmSmem<0, 1, BM, BN>::doubles];
-  const int total = p.nwg * batch;
-  for (int t = (int)blockIdx.x; t < total; t += (int)gridDim.x) {
-    const int by = t / p.nwg;
-    gemm_tile<0, 1, BM, BN, PF, 0, 1>(p, t - by * p.nwg, by, 0, smem);
-    // (the last stage of a tile ends with a barrier behind its LDS reads; the epilogue does not touch LDS)
-  }
-}
-
 template <int TA, int TB, int BM, int BN>
 inline hipError_t launch_gemm_t(hipStream_t st, GemmArgs p, int batch, int nsplit = 1) {
   p.tiles_m = (p.M + BM - 1) / BM;
@@ -593,7 +576,7 @@ inline hipError_t launch_gemm_t(hipStream_t st, GemmArgs p, int batch, int nspli
     // default on (GPRX_CELL_XCD=0 restores the per-cell interleave): measured on the batched step at N = 4096, 128 cells -- FETCH /
     // WRITE traffic of the main update kernel 7.57 -> 6.08 GB per launch, 2092 -> 2113 fits/s; same tiles, same arithmetic
     static const int cell_xcd = getenv("GPRX_CELL_XCD") ? atoi(getenv("GPRX_CELL_XCD")) : 1;
-    p.cell_xcd = (cell_xcd && p.inner == 0 && nsplit == 1 && batch >= 8 && batch % 8 == 0 && p.persist_slots == 0 &&
+    p.cell_xcd = (cell_xcd && p.inner == 0 && nsplit == 1 && batch >= 8 && batch % 8 == 0 &&
                   !(p.flags & (GEMM_A_LOWER | GEMM_A_UPPER | GEMM_B_LOWER | GEMM_B_UPPER))) ? 1 : 0;
   }
   if constexpr (TA == 0 && TB == 1) {
@@ -604,30 +587,12 @@ inline hipError_t launch_gemm_t(hipStream_t st, GemmArgs p, int batch, int nspli
     static const int pfc = getenv("GPRX_GEMM_PFC") ? atoi(getenv("GPRX_GEMM_PFC")) : GPRX_GEMM_PFC_DEFAULT;
     if (dma && p.M % BM == 0 && p.N % BN == 0 && p.K % GEMM_BK == 0 && p.lda % 2 == 0 && p.ldb % 2 == 0) {
       const bool prefetch_c = BM * BN <= 64 * 64 && p.beta != 0.0 && nsplit == 1 && (pfc >= 2 || (pfc == 1 && p.K <= 128));
-      if (p.persist_slots > 0 && nsplit == 1 && !prefetch_c) {
-        static const int n_cu = [] {
-          int dev = 0, cus = 256;
-          hipGetDevice(&dev);
-          hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-          return cus > 0 ? cus : 256;
-        }();
-        int grid = p.persist_slots * n_cu;
-        grid -= grid % 8;
-        if (grid > 0 && (int64_t)p.nwg * batch > grid) {
-          hipLaunchKernelGGL((gemm_f64_nt_dma_persistent_kernel<BM, BN, 0>), dim3(grid), dim3(256), 0, st, p, batch);
-          return hipGetLastError();
-        }
-      }
-      // Experiment knob (GPRX_GEMM_PAD_LDS = bytes of unused dynamic LDS for ONE matrix's updates, default 0): caps this kernel at
-      // 3 (9216) or 2 (22000) workgroups per CU, so that a panel workgroup of the chain (200-224 VGPRs per lane; five resident
-      // workgroups of this kernel leave 72 per SIMD) always finds room.  Measured without effect on the panels' 81 us beside the
-      // bulk update at N = 16384 (29.5 / 29.6 / 31.3 ms for 5 / 3 / 2 workgroups per CU): not a residency effect.
-      static const int pad_env = getenv("GPRX_GEMM_PAD_LDS") ? atoi(getenv("GPRX_GEMM_PAD_LDS")) : -1;
-      const unsigned pad = (batch == 1 && BM * BN <= 64 * 64) ? (unsigned)(pad_env >= 0 ? pad_env : 0) : 0u;
+      // (tried and removed, DESIGN.md 7.3 / 7b.6: a persistent grid that leaves a workgroup slot of every CU to the panel chain -- N = 16384
+      // 31.0 / 30.7 / 31.5 ms against 30.05 -- and capping this kernel's residency with unused dynamic LDS -- 29.5 / 29.6 / 31.3 ms)
       if (prefetch_c)
-        hipLaunchKernelGGL((gemm_f64_kernel<0, 1, (BM > 64 ? 64 : BM), (BN > 64 ? 64 : BN), 1, 0, 1>), dim3(p.nwg, batch, nsplit), dim3(256), pad, st, p);
+        hipLaunchKernelGGL((gemm_f64_kernel<0, 1, (BM > 64 ? 64 : BM), (BN > 64 ? 64 : BN), 1, 0, 1>), dim3(p.nwg, batch, nsplit), dim3(256), 0, st, p);
       else
-        hipLaunchKernelGGL((gemm_f64_kernel<0, 1, BM, BN, 0, 0, 1>), dim3(p.nwg, batch, nsplit), dim3(256), pad, st, p);
+        hipLaunchKernelGGL((gemm_f64_kernel<0, 1, BM, BN, 0, 0, 1>), dim3(p.nwg, batch, nsplit), dim3(256), 0, st, p);
       return hipGetLastError();
     }
   }
@@ -715,7 +680,7 @@ static __global__ __launch_bounds__(256) void syrk_k64_kernel(const double* __re
   // k_local / 4), so that the four consecutive doubles lane group g reads for a step are k = 16 ks + {g, 4 + g, 8 + g,
   // 12 + g}: MFMA j of a step then sums the four CONSECUTIVE k = 16 ks + 4 j + {0..3}, and the 16 MFMAs of a tile walk k
   // in ascending groups of four -- the same order in which the 8-column sub-panel updates of the panel kernels reach an
-  // element, which is what keeps 64- and 128-column panels bit-identical.
+  // element.
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     const int q = tid + 256 * i;
@@ -779,28 +744,25 @@ inline hipError_t launch_syrk_k64(hipStream_t st, int M, int N, const double* A,
 inline hipError_t launch_gemm(hipStream_t st, int ta, int tb, int M, int N, int K, double alpha, const double* A, int64_t lda, const double* B,
                               int64_t ldb, double beta, double* C, int64_t ldc, int flags, int tile, int batch, int64_t strideA, int64_t strideB,
                               int64_t strideC, int cells, int64_t cellA, int64_t cellB, int64_t cellC, const double* alpha_tab, int alpha_stride,
-                              int persist_slots, double* rowsq, int64_t rowsq_ld);
+                              double* rowsq, int64_t rowsq_ld);
 // The K = 64 in-block update: the general NT kernel (LDS-DMA operands, C prefetched: 32 KiB of LDS), or with GPRX_K64_GEMM=0
 // the single-stage kernel above.  syrk_k64_kernel holds both whole operand panels in 64 KiB of LDS; beside the bulk update
 // of a large matrix (whose workgroups own all LDS of every CU) each of its launches waited for TWO of them to retire on
 // one CU: 166 us per launch at N = 16384 (rocprofv3), 21 of the 32 ms of that factorisation.  Measured with the general
 // kernel: N = 16384 31.8 -> 30.2 ms, N = 8192 6.73 -> 6.50 ms, 128 cells of N = 4096 +0.5 %, N <= 4096 single unchanged.
-// (The 128-column panel option keeps syrk_k64's k order inside its sub-panel updates: it is no longer bit-identical to the
-// 64-column default, only equal to rounding.)
 inline hipError_t launch_update_k64(hipStream_t st, int M, int N, const double* A, int64_t lda, double* C, int64_t ldc, int batch, int64_t cs) {
   static const int via_gemm = getenv("GPRX_K64_GEMM") ? atoi(getenv("GPRX_K64_GEMM")) : 1;
   if (!via_gemm) return launch_syrk_k64(st, M, N, A, lda, C, ldc, batch, cs);
-  return launch_gemm(st, 0, 1, M, N, 64, -1.0, A, lda, A, lda, 1.0, C, ldc, GEMM_C_LOWER, 64, batch, cs, cs, cs, 1, 0, 0, 0, nullptr, 0, 0, nullptr, 0);
+  return launch_gemm(st, 0, 1, M, N, 64, -1.0, A, lda, A, lda, 1.0, C, ldc, GEMM_C_LOWER, 64, batch, cs, cs, cs, 1, 0, 0, 0, nullptr, 0, nullptr, 0);
 }
 
 // tile: 0 = choose, 128 or 64 (square workgroup tiles)
 inline hipError_t launch_gemm(hipStream_t st, int ta, int tb, int M, int N, int K, double alpha, const double* A, int64_t lda,
                               const double* B, int64_t ldb, double beta, double* C, int64_t ldc, int flags, int tile = 0, int batch = 1,
                               int64_t strideA = 0, int64_t strideB = 0, int64_t strideC = 0, int cells = 1, int64_t cellA = 0,
-                              int64_t cellB = 0, int64_t cellC = 0, const double* alpha_tab = nullptr, int alpha_stride = 0, int persist_slots = 0,
+                              int64_t cellB = 0, int64_t cellC = 0, const double* alpha_tab = nullptr, int alpha_stride = 0,
                               double* rowsq = nullptr, int64_t rowsq_ld = 0) {
   GemmArgs p{A, B, C, lda, ldb, ldc, M, N, K, alpha, beta, flags, 0, 0, 0, strideA, strideB, strideC, 0, 0};
-  p.persist_slots = persist_slots;
   p.rowsq = rowsq;
   p.rowsq_ld = rowsq_ld;
   if (M <= 0 || N <= 0 || batch <= 0 || cells <= 0) return hipSuccess;

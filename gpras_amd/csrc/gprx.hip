@@ -132,7 +132,6 @@ struct gprx_ctx {
   std::vector<char> slot_ok;
   double batch_ms = 0.0;  // device time of the last batch (events around the whole batch)
   hipEvent_t bev[2] = {nullptr, nullptr};
-  hipEvent_t stagger_evt = nullptr;
 };
 
 namespace {
@@ -606,7 +605,7 @@ int exact_factorize_batch(gprx_handle h, int count, const int* units, const Thet
   HIPCHK(h, hipMemcpyAsync(h->cellpar.p, par, sizeof(double) * CELL_PAR * count, hipMemcpyHostToDevice, st));
   HIPCHK(h, hipMemsetAsync(h->cellres.p, 0, sizeof(double) * CELL_RES * count, st));
   if (h->profiling) h->prof.reset();
-  auto enqueue_group = [&](hipStream_t gs, int c0, int cnt, hipEvent_t wait_evt = nullptr, hipEvent_t record_evt = nullptr) -> int {
+  auto enqueue_group = [&](hipStream_t gs, int c0, int cnt) -> int {
     double* K0 = h->arena.p + (int64_t)c0 * cs;
     const double* cpar = h->cellpar.p + (int64_t)c0 * CELL_PAR;
     double* cres = h->cellres.p + (int64_t)c0 * CELL_RES;
@@ -637,7 +636,6 @@ int exact_factorize_batch(gprx_handle h, int count, const int* units, const Thet
     hipLaunchKernelGGL(set_rhs_rows_batch_kernel, dim3(beta_vector ? 4 : 64, cnt), dim3(256), 0, gs, K0 + (int64_t)np * ld, ld, (const double*)h->Y.p, cpar,
                        (int)h->n, np, beta_vector ? 1 : NB, cs);
     int* info0 = reinterpret_cast<int*>(cres + 2);
-    if (wait_evt) HIPCHK(h, hipStreamWaitEvent(gs, wait_evt, 0));
     if (cell_kernel) {
       // small matrices in many cells: one workgroup owns one cell from the first column to the last (potrf_cell.h)
       if (h->profiling) {
@@ -659,7 +657,7 @@ int exact_factorize_batch(gprx_handle h, int count, const int* units, const Thet
       }
     } else {
       HIPCHK(h, potrf_lower(gs, K0, ld, np, rhs_vector ? 0 : NB, K0 + h->off_invd, info0, K0 + h->off_stage, h->profiling ? &h->prof : nullptr, nullptr, cnt, cs,
-                            2 * CELL_RES, &h->tune, 0, record_evt, rhs_vector ? K0 + (int64_t)np * ld : nullptr));
+                            2 * CELL_RES, &h->tune, 0, rhs_vector ? K0 + (int64_t)np * ld : nullptr));
     }
     const double* beta = K0 + (int64_t)np * ld;
     if (with_alpha) hipLaunchKernelGGL(copy_row_batch_kernel, dim3((np + 255) / 256, cnt), dim3(256), 0, gs, beta, K0 + h->off_alpha, np, cs);
@@ -674,12 +672,9 @@ int exact_factorize_batch(gprx_handle h, int count, const int* units, const Thet
     hipStream_t aux = h->pstreams.aux;
     HIPCHK(h, hipEventRecord(h->pstreams.block_done, st));  // parameter table and cleared results are on the main stream
     HIPCHK(h, hipStreamWaitEvent(aux, h->pstreams.block_done, 0));
-    // GPRX_BATCH_STAGGER=1: the second group's factorisation waits until the first group has left its first in-block phase, so the
-    // HBM-bound in-block kernels of one group run beside the MFMA-bound bulk updates of the other
-    static const bool stagger = getenv("GPRX_BATCH_STAGGER") && atoi(getenv("GPRX_BATCH_STAGGER")) > 0;
-    if (stagger && !h->stagger_evt) HIPCHK(h, hipEventCreateWithFlags(&h->stagger_evt, hipEventDisableTiming));
-    if ((rc = enqueue_group(st, 0, first, nullptr, stagger ? h->stagger_evt : nullptr))) return rc;
-    if ((rc = enqueue_group(aux, first, count - first, stagger ? h->stagger_evt : nullptr, nullptr))) return rc;
+    // (the two groups start in phase; staggering the second behind the first group's first in-block phase measured -1.7 %: DESIGN.md 7b.2)
+    if ((rc = enqueue_group(st, 0, first))) return rc;
+    if ((rc = enqueue_group(aux, first, count - first))) return rc;
     HIPCHK(h, hipEventRecord(h->pstreams.tail_done, aux));
     HIPCHK(h, hipStreamWaitEvent(st, h->pstreams.tail_done, 0));
   }
@@ -1828,7 +1823,6 @@ int gprx_destroy(gprx_handle h) {
   if (h->adam_pin) hipHostFree(h->adam_pin);
   for (auto& ev : h->bev)
     if (ev) hipEventDestroy(ev);
-  if (h->stagger_evt) hipEventDestroy(h->stagger_evt);
   for (auto& ev : h->kev)
     if (ev) hipEventDestroy(ev);
   for (auto& ev : h->cev)
@@ -2323,7 +2317,7 @@ static int exact_predict_inverse(gprx_handle h, const ExactPredictSrc& src, cons
     // 3.65 M points/s = 61.2 TFLOP/s against 3.35 M with the 128 x 128 register-staged kernel)
     static const int ptile = getenv("GPRX_PREDICT_TILE") ? atoi(getenv("GPRX_PREDICT_TILE")) : 64;
     const int nparts = 2 * ((np + ptile - 1) / ptile);
-    HIPCHK(h, launch_gemm(st, 0, 1, tsp, np, np, 1.0, h->Ks.p, ld, src.Xinv, ld, 0.0, Vbuf, ld, GEMM_B_UPPER, ptile, 1, 0, 0, 0, 1, 0, 0, 0, nullptr, 0, 0,
+    HIPCHK(h, launch_gemm(st, 0, 1, tsp, np, np, 1.0, h->Ks.p, ld, src.Xinv, ld, 0.0, Vbuf, ld, GEMM_B_UPPER, ptile, 1, 0, 0, 0, 1, 0, 0, 0, nullptr, 0,
                           Vbuf, (int64_t)tile));
     hipLaunchKernelGGL(rowsq_final_kernel, dim3((ts + 255) / 256), dim3(256), 0, st, (const double*)Vbuf, nparts, (int64_t)tile, ts, src.base, var_dev + t0);
   }
@@ -2781,21 +2775,13 @@ int gprx_panel_stamps(unsigned long long* out64) {
 
 namespace {
 bool apply_tuning(PotrfTuning& t, int& predict_path, int& fused, const std::string& k, int value) {
-  if (k == "panel_width" && (value == 0 || value == 64 || value == 128)) t.panel_width = value;
-  else if (k == "outer_block" && value >= 0 && value % 128 == 0) t.outer_block = value;
+  if (k == "outer_block" && value >= 0 && value % 128 == 0) t.outer_block = value;
   else if (k == "update_tile" && (value == 0 || value == 64 || value == 128)) t.update_tile = value;
   else if (k == "no_lookahead") t.no_lookahead = value != 0;
-  else if (k == "panel_rows" && (value == 0 || value == 128 || value == 256)) t.panel_rows = value;
-  else if (k == "panel_occ" && (value == 0 || value == 2 || value == 3)) t.panel_occ = value;
-  else if (k == "inblock" && (value == 0 || value == 1)) t.inblock = value;
   else if (k == "split_panel" && value >= -1 && value <= 1) t.split_panel = value;
   else if (k == "dag" && value >= -1 && value <= 1) t.dag = value;
   else if (k == "rhs_vector" && value >= -1 && value <= 1) t.rhs_vector = value;
-  else if (k == "rows_inv" && value >= -1 && value <= 1) t.rows_inv = value;
-  else if (k == "rows_inv_rt" && value >= 0 && value <= 2) t.rows_inv_rt = value;
-  else if (k == "rows_inv_lone" && value >= 0 && value <= 1) t.rows_inv_lone = value;
   else if (k == "cell_kernel" && value >= -1 && value <= 1) t.cell_kernel = value;
-  else if (k == "split_updates" && value >= 0 && value <= 1) t.split_updates = value;
   else if (k == "poison_workspace" && value >= 0 && value <= 1) t.poison_workspace = value;
   else if (k == "predict_path" && value >= 0 && value <= 2) predict_path = value;
   else if (k == "sgpr_fused" && value >= 0 && value <= 1) fused = value;

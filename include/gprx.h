@@ -482,20 +482,14 @@ int gprx_gather_rows(int device, const double* field_dev, int64_t rows, int64_t 
 /* Tuning of the Cholesky schedule; value 0 restores the default.  gprx_set_tuning changes the PROCESS DEFAULTS: they
  * are read by the handle-less building blocks (gprx_potrf) and COPIED into a handle when it is created, so a handle never
  * sees a later change (handles on different host threads do not share mutable tuning state); gprx_set_handle_tuning changes
- * one handle's copy.  Set process defaults before creating handles, from one thread.  Keys: "panel_width" (64 | 128),
+ * one handle's copy.  Set process defaults before creating handles, from one thread.  Keys:
  * "outer_block" (multiple of 128), "update_tile" (64 | 128: workgroup tile of the bulk trailing update), "no_lookahead"
- * (1: single stream), "panel_rows" (128 | 256 rows per panel workgroup), "panel_occ" (2 | 3 workgroups per CU),
- * "inblock" (1: right-looking K = 64 strips inside an outer block instead of recursive halving), "split_panel"
- * (1: always one diagonal workgroup + a rows-only kernel per panel, -1: never; default: from 24 cells per launch on).
+ * (1: single stream), "split_panel" (1: always one diagonal workgroup + a rows-only kernel per panel, -1: never; default: from
+ * 24 cells per launch on).
  * "cell_kernel" (1: batched cells always take the one-workgroup-per-cell factorisation, -1: never; default by size, see
  * gprx_factorize_batch).
  * "rhs_vector" (-1: batched cells always carry their right-hand side as a 64-row tile below the matrix, as single calls do; default 0:
  * as a vector wherever the split panel runs -- potrf_rows_kernel<..., YVEC>; see gprx_factorize_batch).
- * "rows_inv" (1: the split panel solves the rows below a diagonal block by ONE MFMA tile product against the block's explicit inverse
- * (potrf_rows_inv_kernel) instead of the eight-step substitution: equal to rounding, not bit for bit; "rows_inv_rt" = 1 | 2 sixteen-row
- * tiles per wave, "rows_inv_lone" = 1: a lone matrix takes the split panel too.  Opt-in: measured no faster).
- * "split_updates" (1: ONE matrix's in-block and HEAD updates with K >= 256 are split by columns -- the 64 columns the next panel
- * needs on the main stream, the rest in dyadic pieces on a side stream behind events; bit-identical factor, measured slower).
  * "dag" (1: ONE matrix is factored by the tile-DAG kernel -- a single persistent launch, the dependent chain of diagonal
  * blocks in one workgroup, every other tile task claimed from a queue and ordered by per-tile version counters in device memory;
  * deterministic, within rounding of the default; default 0 = the launch-per-panel schedule, which measured faster on MI355X:

@@ -189,10 +189,10 @@ def test_potrf_reports_failing_pivot(lib):
 
 
 @pytest.mark.parametrize(
-    "panel,outer,tile,split,inblock",
-    [(64, 256, 0, 0, 0), (128, 128, 128, 0, 0), (64, 512, 64, 0, 1), (128, 256, 64, 0, 0), (64, 1024, 0, 1, 0), (64, 512, 64, 1, 1)],
+    "outer,tile,split",
+    [(256, 0, 0), (128, 128, 0), (512, 64, 0), (256, 64, 0), (1024, 0, 1), (512, 64, 1)],
 )
-def test_potrf_large_every_schedule(lib, panel, outer, tile, split, inblock):
+def test_potrf_large_every_schedule(lib, outer, tile, split):
     """N = 2048 under several schedules, repeated: catches ordering races that small grids hide (every
     workgroup of a panel launch re-reads the diagonal block, so it must not be overwritten in place
     during that launch; the bulk trailing update runs on a second stream)."""
@@ -204,7 +204,7 @@ def test_potrf_large_every_schedule(lib, panel, outer, tile, split, inblock):
     L_ref = cholesky(spd, lower=True)
     full = np.vstack([spd, rhs])
     try:
-        for key, val in ((b"panel_width", panel), (b"outer_block", outer), (b"update_tile", tile), (b"split_panel", split), (b"inblock", inblock)):
+        for key, val in ((b"outer_block", outer), (b"update_tile", tile), (b"split_panel", split)):
             check(lib.gprx_set_tuning(key, val))
         first = None
         for _ in range(3):
@@ -221,22 +221,21 @@ def test_potrf_large_every_schedule(lib, panel, outer, tile, split, inblock):
             dA.free()
             dI.free()
     finally:
-        for key in (b"panel_width", b"outer_block", b"update_tile", b"split_panel", b"inblock"):
+        for key in (b"outer_block", b"update_tile", b"split_panel"):
             lib.gprx_set_tuning(key, 0)
 
 
 def test_split_panel_is_bit_identical_to_the_fused_panel(lib):
-    """The rows-only kernels of the split panel (64 and 128 columns) repeat the fused kernel's arithmetic with L11 read
-    from the staging area: fused 64 == split 64 and fused 128 == split 128 bit for bit."""
+    """The rows-only kernel of the split panel repeats the fused kernel's arithmetic with L11 read from the staging area:
+    fused == split bit for bit."""
     n, extra = 1024, 64
     rng = np.random.default_rng(2)
     g = rng.standard_normal((n, 48))
     full = np.vstack([g @ g.T / 48 + np.eye(n), rng.standard_normal((extra, n))])
     outs = []
     try:
-        for split, width in ((-1, 64), (1, 64), (-1, 128), (1, 128)):
+        for split in (-1, 1):
             check(lib.gprx_set_tuning(b"split_panel", split))
-            check(lib.gprx_set_tuning(b"panel_width", width))
             dA, dI = DeviceBuffer.from_array(full), DeviceBuffer(n * 64 * 8)
             info = C.c_int(0)
             check(lib.gprx_potrf(0, dA.ptr, n, n, extra, dI.ptr, C.byref(info)))
@@ -245,51 +244,8 @@ def test_split_panel_is_bit_identical_to_the_fused_panel(lib):
             dI.free()
     finally:
         lib.gprx_set_tuning(b"split_panel", 0)
-        lib.gprx_set_tuning(b"panel_width", 0)
-    # fused and split panels of one width are bit-identical; the two widths agree to rounding (the K = 64 update between two
-    # 64-column panels runs in the general GEMM kernel, whose k order differs from the 128-column kernels' sub-panel updates)
     for a, b in zip(outs[0], outs[1]):
         assert np.array_equal(a, b)
-    for a, b in zip(outs[2], outs[3]):
-        assert np.array_equal(a, b)
-    for a, b in zip(outs[0], outs[2]):
-        assert rel_err(a, b) < 1e-13
-
-
-@pytest.mark.parametrize("n,extra,rt", [(128, 0, 1), (1024, 64, 1), (1088, 40, 2), (2048, 64, 2), (2048 + 192, 17, 1)])
-def test_rows_by_inverse_product_equals_the_substitution_to_rounding(lib, n, extra, rt):
-    """potrf_rows_inv_kernel (split panel, rows = A21 L11^-T as one MFMA tile product against the diagonal block's inverse,
-    "rows_inv" = 1): against scipy and against the substitution schedule -- equal to rounding, not bit for bit -- for both
-    tile counts per wave, the fused K = 64 update (odd panels) and ragged row counts; repeated runs are bit-identical."""
-    rng = np.random.default_rng(n + rt)
-    g = rng.standard_normal((n, 80))
-    spd = g @ g.T / 80 + np.eye(n)
-    rhs = rng.standard_normal((extra, n))
-    full = np.vstack([spd, rhs]) if extra else spd
-    L_ref = cholesky(spd, lower=True)
-    outs = []
-    try:
-        for inv in (0, 1, 1):
-            check(lib.gprx_set_tuning(b"split_panel", 1))
-            check(lib.gprx_set_tuning(b"rows_inv", inv))
-            check(lib.gprx_set_tuning(b"rows_inv_rt", rt))
-            dA, dI = DeviceBuffer.from_array(full), DeviceBuffer(n * 64 * 8)
-            info = C.c_int(0)
-            check(lib.gprx_potrf(0, dA.ptr, n, n, extra, dI.ptr, C.byref(info)))
-            assert info.value == 0
-            outs.append(dA.to_array((n + extra, n)))
-            dA.free()
-            dI.free()
-    finally:
-        for key in (b"split_panel", b"rows_inv", b"rows_inv_rt"):
-            lib.gprx_set_tuning(key, 0)
-    for out in outs:
-        assert rel_err(np.tril(out[:n]), L_ref) < 1e-11
-        if extra:
-            assert rel_err(out[n:], solve_triangular(L_ref, rhs.T, lower=True).T) < 1e-11
-    assert rel_err(np.tril(outs[1][:n]), np.tril(outs[0][:n])) < 1e-13
-    assert not np.array_equal(np.tril(outs[1][:n]), np.tril(outs[0][:n]))  # (it IS another arithmetic: the knob reached the kernel)
-    assert np.array_equal(outs[1], outs[2])
 
 
 @pytest.mark.parametrize("n,extra,ni", [(64, 64, 4), (192, 0, 4), (2048, 64, 4), (3136, 0, 2), (2112, 128, 1), (4096, 64, 4)])
@@ -370,26 +326,3 @@ def test_fit_through_the_tile_dag_equals_the_launch_schedule(lib):
         lib.gprx_destroy(h)
     assert abs(res[1][0] - res[0][0]) <= 1e-12 * abs(res[0][0])
     assert rel_err(res[1][1], res[0][1]) < 1e-11 and rel_err(res[1][2], res[0][2]) < 1e-11
-
-
-@pytest.mark.parametrize("n,extra", [(2112, 64), (4096, 64)])
-def test_potrf_lookahead_split_is_bit_identical(lib, n, extra):
-    """"split_updates" = 1 (the K >= 256 updates of a lone matrix split by columns over a side stream, potrf.h): the same tiles
-    with the same K ranges, so the factor, the right-hand-side rows and the inverse blocks equal the default schedule bit for bit."""
-    rng = np.random.default_rng(n + 1)
-    g = rng.standard_normal((n, 96))
-    full = np.vstack([g @ g.T / 96 + np.eye(n), rng.standard_normal((extra, n))])
-    outs = []
-    try:
-        for knob in (0, 1, 1):
-            check(lib.gprx_set_tuning(b"split_updates", knob))
-            dA, dI = DeviceBuffer.from_array(full), DeviceBuffer(n * 64 * 8)
-            info = C.c_int(0)
-            check(lib.gprx_potrf(0, dA.ptr, n, n, extra, dI.ptr, C.byref(info)))
-            outs.append((np.tril(dA.to_array((n + extra, n))[:n]), dA.to_array((n + extra, n))[n:], dI.to_array((n // 64, 64, 64))))
-            dA.free()
-            dI.free()
-    finally:
-        lib.gprx_set_tuning(b"split_updates", 0)
-    for other in outs[1:]:
-        assert all(np.array_equal(a, b) for a, b in zip(outs[0], other))

@@ -96,6 +96,21 @@ def test_last_error_is_one_string_for_every_handle_family():
         assert getattr(lib, name)(None) == b"out is null", name
 
 
+RETIRED_TUNING_KEYS = (b"panel_width", b"panel_rows", b"panel_occ", b"inblock", b"split_updates", b"rows_inv", b"rows_inv_rt", b"rows_inv_lone")
+POTRF_TUNING_KEYS = (b"outer_block", b"update_tile", b"no_lookahead", b"split_panel", b"rhs_vector", b"dag", b"cell_kernel", b"poison_workspace")
+
+
+def test_retired_tuning_keys_are_unknown_keys():
+    """The schedule options that were measured dead ends and removed are unknown keys now; every key of the
+    live Cholesky schedule is still accepted (0 = its default).  gprx_set_tuning makes no device call."""
+    lib = _lib.load()
+    for key in RETIRED_TUNING_KEYS:
+        assert lib.gprx_set_tuning(key, 0) == _lib.GPRX_EINVAL, key
+        assert lib.gprx_last_error(None) == b"unknown tuning key or bad value", key
+    for key in POTRF_TUNING_KEYS:
+        assert lib.gprx_set_tuning(key, 0) == _lib.GPRX_OK, key
+
+
 def test_missing_library_is_an_error_not_a_fallback(monkeypatch, tmp_path):
     monkeypatch.setattr(_lib, "_lib", None)
     monkeypatch.setattr(_lib, "LIB_PATH", tmp_path / "libgprx.so")

@@ -2,9 +2,10 @@
 
     hipcc <flags of gpras_amd/_build.py> -S --cuda-device-only -o old/<unit>.s <old tree>/gpras_amd/csrc/<unit>.hip   (every unit)
     hipcc ...                                                    -o new/<unit>.s gpras_amd/csrc/<unit>.hip
-    python tools/isa_compare.py old new
+    python tools/isa_compare.py old new [--rename 'OLD TEXT=NEW TEXT' ...]
 
-Kernels are matched by demangled name.  Two kernels are identical when their instruction text is equal after the local labels
+Kernels are matched by demangled name; each --rename replaces OLD TEXT by NEW TEXT in the old build's demangled names first (a
+template parameter list that shrank: 'potrf_panel_kernel<2, 2, false>=potrf_panel_kernel<false>', profiles/potrf_retire.txt).  Two kernels are identical when their instruction text is equal after the local labels
 (.LBBn_m) are renumbered in order of appearance and the kernel's own mangled name is blanked (internal linkage changes it),
 and their .amdhsa_kernel blocks (VGPR / AGPR / SGPR / scratch / LDS figures) are equal."""
 import collections
@@ -49,6 +50,9 @@ def load(directory):
 
 
 old, new = load(sys.argv[1]), load(sys.argv[2])
+for spec in sys.argv[4::2] if sys.argv[3:4] == ["--rename"] else []:
+    a, _, b = spec.partition("=")
+    old = {name.replace(a, b): copies for name, copies in old.items()}
 same = renamed = 0
 bad = []
 for name, copies in sorted(old.items()):
