@@ -264,11 +264,12 @@ def test_resident_adam_with_frozen_parameters_equals_the_python_loop(frozen):
             assert np.array_equal(np.asarray(ma.lengthscales), l0)
 
 
-@pytest.mark.parametrize("n_inducing", [None, 16])
+@pytest.mark.parametrize("n_inducing", [None, 16, 100])
 def test_adam_inside_the_library_equals_the_python_loops(n_inducing):
     """gprx_adam_batch (the lock-step Adam driver inside libgprx.so) against the packed Python loop and against the serial
     per-model driver: same variables bit for bit and the same number of evaluations per model -- including models that stop
-    early (they start at an L-BFGS optimum, so the loss cannot improve by 1e-5 for 50 steps) beside models that keep going."""
+    early (they start at an L-BFGS optimum, so the loss cannot improve by 1e-5 for 50 steps) beside models that keep going.  16 inducing
+    points run the loop resident on the device, 100 (M > 64) the host-stepped loop over the general launch sequence."""
     from gpras_amd import optimizers
 
     x, y = make_hydrograph_features(260, 3, n_outputs=5, config=1, unit=11)
