@@ -74,11 +74,9 @@ struct gprx_ctx {
   int predict_path = 0;
   std::string err;
   // data
-  Buf X, Y, Z, invls, alpha, red, Kmat, invD, Xinv, Tmp, partial, xs, Ks, pred;
-  // sparse path
-  Buf P, Am, Qm, Bm, invDL, invDB, SM, WP, WHP, WHQ, vecs, dZ, dstage, splitws;
+  Buf X, Y, invls, alpha, red, Kmat, invD, Xinv, Tmp, partial, xs, Ks, pred;
+  Buf dstage;
   std::vector<double> yy;  // y.y per unit
-  double elbo_trAAT = 0.0;
   int* info = nullptr;
   double* pin = nullptr;  // pinned host staging: [0..63] lengthscales up, [64..71] reductions down, [72] info (as int),
                           // [74] variance, [75] noise (graph replay reads them through the device block `gparams`)
@@ -94,8 +92,7 @@ struct gprx_ctx {
   static constexpr int SF_MAX_GROUPS = 2;
   hipStream_t sf_streams[SF_MAX_GROUPS - 1] = {};          // extra streams of the resident Adam loop: large batches run as groups of cells (sf_group_plan)
   hipEvent_t sf_evs[SF_MAX_GROUPS] = {};
-  bool sparse_view = false;                               // the current single-model factorisation lives in cell block 0 of `sarena`
-  // current factorisation
+  // current factorisation (a sparse model's lives in cell block 0 of `sarena`)
   bool factorized = false;
   bool have_linv = false;  // Xinv holds L^-1 of the current factorisation (exact path)
   int cur_unit = -1;
@@ -146,14 +143,6 @@ Args with_form(Args a, gprx_handle h) {
 int& predict_path_tuning() {
   static int v = 0;  // 0: choose, 1: always through L^-1, 2: always forward substitution
   return v;
-}
-
-int ensure_zeroed(gprx_handle h, Buf& b, size_t bytes) {
-  if (b.bytes >= bytes) return GPRX_OK;
-  int rc = ensure(h, b, bytes);
-  if (rc) return rc;
-  HIPCHK(h, hipMemsetAsync(b.p, 0, bytes, h->stream));
-  return GPRX_OK;
 }
 
 // ---- scalar transforms (gpflow positive() / LogNormal(0,1) priors; see oracle/transforms.py) ------
@@ -881,191 +870,56 @@ int exact_gradient(gprx_handle h, const Theta& t, double* g) {
 // Device restatement of gpflow SGPR._common_calculation / elbo / predict_f (oracle/sgpr.py) with
 //   P = Kuf (mp x np), Q = Kuu + jitter I -> L, A' = L^-1 P (unscaled: A = A' / sqrt(s)),
 //   B = I + A' A'^T / s -> LB, c = LB^-1 A' y / s (carried through the Cholesky as an appended row).
-// SM holds nine mp x mp scratch matrices.
+// The SM block of a cell holds ten mp x mp scratch matrices.
 constexpr int SPLITK_CHUNK = 256;
-constexpr int SGPR_PRED_TILE = 4096;  // test points per pass of the batched sparse predict
+constexpr int SGPR_PRED_TILE = 4096;  // test points per pass of the sparse predict
 enum { SM_BFULL = 0, SM_LINV, SM_LBINV, SM_QINV, SM_SINV, SM_R, SM_T1, SM_T2, SM_W, SM_GQ, SM_COUNT };
-
-double* sm(gprx_handle h, int slot) { return h->SM.p + (size_t)slot * h->mp * h->mp; }
-
-int sgpr_alloc(gprx_handle h) {
-  const size_t mp = h->mp, np = h->np;
-  int rc;
-  if ((rc = ensure(h, h->Z, sizeof(double) * h->m * h->d))) return rc;
-  if ((rc = ensure(h, h->P, sizeof(double) * mp * np))) return rc;
-  if ((rc = ensure(h, h->Am, sizeof(double) * mp * np))) return rc;
-  if ((rc = ensure(h, h->Qm, sizeof(double) * mp * mp))) return rc;
-  if ((rc = ensure(h, h->Bm, sizeof(double) * (mp + NB) * mp))) return rc;
-  if ((rc = ensure(h, h->invDL, sizeof(double) * mp * NB))) return rc;
-  if ((rc = ensure(h, h->invDB, sizeof(double) * mp * NB))) return rc;
-  if ((rc = ensure_zeroed(h, h->vecs, sizeof(double) * (4 * mp + np)))) return rc;
-  if ((rc = ensure(h, h->dstage, sizeof(double) * std::max(mp, np) * STAGE_LD))) return rc;
-  // split-K slabs: K = np in slices of SPLITK_CHUNK, outputs up to mp x mp
-  if ((rc = ensure(h, h->splitws, sizeof(double) * ((np + SPLITK_CHUNK - 1) / SPLITK_CHUNK) * mp * mp))) return rc;
-  return GPRX_OK;
-}
-
-int sgpr_factorize(gprx_handle h, int unit, const Theta& t, const double* z, double* elbo_out) {
-  if (!z) return fail(h, GPRX_EINVAL, "z (inducing inputs) is null for a sparse model");
-  for (int64_t e = 0; e < h->m * h->d; ++e)
-    if (!std::isfinite(z[e])) return fail(h, GPRX_EINVAL, "z is not finite");
-  int rc;
-  if ((rc = sgpr_alloc(h))) return rc;
-  const int mp = (int)h->mp, np = (int)h->np, m = (int)h->m, n = (int)h->n;
-  hipStream_t st = h->stream;
-  HIPCHK(h, hipMemcpyAsync(h->Z.p, z, sizeof(double) * h->m * h->d, hipMemcpyHostToDevice, st));
-  if ((rc = upload_inv_ls(h, t))) return rc;
-  const double s = t.noise;
-  HIPCHK(h, hipEventRecord(h->ev[0], st));
-  KmatArgs kp{h->Z.p, h->X.p, h->invls.p, h->P.p, np, m, n, h->d, mp, np, t.variance, 0.0, 0, 0.0, nullptr, 0};
-  HIPCHK(h, launch_kmat(st, h->kid, with_form(kp, h)));
-  KmatArgs kq{h->Z.p, h->Z.p, h->invls.p, h->Qm.p, mp, m, m, h->d, mp, mp, t.variance, JITTER, 2, 1.0, nullptr, 0};
-  HIPCHK(h, launch_kmat(st, h->kid, with_form(kq, h)));
-  HIPCHK(h, hipEventRecord(h->ev[1], st));
-  HIPCHK(h, hipMemsetAsync(h->info, 0, sizeof(int), st));
-  HIPCHK(h, potrf_lower(st, h->Qm.p, mp, mp, 0, h->invDL.p, h->info, h->dstage.p, nullptr, nullptr, 1, 0, 0, &h->tune));
-  HIPCHK(h, hipMemcpyAsync(h->Am.p, h->P.p, sizeof(double) * (size_t)mp * np, hipMemcpyDeviceToDevice, st));
-  HIPCHK(h, trsm_lower_left(st, h->Qm.p, mp, h->invDL.p, h->Am.p, np, mp, np));
-  // B = I + A' A'^T / s (all of it: the gradient needs the symmetric matrix)
-  if (mp <= 512 && np >= 4 * SPLITK_CHUNK) {
-    // (mp/64)^2 output tiles against K = np: cut K over workgroups, reduce the slabs in a fixed order
-    HIPCHK(h, launch_gemm_splitk(st, 0, 1, mp, mp, np, 1.0 / s, h->Am.p, np, h->Am.p, np, 0.0, h->Bm.p, mp, h->splitws.p, SPLITK_CHUNK));
-  } else {
-    HIPCHK(h, launch_gemm(st, 0, 1, mp, mp, np, 1.0 / s, h->Am.p, np, h->Am.p, np, 0.0, h->Bm.p, mp, 0));
-  }
-  hipLaunchKernelGGL(add_diag_kernel, dim3((mp + 255) / 256), dim3(256), 0, st, h->Bm.p, (int64_t)mp, mp, 1.0, (int64_t)0);
-  hipLaunchKernelGGL(diag_sum_kernel, dim3(1), dim3(256), 0, st, (const double*)h->Bm.p, (int64_t)mp, mp, 1.0, h->red.p + 2, (int64_t)0);
-  if ((rc = ensure(h, h->SM, sizeof(double) * (size_t)SM_COUNT * mp * mp))) return rc;
-  HIPCHK(h, hipMemcpyAsync(sm(h, SM_BFULL), h->Bm.p, sizeof(double) * (size_t)mp * mp, hipMemcpyDeviceToDevice, st));
-  // appended row: A' y / s  -> comes out of the Cholesky as c
-  double* crow = h->Bm.p + (size_t)mp * mp;
-  HIPCHK(h, hipMemsetAsync(crow, 0, sizeof(double) * (size_t)NB * mp, st));
-  const double* yu = h->Y.p + (size_t)unit * h->np;
-  if (np >= 4 * SPLITK_CHUNK) {
-    HIPCHK(h, launch_gemm_splitk(st, 0, 0, mp, 1, np, 1.0 / s, h->Am.p, np, yu, 1, 0.0, crow, 1, h->splitws.p, SPLITK_CHUNK));
-  } else {
-    HIPCHK(h, launch_gemm(st, 0, 0, mp, 1, np, 1.0 / s, h->Am.p, np, yu, 1, 0.0, crow, 1, 0, 64));
-  }
-  HIPCHK(h, potrf_lower(st, h->Bm.p, mp, mp, NB, h->invDB.p, h->info, h->dstage.p, nullptr, nullptr, 1, 0, 0, &h->tune));
-  HIPCHK(h, hipEventRecord(h->ev[2], st));
-  hipLaunchKernelGGL(logdet_quad_kernel, dim3(1), dim3(256), 0, st, (const double*)h->Bm.p, (int64_t)mp, (const double*)crow, mp, h->red.p, (int64_t)0, 0);
-  HIPCHK(h, hipEventRecord(h->ev[3], st));
-  double red[3];
-  int info = 0;
-  HIPCHK(h, hipMemcpyAsync(red, h->red.p, sizeof(red), hipMemcpyDeviceToHost, st));
-  HIPCHK(h, hipMemcpyAsync(&info, h->info, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHK(h, wait_stream(h, st));
-  if (info != 0) {
-    h->factorized = false;
-    char msg[128];
-    snprintf(msg, sizeof msg, "Kuu or B not positive definite: pivot %d", info);
-    return fail(h, GPRX_ENOTPD, msg);
-  }
-  h->factorized = true;
-  h->sparse_view = false;
-  h->cur_unit = unit;
-  h->variance = t.variance;
-  h->noise = s;
-  h->ls = t.ls;
-  h->elbo_trAAT = red[2];
-  const double nn = (double)h->n;
-  if (elbo_out)
-    *elbo_out = sgpr_asm_elbo(nn, h->yy[unit], t.variance, s, red);
-  return GPRX_OK;
-}
-
-// derivatives of the ELBO w.r.t. constrained (variance, lengthscales[nlen], noise) -> g, and Z -> gz (m x d, host)
-int sgpr_gradient(gprx_handle h, int unit, const Theta& t, double* g, double* gz) {
-  const int mp = (int)h->mp, np = (int)h->np, m = (int)h->m, n = (int)h->n, d = h->d;
-  const size_t mm = (size_t)mp * mp;
-  const double s = t.noise;
-  hipStream_t st = h->stream;
-  int rc;
-  if ((rc = ensure(h, h->WP, sizeof(double) * (size_t)mp * np))) return rc;
-  if ((rc = ensure_zeroed(h, h->WHP, sizeof(double) * (size_t)mp * np))) return rc;
-  if ((rc = ensure_zeroed(h, h->WHQ, sizeof(double) * mm))) return rc;
-  if ((rc = ensure(h, h->dZ, sizeof(double) * (size_t)m * d))) return rc;
-  const int tiles_m = mp / KM_T, tiles_n = np / KM_T, width = 2 + d;
-  const size_t part_p = (size_t)tiles_m * tiles_n * width, part_q = (size_t)tiles_m * tiles_m * width;
-  if ((rc = ensure(h, h->partial, sizeof(double) * (part_p + part_q + 2 * width)))) return rc;
-  double *Linv = sm(h, SM_LINV), *LBinv = sm(h, SM_LBINV), *Qinv = sm(h, SM_QINV), *Sinv = sm(h, SM_SINV), *R = sm(h, SM_R),
-         *T1 = sm(h, SM_T1), *T2 = sm(h, SM_T2), *W = sm(h, SM_W), *GQ = sm(h, SM_GQ), *Bfull = sm(h, SM_BFULL);
-  double* cvec = h->Bm.p + mm;  // row mp of Bm
-  double* mvec = h->vecs.p;
-  double* qvec = h->vecs.p + 4 * mp;
-  const double* yu = h->Y.p + (size_t)unit * h->np;
-
-  HIPCHK(h, hipMemsetAsync(Linv, 0, sizeof(double) * mm, st));
-  HIPCHK(h, trtri_lower(st, h->Qm.p, mp, h->invDL.p, Linv, mp, T1, mp, mp));
-  HIPCHK(h, hipMemsetAsync(LBinv, 0, sizeof(double) * mm, st));
-  HIPCHK(h, trtri_lower(st, h->Bm.p, mp, h->invDB.p, LBinv, mp, T1, mp, mp));
-  HIPCHK(h, launch_gemm(st, 1, 0, mp, mp, mp, 1.0, Linv, mp, Linv, mp, 0.0, Qinv, mp, GEMM_A_UPPER | GEMM_B_LOWER));
-  HIPCHK(h, launch_gemm(st, 0, 0, mp, mp, mp, 1.0, LBinv, mp, Linv, mp, 0.0, R, mp, GEMM_A_LOWER | GEMM_B_LOWER));
-  HIPCHK(h, launch_gemm(st, 1, 0, mp, mp, mp, 1.0, R, mp, R, mp, 0.0, Sinv, mp, GEMM_A_UPPER | GEMM_B_LOWER));
-  HIPCHK(h, launch_gemm(st, 0, 0, mp, mp, mp, 1.0, Bfull, mp, Linv, mp, 0.0, T2, mp, GEMM_B_LOWER));
-  HIPCHK(h, launch_gemm(st, 1, 0, mp, mp, mp, 1.0, Linv, mp, T2, mp, 0.0, T1, mp, GEMM_A_UPPER));
-  // m = L^-T LB^-T c
-  hipLaunchKernelGGL(copy_row_kernel, dim3((mp + 255) / 256), dim3(256), 0, st, (const double*)cvec, mvec, mp);
-  HIPCHK(h, trsv_lower(st, h->Bm.p, mp, h->invDB.p, mvec, mp, true));
-  HIPCHK(h, trsv_lower(st, h->Qm.p, mp, h->invDL.p, mvec, mp, true));
-  hipLaunchKernelGGL(sgpr_combine_kernel, dim3((mp * mp + 255) / 256), dim3(256), 0, st, (const double*)Qinv, (const double*)Sinv,
-                     (const double*)T1, (const double*)mvec, mp, W, GQ, (int64_t)0);
-  HIPCHK(h, launch_gemm(st, 0, 0, mp, np, mp, 1.0, W, mp, h->P.p, np, 0.0, h->WP.p, np, 0));
-  // contractions with the kernel derivatives
-  double* partP = h->partial.p;
-  double* partQ = partP + part_p;
-  double* sums = partQ + part_q;
-  // (one shared lengthscale -- the reference's default kernels: the per-dimension pass collapses to one FMA per element, round 4 for the
-  // sparse model too: sum_k ds_k^2 is the r2 of the first pass whatever d is and whether or not w v h is stored for dz_kernel)
-  TraceArgs tp{h->Z.p, h->X.p, h->invls.p, h->WP.p, np, mvec, yu, 1.0 / s, 1.0 / s, m, n, d, t.variance, 0, partP, h->WHP.p, np, tiles_n};
-  tp.iso = h->ard ? 0 : 1;
-  HIPCHK(h, launch_trace(st, h->kid, with_form(tp, h), tiles_m * tiles_n));
-  TraceArgs tq{h->Z.p, h->Z.p, h->invls.p, GQ, mp, nullptr, nullptr, 1.0, 0.0, m, m, d, t.variance, 0, partQ, h->WHQ.p, mp, tiles_m};
-  tq.iso = h->ard ? 0 : 1;
-  HIPCHK(h, launch_trace(st, h->kid, with_form(tq, h), tiles_m * tiles_m));
-  hipLaunchKernelGGL(trace_final, dim3(width), dim3(64), 0, st, (const double*)partP, tiles_m * tiles_n, width, sums);
-  hipLaunchKernelGGL(trace_final, dim3(width), dim3(64), 0, st, (const double*)partQ, tiles_m * tiles_m, width, sums + width);
-  hipLaunchKernelGGL(dz_kernel, dim3(dz_grid(m, d)), dim3(256), 0, st, (const double*)h->Z.p, (const double*)h->X.p, (const double*)h->WHP.p,
-                     (int64_t)np, (const double*)h->WHQ.p, (int64_t)mp, (const double*)h->invls.p, m, n, d, h->dZ.p);
-  // noise terms: |y - P^T m|^2 and tr(B^-1) = |LB^-1|_F^2
-  HIPCHK(h, launch_gemm(st, 1, 0, np, 1, mp, 1.0, h->P.p, np, mvec, 1, 0.0, qvec, 1, 0, 64));
-  hipLaunchKernelGGL(resid_sumsq_kernel, dim3(1), dim3(256), 0, st, yu, (const double*)qvec, n, h->red.p + 4, (int64_t)0, (int64_t)0);
-  {
-    const int nb = mp < 64 ? mp : 64;
-    double* part = h->vecs.p + 2 * mp;  // scratch inside the vector block
-    hipLaunchKernelGGL(sumsq_partial_kernel, dim3(nb), dim3(256), 0, st, (const double*)LBinv, (int64_t)mp, mp, mp, part, (int64_t)0);
-    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(64), 0, st, (const double*)part, nb, h->red.p + 3, (int64_t)0);
-  }
-  std::vector<double> hs(2 * width), hz((size_t)m * d);
-  double red[5];
-  HIPCHK(h, hipMemcpyAsync(hs.data(), sums, sizeof(double) * 2 * width, hipMemcpyDeviceToHost, st));
-  HIPCHK(h, hipMemcpyAsync(red, h->red.p, sizeof(red), hipMemcpyDeviceToHost, st));
-  HIPCHK(h, hipMemcpyAsync(hz.data(), h->dZ.p, sizeof(double) * m * d, hipMemcpyDeviceToHost, st));
-  HIPCHK(h, wait_stream(h, st));
-  const double nn = (double)h->n;
-  const double tr_sinv_pp = s * ((double)mp - red[3]);
-  const double tr_qinv_pp = s * h->elbo_trAAT;
-  g[0] = -nn / (2.0 * s) + hs[0] + hs[width];
-  if (h->ard) {
-    for (int k = 0; k < d; ++k) g[1 + k] = hs[2 + k] + hs[width + 2 + k];
-  } else {
-    double acc = 0.0;
-    for (int k = 0; k < d; ++k) acc += hs[2 + k] + hs[width + 2 + k];
-    g[1] = acc;
-  }
-  g[1 + h->nlen] = (tr_sinv_pp - tr_qinv_pp + red[4] + nn * t.variance) / (2.0 * s * s) - nn / (2.0 * s);
-  if (gz) std::memcpy(gz, hz.data(), sizeof(double) * m * d);
-  return GPRX_OK;
-}
 
 // ---- batched sparse models ------------------------------------------------------------------------------------
 // The reference fits its per-mode SGPR models one after the other (gpr.py:272-274); every evaluation is ~45 tiny
 // dependent launches (M = 50 inducing points: every M x M matrix is one 64 x 64 tile), i.e. pure launch latency.
-// Here `count` cells (unit, theta, Z) on the handle's x go through the SAME launch sequence, the cell index in a grid
+// Here `count` cells (unit, theta, Z) on the handle's x go through ONE launch sequence, the cell index in a grid
 // dimension of every kernel: each cell owns one block of `ss` doubles holding all its matrices at fixed offsets, so
 // a kernel adds blockIdx * ss to its per-cell pointers; hyperparameters (and 1 / s for the GEMM scalings) come from the
-// cell-parameter table.  Same kernels, same per-element operation order as sgpr_factorize / sgpr_gradient:
-// bit-identical values.
+// cell-parameter table.  A lone model (gprx_objective / gprx_factorize / gprx_predict) is a batch of one cell: a cell's
+// values do not depend on its position in a batch or on the batch's size, bit for bit.
+// M <= 64 takes the five launches of sgpr_fused.h unless "sgpr_fused" = 0; its kernels read the lengthscales from the parameter table only
+bool sgpr_five_launches(gprx_handle h) { return h->mp == NB && h->sgpr_fused != 0 && h->d <= CELL_PAR - CELL_PAR_LS; }
+
+// Where the kernels of the launch sequence and of the predict read a cell's hyperparameters.  Table: row `cell` of the cell-parameter
+// table -- the values travel through device memory, so the sequence can be captured and replayed.  Direct (d > 64: a row has 64
+// lengthscale slots): the handle's lengthscale vector and the scalars themselves in the launch arguments; the kernels then apply no
+// per-cell stride, so it serves ONE cell and is never captured.
+struct SgprParSrc {
+  const double* table = nullptr;  // nullptr: direct
+  const double* ls = nullptr;
+  double variance = 0.0, noise = 0.0, inv_noise = 0.0;
+  void stamp(KmatArgs& a) const {
+    a.cell_par = table;
+    a.ls = ls;
+    a.variance = variance;
+  }
+  void stamp(TraceArgs& a, bool noise_scaled) const {
+    a.cell_par = table;
+    a.ls = ls;
+    a.variance = variance;
+    a.scale_inv_noise = noise_scaled ? 1 : 0;
+    if (noise_scaled) a.w_scale = a.uv_scale = inv_noise;
+  }
+};
+SgprParSrc sgpr_par_src(gprx_handle h, double variance, double noise) {  // (direct: the one cell's values; upload_inv_ls has filled invls)
+  SgprParSrc ps;
+  if (h->d <= CELL_PAR - CELL_PAR_LS) {
+    ps.table = h->cellpar.p;
+  } else {
+    ps.ls = h->invls.p;
+    ps.variance = variance;
+    ps.noise = noise;
+    ps.inv_noise = 1.0 / noise;
+  }
+  return ps;
+}
+
 struct SgprLayout {
   int64_t oZ, oY, oP, oAm, oQm, oBm, oInvDL, oInvDB, oSM, oWP, oWHP, oWHQ, oVecs, odZ, oStage, oPart, oWs, oRed, oKs, oPred, ss;
   int64_t oFU, oFP2;  // fused evaluation (sgpr_fused.h): u partials of the chunks, pass-2 partial blocks
@@ -1088,7 +942,7 @@ SgprLayout sgpr_batch_layout(gprx_handle h) {
   };
   // (the five-launch evaluation of sgpr_fused.h never stores Kuf, A', W Kuf or the weighted derivative: the four M x N matrices and the
   // trace partials of the launch sequence shrink to nothing -- 8.4 of 9.9 MB per cell at M = 50, N = 4096, which a fit allocated and cleared)
-  const bool fused = mp == NB && h->sgpr_fused != 0;
+  const bool fused = sgpr_five_launches(h);
   const int64_t big = fused ? 0 : mp * np;
   L.oZ = take(m * d);
   L.oY = take(np);
@@ -1121,10 +975,7 @@ int ensure_sarena(gprx_handle h, int slots, const SgprLayout& L) {
   if (h->sarena_slots >= slots) return GPRX_OK;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   drop_graphs(h);  // captured evaluations hold the addresses of the buffers released below
-  if (h->sparse_view) {  // the single-model factorisation lived in cell block 0 of the arena released below
-    h->sparse_view = false;
-    h->factorized = false;
-  }
+  h->factorized = false;  // a lone model's factorisation lived in cell block 0 of the arena released below
   if (h->sarena.p) HIPCHK(h, hipFree(h->sarena.p));
   h->sarena.p = nullptr;
   h->sarena.bytes = 0;
@@ -1161,7 +1012,7 @@ SgprStage sgpr_stage(gprx_handle h, int count, const SgprLayout& L) {
 }
 
 // M <= 64: the five launches of sgpr_fused.h (prep, pass 1, mid, pass 2, final) instead of the 21 below; same staging block, same host
-// tail.  "sgpr_fused" = 0 (gprx_set_tuning) keeps the launch sequence -- which larger M always takes.
+// tail.  "sgpr_fused" = 0 (gprx_set_tuning) keeps the launch sequence -- which larger M and d > 64 always take.
 int& sgpr_fused_tuning() {
   static int v = 1;
   return v;
@@ -1259,32 +1110,31 @@ int sgpr_fused_enqueue(gprx_handle h, int count, const SgprLayout& L, bool want_
 // the staged outputs (pivot status, reductions, trace sums, dZ in pinned memory).  Nothing here depends on the VALUES of the
 // parameters -- they travel through the cell-parameter table -- so the sequence is captured once per (cells, gradient) into a
 // hipGraph and replayed (sgpr_objective_batch): ~45 launches whose enqueue cost, not their device time, bounded a step.
-int sgpr_batch_enqueue(gprx_handle h, int count, const SgprLayout& L, bool want_grad) {
+int sgpr_batch_enqueue(gprx_handle h, int count, const SgprLayout& L, bool want_grad, const SgprParSrc& ps) {
   const int mp = (int)h->mp, np = (int)h->np, m = (int)h->m, n = (int)h->n, d = h->d;
   const int64_t ss = L.ss, mm = (int64_t)mp * mp;
   const size_t pitch = sizeof(double) * (size_t)ss;
   hipStream_t st = h->stream;
   double* A0 = h->sarena.p;
-  if (mp == NB && h->sgpr_fused) return sgpr_fused_enqueue(h, count, L, want_grad);
+  if (sgpr_five_launches(h)) return sgpr_fused_enqueue(h, count, L, want_grad);
   const SgprStage sg = sgpr_stage(h, count, L);
   // (Tried: the independent branches of the evaluation -- Kuf beside Kuu's factorisation; R, Sinv / T2, T1 / Qinv, m; the
   // two contractions and the noise terms -- on side streams, i.e. parallel branches of the captured graph.  The dependent chain
   // drops from 34 to 20 launches, but every cross-branch edge costs more than an in-order kernel boundary on this runtime:
   // 16 cells 0.427 ms against 0.400 ms serial.  One stream it is.)
-  const double* cpar = h->cellpar.p;
-  const double* inv_s = cpar + 3;  // alpha table: 1 / s, CELL_PAR apart
+  const double* inv_s = h->cellpar.p + 3;  // alpha table: 1 / s, CELL_PAR apart
   static_assert(CELL_RES <= 256 && CELL_PAR <= 256, "sgpr_stage_in_kernel moves them with its first workgroup");
   hipLaunchKernelGGL(sgpr_stage_in_kernel, dim3((std::max(np, m * d) + 255) / 256, count), dim3(256), 0, st, (const double*)h->Y.p, np,
                      (const double*)(h->spin + sg.par), CELL_PAR, h->cellpar.p, (const double*)(h->spin + sg.z), m * d, A0 + L.oZ, A0 + L.oY, ss,
                      h->cellres.p, CELL_RES);
-  // ---- factorisation (sgpr_factorize) ----
+  // ---- factorisation ----
   KmatArgs kp{A0 + L.oZ, h->X.p, nullptr, A0 + L.oP, np, m, n, d, mp, np, 0.0, 0.0, 0, 0.0, nullptr, 0};
-  kp.cell_par = cpar;
+  ps.stamp(kp);
   kp.out_stride = ss;
   kp.a_stride = ss;
   kp.diag_const = 1;
   KmatArgs kq{A0 + L.oZ, A0 + L.oZ, nullptr, A0 + L.oQm, mp, m, m, d, mp, mp, 0.0, JITTER, 2, 1.0, nullptr, 0};
-  kq.cell_par = cpar;
+  ps.stamp(kq);
   kq.out_stride = ss;
   kq.a_stride = ss;
   kq.b_stride = ss;
@@ -1328,7 +1178,7 @@ int sgpr_batch_enqueue(gprx_handle h, int count, const SgprLayout& L, bool want_
   if (!fused_small)
     hipLaunchKernelGGL(logdet_quad_kernel, dim3(count), dim3(256), 0, st, (const double*)(A0 + L.oBm), (int64_t)mp, (const double*)crow, mp,
                        A0 + L.oRed, ss, (int)ss);
-  // ---- gradient (sgpr_gradient) ----
+  // ---- gradient ----
   // one block: L^-1 and LB^-1 ARE the inverses of the diagonal blocks that the factorisations left behind (trtri_lower would
   // clear a matrix and copy them into it)
   double *Linv = one_block ? A0 + L.oInvDL : smb(SM_LINV), *LBinv = one_block ? A0 + L.oInvDB : smb(SM_LBINV), *Qinv = smb(SM_QINV), *Sinv = smb(SM_SINV), *R = smb(SM_R), *T1 = smb(SM_T1),
@@ -1367,16 +1217,15 @@ int sgpr_batch_enqueue(gprx_handle h, int count, const SgprLayout& L, bool want_
     }
     HIPCHK(h, launch_gemm(st, 0, 0, mp, np, mp, 1.0, W, mp, A0 + L.oP, np, 0.0, A0 + L.oWP, np, 0, 0, 1, 0, 0, 0, count, ss, ss, ss));
     TraceArgs tp{A0 + L.oZ, h->X.p, nullptr, A0 + L.oWP, np, mvec, A0 + L.oY, 0.0, 0.0, m, n, d, 0.0, 0, partP, A0 + L.oWHP, np, tiles_n};
-    tp.cell_par = cpar;
+    ps.stamp(tp, true);
     tp.w_stride = ss;
     tp.uv_stride = ss;
     tp.partial_stride = ss;
     tp.a_stride = ss;
     tp.wh_stride = ss;
-    tp.scale_inv_noise = 1;
     tp.iso = h->ard ? 0 : 1;
     TraceArgs tq{A0 + L.oZ, A0 + L.oZ, nullptr, GQ, mp, nullptr, nullptr, 1.0, 0.0, m, m, d, 0.0, 0, partQ, A0 + L.oWHQ, mp, tiles_m};
-    tq.cell_par = cpar;
+    ps.stamp(tq, false);
     tq.w_stride = ss;
     tq.partial_stride = ss;
     tq.a_stride = ss;
@@ -1396,8 +1245,8 @@ int sgpr_batch_enqueue(gprx_handle h, int count, const SgprLayout& L, bool want_
       hipLaunchKernelGGL(sum_partials_kernel, dim3(1, count), dim3(64), 0, st, (const double*)part, nb, A0 + L.oRed + 3, ss);
     }
     hipLaunchKernelGGL(dz_kernel, dim3(dz_grid(m, d), count), dim3(256), 0, st, (const double*)(A0 + L.oZ), (const double*)h->X.p,
-                       (const double*)(A0 + L.oWHP), (int64_t)np, (const double*)(A0 + L.oWHQ), (int64_t)mp, (const double*)nullptr, m, n, d,
-                       A0 + L.odZ, ss, cpar);
+                       (const double*)(A0 + L.oWHP), (int64_t)np, (const double*)(A0 + L.oWHQ), (int64_t)mp, ps.ls, m, n, d,
+                       A0 + L.odZ, ss, ps.table);
   }
   // ---- results: reductions, pivot status, trace sums, dZ -> pinned memory ----
   hipLaunchKernelGGL(sgpr_stage_out_kernel, dim3(count), dim3(256), 0, st, (const double*)h->cellres.p, CELL_RES, h->spin + sg.res,
@@ -1414,7 +1263,11 @@ int sgpr_objective_batch(gprx_handle h, int count, const int* units, const Theta
                          int* status) {
   const SgprLayout L = sgpr_batch_layout(h);
   int rc;
+  const bool direct = h->d > CELL_PAR - CELL_PAR_LS;  // (SgprParSrc)
+  if (direct && count != 1) return fail(h, GPRX_EINVAL, "d > 64: sparse models are evaluated one cell at a time");
   if ((rc = ensure_sarena(h, count, L))) return rc;
+  if (direct && (rc = upload_inv_ls(h, ts[0]))) return rc;
+  const SgprParSrc ps = sgpr_par_src(h, ts[0].variance, ts[0].noise);
   const int mp = (int)h->mp, m = (int)h->m, d = h->d;
   const int width = L.width;
   hipStream_t st = h->stream;
@@ -1427,7 +1280,7 @@ int sgpr_objective_batch(gprx_handle h, int count, const int* units, const Theta
     row[1] = ts[c].noise;
     row[2] = (double)units[c];
     row[3] = 1.0 / ts[c].noise;
-    for (int k = 0; k < d; ++k) row[CELL_PAR_LS + k] = ts[c].ls[k];
+    for (int k = 0; k < std::min(d, CELL_PAR - CELL_PAR_LS); ++k) row[CELL_PAR_LS + k] = ts[c].ls[k];
   }
   std::memcpy(h->spin + sg.z, zs, sizeof(double) * (size_t)count * m * d);
   static const bool no_graph = getenv("GPRX_NO_GRAPH") != nullptr;  // escape hatch: eager launches
@@ -1435,8 +1288,7 @@ int sgpr_objective_batch(gprx_handle h, int count, const int* units, const Theta
   bool replayed = false;
   // (the five launches of the fused evaluation go out eagerly: replaying them from a graph starts the first kernel later than a direct
   // launch does -- 178.8 against 172.5 us per 16-cell evaluation, MI355X_MICROARCH.md "graph-replay-floor")
-  const bool five_launches = mp == NB && h->sgpr_fused != 0;
-  if (!no_graph && !h->sgraph_off && !h->profiling && !five_launches) {
+  if (!no_graph && !h->sgraph_off && !h->profiling && !sgpr_five_launches(h) && !direct) {
     const std::pair<int, int> key(count, want_grad ? 1 : 0);
     auto it = h->sgraphs.find(key);
     if (it == h->sgraphs.end()) {
@@ -1454,7 +1306,7 @@ int sgpr_objective_batch(gprx_handle h, int count, const int* units, const Theta
       hipGraphExec_t exec = nullptr;
       hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed);
       if (e == hipSuccess) {
-        const int crc = sgpr_batch_enqueue(h, count, L, want_grad);
+        const int crc = sgpr_batch_enqueue(h, count, L, want_grad, ps);
         e = hipStreamEndCapture(st, &graph);
         if (!crc && e == hipSuccess && graph) e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
         if (crc) e = hipErrorUnknown;
@@ -1475,13 +1327,13 @@ int sgpr_objective_batch(gprx_handle h, int count, const int* units, const Theta
       replayed = true;
     }
   }
-  if (!replayed && (rc = sgpr_batch_enqueue(h, count, L, want_grad))) return rc;
+  if (!replayed && (rc = sgpr_batch_enqueue(h, count, L, want_grad, ps))) return rc;
   const double* hres = h->spin + sg.res;
   const double* hred = h->spin + sg.red;
   const double* hsum = h->spin + sg.sum;
   const double* hdz = h->spin + sg.dz;
   HIPCHK(h, wait_stream(h, st));
-  h->factorized = false;  // the single-model state of the handle is untouched but no longer "the last evaluation"
+  h->factorized = false;  // (objective_impl sets it for a lone model: cell block 0 is then what gprx_predict reads)
   int first_error = GPRX_OK;
   const double nn = (double)h->n;
   for (int c = 0; c < count; ++c) {
@@ -1512,14 +1364,16 @@ int sgpr_objective_batch(gprx_handle h, int count, const int* units, const Theta
 // SGPR.predict_y for every cell of the batch that sgpr_objective_batch has just factorised (its cell blocks hold L, invDL, LB,
 // invDB and c): the nine small launches of one model's predict serve all cells -- Kus per cell (own Z and hyperparameters),
 // tmp1 = L^-1 Kus, tmp2 = LB^-1 tmp1, mean = tmp2^T c, var = v + colsum(tmp2^2) - colsum(tmp1^2) (+ s).  Same kernels and
-// operation order as gprx_predict_dev on each cell: bit-identical values.  means / vars: (count, ns) device, row-major.
+// operation order whatever the count (gprx_predict_dev is count = 1): bit-identical values.  means / vars: (count, ns) device, row-major.
 int sgpr_predict_batch(gprx_handle h, int count, const double* xs_dev, int64_t ns, double* means_dev, double* vars_dev, int include_noise) {
   const SgprLayout L = sgpr_batch_layout(h);
   const int mp = (int)h->mp, m = (int)h->m;
   const int64_t ss = L.ss;
   hipStream_t st = h->stream;
   double* A0 = h->sarena.p;
-  const double* cpar = h->cellpar.p;
+  const SgprParSrc ps = sgpr_par_src(h, h->variance, h->noise);
+  const double* cpar = ps.table;
+  const double base = ps.variance + (include_noise ? ps.noise : 0.0);  // (direct only: 0 beside a table)
   const int rows_per_chunk = 256;
   const int nchunks = (mp + rows_per_chunk - 1) / rows_per_chunk;
   const int tile = SGPR_PRED_TILE;
@@ -1528,7 +1382,7 @@ int sgpr_predict_batch(gprx_handle h, int count, const double* xs_dev, int64_t n
     const int ts = (int)std::min<int64_t>(tile, ns - t0);
     const int tsp = (int)round_up(ts, NB);
     KmatArgs ka{A0 + L.oZ, xs_dev + t0 * h->d, nullptr, A0 + L.oKs, tile, m, ts, h->d, mp, tsp, 0.0, 0.0, 0, 0.0, nullptr, 0};
-    ka.cell_par = cpar;
+    ps.stamp(ka);
     ka.out_stride = ss;
     ka.a_stride = ss;
     ka.diag_const = 1;
@@ -1538,8 +1392,8 @@ int sgpr_predict_batch(gprx_handle h, int count, const double* xs_dev, int64_t n
     hipLaunchKernelGGL(colreduce_partial, pgrid, dim3(256), 0, st, (const double*)(A0 + L.oKs), (int64_t)tile, (const double*)nullptr, mp, ts,
                        rows_per_chunk, A0 + L.oPred, ss, (int64_t)0, ss);
     // var = (v [+ s]) - colsum(tmp1^2): per-cell base from the parameter table ([0] variance, [1] noise)
-    hipLaunchKernelGGL(colreduce_final, fgrid, dim3(256), 0, st, (const double*)(A0 + L.oPred), nchunks, ts, 0.0, -1.0, 0, vars_dev + t0, ss, ns, cpar,
-                       include_noise ? cpar + 1 : (const double*)nullptr, CELL_PAR);
+    hipLaunchKernelGGL(colreduce_final, fgrid, dim3(256), 0, st, (const double*)(A0 + L.oPred), nchunks, ts, base, -1.0, 0, vars_dev + t0, ss, ns, cpar,
+                       include_noise && cpar ? cpar + 1 : (const double*)nullptr, CELL_PAR);
     HIPCHK(h, trsm_lower_left(st, A0 + L.oBm, mp, A0 + L.oInvDB, A0 + L.oKs, tile, mp, tsp, count, ss));
     hipLaunchKernelGGL(colreduce_partial, pgrid, dim3(256), 0, st, (const double*)(A0 + L.oKs), (int64_t)tile, cvec, mp, ts, rows_per_chunk,
                        A0 + L.oPred, ss, ss, ss);
@@ -1634,7 +1488,6 @@ int sgpr_adam_resident(gprx_handle h, int count, const int* units, double* theta
   int* flags = reinterpret_cast<int*>(h->adam_pin + check_every);
   int error_cell = 0;
   h->factorized = false;  // the cell blocks are overwritten
-  h->sparse_view = false;
   // (large batches: two groups of cells on two streams, one launch apart -- sf_group_count)
   constexpr int MAXG = gprx_ctx::SF_MAX_GROUPS;
   const int ngroups = sf_group_count(count, L.nsplit);
@@ -1808,9 +1661,8 @@ int gprx_destroy(gprx_handle h) {
   if (!h) return GPRX_OK;
   hipSetDevice(h->device);
   if (h->stream) hipStreamSynchronize(h->stream);
-  for (Buf* b : {&h->X, &h->Y, &h->Z, &h->invls, &h->alpha, &h->red, &h->Kmat, &h->invD, &h->Xinv, &h->Tmp, &h->partial, &h->xs, &h->Ks,
-                 &h->pred, &h->P, &h->Am, &h->Qm, &h->Bm, &h->invDL, &h->invDB, &h->SM, &h->WP, &h->WHP, &h->WHQ, &h->vecs, &h->dZ,
-                 &h->dstage, &h->splitws, &h->arena, &h->cellpar, &h->cellres, &h->garena, &h->gpartial, &h->apart, &h->twork, &h->sarena})
+  for (Buf* b : {&h->X, &h->Y, &h->invls, &h->alpha, &h->red, &h->Kmat, &h->invD, &h->Xinv, &h->Tmp, &h->partial, &h->xs, &h->Ks, &h->pred,
+                 &h->dstage, &h->arena, &h->cellpar, &h->cellres, &h->garena, &h->gpartial, &h->apart, &h->twork, &h->sarena})
     if (b->p && !b->borrowed) hipFree(b->p);
   if (h->bpin) hipHostFree(h->bpin);
   if (h->spin) hipHostFree(h->spin);
@@ -1918,12 +1770,10 @@ static int objective_impl(gprx_handle h, int unit, const double* theta, const do
   for (int k = 0; k < h->ntheta; ++k)
     if (!std::isfinite(theta[k])) return fail(h, GPRX_EINVAL, "theta is not finite");
   const Theta t = decode_theta(h, theta);
-  const bool sparse = h->m != 0;
   double value = 0.0;  // LML (exact) or ELBO (sparse)
-  if (sparse && h->mp == NB && h->sgpr_fused && h->d <= CELL_PAR - CELL_PAR_LS && !h->profiling) {
-    // M <= 64: one model is a batch of one cell through the five launches of sgpr_fused.h -- the same kernels, the same summation
-    // order as any batch (a model evaluated alone and inside a batch agree bit for bit); the factorisation stays in cell block 0,
-    // where gprx_predict reads it (sparse_view)
+  if (h->m != 0) {
+    // one model is a batch of one cell -- the same kernels, the same summation order as any batch (a model evaluated alone and
+    // inside a batch agree bit for bit); the factorisation stays in cell block 0, where gprx_predict reads it
     if (!z) return fail(h, GPRX_EINVAL, "z (inducing inputs) is null for a sparse model");
     const int64_t nz = h->m * h->d;
     for (int64_t e = 0; e < nz; ++e)
@@ -1937,10 +1787,8 @@ static int objective_impl(gprx_handle h, int unit, const double* theta, const do
       double* gz = grad + h->ntheta;
       for (int64_t e = 0; e < nz; ++e) gz[e] = (mask & GPRX_TRAIN_Z) ? -gzv[e] : 0.0;
     }
-    for (auto& ev : h->ev) HIPCHK(h, hipEventRecord(ev, h->stream));
-    for (double& tm : h->timings) tm = 0.0;
+    for (double& tm : h->timings) tm = 0.0;  // (no phase events inside a sequence that is replayed from a graph)
     h->factorized = true;
-    h->sparse_view = true;
     h->cur_unit = unit;
     h->variance = t.variance;
     h->noise = t.noise;
@@ -1951,11 +1799,9 @@ static int objective_impl(gprx_handle h, int unit, const double* theta, const do
   // 64 dependent launches of the backward substitution drop out of the evaluation); a non-PD matrix is reported by the
   // factorisation's status as before (the gradient launches behind it are then wasted, not wrong: nothing is read back)
   static const bool fused_eval = !(getenv("GPRX_FUSED_EVAL") && atoi(getenv("GPRX_FUSED_EVAL")) == 0);
-  const bool fused = !sparse && grad && fused_eval && !h->profiling;
+  const bool fused = grad && fused_eval && !h->profiling;
   std::vector<double> ghost(fused ? 2 + h->d : 0);
-  if (sparse) {
-    if ((rc = sgpr_factorize(h, unit, t, z, &value))) return rc;
-  } else if (fused) {
+  if (fused) {
     if ((rc = exact_factorize_enqueue(h, unit, t, true, false, false))) return rc;
     if ((rc = exact_gradient_enqueue(h, t, ghost.data(), true))) {
       hipStreamSynchronize(h->stream);
@@ -1969,24 +1815,13 @@ static int objective_impl(gprx_handle h, int unit, const double* theta, const do
   if (loss) *loss = -(value + lp);
   if (grad) {
     std::vector<double> g(h->ntheta, 0.0);
-    double* gz = sparse ? grad + h->ntheta : nullptr;
-    if (sparse) {
-      if ((rc = sgpr_gradient(h, unit, t, g.data(), gz))) return rc;
-    } else if (fused) {
+    if (fused) {
       exact_gradient_collect(h, ghost.data(), g.data());
     } else {
       if ((rc = exact_gradient(h, t, g.data()))) return rc;
     }
     HIPCHK(h, hipEventRecord(h->ev[4], h->stream));
     chain_rule(h, t, mask, g.data(), grad);
-    if (sparse) {
-      const int64_t nz = h->m * h->d;
-      if (mask & GPRX_TRAIN_Z) {
-        for (int64_t e = 0; e < nz; ++e) gz[e] = -gz[e];
-      } else {
-        for (int64_t e = 0; e < nz; ++e) gz[e] = 0.0;
-      }
-    }
   } else {
     HIPCHK(h, hipEventRecord(h->ev[4], h->stream));
   }
@@ -2224,10 +2059,7 @@ int gprx_objective_batch(gprx_handle h, int count, const int* units, const doubl
     }
     return frc;
   }
-  static const bool no_sparse_batch = getenv("GPRX_NO_SPARSE_BATCH") != nullptr;  // escape hatch: one model after the other
-  // (count == 1 too, round 4: the batched evaluation is 21 launches replayed from a graph, the single-model path ~40 launches and a dozen
-  // copies -- 0.30 against 0.42 ms per evaluation at N = 4096, M = 50; same values bit for bit, as for every other count)
-  if (h->m != 0 && count >= 1 && h->d <= CELL_PAR - CELL_PAR_LS && !no_sparse_batch) {
+  if (h->m != 0 && count > 1 && h->d <= CELL_PAR - CELL_PAR_LS) {
     if (!z) return fail(h, GPRX_EINVAL, "z (inducing inputs) is null for a sparse model");
     const int64_t nz = h->m * h->d;
     for (int64_t e = 0; e < (int64_t)count * nz; ++e)
@@ -2257,7 +2089,7 @@ int gprx_objective_batch(gprx_handle h, int count, const int* units, const doubl
     }
     return frc;
   }
-  // one cell after the other (a single cell, d > 64, or GPRX_NO_SPARSE_BATCH): same contract as the batched paths -- a cell
+  // one cell after the other (a single cell, or d > 64): same contract as the batched paths -- a cell
   // whose matrix is not positive definite gets NaN, the others are still evaluated, the first failure is returned
   int first_error = GPRX_OK;
   for (int i = 0; i < count; ++i) {
@@ -2332,37 +2164,7 @@ int gprx_predict_dev(gprx_handle h, const double* xs_dev, int64_t ns, double* me
   if (ns < 0 || (ns > 0 && (!xs_dev || !mean_dev || !var_dev))) return fail(h, GPRX_EINVAL, "null argument");
   hipStream_t st = h->stream;
   const int rows_per_chunk = 256;
-  if (h->m != 0 && h->sparse_view) return sgpr_predict_batch(h, 1, xs_dev, ns, mean_dev, var_dev, include_noise);  // cell block 0
-  if (h->m != 0) {
-    // gpflow SGPR.predict_f: tmp1 = L^-1 Kus, tmp2 = LB^-1 tmp1, mean = tmp2^T c,
-    // var = v + colsum(tmp2^2) - colsum(tmp1^2) (+ s for predict_y)
-    const int mp = (int)h->mp, m = (int)h->m;
-    const int tile = (int)std::min<int64_t>(PRED_TILE, round_up(ns, NB));
-    if ((rc = ensure(h, h->Ks, sizeof(double) * (size_t)mp * tile))) return rc;
-    const int nchunks = (mp + rows_per_chunk - 1) / rows_per_chunk;
-    if ((rc = ensure(h, h->pred, sizeof(double) * (size_t)nchunks * tile))) return rc;
-    const double base = h->variance + (include_noise ? h->noise : 0.0);
-    const double* cvec = h->Bm.p + (size_t)mp * mp;
-    for (int64_t t0 = 0; t0 < ns; t0 += tile) {
-      const int ts = (int)std::min<int64_t>(tile, ns - t0);
-      const int tsp = (int)round_up(ts, NB);
-      KmatArgs ka{h->Z.p, xs_dev + t0 * h->d, h->invls.p, h->Ks.p, tile, m, ts, h->d, mp, tsp, h->variance, 0.0, 0, 0.0, nullptr, 0};
-      HIPCHK(h, launch_kmat(st, h->kid, with_form(ka, h)));
-      dim3 grid((ts + 255) / 256, nchunks);
-      HIPCHK(h, trsm_lower_left(st, h->Qm.p, mp, h->invDL.p, h->Ks.p, tile, mp, tsp));
-      hipLaunchKernelGGL(colreduce_partial, grid, dim3(256), 0, st, h->Ks.p, (int64_t)tile, (const double*)nullptr, mp, ts, rows_per_chunk,
-                         h->pred.p);
-      hipLaunchKernelGGL(colreduce_final, dim3((ts + 255) / 256), dim3(256), 0, st, h->pred.p, nchunks, ts, base, -1.0, 0, var_dev + t0);
-      HIPCHK(h, trsm_lower_left(st, h->Bm.p, mp, h->invDB.p, h->Ks.p, tile, mp, tsp));
-      hipLaunchKernelGGL(colreduce_partial, grid, dim3(256), 0, st, h->Ks.p, (int64_t)tile, cvec, mp, ts, rows_per_chunk, h->pred.p);
-      hipLaunchKernelGGL(colreduce_final, dim3((ts + 255) / 256), dim3(256), 0, st, h->pred.p, nchunks, ts, 0.0, 1.0, 0, mean_dev + t0);
-      hipLaunchKernelGGL(colreduce_partial, grid, dim3(256), 0, st, h->Ks.p, (int64_t)tile, (const double*)nullptr, mp, ts, rows_per_chunk,
-                         h->pred.p);
-      hipLaunchKernelGGL(colreduce_final, dim3((ts + 255) / 256), dim3(256), 0, st, h->pred.p, nchunks, ts, 0.0, 1.0, 1, var_dev + t0);
-    }
-    HIPCHK(h, hipGetLastError());
-    return GPRX_OK;
-  }
+  if (h->m != 0) return sgpr_predict_batch(h, 1, xs_dev, ns, mean_dev, var_dev, include_noise);  // cell block 0
   const int np = (int)h->np;
   const int64_t ld = h->np;
   const int tile = (int)std::min<int64_t>(pred_tile_for(h->np), round_up(ns, NB));
@@ -2430,7 +2232,6 @@ int gprx_predict(gprx_handle h, const double* xs, int64_t ns, double* mean, doub
 static int predict_batch_core(gprx_handle h, int count, const int* units, const double* thetas, const double* z, const double* xs_dev, int64_t ns,
                               double* means_dev, double* vars_dev, int include_noise) {
   int rc;
-  static const bool no_sparse_batch = getenv("GPRX_NO_SPARSE_BATCH") != nullptr;
   hipStream_t st = h->stream;
   if (h->m == 0 && h->d <= CELL_PAR - CELL_PAR_LS) {
     // exact models: all factorisations by one batched launch sequence, then every slot predicts
@@ -2464,7 +2265,7 @@ static int predict_batch_core(gprx_handle h, int count, const int* units, const 
     h->have_linv = false;  // the single-cell views of the handle may point into the arena: their cached L^-1 is not this batch's
     return GPRX_OK;
   }
-  if (h->m != 0 && count > 1 && h->d <= CELL_PAR - CELL_PAR_LS && !no_sparse_batch) {
+  if (h->m != 0 && count > 1 && h->d <= CELL_PAR - CELL_PAR_LS) {
     // sparse models (what gpras runs): every cell factorised by ONE batched launch sequence, then one batched predict
     if (!z) return fail(h, GPRX_EINVAL, "z (inducing inputs) is null for a sparse model");
     const int64_t nz = h->m * h->d;
@@ -2805,8 +2606,7 @@ int gprx_set_handle_tuning(gprx_handle h, const char* key, int value) {
   if (hipSetDevice(h->device) == hipSuccess && hipStreamSynchronize(h->stream) == hipSuccess) drop_graphs(h);  // captured with the old schedule
   if (h->sgpr_fused != fused_before) {  // the cell blocks of the two sparse schedules differ (sgpr_batch_layout): the arena is rebuilt on the next call
     h->sarena_slots = 0;
-    h->factorized = h->sparse_view ? false : h->factorized;
-    h->sparse_view = false;
+    if (h->m != 0) h->factorized = false;
   }
   return GPRX_OK;
 }

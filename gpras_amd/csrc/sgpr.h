@@ -158,7 +158,7 @@ __global__ __launch_bounds__(256) void sumsq_small_kernel(const double* __restri
 // One launch for: logdet_quad_kernel, R = LB^-1 L^-1, Sinv = R^T R, T2 = B L^-1, T1 = L^-T T2, Qinv = L^-T L^-1 (five
 // launch_gemm calls), m = L^-T LB^-T c (a copy and two trsv steps), sgpr_combine_kernel and the sum of squares of LB^-1 --
 // eleven dependent launches of ~10 us each whose arithmetic is microseconds.  Every value is computed by the same operations
-// in the same order as those kernels (the single-model path still runs them one by one; tests hold the two equal).
+// in the same order as those kernels (M > 64 still runs them one by one).
 // LB: second factor (its diagonal), crow: c, invDL / invDB: L^-1 / LB^-1, Bfull: B.  red: [0] sum log diag LB, [1] |c|^2, [3] |LB^-1|_F^2
 __global__ __launch_bounds__(256) void sgpr_small_kernel(const double* __restrict__ LB, const double* __restrict__ crow,
                                                          const double* __restrict__ invDL, const double* __restrict__ invDB,

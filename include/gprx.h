@@ -107,7 +107,11 @@ int gprx_set_data(gprx_handle h, const double* x, const double* y, int n_units);
  *   loss  : out, scalar
  *   grad  : out or NULL; n_theta values followed by m*d values for Z; entries of
  *           parameters whose mask bit is clear are written as 0.
- * Leaves the factorisation resident, so gprx_predict may follow for the same (unit, theta, z). */
+ * Leaves the factorisation resident, so gprx_predict may follow for the same (unit, theta, z).
+ * A sparse model (m > 0) is evaluated as a batch of ONE cell of gprx_objective_batch, for every M, d and tuning: the same launches,
+ * the same bits as that cell inside any batch, and the same GPRX_ENOTPD text ("cell 0: Kuu or B not positive definite: pivot N").
+ * d > 64 exceeds the lengthscale slots of a row of the cell-parameter table: the cell's hyperparameters then travel in the launch
+ * arguments and the sequence is launched eagerly instead of replayed from a graph. */
 int gprx_objective(gprx_handle h, int unit, const double* theta, const double* z, int mask, double* loss, double* grad);
 
 /* Factorise only (kernel build + Cholesky + weights); what SGPR.predict_y recomputes on
@@ -144,13 +148,15 @@ int gprx_last_batch_ms(gprx_handle h, double* ms);
 
 /* SGPR.predict_y (gpr.py:336-339): predictive mean and variance at xs (ns, d) for the unit
  * factorised last.  include_noise != 0 adds the likelihood variance (predict_y); 0 gives
- * predict_f.  mean/var: ns values each. */
+ * predict_f.  mean/var: ns values each.  Works after every successful gprx_factorize / gprx_objective (GPRX_ESTATE otherwise);
+ * a sparse model predicts from its cell block, 4096 points per pass, as a cell of gprx_predict_batch does. */
 int gprx_predict(gprx_handle h, const double* xs, int64_t ns, double* mean, double* var, int include_noise);
 /* same, every pointer is a device pointer; asynchronous on the handle's stream */
 int gprx_predict_dev(gprx_handle h, const double* xs_dev, int64_t ns, double* mean_dev, double* var_dev, int include_noise);
 
 /* timings (ms, HIP events on the handle's stream) of the stages of the last
- * gprx_objective / gprx_factorize call: [kernel build, cholesky, solves, gradient]. */
+ * gprx_objective / gprx_factorize call: [kernel build, cholesky, solves, gradient].  Exact models only: after a sparse
+ * evaluation (one launch sequence, replayed from a graph: no events inside) all four are 0. */
 int gprx_last_timings(gprx_handle h, double* ms4);
 
 /* Per-launch timing of the Cholesky's two kernels (exact path), for bench.py's roofline line.
@@ -182,12 +188,14 @@ int gprx_last_cell_kernel(gprx_handle h, double* ms, double* flops, double* cell
  * Sparse models with M <= 64 inducing points (the reference's example configuration has 50) take FIVE launches per evaluation
  * whatever the cell count (round 5, csrc/sgpr_fused.h: Kuu and its factor | Kuf tile by tile on MFMA against the register-resident
  * L^-1, never stored | B, its factor and the M x M algebra of the gradient | the contractions with dk/dtheta and dk/dZ | sums in a
- * fixed order); count == 1 takes them too, and so does gprx_objective: a model evaluated alone and inside a batch gives the
- * same bits.  Larger M takes the general launch sequence (Kuf, Kuu, both Cholesky factorisations, A, B (split-K), c, the M x M
- * products of the gradient, both trace passes, dZ: ~45 launches serve all cells), bit-identical to gprx_objective on each cell.
+ * fixed order).  Larger M takes the general launch sequence (Kuf, Kuu, both Cholesky factorisations, A, B (split-K), c, the M x M
+ * products of the gradient, both trace passes, dZ: ~45 launches serve all cells, replayed from a graph).  gprx_objective is the
+ * same sequence with one cell: a model evaluated alone and inside a batch gives the same bits.
  * The tuning key "sgpr_fused" = 0 sends M <= 64 through that sequence as well (equal to rounding, not bit for bit).  A cell
  * whose matrix is not positive definite gets NaN loss and gradient and the call returns GPRX_ENOTPD after finishing the
- * others.  The single-model state of the handle is left unfactorised (gprx_predict needs a gprx_factorize / gprx_objective). */
+ * others.  count == 1, and every count with d > 64 (one cell after the other), is gprx_objective per cell: the last cell stays
+ * resident for gprx_predict.  A batch of several cells leaves the handle unfactorised (gprx_predict needs a gprx_factorize /
+ * gprx_objective). */
 int gprx_objective_batch(gprx_handle h, int count, const int* units, const double* theta, const double* z, int mask,
                          double* losses, double* grads);
 

@@ -257,8 +257,9 @@ def test_wait_hands_over_to_stream_synchronize_and_the_next_call_is_clean(lib):
 
 @pytest.mark.parametrize("m", [40, 100])
 def test_engine_objective_with_gradient_then_predict(lib, m):
-    """Engine.objective(want_grad=True) followed by Engine.predict either works (M <= 64: the fused evaluation keeps the
-    factorisation in cell block 0) or raises a clear error (M > 64: the one-cell batch keeps none), never a stale prediction."""
+    """Engine.objective(want_grad=True) followed by Engine.predict works for every M -- a lone sparse model is a one-cell batch
+    whose factorisation stays in cell block 0 (M <= 64: the fused evaluation; M > 64: the launch sequence) -- and so does the loss-only
+    call after it: never an error, never a stale prediction."""
     from gpras_amd.engine import Engine
 
     n, d = 600, 4
@@ -268,17 +269,10 @@ def test_engine_objective_with_gradient_then_predict(lib, m):
     theta = theta_of(1.1, 0.9, 0.2)
     eng = Engine("Matern32", x, y, m)
     try:
-        eng.objective(1, theta, z, 15, want_grad=True)
-        if m <= 64:
+        ref_mean, ref_var = osg.predict("Matern32", x, y[:, 1], z, 1.1, 0.9, 0.2, xs)
+        for want_grad in (True, False):
+            eng.objective(1, theta, z, 15, want_grad=want_grad)
             mean, var = eng.predict(xs)
-            ref_mean, ref_var = osg.predict("Matern32", x, y[:, 1], z, 1.1, 0.9, 0.2, xs)
-            assert np.max(np.abs(mean - ref_mean)) <= 1e-8 * np.max(np.abs(ref_mean)) and np.max(np.abs(var - ref_var) / ref_var) <= 1e-8
-        else:
-            with pytest.raises(Exception, match="gprx_factorize"):
-                eng.predict(xs)
-            eng.objective(1, theta, z, 15, want_grad=False)
-            mean, var = eng.predict(xs)
-            ref_mean, ref_var = osg.predict("Matern32", x, y[:, 1], z, 1.1, 0.9, 0.2, xs)
             assert np.max(np.abs(mean - ref_mean)) <= 1e-8 * np.max(np.abs(ref_mean)) and np.max(np.abs(var - ref_var) / ref_var) <= 1e-8
     finally:
         eng.close()

@@ -45,8 +45,10 @@ def ref_eval(kernel, x, y, z, theta, ard, mask_tuple):
 
 
 @pytest.mark.parametrize("kernel", okn.KERNEL_NAMES)
-@pytest.mark.parametrize("n,d,m,ard", [(256, 4, 32, False), (700, 5, 100, True), (1000, 8, 200, False)])
+@pytest.mark.parametrize("n,d,m,ard", [(256, 4, 32, False), (700, 5, 100, True), (1000, 8, 200, False), (600, 70, 40, True)])
 def test_sgpr_loss_grad_predict(lib, kernel, n, d, m, ard):
+    """(d = 70: more lengthscales than a row of the cell-parameter table holds -- the one-cell batch of a lone model then carries its
+    hyperparameters in the launch arguments, and M = 40 takes the launch sequence instead of the fused evaluation)"""
     x, y, xs = make_regression(n, d, n_outputs=2, n_test=300, config=3, unit=n + m)
     z = gpras_oracle.create_inducing(x, m, "kmeans")
     # k-means with many centres leaves single-point clusters, i.e. z_i == x_n up to rounding.  For the
@@ -56,6 +58,8 @@ def test_sgpr_loss_grad_predict(lib, kernel, n, d, m, ard):
     h = make_handle(lib, n, d, m, kernel, ard, x, y)
     try:
         ls = np.linspace(0.7, 1.3, d) if ard else 0.85
+        if d > 64:  # (lengthscales of order 1 leave nothing of Kuf in 70 dimensions -- median k / v = 5e-21 for RBF; of order sqrt(d): 0.3 .. 0.6)
+            ls = ls * np.sqrt(d)
         variance, noise = 1.2, 0.08
         wv, wl, wn = otr.unconstrain(variance, ls, noise)
         theta = np.ascontiguousarray(np.concatenate([[wv], np.atleast_1d(wl), [wn]]))

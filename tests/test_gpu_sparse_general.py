@@ -1,11 +1,14 @@
-"""Every branch of the sparse launch sequence for 64 < M <= 320 (gprx.hip sgpr_batch_enqueue, the single-model sgpr_factorize /
-sgpr_gradient, sgpr_predict_batch and the host-stepped Adam loop) against the oracle, and its bit-identity contracts.
+"""Every branch of the sparse launch sequence for 64 < M <= 320 (gprx.hip sgpr_batch_enqueue -- a lone gprx_objective / gprx_factorize is
+a batch of one cell through it --, sgpr_predict_batch and the host-stepped Adam loop) against the oracle, and its bit-identity contracts:
+a cell's bits do not depend on its position in a batch or on the batch's size.
 
 M <= 64 takes the five fused launches (test_gpu_sparse_variants.py); every larger model runs ~45 launches per evaluation, eagerly on the
 first call of a (cells, gradient) shape, captured into a graph on the second and replayed from the third on.  The case table below holds
 two cases per (kernel id, distance form, isotropy) instantiation of launch_kmat_pair / launch_trace_pair and rotates the edges of M, d, N
 and the cell count through them; ``test_case_table_covers_every_branch_and_edge`` (no GPU) checks that every size branch of the sequence
-is reached and that the inputs are well posed: it fails when a case is removed from the table.
+is reached and that the inputs are well posed: it fails when a case is removed from the table.  One case beside the table has d = 70:
+more lengthscales than a row of the cell-parameter table holds, so its cells run one at a time with the hyperparameters in the launch
+arguments (gprx.hip SgprParSrc).
 
 Inputs as in the variants file: lengthscales sqrt(d) U(0.6, 1.6) keep Kuf away from underflow at d = 64, Z sits on data rows plus 1e-3
 noise.  RBF and Matern52 carry no d <= 8 (their Kuu is jitter-saturated there: cond 1e7 .. 2.6e8); Matern12, Matern32 and Exponential
@@ -39,15 +42,15 @@ HIGH_D = (9, 15, 16, 17, 32, 33, 50, 64)
 N_EDGES = (70, 255, 257, 960, 961, 1025, 1100, 2049)
 N_LARGE = 4097
 CELL_COUNTS = (1, 3, 7, 23, 24, 50)
-NB = 64  # gprx_common.h:12 -- mp = round_up(m, NB), np = round_up(n, NB) (gprx.hip:1774-1775)
-SPLITK_CHUNK = 256  # gprx.hip:885 -- B = A A^T and A y run split-K when np >= 4 * SPLITK_CHUNK (gprx.hip:1302, :1320)
-B_FINISH_MP = 128  # gprx.hip:1312 -- mp <= 128: sgpr_b_finish_kernel, above: add_diag / diag_sum / 2-D copy / 2-D memset
+NB = 64  # gprx_common.h:12 -- mp = round_up(m, NB), np = round_up(n, NB) (gprx.hip:1627-1628)
+SPLITK_CHUNK = 256  # gprx.hip:874 -- B = A A^T and A y run split-K when np >= 4 * SPLITK_CHUNK (gprx.hip:1152, :1170)
+B_FINISH_MP = 128  # gprx.hip:1162 -- mp <= 128: sgpr_b_finish_kernel, above: add_diag / diag_sum / 2-D copy / 2-D memset
 SPLIT_PANEL_FROM = 24  # potrf.h:730 -- potrf_split_panel: batch >= 24 factorises with the split panel
 KM_DC = 8  # kmat.h:20 -- trace_body's p.d > KM_DC branch (grad.h:243)
 DZ_IG, DZ_DC = 4, 16  # grad.h:300 -- dz_kernel: groups of 4 inducing points, chunks of 16 dimensions (dz_grid, grad.h:366)
 MAX_D = 64  # kfun.h:11-12 -- CELL_PAR - CELL_PAR_LS lengthscales fit a row of the cell-parameter table
-SGPR_PRED_TILE = 4096  # gprx.hip:886 -- test points per pass of sgpr_predict_batch
-PRED_ROWS = 256  # gprx.hip:1523 -- rows per chunk of colreduce_partial
+SGPR_PRED_TILE = 4096  # gprx.hip:875 -- test points per pass of sgpr_predict_batch
+PRED_ROWS = 256  # gprx.hip:1377 -- rows per chunk of colreduce_partial
 HYPER = _lib.TRAIN_VARIANCE | _lib.TRAIN_LENGTHSCALE | _lib.TRAIN_NOISE
 ALL = HYPER | _lib.TRAIN_Z
 # Matern12 / Exponential in the expanded form (see NONSMOOTH_EXPANDED_TOL in test_gpu_sparse_variants.py: r^2 = |a|^2 + |b|^2 - 2 a.b
@@ -67,7 +70,7 @@ def mp_of(m):
 
 
 def splitk_of(n):
-    """gprx.hip:1302, :1320 -- np >= 4 * SPLITK_CHUNK (mp <= 512 holds for every M <= 320)."""
+    """gprx.hip:1152, :1170 -- np >= 4 * SPLITK_CHUNK (mp <= 512 holds for every M <= 320)."""
     return mp_of(n) >= 4 * SPLITK_CHUNK
 
 
@@ -112,7 +115,12 @@ def _cases():
     return out
 
 
-CASES = _cases()
+TABLE = _cases()
+# d > MAX_D: gprx_objective_batch evaluates the cells one after the other, each a one-cell batch in the direct parameter mode (N = 1100:
+# split-K; mp = 192: the add_diag route; ARD: 70 lengthscales); bounds of its class (ARD, difference form: 1e-9 / 1e-7)
+WIDE_D = dict(id="Matern32-ard-d70-m130-n1100-c3", kernel="Matern32", cls="ard", d=70, m=130, n=1100, ard=True, form=0, cells=3, seed=30,
+              cond_scaled=False)
+CASES = TABLE + [WIDE_D]
 
 
 def compared_cells(cells):
@@ -185,7 +193,8 @@ def batch(lib, h, units, thetas, zs, mask, want_grad=True):
 
 
 def single(lib, h, unit, theta, z, mask=ALL):
-    """gprx_objective of one model: sgpr_factorize + sgpr_gradient (every array passed by address stays bound for the call)."""
+    """gprx_objective of one model: a batch of one cell that stays resident for gprx_predict (every array passed by address stays bound
+    for the call)."""
     th, zc = np.ascontiguousarray(theta), np.ascontiguousarray(z)
     loss, g1 = C.c_double(), np.zeros(th.size + zc.size)
     check(lib.gprx_objective(h, int(unit), ptr(th), ptr(zc), mask, C.byref(loss), ptr(g1)), h)
@@ -226,33 +235,34 @@ def assert_parity(case, x, y, units, thetas, zs, variance, ls, losses, grads, ce
 def test_case_table_covers_every_branch_and_edge():
     """The table reaches all 15 launch_kmat_pair / launch_trace_pair instantiations, every mp step, the listed edges of M, d, N and the
     cell count, both sides of every size branch of sgpr_batch_enqueue -- and its inputs are well posed (cell 0 of every case: median of
-    Kuf / variance >= 0.05, cond(Kuu + 1e-6 I) <= 1e6 unless the case is in COND_SCALED)."""
-    assert len(CASES) == 30 and len({c["id"] for c in CASES}) == 30
-    inst = [instantiation(c["kernel"], c["ard"], c["form"]) for c in CASES]
+    Kuf / variance >= 0.05, cond(Kuu + 1e-6 I) <= 1e6 unless the case is in COND_SCALED; every cell of the d = 70 case)."""
+    assert len(TABLE) == 30 and len(CASES) == 31 and len({c["id"] for c in CASES}) == 31
+    assert WIDE_D["d"] > MAX_D and WIDE_D["ard"] and WIDE_D["cells"] > 1 and splitk_of(WIDE_D["n"]) and mp_of(WIDE_D["m"]) > B_FINISH_MP
+    inst = [instantiation(c["kernel"], c["ard"], c["form"]) for c in TABLE]
     want = {(kid, form, iso) for kid in range(5) for (form, iso) in ((0, 1), (0, 0), (1, 0))}
     assert set(inst) == want and all(inst.count(w) == 2 for w in want)
-    assert {(c["kernel"], c["ard"]) for c in CASES if c["form"] == 1} == {(k, k not in EXPANDED_ISO) for k in KERNELS}
-    assert all(64 < c["m"] <= 320 and 1 <= c["d"] <= MAX_D for c in CASES)
-    assert {mp_of(c["m"]) for c in CASES} == {128, 192, 256, 320}  # (2, 3, 4 and 5 diagonal blocks of trtri_lower and the panel loops)
-    assert {c["m"] for c in CASES} == set(M_EDGES)
-    assert {c["d"] for c in CASES} == set(LOW_D) | set(HIGH_D) and {1, 7, 8, 9, 15, 16, 17, 32, 33, 50, 64} <= {c["d"] for c in CASES}
-    assert {c["n"] for c in CASES} == set(N_EDGES) | {N_LARGE}
-    assert sum(c["n"] == N_LARGE for c in CASES) == 1
-    assert any(c["n"] == 70 for c in CASES) and all(c["m"] > c["n"] and c["d"] > 1 for c in CASES if c["n"] == 70)
-    assert {c["cells"] for c in CASES} == set(CELL_COUNTS)
-    assert {c["cells"] >= SPLIT_PANEL_FROM for c in CASES} == {False, True}
-    assert all(mp_of(c["m"]) >= 128 for c in CASES if c["cells"] >= SPLIT_PANEL_FROM)
-    assert {mp_of(c["m"]) <= B_FINISH_MP for c in CASES if c["cells"] >= SPLIT_PANEL_FROM} == {False, True}
+    assert {(c["kernel"], c["ard"]) for c in TABLE if c["form"] == 1} == {(k, k not in EXPANDED_ISO) for k in KERNELS}
+    assert all(64 < c["m"] <= 320 and 1 <= c["d"] <= MAX_D for c in TABLE)
+    assert {mp_of(c["m"]) for c in TABLE} == {128, 192, 256, 320}  # (2, 3, 4 and 5 diagonal blocks of trtri_lower and the panel loops)
+    assert {c["m"] for c in TABLE} == set(M_EDGES)
+    assert {c["d"] for c in TABLE} == set(LOW_D) | set(HIGH_D) and {1, 7, 8, 9, 15, 16, 17, 32, 33, 50, 64} <= {c["d"] for c in TABLE}
+    assert {c["n"] for c in TABLE} == set(N_EDGES) | {N_LARGE}
+    assert sum(c["n"] == N_LARGE for c in TABLE) == 1
+    assert any(c["n"] == 70 for c in TABLE) and all(c["m"] > c["n"] and c["d"] > 1 for c in TABLE if c["n"] == 70)
+    assert {c["cells"] for c in TABLE} == set(CELL_COUNTS)
+    assert {c["cells"] >= SPLIT_PANEL_FROM for c in TABLE} == {False, True}
+    assert all(mp_of(c["m"]) >= 128 for c in TABLE if c["cells"] >= SPLIT_PANEL_FROM)
+    assert {mp_of(c["m"]) <= B_FINISH_MP for c in TABLE if c["cells"] >= SPLIT_PANEL_FROM} == {False, True}
     # split-K or plain GEMM, with sgpr_b_finish_kernel or the add_diag route: all four pairs, and N on both sides of the first split-K size
-    assert {(splitk_of(c["n"]), mp_of(c["m"]) <= B_FINISH_MP) for c in CASES} == {(a, b) for a in (False, True) for b in (False, True)}
+    assert {(splitk_of(c["n"]), mp_of(c["m"]) <= B_FINISH_MP) for c in TABLE} == {(a, b) for a in (False, True) for b in (False, True)}
     assert not splitk_of(960) and splitk_of(961) and mp_of(961) == 4 * SPLITK_CHUNK
     # trace_body: d <= KM_DC and above; dz_kernel: one to four chunks of 16 dimensions, M not a multiple of its groups of 4 at an mp edge
-    assert {c["d"] > KM_DC for c in CASES} == {False, True}
-    assert {(c["d"] + DZ_DC - 1) // DZ_DC for c in CASES} == {1, 2, 3, 4}
-    assert {c["m"] % DZ_IG for c in CASES} == {0, 1, 2, 3}
-    assert {c["m"] - (mp_of(c["m"]) - NB) for c in CASES if c["m"] % DZ_IG} >= {1, NB - 1}  # (one past an mp step, one short of the next)
-    assert len(COND_SCALED) <= 3 and {c["id"] for c in CASES if c["cond_scaled"]} == {i + "-condscaled" for i in COND_SCALED}
-    assert all(c["d"] <= 3 for c in CASES if c["cond_scaled"])
+    assert {c["d"] > KM_DC for c in TABLE} == {False, True}
+    assert {(c["d"] + DZ_DC - 1) // DZ_DC for c in TABLE} == {1, 2, 3, 4}
+    assert {c["m"] % DZ_IG for c in TABLE} == {0, 1, 2, 3}
+    assert {c["m"] - (mp_of(c["m"]) - NB) for c in TABLE if c["m"] % DZ_IG} >= {1, NB - 1}  # (one past an mp step, one short of the next)
+    assert len(COND_SCALED) <= 3 and {c["id"] for c in TABLE if c["cond_scaled"]} == {i + "-condscaled" for i in COND_SCALED}
+    assert all(c["d"] <= 3 for c in TABLE if c["cond_scaled"])
     for case in CASES:
         x, _, _, zs, _, variance, ls, _ = draw_inputs(case)
         med, cond = preconditions(case, x, zs[0], variance[0], ls[0])
@@ -261,6 +271,10 @@ def test_case_table_covers_every_branch_and_edge():
             assert max(preconditions(case, x, zs[c], variance[c], ls[c])[1] for c in compared_cells(case["cells"])) > 1e6, case["id"]
         else:
             assert cond <= 1e6, (case["id"], cond)
+    x, _, _, zs, _, variance, ls, _ = draw_inputs(WIDE_D)
+    for c in range(WIDE_D["cells"]):
+        med, cond = preconditions(WIDE_D, x, zs[c], variance[c], ls[c])
+        assert med >= 0.05 and cond <= 1e6, (c, med, cond)
 
 
 # ---- 2. parity and bits of every case ---------------------------------------------------------------------------------------------
@@ -271,7 +285,7 @@ def test_case_table_covers_every_branch_and_edge():
 def test_general_sequence_against_the_oracle_and_bit_for_bit(lib, case):
     """One gprx_objective_batch call with mask 15 and mixed units: loss 1e-9, gradient blocks 1e-7 of their largest entry against the
     oracle (every cell of a batch of at most 7, five cells of a larger one).  Then the bits: cells 0 and -1 equal single gprx_objective
-    calls (sgpr_factorize + sgpr_gradient) and one-cell batches; the loss-only batch (grads = NULL: logdet_quad_kernel) equals
+    calls and one-cell batches (a cell's bits depend neither on its position nor on its batch's size); the loss-only batch (grads = NULL: logdet_quad_kernel) equals
     gprx_factorize; masks 7 and 8 give the full gradient's entries where trained and exact zeros elsewhere.  The masked calls are the
     second and third of the shape: captured, then replayed."""
     x, y, thetas, zs, units, variance, ls, noise = draw_inputs(case)
