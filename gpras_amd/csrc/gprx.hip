@@ -1413,7 +1413,25 @@ int sgpr_predict_batch(gprx_handle h, int count, const double* xs_dev, int64_t n
 // every step synchronised, downloaded the gradients, updated on the host and uploaded).  Same variables as the host-stepped loop, bit
 // for bit (sgpr_asm.h, px_math.h; tests/test_gpu_gpras.py).  A cell whose Kuu or B stops being positive definite ends the call with
 // GPRX_ENOTPD at the next check; the other cells may then be up to check_every - 1 steps past that evaluation.
-int sgpr_adam_resident(gprx_handle h, int count, const int* units, double* theta, double* z, int mask, int max_iter, int* n_evals, int* batches) {
+// kind = SF_OPT_ADADELTA (gprx_adadelta_batch): the same loop with Keras's Adadelta update (gpr.py:176-192) in the fourth launch -- no alpha
+// table, every cell runs max_iter steps; `losses` (optional) receives the loss of each cell's last evaluation.
+// The other groups' streams are joined into the handle's stream before EVERY return (SfJoin): after a failed HIP call inside the step
+// loop nothing may stay in flight on buffers the handle reuses.
+struct SfJoin {
+  gprx_handle h;
+  hipStream_t st;
+  int n = 0;
+  hipStream_t other[gprx_ctx::SF_MAX_GROUPS] = {};
+  void join() {
+    for (int g = 1; g < n; ++g)
+      if (hipEventRecord(h->sf_evs[g], other[g]) == hipSuccess) (void)hipStreamWaitEvent(st, h->sf_evs[g], 0);
+    n = 0;
+  }
+  ~SfJoin() { join(); }
+};
+
+int sgpr_adam_resident(gprx_handle h, int kind, int count, const int* units, double* theta, double* z, int mask, int max_iter, double* losses,
+                       int* n_evals, int* batches) {
   const SgprLayout L = sgpr_batch_layout(h);
   int rc;
   if ((rc = ensure_sarena(h, count, L))) return rc;
@@ -1468,7 +1486,9 @@ int sgpr_adam_resident(gprx_handle h, int count, const int* units, double* theta
   std::memcpy(hd.data(), theta, sizeof(double) * (size_t)count * nt);
   {
     double* hbest = hd.data() + (ad.best - h->adam_dev.p);
+    double* hloss = hd.data() + (ad.loss - h->adam_dev.p);
     for (int c = 0; c < count; ++c) hbest[c] = std::numeric_limits<double>::infinity();
+    for (int c = 0; c < count; ++c) hloss[c] = std::numeric_limits<double>::quiet_NaN();  // (no evaluation yet)
     std::memcpy(hd.data() + (d_yy - h->adam_dev.p), h->yy.data(), sizeof(double) * h->n_units);
     for (int c = 0; c < count; ++c) {
       hi[(size_t)count + c] = 1;          // active
@@ -1496,6 +1516,7 @@ int sgpr_adam_resident(gprx_handle h, int count, const int* units, double* theta
   SfAdam adg[MAXG];
   int cells_g[MAXG], cell0_g[MAXG];
   hipStream_t sg_[MAXG];
+  SfJoin joiner{h, st};
   for (int g = 0, cell0 = 0; g < ngroups; ++g) {
     const int cells = count / ngroups + (g < count % ngroups ? 1 : 0);
     sg_[g] = g == 0 ? st : h->sf_streams[g - 1];
@@ -1514,20 +1535,23 @@ int sgpr_adam_resident(gprx_handle h, int count, const int* units, double* theta
     adg[g].tstep += cell0;
     adg[g].units += cell0;
     adg[g].error += g;
+    joiner.other[g] = sg_[g];
     cell0 += cells;
   }
+  joiner.n = ngroups;
+  const bool adam = kind == SF_OPT_ADAM;
   for (int g = 0; g < ngroups; ++g)
     HIPCHK(h, sf_launch_prep(sg_[g], h->kid, h->dist_form, pg[g], cells_g[g], nullptr, nullptr, h->cellpar.p + (size_t)cell0_g[g] * CELL_PAR, &adg[g]));  // opens step 1
   for (int done = 0; done < max_iter;) {
     const int k = std::min(check_every, max_iter - done);
     // this window's alpha values (steps done + 1 .. done + k; every active cell is at the same step): the pinned block is free, the
     // previous window's upload has completed before its stop flags were read
-    for (int i = 0; i < k; ++i) {
+    for (int i = 0; adam && i < k; ++i) {
       const double t = (double)done + 1.0 + i;
       halpha[i] = ADAM_LR * std::sqrt(1.0 - std::pow(ADAM_BETA2, t)) / (1.0 - std::pow(ADAM_BETA1, t));  // gprx_adam_batch's expression
     }
-    HIPCHK(h, hipMemcpyAsync(d_alpha, halpha, sizeof(double) * (size_t)k, hipMemcpyHostToDevice, st));
-    if (ngroups > 1) {
+    if (adam) HIPCHK(h, hipMemcpyAsync(d_alpha, halpha, sizeof(double) * (size_t)k, hipMemcpyHostToDevice, st));
+    if (adam && ngroups > 1) {
       HIPCHK(h, hipEventRecord(h->sf_evs[0], st));
       for (int g = 1; g < ngroups; ++g) HIPCHK(h, hipStreamWaitEvent(sg_[g], h->sf_evs[0], 0));
     }
@@ -1545,7 +1569,8 @@ int sgpr_adam_resident(gprx_handle h, int count, const int* units, double* theta
         HIPCHK(h, sf_launch_mid(sg_[g], pg[g], cells_g[g]));
         HIPCHK(h, sf_launch_pass2(sg_[g], h->kid, h->dist_form, iso, pg[g], cells_g[g]));
         // closes this step, opens the next
-        HIPCHK(h, sf_launch_adam_prep(sg_[g], h->kid, h->dist_form, iso, pg[g], cells_g[g], adg[g], h->cellpar.p + (size_t)cell0_g[g] * CELL_PAR));
+        HIPCHK(h, (adam ? sf_launch_adam_prep : sf_launch_adadelta_prep)(sg_[g], h->kid, h->dist_form, iso, pg[g], cells_g[g], adg[g],
+                                                                         h->cellpar.p + (size_t)cell0_g[g] * CELL_PAR));
       }
     }
     done += k;
@@ -1564,14 +1589,12 @@ int sgpr_adam_resident(gprx_handle h, int count, const int* units, double* theta
     if (error_cell != 0 || !any) break;
   }
   // ---- results ----
-  for (int g = 1; g < ngroups; ++g) {  // (nothing of the other group's stream may outlive the call: max_iter = 0 enqueued its prep launch only)
-    HIPCHK(h, hipEventRecord(h->sf_evs[g], sg_[g]));
-    HIPCHK(h, hipStreamWaitEvent(st, h->sf_evs[g], 0));
-  }
+  joiner.join();  // (nothing of the other group's stream may outlive the call: max_iter = 0 enqueued its prep launch only)
   HIPCHK(h, hipMemcpyAsync(theta, ad.theta, sizeof(double) * (size_t)count * nt, hipMemcpyDeviceToHost, st));
   HIPCHK(h, hipMemcpy2DAsync(z, sizeof(double) * (size_t)nz, h->sarena.p + L.oZ, sizeof(double) * (size_t)L.ss, sizeof(double) * (size_t)nz, count,
                              hipMemcpyDeviceToHost, st));
   HIPCHK(h, hipMemcpyAsync(n_evals, ad.n_evals, sizeof(int) * count, hipMemcpyDeviceToHost, st));
+  if (losses) HIPCHK(h, hipMemcpyAsync(losses, ad.loss, sizeof(double) * count, hipMemcpyDeviceToHost, st));
   HIPCHK(h, hipStreamSynchronize(st));
   if (batches) {
     int mx = 0;
@@ -1871,7 +1894,10 @@ int gprx_factorize_many(int count, gprx_handle* handles, const int* units, const
   return first_error;
 }
 
-static int adam_batch(gprx_handle h, int count, const int* units, double* theta, double* z, int mask, int max_iter, int* n_evals, int* batches) {
+// gprx_adam_batch and gprx_adadelta_batch: one loop, two updates (kind: SF_OPT_ADAM, SF_OPT_ADADELTA of sgpr_asm.h).  Adadelta has no stop
+// rule, so its batch never shrinks.  last_losses (optional): the loss of each cell's last evaluation.
+static int optimizer_batch(gprx_handle h, int kind, int count, const int* units, double* theta, double* z, int mask, int max_iter,
+                           double* last_losses, int* n_evals, int* batches) {
 #pragma clang fp contract(off)
   int rc;
   if ((rc = check_handle(h))) return rc;
@@ -1881,6 +1907,9 @@ static int adam_batch(gprx_handle h, int count, const int* units, double* theta,
   const int64_t nz = h->m * h->d, gw = nt + nz;
   if (batches) *batches = 0;
   for (int i = 0; i < count; ++i) n_evals[i] = 0;
+  if (last_losses)
+    for (int i = 0; i < count; ++i) last_losses[i] = std::numeric_limits<double>::quiet_NaN();  // (no evaluation yet)
+  const bool adam = kind == SF_OPT_ADAM;
   // trainable elements of a cell's gradient row [d theta | d Z] (theta: [variance, lengthscales..., noise])
   std::vector<char> train((size_t)gw, 0);
   train[0] = (mask & GPRX_TRAIN_VARIANCE) != 0;
@@ -1899,7 +1928,7 @@ static int adam_batch(gprx_handle h, int count, const int* units, double* theta,
     }
     for (int64_t e = 0; e < (int64_t)count * nz; ++e)
       if (!std::isfinite(z[e])) return fail(h, GPRX_EINVAL, "z is not finite");
-    return sgpr_adam_resident(h, count, units, theta, z, mask, max_iter, n_evals, batches);
+    return sgpr_adam_resident(h, kind, count, units, theta, z, mask, max_iter, last_losses, n_evals, batches);
   }
   const double lr = ADAM_LR, beta1 = ADAM_BETA1, beta2 = ADAM_BETA2;
   std::vector<double> mom((size_t)count * gw, 0.0), vel((size_t)count * gw, 0.0), best(count, std::numeric_limits<double>::infinity());
@@ -1918,8 +1947,10 @@ static int adam_batch(gprx_handle h, int count, const int* units, double* theta,
     rc = gprx_objective_batch(h, na, a_units.data(), a_theta.data(), nz ? a_z.data() : nullptr, mask, losses.data(), grads.data());
     if (batches) ++*batches;
     for (int j = 0; j < na; ++j) ++n_evals[active[j]];
+    if (last_losses)  // (a failed cell holds NaN; after any other error the evaluation wrote no loss)
+      for (int j = 0; j < na; ++j) last_losses[active[j]] = (rc == GPRX_OK || rc == GPRX_ENOTPD) ? losses[j] : std::numeric_limits<double>::quiet_NaN();
     if (rc) return rc;  // (GPRX_ENOTPD included: the reference's optimiser dies with the exception of that evaluation)
-    const double alpha = lr * std::sqrt(1.0 - std::pow(beta2, (double)t)) / (1.0 - std::pow(beta1, (double)t));
+    const double alpha = adam ? lr * std::sqrt(1.0 - std::pow(beta2, (double)t)) / (1.0 - std::pow(beta1, (double)t)) : 0.0;
     std::vector<int> next;
     next.reserve(na);
     for (int j = 0; j < na; ++j) {
@@ -1930,9 +1961,12 @@ static int adam_batch(gprx_handle h, int count, const int* units, double* theta,
       for (int64_t e = 0; e < gw; ++e) {
         if (!train[e]) continue;
         double* x = e < nt ? theta + (size_t)i * nt + e : z + (size_t)i * nz + (e - nt);
-        adam_element(g[e], alpha, mo[e], ve[e], *x);  // (sgpr_asm.h: the resident loop's kernel runs the same function)
+        if (adam)
+          adam_element(g[e], alpha, mo[e], ve[e], *x);  // (sgpr_asm.h: the resident loop's kernel runs the same function)
+        else
+          adadelta_element(g[e], mo[e], ve[e], *x);  // (the accumulated squared gradients and updates in the moments' arrays)
       }
-      if (adam_keep_running(losses[j], best[i], stale[i])) next.push_back(i);
+      if (!adam || adam_keep_running(losses[j], best[i], stale[i])) next.push_back(i);
     }
     active.swap(next);
   }
@@ -1941,8 +1975,17 @@ static int adam_batch(gprx_handle h, int count, const int* units, double* theta,
 
 int gprx_adam_batch(gprx_handle h, int count, const int* units, double* theta, double* z, int mask, int max_iter, int* n_evals, int* batches) {
   try {
-    return adam_batch(h, count, units, theta, z, mask, max_iter, n_evals, batches);
+    return optimizer_batch(h, SF_OPT_ADAM, count, units, theta, z, mask, max_iter, nullptr, n_evals, batches);
   } catch (const std::bad_alloc&) {  // (no C++ exception may cross the C ABI)
+    return fail(h, GPRX_ENOMEM, "host allocation failed");
+  }
+}
+
+int gprx_adadelta_batch(gprx_handle h, int count, const int* units, double* theta, double* z, int mask, int max_iter, double* losses, int* n_evals,
+                        int* batches) {
+  try {
+    return optimizer_batch(h, SF_OPT_ADADELTA, count, units, theta, z, mask, max_iter, losses, n_evals, batches);
+  } catch (const std::bad_alloc&) {
     return fail(h, GPRX_ENOMEM, "host allocation failed");
   }
 }

@@ -127,7 +127,9 @@ __device__ __forceinline__ void sf_reduce_sums(const SfParams& p, const double* 
 // sTh (nt) and sZnew (m d), when given, receive the variables after the update (LDS: the merged launch goes on to the next step's
 // Kuu from them).  Returns through *keep (LDS int, written by thread 255) whether the cell keeps running.  Every thread must call it;
 // it contains one __syncthreads().
-template <int ISO>
+// OPT (sgpr_asm.h): SF_OPT_ADAM as above; SF_OPT_ADADELTA runs Keras's Adadelta update (gpr.py:176-192) instead -- its two accumulators
+// live in mom / vel, no alpha table is read, the cell runs exactly max_iter steps (best / stale stay untouched).
+template <int ISO, int OPT = SF_OPT_ADAM>
 __device__ __forceinline__ void sf_adam_body(const SfParams& p, const SfAdam& ad, int cell, int tid, double* __restrict__ shs, double* __restrict__ sred,
                                              double* __restrict__ sTh, double* __restrict__ sZnew, int* __restrict__ keep) {
   const double* par = p.cpar + (int64_t)cell * CELL_PAR;
@@ -138,7 +140,8 @@ __device__ __forceinline__ void sf_adam_body(const SfParams& p, const SfAdam& ad
   // (the step and its alpha are read before the barrier: thread 255 stores tstep[cell] = t below, and a wave that reached this
   // read after that store would take the next step's alpha -- at the end of a window one entry past it)
   const int t = ad.tstep[cell] + 1;
-  const double alpha = ad.alpha[t - ad.alpha_t1];
+  double alpha = 0.0;
+  if constexpr (OPT == SF_OPT_ADAM) alpha = ad.alpha[t - ad.alpha_t1];
   if (tid < 4) sred[tid] = A[p.oRed + tid];
   sf_reduce_sums<ISO>(p, P2, ls, tid, &sred[4], shs);
   __syncthreads();
@@ -165,7 +168,10 @@ __device__ __forceinline__ void sf_adam_body(const SfParams& p, const SfAdam& ad
     const double ge = sgpr_asm_chain(du, u, w, trainable);
     if (trainable) {
       double mo = mom[k], ve = vel[k];
-      adam_element(ge, alpha, mo, ve, w);
+      if constexpr (OPT == SF_OPT_ADAM)
+        adam_element(ge, alpha, mo, ve, w);
+      else
+        adadelta_element(ge, mo, ve, w);
       mom[k] = mo;
       vel[k] = ve;
       th[k] = w;
@@ -192,7 +198,10 @@ __device__ __forceinline__ void sf_adam_body(const SfParams& p, const SfAdam& ad
         if (e < nz) {
           if (train_z) {
             const double ge = -(acc[u] / ls[e % p.d]);
-            adam_element(ge, alpha, mo[u], ve[u], x[u]);
+            if constexpr (OPT == SF_OPT_ADAM)
+              adam_element(ge, alpha, mo[u], ve[u], x[u]);
+            else
+              adadelta_element(ge, mo[u], ve[u], x[u]);
             mom[nt + e] = mo[u];
             vel[nt + e] = ve[u];
             A[p.oZ + e] = x[u];
@@ -213,11 +222,14 @@ __device__ __forceinline__ void sf_adam_body(const SfParams& p, const SfAdam& ad
       if (ad.mask & ASM_TRAIN_NOISE) lp += px_ln_logpdf(noise);
     }
     const double loss = -(elbo + lp);
-    double best = ad.best[cell];
-    int stale = ad.stale[cell];
-    const bool go = adam_keep_running(loss, best, stale) && t < ad.max_iter;
-    ad.best[cell] = best;
-    ad.stale[cell] = stale;
+    bool go = t < ad.max_iter;
+    if constexpr (OPT == SF_OPT_ADAM) {
+      double best = ad.best[cell];
+      int stale = ad.stale[cell];
+      go = adam_keep_running(loss, best, stale) && go;
+      ad.best[cell] = best;
+      ad.stale[cell] = stale;
+    }
     ad.loss[cell] = loss;
     ad.n_evals[cell] += 1;
     ad.tstep[cell] = t;

@@ -1,6 +1,7 @@
 // The scalar tail of one SGPR evaluation -- ELBO from the device reductions, derivatives w.r.t. the constrained hyperparameters,
-// LogNormal priors, the chain rule through softplus -- and one element of Keras's Adam update (gpr.py:147-173), written ONCE for the
-// host (sgpr_objective_batch's tail, gprx_adam_batch's host-stepped loop) and the device (sf_adam_kernel, the resident loop): the same
+// LogNormal priors, the chain rule through softplus -- and one element of Keras's Adam update (gpr.py:147-173) and of its Adadelta
+// update (gpr.py:176-192), written ONCE for the host (sgpr_objective_batch's tail, the host-stepped loop of gprx_adam_batch /
+// gprx_adadelta_batch) and the device (sf_adam_prep_kernel, the resident loop): the same
 // operations in the same order with one rounding each (px_math.h), so both give the same bits.
 // Formulas: oracle/sgpr.py elbo_grads / loss_and_grad (gpflow SGPR.elbo, priors over trainable parameters only).
 #pragma once
@@ -58,5 +59,19 @@ GPRX_HD bool adam_keep_running(double loss, double& best, int& stale) {
   }
   return ++stale <= ADAM_PATIENCE;
 }
+
+// Keras Adadelta, one element (optimizers._optimize_adadelta, gpr.py:176-192): the two accumulators and the variable updated in place,
+// NumPy's evaluation order, one rounding per operation.
+constexpr double ADADELTA_RHO = 0.95, ADADELTA_EPS = 1e-7, ADADELTA_LR = 1e-3;
+GPRX_HD void adadelta_element(double ge, double& acc_g, double& acc_d, double& x) {
+#pragma clang fp contract(off)
+  acc_g = ADADELTA_RHO * acc_g + ((1.0 - ADADELTA_RHO) * ge) * ge;
+  const double delta = ((-sqrt(acc_d + ADADELTA_EPS)) * ge) / sqrt(acc_g + ADADELTA_EPS);
+  acc_d = ADADELTA_RHO * acc_d + ((1.0 - ADADELTA_RHO) * delta) * delta;
+  x = x + ADADELTA_LR * delta;
+}
+
+// which optimiser a loop runs (compile-time parameter of the resident loop's kernels, run-time argument of the host-stepped loop)
+constexpr int SF_OPT_ADAM = 0, SF_OPT_ADADELTA = 1;
 
 }  // namespace gprx

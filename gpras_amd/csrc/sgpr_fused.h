@@ -57,8 +57,8 @@ struct SfParams {
 // launches with sf_adam_kernel as the fifth, the host looks at the stop flags every few steps only.
 struct SfAdam {
   double* theta;      // (cells, nt) unconstrained variables [variance, lengthscales .., noise]; Z lives in the cell blocks (oZ)
-  double* mom;        // (cells, nt + m d) first moments  [theta | Z]
-  double* vel;        // (cells, nt + m d) second moments
+  double* mom;        // (cells, nt + m d) first moments  [theta | Z]   (Adadelta: the accumulated squared gradients)
+  double* vel;        // (cells, nt + m d) second moments               (Adadelta: the accumulated squared updates)
   double* best;       // (cells) best loss so far
   double* loss;       // (cells) loss of the last evaluation
   int* stale;         // (cells) steps without an improvement of more than tol
@@ -91,6 +91,10 @@ hipError_t sf_launch_prep(hipStream_t st, int kid, int form, const SfParams& p, 
 // step t, then -- for cells that keep running -- Kuu, L, L^-1 of the new variables (the prep of step t + 1).  A step is FOUR launches:
 // pass 1, mid, pass 2, this one; sf_launch_prep opens the first step.
 hipError_t sf_launch_adam_prep(hipStream_t st, int kid, int form, int iso, const SfParams& p, int cells, const SfAdam& adam, double* cpar_dst);
+// The same launch with Keras's Adadelta update (gpr.py:176-192; sf_adadelta.hip): the accumulators in adam.mom / adam.vel, no alpha table,
+// no early stop -- a cell runs until adam.max_iter.
+hipError_t sf_launch_adadelta_prep(hipStream_t st, int kid, int form, int iso, const SfParams& p, int cells, const SfAdam& adam,
+                                   double* cpar_dst);
 hipError_t sf_launch_pass1(hipStream_t st, int kid, int form, const SfParams& p, int cells);
 hipError_t sf_launch_mid(hipStream_t st, const SfParams& p, int cells);
 hipError_t sf_launch_pass2(hipStream_t st, int kid, int form, int iso, const SfParams& p, int cells);

@@ -179,6 +179,36 @@ class Engine:
                 raise
         return thetas, (zs if self.m != 0 else None), n_evals, batches.value
 
+    @_locked
+    def adadelta_batch(self, units, thetas, mask: int, max_iter: int, zs=None):
+        """``_optimize_adadelta`` (gpr.py:176-192) for ``len(units)`` cells in lock step inside the library (``gprx_adadelta_batch``),
+        the twin of ``adam_batch``: exactly ``max_iter`` steps per cell.  Returns ``(thetas, zs, n_evals, batches, losses)`` --
+        ``losses`` holds each cell's last loss (NaN where no evaluation was made).  Raises as ``adam_batch`` does, with ``.state``
+        ``(thetas, zs, n_evals, batches)``."""
+        units = np.ascontiguousarray(units, dtype=np.int32)
+        thetas = np.array(thetas, dtype=np.float64, order="C")
+        if thetas.shape != (units.size, self.n_theta):
+            raise ValueError(f"thetas must be ({units.size}, {self.n_theta})")
+        zp = None
+        if self.m != 0:
+            zs = np.array(zs, dtype=np.float64, order="C")
+            if zs.shape != (units.size, self.m, self.d):
+                raise ValueError(f"zs must be ({units.size}, {self.m}, {self.d})")
+            zp = ptr(zs)
+        n_evals = np.zeros(units.size, dtype=np.int32)
+        losses = np.full(units.size, np.nan)
+        batches = C.c_int()
+        rc = self._lib.gprx_adadelta_batch(
+            self._h, units.size, ptr(units), ptr(thetas), zp, int(mask), int(max_iter), ptr(losses), ptr(n_evals), C.byref(batches)
+        )
+        if rc != _lib.GPRX_OK:
+            try:
+                check(rc, self._h)
+            except Exception as exc:  # noqa: BLE001
+                exc.state = (thetas, zs, n_evals, batches.value)
+                raise
+        return thetas, (zs if self.m != 0 else None), n_evals, batches.value, losses
+
     def max_cells(self, want_grad: bool = False, reserve: float = 0.15) -> int:
         """How many cells of a batched call fit into the free device memory (``gprx_cell_bytes`` against ``gprx_mem_info``,
         keeping ``reserve`` of the total free for predict tiles and other handles); at least 1."""

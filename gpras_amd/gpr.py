@@ -102,10 +102,13 @@ class GPRAS:
         if lockstep and not can_lockstep:
             raise ValueError("lockstep fitting needs several modes on one engine (workers=1)")
         if len(models) == 1 and len(self.engines) == 1 and lockstep is None and optimization_method in BATCHED_OPTIMIZERS and hasattr(self.engine, "adam_batch"):
-            # one mode with an Adam-based driver: the loop inside the library as well (sparse models with M <= 64: resident on the
-            # device, no host round trip per step); same variables as the serial driver bit for bit (tests/test_gpu_gpras.py)
+            # one mode with a batched driver: its Adam / Adadelta loops inside the library as well (sparse models with M <= 64: resident
+            # on the device, no host round trip per step); same variables as the serial driver bit for bit (tests/test_gpu_gpras.py,
+            # tests/test_gpu_drivers.py)
             stats1: dict[str, int] = {"batches": 0}
+            before = models[0].n_evals
             BATCHED_OPTIMIZERS[optimization_method](models, stats=stats1, **opt_kwargs)
+            self.lockstep_stats = {"batches": stats1["batches"], "evaluations": models[0].n_evals - before}
             return
         if can_lockstep and (lockstep is None or lockstep):
             # modes per batched launch sequence: 32, or fewer when the per-cell workspaces (kernel matrix, L^-1 and K^-1 of
@@ -114,7 +117,7 @@ class GPRAS:
             if hasattr(self.engine, "max_cells"):
                 per_batch = max(1, min(per_batch, self.engine.max_cells(want_grad=True)))
             if optimization_method in BATCHED_OPTIMIZERS:
-                # Adam-based drivers: one loop over all modes (rows of 2-D state arrays; no thread per mode), so up to 128 cells
+                # drivers with a batched form (their Adam / Adadelta loops): one loop over all modes (rows of 2-D state arrays; no thread per mode), so up to 128 cells
                 # per batched evaluation -- the fixed latency of an evaluation is shared by more modes (50 modes: one loop of
                 # 50 instead of 32 + 18)
                 if hasattr(self.engine, "max_cells"):

@@ -95,6 +95,11 @@ def _optimize_three_stage(model, max_iter: int = 100) -> None:
     model.set_all_trainable(False)
     model.set_trainable(Z=True)
     _optimize_adam(model, max_iter)
+    _three_stage_bfgs_legs(model, max_iter)
+
+
+def _three_stage_bfgs_legs(model, max_iter: int) -> None:
+    """Stages two and three of ``three-stage`` (gpr.py:138-144)."""
     model.set_all_trainable(True)
     model.set_trainable(Z=False)
     _optimize_bfgs(model, max_iter)
@@ -139,6 +144,11 @@ def _optimize_differential_evolutions(
     model.set_all_trainable(False)
     model.set_trainable(Z=True)
     _optimize_adam(model, adam_iter)
+    return _differential_evolution_leg(model, popsize, max_iter, seed, verbose, batched)
+
+
+def _differential_evolution_leg(model, popsize: int, max_iter: int, seed, verbose, batched: bool) -> Any:
+    """The search of ``_optimize_differential_evolutions`` after its Adam stage (gpr.py:52-70)."""
     param_bounds = [(-1, 1), (-1, 1), (-3, 0)]
 
     def objective(params):
@@ -171,7 +181,8 @@ def _optimize_differential_evolutions(
 # The Adam-based drivers are simple enough to run for all modes of one engine in ONE host loop: the per-mode state lives
 # in the rows of 2-D arrays (numpy applies the same IEEE operations per element as the per-mode code above, so every
 # mode's trajectory -- including its own early stop -- is bit-identical), and every step is one batched evaluation
-# (Engine.objective_batch).  GPRAS.fit uses them in lock-step mode; the other drivers run under gpras_amd.lockstep.
+# (Engine.objective_batch).  GPRAS.fit uses them in lock-step mode.  The drivers that mix Adam stages with L-BFGS-B or differential
+# evolution batch their Adam stages the same way and run the rest under gpras_amd.lockstep (_run_leg); L-BFGS-B alone runs there whole.
 def _evaluate_many(models, want_grad: bool = True, stats: dict | None = None):
     if stats is not None:
         stats["batches"] = stats.get("batches", 0) + 1
@@ -267,7 +278,7 @@ def _optimize_adam_many(models, max_iter: int, stats: dict | None = None) -> Non
     if _PackedBatch.usable(models):
         batch = _PackedBatch(models)
         if hasattr(batch.eng, "adam_batch"):
-            return _adam_in_library(batch, x, int(max_iter), stats)
+            return _loop_in_library(batch, x, int(max_iter), stats, batch.eng.adam_batch, _adam_packed)
         return _adam_packed(batch, x, int(max_iter), stats)
     mom = np.zeros_like(x)
     v = np.zeros_like(x)
@@ -298,9 +309,11 @@ def _optimize_adam_many(models, max_iter: int, stats: dict | None = None) -> Non
                     active[i] = False
 
 
-def _adam_in_library(batch: "_PackedBatch", x, max_iter: int, stats) -> None:
-    """The same loop inside ``libgprx.so`` (``gprx_adam_batch``): nothing of a step runs in Python.  Same numbers as
-    ``_adam_packed`` (the C loop restates the NumPy expressions operation by operation; tests hold both against the serial driver)."""
+def _loop_in_library(batch: "_PackedBatch", x, max_iter: int, stats, library_loop, packed_loop):
+    """The same loop inside ``libgprx.so`` (``library_loop``: ``Engine.adam_batch`` / ``Engine.adadelta_batch``): nothing of a step
+    runs in Python.  Same numbers as ``packed_loop`` (``_adam_packed`` / ``_adadelta_packed``: the C loop restates the NumPy
+    expressions operation by operation; tests hold both against the serial driver), which takes over when the batch does not fit
+    in device memory.  Returns the last losses where the loop reports them."""
     from .model import TRAIN_Z
 
     def store(thetas, zs, n_evals, batches):
@@ -319,17 +332,18 @@ def _adam_in_library(batch: "_PackedBatch", x, max_iter: int, stats) -> None:
         batch.write_back(x)
 
     try:
-        out = batch.eng.adam_batch(batch.units, batch.thetas, batch.mask, max_iter, zs=batch.zs)
+        out = library_loop(batch.units, batch.thetas, batch.mask, max_iter, zs=batch.zs)
     except MemoryError:
         # the batch does not fit in device memory: the Python loop splits its evaluations (Engine.objective_batch); the library
         # ran out on the first evaluation, before any update
-        return _adam_packed(batch, x, max_iter, stats)
+        return packed_loop(batch, x, max_iter, stats)
     except Exception as exc:  # noqa: BLE001
         state = getattr(exc, "state", None)
         if state is not None:
             store(*state)  # the models keep the variables of the step that failed, as in the Python loop
         raise
-    store(*out)
+    store(*out[:4])
+    return out[4] if len(out) > 4 else None
 
 
 def _adam_packed(batch: "_PackedBatch", x, max_iter: int, stats) -> None:
@@ -380,7 +394,135 @@ def _optimize_two_stage_many(models, max_iter: int = 100, stats: dict | None = N
     _evaluate_many(models, want_grad=False, stats=stats)  # the final training_loss() of the reference's driver
 
 
-BATCHED_OPTIMIZERS: dict[str, Any] = {"adam": _optimize_adam_many, "two-stage": _optimize_two_stage_many}
+def _optimize_adadelta_many(models, max_iter: int, stats: dict | None = None) -> Any:
+    """``_optimize_adadelta`` for every model (gpr.py:176-192), one batched evaluation per step.  Returns the last losses."""
+    lr, rho, eps = 1e-3, 0.95, 1e-7
+    x = np.stack([m.get_vector() for m in models])
+    if x.shape[1] and _PackedBatch.usable(models):
+        batch = _PackedBatch(models)
+        if hasattr(batch.eng, "adadelta_batch"):
+            return _loop_in_library(batch, x, int(max_iter), stats, batch.eng.adadelta_batch, _adadelta_packed)
+        return _adadelta_packed(batch, x, int(max_iter), stats)
+    # (nothing trainable, or models that cannot share one packed batch: the serial driver's loop on every model, step by step)
+    acc_grad = np.zeros_like(x)
+    acc_delta = np.zeros_like(x)
+    losses = None
+    for _ in range(int(max_iter)):
+        losses, grads = _evaluate_many(models, stats=stats)
+        g = np.stack(grads)
+        acc_grad = rho * acc_grad + (1.0 - rho) * g * g
+        delta = -np.sqrt(acc_delta + eps) * g / np.sqrt(acc_grad + eps)
+        acc_delta = rho * acc_delta + (1.0 - rho) * delta * delta
+        x = x + lr * delta
+        for m, row in zip(models, x):
+            m.set_vector(row)
+    return losses
+
+
+def _adadelta_packed(batch: "_PackedBatch", x, max_iter: int, stats) -> Any:
+    """The loop of ``_optimize_adadelta`` on packed arrays: per element the same operations in the same order."""
+    lr, rho, eps = 1e-3, 0.95, 1e-7
+    rows = np.arange(x.shape[0])
+    acc_grad = np.zeros_like(x)
+    acc_delta = np.zeros_like(x)
+    losses = None
+    try:
+        for _ in range(max_iter):
+            losses, g = batch.evaluate(rows, stats)
+            acc_grad = rho * acc_grad + (1.0 - rho) * g * g
+            delta = -np.sqrt(acc_delta + eps) * g / np.sqrt(acc_grad + eps)
+            acc_delta = rho * acc_delta + (1.0 - rho) * delta * delta
+            x += lr * delta
+            batch.assign(rows, x)
+    finally:
+        batch.write_back(x)
+    return losses
+
+
+def _run_leg(models, leg, leg_kwargs: dict[str, Any], stats: dict | None) -> None:
+    """``leg(model, **leg_kwargs)`` for every model -- a part of a driver that is not one packed loop (L-BFGS-B, differential
+    evolution): for several models the legs run in lock step (``gpras_amd.lockstep``: one thread per model, every round of
+    evaluations one batched launch sequence, at most 32 models at a time), a lone model runs its leg directly."""
+    if len(models) == 1 or not hasattr(models[0].backend, "objective_batch"):
+        before = sum(m.n_evals for m in models)
+        for m in models:
+            leg(m, **leg_kwargs)
+        if stats is not None:
+            stats["batches"] = stats.get("batches", 0) + sum(m.n_evals for m in models) - before
+        return
+    from .lockstep import fit_lockstep
+
+    max_batch = 32
+    if hasattr(models[0].backend, "max_cells"):
+        max_batch = max(1, min(max_batch, models[0].backend.max_cells(want_grad=True)))
+    counters = fit_lockstep(models, leg, leg_kwargs, max_batch=max_batch)
+    if stats is not None:
+        stats["batches"] = stats.get("batches", 0) + counters["batches"]
+
+
+def _optimize_three_stage_many(models, max_iter: int = 100, stats: dict | None = None) -> None:
+    """``_optimize_three_stage`` for every model (gpr.py:130-144): the Adam stage on Z as one batched loop, the two L-BFGS-B
+    stages in lock step."""
+    for m in models:
+        m.set_all_trainable(False)
+        m.set_trainable(Z=True)
+    _optimize_adam_many(models, max_iter, stats)
+    _run_leg(models, _three_stage_bfgs_legs, {"max_iter": max_iter}, stats)
+
+
+def _optimize_differential_evolutions_many(
+    models, popsize: int = 15, max_iter: int = 500, seed=None, adam_iter: int = 3000, verbose=True, batched: bool = False, stats: dict | None = None
+) -> None:
+    """``_optimize_differential_evolutions`` for every model (gpr.py:44-70): the Adam stage on Z as one batched loop, then every
+    model's own search (same ``seed`` for each, as the serial loop passes it) in lock step."""
+    for m in models:
+        m.set_all_trainable(False)
+        m.set_trainable(Z=True)
+    _optimize_adam_many(models, adam_iter, stats)
+    _run_leg(models, _differential_evolution_leg, {"popsize": popsize, "max_iter": max_iter, "seed": seed, "verbose": verbose, "batched": batched}, stats)
+
+
+def _optimize_multi_start_many(models, n_starts: int = 40, iter_initial: int = 20, iter_final: int = 1000, rng=None, stats: dict | None = None) -> None:
+    """``_optimize_multi_start`` for every model (gpr.py:73-109).  The random starts do not depend on any result and have fixed
+    sizes, so all of them are drawn up front in the serial loop's order -- model by model, per start variance, lengthscale, noise,
+    Z -- and a seeded ``rng`` gives every model the numbers the serial loop gives it, whatever the threads of a later leg do.
+    Then start by start for all models at once: the Adam steps as one batched loop, one batched loss-only evaluation."""
+    np.random.seed(1)  # gpr.py:76 -- has no effect on default_rng(), kept for fidelity
+    rng = np.random.default_rng() if rng is None else rng
+    draws = []
+    for model in models:
+        x = model.backend_x()
+        mins, maxs = x.min(axis=0), x.max(axis=0)
+        z_shape = (model.Z.shape[0], x.shape[1])
+        draws.append([(10 ** rng.uniform(-1, 1), 10 ** rng.uniform(-1, 1), 10 ** rng.uniform(-3, 0), rng.uniform(mins, maxs, size=z_shape))
+                      for _ in range(int(n_starts))])
+    best_params = [None] * len(models)
+    for s in range(int(n_starts)):
+        for model, mine in zip(models, draws):
+            variance, lengthscales, noise, z = mine[s]
+            model.assign(variance=variance)
+            model.assign(lengthscales=lengthscales)
+            model.assign(noise=noise)
+            model.Z = z
+            model.set_trainable(Z=False)  # gpr.py:91 swaps the Parameter for an ndarray: Z is no longer trainable
+        _optimize_adam_many(models, iter_initial, stats)
+        _evaluate_many(models, want_grad=False, stats=stats)  # the training_loss() of gpr.py:94
+        # gpr.py:96 never assigns best_loss, so every start overwrites best_params
+        best_params = [[m.variance, m.lengthscales, m.noise, m.Z.copy()] for m in models]
+    for model, best in zip(models, best_params):
+        model.assign(variance=best[0], lengthscales=best[1], noise=best[2])
+        model.Z = best[3]
+    _run_leg(models, _optimize_bfgs, {"max_iter": iter_final}, stats)
+
+
+BATCHED_OPTIMIZERS: dict[str, Any] = {
+    "adam": _optimize_adam_many,
+    "two-stage": _optimize_two_stage_many,
+    "three-stage": _optimize_three_stage_many,
+    "adadelta": _optimize_adadelta_many,
+    "stochastic": _optimize_multi_start_many,
+    "diffential_evolution": _optimize_differential_evolutions_many,
+}
 
 OPTIMIZERS: dict[str, Any] = {
     "two-stage": _optimize_two_stage,

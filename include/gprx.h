@@ -310,8 +310,23 @@ int gprx_predict_batch_dev(gprx_handle h, int count, const int* units, const dou
  * is that of the NumPy statement of the update (one rounding per operation, no contraction): the result equals
  * gpras_amd.optimizers._optimize_adam on each cell bit for bit.  A cell whose matrix stops being positive definite ends the
  * call with GPRX_ENOTPD (gpr.py: the exception leaves the optimiser); theta / z hold the state of that step (resident loop: the
- * failing cell is as it was before the failing evaluation, the others may be up to 24 steps further: the flags are read every 25). */
+ * failing cell is as it was before the failing evaluation, the others may be up to 24 steps further: the flags are read every 25).
+ * Its twin with Keras's Adadelta update is gprx_adadelta_batch below: same routes, same launches, another update. */
 int gprx_adam_batch(gprx_handle h, int count, const int* units, double* theta, double* z, int mask, int max_iter, int* n_evals, int* batches);
+
+/* The reference's Adadelta driver, _optimize_adadelta (gpr.py:176-192: tf.keras.optimizers.Adadelta() defaults -- learning rate 1e-3,
+ * rho 0.95, epsilon 1e-7), for `count` cells in lock step: exactly max_iter steps for every cell, no early stop, fresh accumulators
+ * per call.  The routes are those of gprx_adam_batch: sparse models with M <= 64 run the loop resident on the device (the same four
+ * launches per step, the last one with this update; the error word is read every 25 steps), every other model -- and every model
+ * under GPRX_ADAM_HOST=1 -- takes one batched evaluation per step with the update on the host side of the library; both give the
+ * same variables bit for bit (the update is one source for host and device, csrc/sgpr_asm.h adadelta_element: one rounding per
+ * operation in the order of the NumPy statement in gpras_amd/optimizers.py).  theta, z, mask, n_evals and batches as in
+ * gprx_adam_batch; a mask with nothing trainable returns at once.  losses (optional, count doubles) receives the loss of each
+ * cell's last evaluation -- what the reference's driver returns -- and NaN where none was made or the last one failed.  A cell that
+ * stops being positive definite ends the call with GPRX_ENOTPD and is named in gprx_last_error; theta / z as gprx_adam_batch
+ * leaves them in that case. */
+int gprx_adadelta_batch(gprx_handle h, int count, const int* units, double* theta, double* z, int mask, int max_iter, double* losses,
+                        int* n_evals, int* batches);
 
 /* ---- EOF (PCA) projection either side of the GP path: SURVEY.md section 8(f) row N1 ------------------- */
 /* One projector = the fitted state of a reference PreProcessor (gpras/preprocess.py:868-927): `dry` (n_cells bytes, 1 =
