@@ -64,6 +64,7 @@ PROTOTYPES = {
     "gprx_objective_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp]),
     "gprx_adam_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp]),
     "gprx_adadelta_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "gprx_last_optimizer_route": (C.c_int, [_vp, _ip, _ip]),
     "gprx_comm_runtime_check": (C.c_int, [C.c_int]),
     "gprx_comm_unique_id": (C.c_int, [_vp]),
     "gprx_comm_init": (C.c_int, [C.c_int, C.c_int, C.c_int, _vp, C.POINTER(_vp)]),
@@ -135,6 +136,12 @@ PROTOTYPES = {
     "gprx_mfma_f64_peak": (C.c_int, [C.c_int, _dp]),
     "gprx_exp_probe": (C.c_int, [C.c_int, C.c_int, _vp, _i64, _vp]),
 }
+
+# keys of gprx_set_tuning / gprx_set_handle_tuning (include/gprx.h)
+TUNING_KEYS = (
+    "outer_block", "update_tile", "no_lookahead", "split_panel", "dag", "rhs_vector", "cell_kernel", "poison_workspace", "predict_path",
+    "sgpr_fused", "sgpr_resident", "wait_handover_us", "sgpr_groups_from",
+)
 
 _lib = None
 

@@ -26,6 +26,7 @@
 #include "sgpr.h"
 #include "sgpr_asm.h"
 #include "sgpr_fused.h"
+#include "sgpr_step.h"
 #include "solve.h"
 
 using namespace gprx;
@@ -84,6 +85,10 @@ struct gprx_ctx {
   std::map<int, hipGraphExec_t> graphs;  // unit -> captured single-stream exact factorisation
   std::map<std::pair<int, int>, hipGraphExec_t> sgraphs;  // (cells, with gradient) -> captured sparse batch evaluation
   bool sgraph_off = false;                                // a capture failed once: this handle stays on eager launches
+  std::map<std::pair<int, int>, hipGraphExec_t> rgraphs;  // (cells, optimiser) -> captured step of the resident loop of the launch sequence
+  int sgpr_resident = 1;                                  // sparse models: the optimiser loops stay on the device ("sgpr_resident" tuning key)
+  int last_route = 0, last_host_waits = 0;                // gprx_last_optimizer_route
+  int host_waits = 0;                                     // stream waits of the running optimiser call (wait_stream and the loops' own)
   int sgpr_fused = 1;                                     // M <= 64: the five-launch evaluation of sgpr_fused.h ("sgpr_fused" tuning key)
   Buf adam_dev;                                           // device state of the resident Adam loop (sgpr_adam_resident)
   double* adam_pin = nullptr;                             // pinned: stop flags of the cells + the error word, read every few steps
@@ -211,13 +216,17 @@ int& wait_handover_us() {
 }
 hipError_t wait_stream(gprx_handle h, hipStream_t st) {
   static const bool blocking = getenv("GPRX_WAIT_BLOCKING") && atoi(getenv("GPRX_WAIT_BLOCKING")) != 0;
-  if (blocking) return hipStreamSynchronize(st);
+  if (blocking) {
+    ++h->host_waits;
+    return hipStreamSynchronize(st);
+  }
   if (!h->wev) {
     hipError_t e = hipEventCreateWithFlags(&h->wev, hipEventDisableTiming);
     if (e != hipSuccess) return e;
   }
   hipError_t e = hipEventRecord(h->wev, st);
   if (e != hipSuccess) return e;
+  ++h->host_waits;
   const auto t0 = std::chrono::steady_clock::now();
   for (int spins = 0;; ++spins) {
     e = hipEventQuery(h->wev);
@@ -518,6 +527,9 @@ void drop_graphs(gprx_handle h) {
   for (auto& kv : h->sgraphs)
     if (kv.second) hipGraphExecDestroy(kv.second);
   h->sgraphs.clear();
+  for (auto& kv : h->rgraphs)
+    if (kv.second) hipGraphExecDestroy(kv.second);
+  h->rgraphs.clear();
 }
 
 // views of the single-cell buffers into the arena are invalid once it moves
@@ -1017,6 +1029,11 @@ int& sgpr_fused_tuning() {
   static int v = 1;
   return v;
 }
+// 1: the optimiser loops of sparse models (d <= 64) stay on the device; 0: the host-stepped loop for all of them (one process can compare)
+int& sgpr_resident_tuning() {
+  static int v = 1;
+  return v;
+}
 static_assert(SF_CHUNK == SPLITK_CHUNK, "the fused evaluation stores its slabs in the split-K workspace of the cell block");
 
 SfParams sgpr_fused_params(gprx_handle h, const SgprLayout& L, bool want_grad) {
@@ -1110,23 +1127,30 @@ int sgpr_fused_enqueue(gprx_handle h, int count, const SgprLayout& L, bool want_
 // the staged outputs (pivot status, reductions, trace sums, dZ in pinned memory).  Nothing here depends on the VALUES of the
 // parameters -- they travel through the cell-parameter table -- so the sequence is captured once per (cells, gradient) into a
 // hipGraph and replayed (sgpr_objective_batch): ~45 launches whose enqueue cost, not their device time, bounded a step.
-int sgpr_batch_enqueue(gprx_handle h, int count, const SgprLayout& L, bool want_grad, const SgprParSrc& ps) {
+// The sequence in three parts -- stage-in, body, stage-out -- so that the resident optimiser loop (sgpr_resident_general) can run the body
+// alone between two launches of its step kernel; a host-driven evaluation (sgpr_batch_enqueue) is the three in a row.
+int sgpr_stage_in_enqueue(gprx_handle h, int count, const SgprLayout& L) {
+  const int np = (int)h->np, m = (int)h->m, d = h->d;
+  const SgprStage sg = sgpr_stage(h, count, L);
+  double* A0 = h->sarena.p;
+  static_assert(CELL_RES <= 256 && CELL_PAR <= 256, "sgpr_stage_in_kernel moves them with its first workgroup");
+  hipLaunchKernelGGL(sgpr_stage_in_kernel, dim3((std::max(np, m * d) + 255) / 256, count), dim3(256), 0, h->stream, (const double*)h->Y.p, np,
+                     (const double*)(h->spin + sg.par), CELL_PAR, h->cellpar.p, (const double*)(h->spin + sg.z), m * d, A0 + L.oZ, A0 + L.oY, L.ss,
+                     h->cellres.p, CELL_RES);
+  return GPRX_OK;
+}
+
+int sgpr_body_enqueue(gprx_handle h, int count, const SgprLayout& L, bool want_grad, const SgprParSrc& ps) {
   const int mp = (int)h->mp, np = (int)h->np, m = (int)h->m, n = (int)h->n, d = h->d;
   const int64_t ss = L.ss, mm = (int64_t)mp * mp;
   const size_t pitch = sizeof(double) * (size_t)ss;
   hipStream_t st = h->stream;
   double* A0 = h->sarena.p;
-  if (sgpr_five_launches(h)) return sgpr_fused_enqueue(h, count, L, want_grad);
-  const SgprStage sg = sgpr_stage(h, count, L);
   // (Tried: the independent branches of the evaluation -- Kuf beside Kuu's factorisation; R, Sinv / T2, T1 / Qinv, m; the
   // two contractions and the noise terms -- on side streams, i.e. parallel branches of the captured graph.  The dependent chain
   // drops from 34 to 20 launches, but every cross-branch edge costs more than an in-order kernel boundary on this runtime:
   // 16 cells 0.427 ms against 0.400 ms serial.  One stream it is.)
   const double* inv_s = h->cellpar.p + 3;  // alpha table: 1 / s, CELL_PAR apart
-  static_assert(CELL_RES <= 256 && CELL_PAR <= 256, "sgpr_stage_in_kernel moves them with its first workgroup");
-  hipLaunchKernelGGL(sgpr_stage_in_kernel, dim3((std::max(np, m * d) + 255) / 256, count), dim3(256), 0, st, (const double*)h->Y.p, np,
-                     (const double*)(h->spin + sg.par), CELL_PAR, h->cellpar.p, (const double*)(h->spin + sg.z), m * d, A0 + L.oZ, A0 + L.oY, ss,
-                     h->cellres.p, CELL_RES);
   // ---- factorisation ----
   KmatArgs kp{A0 + L.oZ, h->X.p, nullptr, A0 + L.oP, np, m, n, d, mp, np, 0.0, 0.0, 0, 0.0, nullptr, 0};
   ps.stamp(kp);
@@ -1188,7 +1212,7 @@ int sgpr_batch_enqueue(gprx_handle h, int count, const SgprLayout& L, bool want_
   double* partP = A0 + L.oPart;
   double* partQ = partP + L.part_p;
   double* sums = partQ + L.part_q;
-  const int tiles_m = mp / KM_T, tiles_n = np / KM_T, width = L.width;
+  const int tiles_m = mp / KM_T, tiles_n = np / KM_T;
   if (want_grad) {
     auto gemm_mm = [&](hipStream_t sx, int ta, int tb, const double* A, const double* B, double* C, int flags) {
       return launch_gemm(sx, ta, tb, mp, mp, mp, 1.0, A, mp, B, mp, 0.0, C, mp, flags, 0, 1, 0, 0, 0, count, ss, ss, ss);
@@ -1248,12 +1272,85 @@ int sgpr_batch_enqueue(gprx_handle h, int count, const SgprLayout& L, bool want_
                        (const double*)(A0 + L.oWHP), (int64_t)np, (const double*)(A0 + L.oWHQ), (int64_t)mp, ps.ls, m, n, d,
                        A0 + L.odZ, ss, ps.table);
   }
-  // ---- results: reductions, pivot status, trace sums, dZ -> pinned memory ----
-  hipLaunchKernelGGL(sgpr_stage_out_kernel, dim3(count), dim3(256), 0, st, (const double*)h->cellres.p, CELL_RES, h->spin + sg.res,
-                     (const double*)(A0 + L.oRed), h->spin + sg.red, want_grad ? (const double*)partP : nullptr, tiles_m * tiles_n,
-                     (const double*)partQ, tiles_m * tiles_m, width, h->spin + sg.sum, want_grad ? (const double*)(A0 + L.odZ) : nullptr, m * d,
-                     h->spin + sg.dz, ss);
+  return GPRX_OK;
+}
+
+// ---- results: reductions, pivot status, trace sums, dZ -> pinned memory ----
+int sgpr_stage_out_enqueue(gprx_handle h, int count, const SgprLayout& L, bool want_grad) {
+  const int mp = (int)h->mp, np = (int)h->np, m = (int)h->m, d = h->d;
+  const SgprStage sg = sgpr_stage(h, count, L);
+  double* A0 = h->sarena.p;
+  const double* partP = A0 + L.oPart;
+  const double* partQ = partP + L.part_p;
+  const int tiles_m = mp / KM_T, tiles_n = np / KM_T;
+  hipLaunchKernelGGL(sgpr_stage_out_kernel, dim3(count), dim3(256), 0, h->stream, (const double*)h->cellres.p, CELL_RES, h->spin + sg.res,
+                     (const double*)(A0 + L.oRed), h->spin + sg.red, want_grad ? partP : nullptr, tiles_m * tiles_n, partQ, tiles_m * tiles_m,
+                     L.width, h->spin + sg.sum, want_grad ? (const double*)(A0 + L.odZ) : nullptr, m * d, h->spin + sg.dz, L.ss);
+  return GPRX_OK;
+}
+
+int sgpr_batch_enqueue(gprx_handle h, int count, const SgprLayout& L, bool want_grad, const SgprParSrc& ps) {
+  if (sgpr_five_launches(h)) return sgpr_fused_enqueue(h, count, L, want_grad);
+  int rc;
+  if ((rc = sgpr_stage_in_enqueue(h, count, L))) return rc;
+  if ((rc = sgpr_body_enqueue(h, count, L, want_grad, ps))) return rc;
+  if ((rc = sgpr_stage_out_enqueue(h, count, L, want_grad))) return rc;
   HIPCHK(h, hipGetLastError());
+  return GPRX_OK;
+}
+
+// a cell's row of the parameter table (kfun.h CELL_PAR layout) as the stage-in reads it from pinned memory
+void sgpr_par_row(gprx_handle h, double* row, int unit, const Theta& t) {
+  std::memset(row, 0, sizeof(double) * CELL_PAR);
+  row[0] = t.variance;
+  row[1] = t.noise;
+  row[2] = (double)unit;
+  row[3] = 1.0 / t.noise;
+  for (int k = 0; k < std::min(h->d, CELL_PAR - CELL_PAR_LS); ++k) row[CELL_PAR_LS + k] = t.ls[k];
+}
+
+// Eager, capture, replay: the first launch sequence of a shape (`key` in `graphs`) goes out eagerly -- every kernel's code object gets
+// loaded outside a capture -- the second is captured into a hipGraph, and from then on the graph is replayed.  *replayed = false: the
+// caller enqueues the sequence itself (the first time, GPRX_NO_GRAPH, profiling, or after a capture that failed).
+template <class Enqueue>
+int sgpr_replay(gprx_handle h, std::map<std::pair<int, int>, hipGraphExec_t>& graphs, const std::pair<int, int> key, Enqueue enqueue, bool* replayed) {
+  static const bool no_graph = getenv("GPRX_NO_GRAPH") != nullptr;  // escape hatch: eager launches
+  hipStream_t st = h->stream;
+  *replayed = false;
+  if (no_graph || h->sgraph_off || h->profiling) return GPRX_OK;
+  auto it = graphs.find(key);
+  if (it == graphs.end()) {
+    graphs.emplace(key, nullptr);
+    return GPRX_OK;
+  }
+  if (it->second == nullptr) {
+    // Relaxed capture mode: another host thread may call a legacy-stream API (hipMemset / hipMemcpy of another handle's set-up)
+    // while this capture runs; in the global and thread-local modes the runtime refuses that call ("operation would make the
+    // legacy stream depend on a capturing blocking stream") AND invalidates this capture.  The handle's streams are
+    // non-blocking, so no implicit dependency on the legacy stream exists that the capture could miss.  Captures are
+    // serialised over the process as well; one that fails anyway is abandoned and the handle stays on eager launches.
+    std::lock_guard<std::mutex> lock(capture_mutex());
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed);
+    if (e == hipSuccess) {
+      const int crc = enqueue();
+      e = hipStreamEndCapture(st, &graph);
+      if (!crc && e == hipSuccess && graph) e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+      if (crc) e = hipErrorUnknown;
+    }
+    if (graph) hipGraphDestroy(graph);
+    if (e != hipSuccess || !exec) {
+      (void)hipGetLastError();
+      h->err.clear();
+      h->sgraph_off = true;
+      graphs.erase(it);
+      return GPRX_OK;
+    }
+    it->second = exec;
+  }
+  HIPCHK(h, hipGraphLaunch(it->second, st));
+  *replayed = true;
   return GPRX_OK;
 }
 
@@ -1273,60 +1370,16 @@ int sgpr_objective_batch(gprx_handle h, int count, const int* units, const Theta
   hipStream_t st = h->stream;
   const SgprStage sg = sgpr_stage(h, count, L);
   double* par = h->spin + sg.par;
-  for (int c = 0; c < count; ++c) {
-    double* row = par + (size_t)c * CELL_PAR;
-    std::memset(row, 0, sizeof(double) * CELL_PAR);
-    row[0] = ts[c].variance;
-    row[1] = ts[c].noise;
-    row[2] = (double)units[c];
-    row[3] = 1.0 / ts[c].noise;
-    for (int k = 0; k < std::min(d, CELL_PAR - CELL_PAR_LS); ++k) row[CELL_PAR_LS + k] = ts[c].ls[k];
-  }
+  for (int c = 0; c < count; ++c)
+    sgpr_par_row(h, par + (size_t)c * CELL_PAR, units[c], ts[c]);
   std::memcpy(h->spin + sg.z, zs, sizeof(double) * (size_t)count * m * d);
-  static const bool no_graph = getenv("GPRX_NO_GRAPH") != nullptr;  // escape hatch: eager launches
   const bool want_grad = g != nullptr;
   bool replayed = false;
   // (the five launches of the fused evaluation go out eagerly: replaying them from a graph starts the first kernel later than a direct
   // launch does -- 178.8 against 172.5 us per 16-cell evaluation, MI355X_MICROARCH.md "graph-replay-floor")
-  if (!no_graph && !h->sgraph_off && !h->profiling && !sgpr_five_launches(h) && !direct) {
-    const std::pair<int, int> key(count, want_grad ? 1 : 0);
-    auto it = h->sgraphs.find(key);
-    if (it == h->sgraphs.end()) {
-      // first evaluation of this shape: eager (every kernel's code object gets loaded outside a capture); the capture happens
-      // on the second one
-      h->sgraphs.emplace(key, nullptr);
-    } else if (it->second == nullptr) {
-      // Relaxed capture mode: another host thread may call a legacy-stream API (hipMemset / hipMemcpy of another handle's set-up)
-      // while this capture runs; in the global and thread-local modes the runtime refuses that call ("operation would make the
-      // legacy stream depend on a capturing blocking stream") AND invalidates this capture.  The handle's streams are
-      // non-blocking, so no implicit dependency on the legacy stream exists that the capture could miss.  Captures are
-      // serialised over the process as well; one that fails anyway is abandoned and the handle stays on eager launches.
-      std::lock_guard<std::mutex> lock(capture_mutex());
-      hipGraph_t graph = nullptr;
-      hipGraphExec_t exec = nullptr;
-      hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed);
-      if (e == hipSuccess) {
-        const int crc = sgpr_batch_enqueue(h, count, L, want_grad, ps);
-        e = hipStreamEndCapture(st, &graph);
-        if (!crc && e == hipSuccess && graph) e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        if (crc) e = hipErrorUnknown;
-      }
-      if (graph) hipGraphDestroy(graph);
-      if (e != hipSuccess || !exec) {
-        (void)hipGetLastError();
-        h->err.clear();
-        h->sgraph_off = true;
-        h->sgraphs.erase(it);
-      } else {
-        it->second = exec;
-      }
-    }
-    it = h->sgraphs.find(key);
-    if (!h->sgraph_off && it != h->sgraphs.end() && it->second != nullptr) {
-      HIPCHK(h, hipGraphLaunch(it->second, st));
-      replayed = true;
-    }
-  }
+  if (!sgpr_five_launches(h) && !direct &&
+      (rc = sgpr_replay(h, h->sgraphs, {count, want_grad ? 1 : 0}, [&] { return sgpr_batch_enqueue(h, count, L, want_grad, ps); }, &replayed)))
+    return rc;
   if (!replayed && (rc = sgpr_batch_enqueue(h, count, L, want_grad, ps))) return rc;
   const double* hres = h->spin + sg.res;
   const double* hred = h->spin + sg.red;
@@ -1417,6 +1470,16 @@ int sgpr_predict_batch(gprx_handle h, int count, const double* xs_dev, int64_t n
 // table, every cell runs max_iter steps; `losses` (optional) receives the loss of each cell's last evaluation.
 // The other groups' streams are joined into the handle's stream before EVERY return (SfJoin): after a failed HIP call inside the step
 // loop nothing may stay in flight on buffers the handle reuses.
+// The state block of both resident loops.  The captured steps of sgpr_resident_general (h->rgraphs) hold addresses inside it: whoever
+// reallocates it drops them (the stream is idle: every optimiser call ends with a synchronisation).
+int ensure_adam_dev(gprx_handle h, size_t bytes) {
+  if (h->adam_dev.bytes >= bytes) return GPRX_OK;
+  for (auto& kv : h->rgraphs)
+    if (kv.second) hipGraphExecDestroy(kv.second);
+  h->rgraphs.clear();
+  return ensure(h, h->adam_dev, bytes);
+}
+
 struct SfJoin {
   gprx_handle h;
   hipStream_t st;
@@ -1447,7 +1510,7 @@ int sgpr_adam_resident(gprx_handle h, int kind, int count, const int* units, dou
   // the early stop" passes max_iter = 2^31 - 1) ----
   const size_t n_dbl = (size_t)count * nt + 2 * (size_t)count * gw + 2 * (size_t)count + (size_t)check_every + (size_t)h->n_units;
   const size_t n_int = 5 * (size_t)count + gprx_ctx::SF_MAX_GROUPS;  // (one error word per group of cells)
-  if ((rc = ensure(h, h->adam_dev, sizeof(double) * n_dbl + sizeof(int) * n_int))) return rc;
+  if ((rc = ensure_adam_dev(h, sizeof(double) * n_dbl + sizeof(int) * n_int))) return rc;
   // pinned: the window's alpha values, then the stop flags of the cells and the error words
   const size_t pin_need = sizeof(double) * (size_t)check_every + sizeof(int) * ((size_t)count + gprx_ctx::SF_MAX_GROUPS);
   if (h->adam_pin_bytes < pin_need) {
@@ -1499,6 +1562,7 @@ int sgpr_adam_resident(gprx_handle h, int kind, int count, const int* units, dou
   HIPCHK(h, hipMemcpyAsync(ad.stale, hi.data(), sizeof(int) * n_int, hipMemcpyHostToDevice, st));
   HIPCHK(h, hipMemcpy2DAsync(h->sarena.p + L.oZ, sizeof(double) * (size_t)L.ss, z, sizeof(double) * (size_t)nz, sizeof(double) * (size_t)nz, count,
                              hipMemcpyHostToDevice, st));
+  ++h->host_waits;
   HIPCHK(h, hipStreamSynchronize(st));
   SfParams p = sgpr_fused_params(h, L, true);
   p.active = ad.active;
@@ -1595,6 +1659,7 @@ int sgpr_adam_resident(gprx_handle h, int kind, int count, const int* units, dou
                              hipMemcpyDeviceToHost, st));
   HIPCHK(h, hipMemcpyAsync(n_evals, ad.n_evals, sizeof(int) * count, hipMemcpyDeviceToHost, st));
   if (losses) HIPCHK(h, hipMemcpyAsync(losses, ad.loss, sizeof(double) * count, hipMemcpyDeviceToHost, st));
+  ++h->host_waits;
   HIPCHK(h, hipStreamSynchronize(st));
   if (batches) {
     int mx = 0;
@@ -1604,6 +1669,197 @@ int sgpr_adam_resident(gprx_handle h, int kind, int count, const int* units, dou
   if (error_cell != 0) {
     char msg[160];
     snprintf(msg, sizeof msg, "cell %d: Kuu or B not positive definite", error_cell - 1);
+    return fail(h, GPRX_ENOTPD, msg);
+  }
+  return GPRX_OK;
+}
+
+// gprx_adam_batch / gprx_adadelta_batch for the sparse models that the fused route above does not take (M > 64, or M <= 64 with
+// "sgpr_fused" = 0; d <= 64): the loop resident on the device around the GENERAL launch sequence.  A step is the body of
+// sgpr_batch_enqueue (no stage-in, no stage-out) followed by sgpr_step_kernel (sgpr_step.h), which forms the loss and the gradient, runs
+// the update and the stop rule and writes the next step's parameter row -- what the host did between two evaluations of the host-stepped
+// loop, with the same arithmetic: the same bits.  One stream, a linear graph per (cells, optimiser): the first step of a shape goes out
+// eagerly, the second is captured, later ones are replayed (sgpr_replay); everything that changes between steps, windows or calls
+// (step count, mask, max_iter, the window's alpha values and their first step) is read from device memory.  Every `check_every` steps
+// the host reads the stop flags and the error word.  Between two reads a stopped cell is still evaluated but the step kernel leaves it
+// alone; at a read where cells have stopped the residency is closed (state down) and reopened for the cells that still run (state up,
+// stage-in): a cell's bits depend neither on its slot nor on the batch size.  Failure: as sgpr_adam_resident.
+int sgpr_resident_general(gprx_handle h, int kind, int count, const int* units, double* theta, double* z, int mask, int max_iter, double* losses,
+                          int* n_evals, int* batches) {
+  const SgprLayout L = sgpr_batch_layout(h);
+  int rc;
+  if ((rc = ensure_sarena(h, count, L))) return rc;
+  hipStream_t st = h->stream;
+  const int nt = h->ntheta, mp = (int)h->mp, np = (int)h->np;
+  const int64_t nz = h->m * h->d, gw = nt + nz;
+  static const int check_every = [] {
+    const char* e = getenv("GPRX_ADAM_CHECK_EVERY");
+    const int v = e ? atoi(e) : 0;
+    return v > 0 ? v : 25;
+  }();
+  const bool adam = kind == SF_OPT_ADAM;
+  // the window block (device and pinned): the alpha values of one window of check_every steps, then the control words
+  static_assert(SGPR_CTL_WORDS * sizeof(int) == 2 * sizeof(double), "the control words travel as two doubles behind the alpha table");
+  const size_t win_dbl = (size_t)check_every + 2;
+  auto dbl_of = [&](size_t cells) { return cells * nt + 2 * cells * gw + 2 * cells + win_dbl + (size_t)h->n_units; };
+  auto int_of = [&](size_t cells) { return 5 * cells + 1; };
+  if ((rc = ensure_adam_dev(h, sizeof(double) * dbl_of(count) + sizeof(int) * int_of(count)))) return rc;
+  const size_t pin_need = sizeof(double) * win_dbl + sizeof(int) * ((size_t)count + 1);
+  if (h->adam_pin_bytes < pin_need) {
+    if (h->adam_pin) HIPCHK(h, hipHostFree(h->adam_pin));
+    h->adam_pin = nullptr;
+    h->adam_pin_bytes = 0;
+    HIPCHK(h, hipHostMalloc((void**)&h->adam_pin, pin_need, hipHostMallocDefault));
+    h->adam_pin_bytes = pin_need;
+  }
+  double* hwin = h->adam_pin;
+  int* hctl = reinterpret_cast<int*>(hwin + check_every);
+  int* flags = reinterpret_cast<int*>(hwin + win_dbl);
+  for (int i = 0; i < check_every; ++i) hwin[i] = 0.0;  // (Adadelta reads no alpha)
+  // ---- the optimiser's state of every cell on the host: what a residency is opened from and closed into ----
+  std::vector<double> mom((size_t)count * gw, 0.0), vel((size_t)count * gw, 0.0), best(count, std::numeric_limits<double>::infinity()),
+      loss(count, std::numeric_limits<double>::quiet_NaN());
+  std::vector<int> stale(count, 0), active(count);
+  for (int c = 0; c < count; ++c) active[c] = c;
+  const SgprParSrc ps = sgpr_par_src(h, 0.0, 0.0);  // (d <= 64: the parameter table)
+  h->factorized = false;                            // the cell blocks are overwritten
+  int done = 0, error_cell = -1;
+  while (!active.empty() && done < max_iter && error_cell < 0) {
+    // ---- open: state and staged inputs of the `na` running cells up, stage-in ----
+    const int na = (int)active.size();
+    const size_t n_dbl = dbl_of(na), n_int = int_of(na);
+    SfAdam ad{};
+    double* dp = h->adam_dev.p;
+    ad.theta = dp;                 dp += (size_t)na * nt;
+    ad.mom = dp;                   dp += (size_t)na * gw;
+    ad.vel = dp;                   dp += (size_t)na * gw;
+    ad.best = dp;                  dp += na;
+    ad.loss = dp;                  dp += na;
+    double* d_win = dp;            dp += win_dbl;
+    double* d_yy = dp;             dp += h->n_units;
+    int* ip = reinterpret_cast<int*>(dp);
+    ad.stale = ip;                 ip += na;
+    ad.active = ip;                ip += na;
+    ad.n_evals = ip;               ip += na;
+    ad.tstep = ip;                 ip += na;
+    int* d_units = ip;             ip += na;
+    ad.error = ip;
+    ad.units = d_units;
+    ad.alpha = d_win;
+    ad.yy = d_yy;
+    ad.nt = nt;
+    ad.nlen = h->nlen;
+    ad.ard = h->ard;
+    std::vector<double> hd(n_dbl, 0.0), zc((size_t)na * nz);
+    std::vector<int> hi(n_int, 0);
+    const SgprStage sg = sgpr_stage(h, na, L);
+    for (int j = 0; j < na; ++j) {
+      const int i = active[j];
+      std::memcpy(&hd[(size_t)j * nt], theta + (size_t)i * nt, sizeof(double) * nt);
+      std::memcpy(&hd[(ad.mom - h->adam_dev.p) + (size_t)j * gw], &mom[(size_t)i * gw], sizeof(double) * gw);
+      std::memcpy(&hd[(ad.vel - h->adam_dev.p) + (size_t)j * gw], &vel[(size_t)i * gw], sizeof(double) * gw);
+      hd[(ad.best - h->adam_dev.p) + j] = best[i];
+      hd[(ad.loss - h->adam_dev.p) + j] = loss[i];
+      hi[j] = stale[i];
+      hi[(size_t)na + j] = 1;  // active
+      hi[2 * (size_t)na + j] = n_evals[i];
+      hi[3 * (size_t)na + j] = done;
+      hi[4 * (size_t)na + j] = units[i];
+      sgpr_par_row(h, h->spin + sg.par + (size_t)j * CELL_PAR, units[i], decode_theta(h, theta + (size_t)i * nt));
+      std::memcpy(h->spin + sg.z + (size_t)j * nz, z + (size_t)i * nz, sizeof(double) * nz);
+    }
+    std::memcpy(&hd[d_yy - h->adam_dev.p], h->yy.data(), sizeof(double) * h->n_units);
+    HIPCHK(h, hipMemcpyAsync(h->adam_dev.p, hd.data(), sizeof(double) * n_dbl, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(ad.stale, hi.data(), sizeof(int) * n_int, hipMemcpyHostToDevice, st));
+    if ((rc = sgpr_stage_in_enqueue(h, na, L))) return rc;
+    HIPCHK(h, hipGetLastError());
+    ++h->host_waits;
+    HIPCHK(h, hipStreamSynchronize(st));  // (the host vectors and the pinned rows are free again)
+    SgprStep sa{};
+    sa.arena = h->sarena.p;
+    sa.ss = L.ss;
+    sa.oZ = L.oZ;
+    sa.odZ = L.odZ;
+    sa.oRed = L.oRed;
+    sa.oPartP = L.oPart;
+    sa.oPartQ = L.oPart + L.part_p;
+    sa.nwg_p = (mp / KM_T) * (np / KM_T);
+    sa.nwg_q = (mp / KM_T) * (mp / KM_T);
+    sa.width = L.width;
+    sa.n = (int)h->n;
+    sa.m = (int)h->m;
+    sa.d = h->d;
+    sa.mp = mp;
+    sa.cellpar = h->cellpar.p;
+    sa.cellres = h->cellres.p;
+    sa.res_doubles = CELL_RES;
+    sa.ctl = reinterpret_cast<const int*>(d_win + check_every);
+    auto step_enqueue = [&]() -> int {
+      int erc;
+      if ((erc = sgpr_body_enqueue(h, na, L, true, ps))) return erc;
+      HIPCHK(h, sgpr_launch_step(st, kind, sa, ad, na));
+      return GPRX_OK;
+    };
+    // ---- windows of check_every steps until a cell stops ----
+    int running = na;
+    while (done < max_iter && running == na && error_cell < 0) {
+      const int k = std::min(check_every, max_iter - done);
+      // this window's alpha values (steps done + 1 .. done + k; every running cell is at the same step) and the control words: the pinned
+      // block is free, the previous window's upload had completed before its stop flags were read
+      for (int i = 0; adam && i < k; ++i) {
+        const double t = (double)done + 1.0 + i;
+        hwin[i] = ADAM_LR * std::sqrt(1.0 - std::pow(ADAM_BETA2, t)) / (1.0 - std::pow(ADAM_BETA1, t));  // gprx_adam_batch's expression
+      }
+      hctl[SGPR_CTL_MASK] = mask;
+      hctl[SGPR_CTL_MAX_ITER] = max_iter;
+      hctl[SGPR_CTL_ALPHA_T1] = done + 1;
+      hctl[3] = 0;
+      HIPCHK(h, hipMemcpyAsync(d_win, hwin, sizeof(double) * win_dbl, hipMemcpyHostToDevice, st));
+      for (int i = 0; i < k; ++i) {
+        bool replayed = false;
+        if ((rc = sgpr_replay(h, h->rgraphs, {na, kind}, step_enqueue, &replayed))) return rc;
+        if (!replayed && (rc = step_enqueue())) return rc;
+      }
+      done += k;
+      HIPCHK(h, hipMemcpyAsync(flags, ad.active, sizeof(int) * na, hipMemcpyDeviceToHost, st));
+      HIPCHK(h, hipMemcpyAsync(flags + na, ad.error, sizeof(int), hipMemcpyDeviceToHost, st));
+      HIPCHK(h, wait_stream(h, st));
+      if (flags[na] != 0) error_cell = active[flags[na] - 1];
+      running = 0;
+      for (int j = 0; j < na; ++j) running += flags[j] != 0 ? 1 : 0;
+    }
+    // ---- close: the state of the na cells down ----
+    HIPCHK(h, hipMemcpyAsync(hd.data(), h->adam_dev.p, sizeof(double) * n_dbl, hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(hi.data(), ad.stale, sizeof(int) * n_int, hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpy2DAsync(zc.data(), sizeof(double) * (size_t)nz, h->sarena.p + L.oZ, sizeof(double) * (size_t)L.ss, sizeof(double) * (size_t)nz, na,
+                               hipMemcpyDeviceToHost, st));
+    ++h->host_waits;
+    HIPCHK(h, hipStreamSynchronize(st));
+    std::vector<int> next;
+    for (int j = 0; j < na; ++j) {
+      const int i = active[j];
+      std::memcpy(theta + (size_t)i * nt, &hd[(size_t)j * nt], sizeof(double) * nt);
+      std::memcpy(&mom[(size_t)i * gw], &hd[(ad.mom - h->adam_dev.p) + (size_t)j * gw], sizeof(double) * gw);
+      std::memcpy(&vel[(size_t)i * gw], &hd[(ad.vel - h->adam_dev.p) + (size_t)j * gw], sizeof(double) * gw);
+      best[i] = hd[(ad.best - h->adam_dev.p) + j];
+      loss[i] = hd[(ad.loss - h->adam_dev.p) + j];
+      stale[i] = hi[j];
+      n_evals[i] = hi[2 * (size_t)na + j];
+      std::memcpy(z + (size_t)i * nz, &zc[(size_t)j * nz], sizeof(double) * nz);
+      if (hi[(size_t)na + j] != 0) next.push_back(i);
+    }
+    active.swap(next);
+  }
+  if (losses)
+    for (int c = 0; c < count; ++c) losses[c] = loss[c];
+  if (batches) {
+    int mx = 0;
+    for (int c = 0; c < count; ++c) mx = std::max(mx, n_evals[c]);
+    *batches = mx;
+  }
+  if (error_cell >= 0) {
+    char msg[160];
+    snprintf(msg, sizeof msg, "cell %d: Kuu or B not positive definite", error_cell);
     return fail(h, GPRX_ENOTPD, msg);
   }
   return GPRX_OK;
@@ -1652,6 +1908,7 @@ int gprx_create(int device, int64_t n, int d, int64_t m, int kernel_id, int ard,
   h->tune = potrf_tuning();  // a private copy: later gprx_set_tuning calls (process defaults) do not reach this handle
   h->predict_path = predict_path_tuning();
   h->sgpr_fused = sgpr_fused_tuning();
+  h->sgpr_resident = sgpr_resident_tuning();
   // normal priority on purpose: measured on MI355X, raised/lowered stream priorities do nothing for a single
   // cell and cut the throughput of several concurrent cells by up to 2x
   hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
@@ -1920,7 +2177,9 @@ static int optimizer_batch(gprx_handle h, int kind, int count, const int* units,
   for (char t : train) any = any || t;
   if (!any) return GPRX_OK;  // nothing trainable: no step can change anything (optimizers._optimize_adam returns at once)
   static const bool adam_on_host = getenv("GPRX_ADAM_HOST") && atoi(getenv("GPRX_ADAM_HOST")) != 0;  // escape hatch: the host-stepped loop
-  if (h->m != 0 && h->mp == NB && h->sgpr_fused && h->d <= CELL_PAR - CELL_PAR_LS && !adam_on_host && max_iter > 0) {
+  // sparse models with d <= 64 keep the loop on the device ("sgpr_resident" = 0: never): around the five fused launches where the
+  // evaluation takes them (M <= 64), around the general launch sequence otherwise
+  if (h->m != 0 && h->sgpr_resident && h->d <= CELL_PAR - CELL_PAR_LS && !adam_on_host && max_iter > 0) {
     for (int i = 0; i < count; ++i) {
       if (units[i] < 0 || units[i] >= h->n_units) return fail(h, GPRX_EINVAL, "unit out of range (call gprx_set_data first)");
       for (int k = 0; k < nt; ++k)
@@ -1928,7 +2187,9 @@ static int optimizer_batch(gprx_handle h, int kind, int count, const int* units,
     }
     for (int64_t e = 0; e < (int64_t)count * nz; ++e)
       if (!std::isfinite(z[e])) return fail(h, GPRX_EINVAL, "z is not finite");
-    return sgpr_adam_resident(h, kind, count, units, theta, z, mask, max_iter, last_losses, n_evals, batches);
+    h->last_route = sgpr_five_launches(h) ? 1 : 2;
+    return (sgpr_five_launches(h) ? sgpr_adam_resident : sgpr_resident_general)(h, kind, count, units, theta, z, mask, max_iter, last_losses, n_evals,
+                                                                                  batches);
   }
   const double lr = ADAM_LR, beta1 = ADAM_BETA1, beta2 = ADAM_BETA2;
   std::vector<double> mom((size_t)count * gw, 0.0), vel((size_t)count * gw, 0.0), best(count, std::numeric_limits<double>::infinity());
@@ -1973,9 +2234,28 @@ static int optimizer_batch(gprx_handle h, int kind, int count, const int* units,
   return GPRX_OK;
 }
 
+// (gprx_last_optimizer_route: the route and the stream waits of this call)
+static int optimizer_routed(gprx_handle h, int kind, int count, const int* units, double* theta, double* z, int mask, int max_iter,
+                            double* last_losses, int* n_evals, int* batches) {
+  if (h) {
+    h->last_route = 0;
+    h->host_waits = 0;
+  }
+  const int rc = optimizer_batch(h, kind, count, units, theta, z, mask, max_iter, last_losses, n_evals, batches);
+  if (h) h->last_host_waits = h->host_waits;
+  return rc;
+}
+
+int gprx_last_optimizer_route(gprx_handle h, int* route, int* host_waits) {
+  if (!h || !route || !host_waits) return fail(h, GPRX_EINVAL, "null argument");
+  *route = h->last_route;
+  *host_waits = h->last_host_waits;
+  return GPRX_OK;
+}
+
 int gprx_adam_batch(gprx_handle h, int count, const int* units, double* theta, double* z, int mask, int max_iter, int* n_evals, int* batches) {
   try {
-    return optimizer_batch(h, SF_OPT_ADAM, count, units, theta, z, mask, max_iter, nullptr, n_evals, batches);
+    return optimizer_routed(h, SF_OPT_ADAM, count, units, theta, z, mask, max_iter, nullptr, n_evals, batches);
   } catch (const std::bad_alloc&) {  // (no C++ exception may cross the C ABI)
     return fail(h, GPRX_ENOMEM, "host allocation failed");
   }
@@ -1984,7 +2264,7 @@ int gprx_adam_batch(gprx_handle h, int count, const int* units, double* theta, d
 int gprx_adadelta_batch(gprx_handle h, int count, const int* units, double* theta, double* z, int mask, int max_iter, double* losses, int* n_evals,
                         int* batches) {
   try {
-    return optimizer_batch(h, SF_OPT_ADADELTA, count, units, theta, z, mask, max_iter, losses, n_evals, batches);
+    return optimizer_routed(h, SF_OPT_ADADELTA, count, units, theta, z, mask, max_iter, losses, n_evals, batches);
   } catch (const std::bad_alloc&) {
     return fail(h, GPRX_ENOMEM, "host allocation failed");
   }
@@ -2618,7 +2898,7 @@ int gprx_panel_stamps(unsigned long long* out64) {
 #endif
 
 namespace {
-bool apply_tuning(PotrfTuning& t, int& predict_path, int& fused, const std::string& k, int value) {
+bool apply_tuning(PotrfTuning& t, int& predict_path, int& fused, int& resident, const std::string& k, int value) {
   if (k == "outer_block" && value >= 0 && value % 128 == 0) t.outer_block = value;
   else if (k == "update_tile" && (value == 0 || value == 64 || value == 128)) t.update_tile = value;
   else if (k == "no_lookahead") t.no_lookahead = value != 0;
@@ -2629,6 +2909,7 @@ bool apply_tuning(PotrfTuning& t, int& predict_path, int& fused, const std::stri
   else if (k == "poison_workspace" && value >= 0 && value <= 1) t.poison_workspace = value;
   else if (k == "predict_path" && value >= 0 && value <= 2) predict_path = value;
   else if (k == "sgpr_fused" && value >= 0 && value <= 1) fused = value;
+  else if (k == "sgpr_resident" && value >= 0 && value <= 1) resident = value;  // 0: sparse optimiser loops are stepped by the host
   else if (k == "wait_handover_us" && value >= 0) wait_handover_us() = value;  // (process-wide whichever entry point sets it)
   else if (k == "sgpr_groups_from" && value >= 0) sf_groups_from() = value;    // (process-wide; 0: the resident Adam loop never splits a batch into groups)
   else return false;
@@ -2638,14 +2919,14 @@ bool apply_tuning(PotrfTuning& t, int& predict_path, int& fused, const std::stri
 
 int gprx_set_tuning(const char* key, int value) {
   if (!key) return fail(nullptr, GPRX_EINVAL, "null key");
-  if (!apply_tuning(potrf_tuning(), predict_path_tuning(), sgpr_fused_tuning(), key, value)) return fail(nullptr, GPRX_EINVAL, "unknown tuning key or bad value");
+  if (!apply_tuning(potrf_tuning(), predict_path_tuning(), sgpr_fused_tuning(), sgpr_resident_tuning(), key, value)) return fail(nullptr, GPRX_EINVAL, "unknown tuning key or bad value");
   return GPRX_OK;
 }
 
 int gprx_set_handle_tuning(gprx_handle h, const char* key, int value) {
   if (!h || !key) return fail(h, GPRX_EINVAL, "null argument");
   const int fused_before = h->sgpr_fused;
-  if (!apply_tuning(h->tune, h->predict_path, h->sgpr_fused, key, value)) return fail(h, GPRX_EINVAL, "unknown tuning key or bad value");
+  if (!apply_tuning(h->tune, h->predict_path, h->sgpr_fused, h->sgpr_resident, key, value)) return fail(h, GPRX_EINVAL, "unknown tuning key or bad value");
   if (hipSetDevice(h->device) == hipSuccess && hipStreamSynchronize(h->stream) == hipSuccess) drop_graphs(h);  // captured with the old schedule
   if (h->sgpr_fused != fused_before) {  // the cell blocks of the two sparse schedules differ (sgpr_batch_layout): the arena is rebuilt on the next call
     h->sarena_slots = 0;

@@ -273,19 +273,7 @@ __global__ __launch_bounds__(256) void sgpr_stage_out_kernel(const double* __res
   const int t = threadIdx.x;
   if (t < res_doubles) res_host[cell * res_doubles + t] = cell_res[cell * res_doubles + t];
   if (t < 8) red_host[cell * 8 + t] = red[cell * cs + t];
-  if (part_a) {
-    const int lane = t & 63;
-    for (int o = t >> 6; o < 2 * width; o += 4) {
-      const bool second = o >= width;
-      const int e = second ? o - width : o;
-      const double* partial = (second ? part_b : part_a) + cell * cs;
-      const int nwg = second ? nwg_b : nwg_a;
-      double s = 0.0;
-      for (int w = lane; w < nwg; w += 64) s += partial[(int64_t)w * width + e];
-      s = wave_sum(s);
-      if (lane == 0) sums_host[cell * 2 * width + o] = s;
-    }
-  }
+  if (part_a) sgpr_trace_sums(part_a + cell * cs, nwg_a, part_b + cell * cs, nwg_b, width, t, sums_host + cell * 2 * width);
   if (dz)
     for (int e = t; e < zn; e += 256) dz_host[cell * zn + e] = dz[cell * cs + e];
 }

@@ -1,7 +1,7 @@
 // The scalar tail of one SGPR evaluation -- ELBO from the device reductions, derivatives w.r.t. the constrained hyperparameters,
 // LogNormal priors, the chain rule through softplus -- and one element of Keras's Adam update (gpr.py:147-173) and of its Adadelta
 // update (gpr.py:176-192), written ONCE for the host (sgpr_objective_batch's tail, the host-stepped loop of gprx_adam_batch /
-// gprx_adadelta_batch) and the device (sf_adam_prep_kernel, the resident loop): the same
+// gprx_adadelta_batch) and the device (sf_adam_prep_kernel and sgpr_step_kernel, the resident loops): the same
 // operations in the same order with one rounding each (px_math.h), so both give the same bits.
 // Formulas: oracle/sgpr.py elbo_grads / loss_and_grad (gpflow SGPR.elbo, priors over trainable parameters only).
 #pragma once

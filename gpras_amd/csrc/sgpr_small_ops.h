@@ -15,6 +15,25 @@ __device__ __forceinline__ void sgpr_combine(double q, double s, double t, doubl
   gq = 0.5 * (2.0 * q - s - t - mm);
 }
 
+// The 2 * width trace sums of one cell from the partials of its two contraction launches (part_a: nwg_a rows of `width` sums through
+// Kuf, part_b: nwg_b rows through Kuu), in trace_final's order: one wave per output, lanes stride over the partials by 64, wave_sum
+// finishes; lane 0 stores out[o].  Called by all 256 threads (t) of a workgroup; sgpr_stage_out_kernel (out: the pinned host block) and
+// the resident loop's step kernel (out: LDS) share it, so both see the same bits.
+__device__ __forceinline__ void sgpr_trace_sums(const double* __restrict__ part_a, int nwg_a, const double* __restrict__ part_b, int nwg_b,
+                                                int width, int t, double* __restrict__ out) {
+  const int lane = t & 63;
+  for (int o = t >> 6; o < 2 * width; o += 4) {
+    const bool second = o >= width;
+    const int e = second ? o - width : o;
+    const double* partial = second ? part_b : part_a;
+    const int nwg = second ? nwg_b : nwg_a;
+    double s = 0.0;
+    for (int w = lane; w < nwg; w += 64) s += partial[(int64_t)w * width + e];
+    s = wave_sum(s);
+    if (lane == 0) out[o] = s;
+  }
+}
+
 // ---- M <= 64: the M x M algebra between the second factorisation and the contractions, one workgroup per cell ----
 // 64 x 64 product in gemm_f64's operation order (stages of 16 along k; instruction j of a stage takes k = k0 + 4 g + j from
 // lane group g; accumulators start at zero; alpha = 1, beta = 0), so the values equal those of launch_gemm bit for bit.

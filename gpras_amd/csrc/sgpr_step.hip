@@ -1,0 +1,143 @@
+// Resident optimiser loop of the general sparse launch sequence: the step kernel (sgpr_step.h), one instantiation per optimiser.
+// Sibling of sf_adam_body (sf_cell_dev.h), which serves the fused evaluation: same thread assignment (thread k owns hyperparameter k,
+// thread 255 the loss and the stop rule, four Z elements per thread and pass), same functions in the same order.  What differs is where
+// the evaluation left its results: the trace sums come from the contraction partials (sgpr_trace_sums, shared with
+// sgpr_stage_out_kernel), dZ is already scaled (dz_kernel), and sgpr_asm_dparam gets the padded M of the launch sequence (mp).
+#include "sgpr_step.h"
+#include "sf_cell_dev.h"
+#include "sgpr_small_ops.h"
+
+namespace gprx {
+
+template <int OPT>
+__global__ __launch_bounds__(256) void sgpr_step_kernel(SgprStep a, SfAdam ad) {
+  __shared__ double shs[2 * (2 + CELL_PAR - CELL_PAR_LS)];  // trace sums
+  __shared__ double sred[8];
+  __shared__ double sPar[CELL_PAR];                          // the cell's parameter row of THIS step (the row in memory is overwritten below)
+  __shared__ double sTh[2 + CELL_PAR - CELL_PAR_LS];         // the variables after the update
+  __shared__ int keep;
+  const int cell = blockIdx.x, tid = threadIdx.x;
+  if (ad.active[cell] == 0) return;
+  double* res = a.cellres + (int64_t)cell * a.res_doubles;
+  int info = 0;
+  __builtin_memcpy(&info, res + 2, sizeof(int));
+  if (info != 0) {
+    sf_adam_failed(ad, cell, tid);
+    return;
+  }
+  double* A = a.arena + (int64_t)cell * a.ss;
+  double* par = a.cellpar + (int64_t)cell * CELL_PAR;
+  const int mask = a.ctl[SGPR_CTL_MASK], max_iter = a.ctl[SGPR_CTL_MAX_ITER];
+  const int width = a.width, nt = ad.nt, nz = a.m * a.d, gw = nt + nz;
+  // (the step and its alpha are read before the barrier: thread 255 stores tstep[cell] = t below -- sf_adam_body)
+  const int t = ad.tstep[cell] + 1;
+  double alpha = 0.0;
+  if constexpr (OPT == SF_OPT_ADAM) alpha = ad.alpha[t - a.ctl[SGPR_CTL_ALPHA_T1]];
+  if (tid < 8) sred[tid] = A[a.oRed + tid];
+  if (tid < CELL_PAR) sPar[tid] = par[tid];
+  sgpr_trace_sums(A + a.oPartP, a.nwg_p, A + a.oPartQ, a.nwg_q, width, tid, shs);
+  __syncthreads();
+  const double* ls = sPar + CELL_PAR_LS;
+  const double variance = sPar[0], noise = sPar[1];
+  const double nn = (double)a.n;
+  double* th = ad.theta + (int64_t)cell * nt;
+  double* mom = ad.mom + (int64_t)cell * gw;
+  double* vel = ad.vel + (int64_t)cell * gw;
+  if (tid < nt) {
+    const int k = tid;
+    const double du = sgpr_asm_dparam(k, ad.nlen, ad.ard, a.d, width, nn, a.mp, variance, noise, sred, shs);
+    double u, w = th[k];
+    bool trainable;
+    if (k == 0) {
+      u = variance;
+      trainable = (mask & ASM_TRAIN_VARIANCE) != 0;
+    } else if (k < nt - 1) {
+      u = ls[k - 1];
+      trainable = (mask & ASM_TRAIN_LENGTHSCALE) != 0;
+    } else {
+      u = noise;
+      trainable = (mask & ASM_TRAIN_NOISE) != 0;
+    }
+    const double ge = sgpr_asm_chain(du, u, w, trainable);
+    if (trainable) {
+      double mo = mom[k], ve = vel[k];
+      if constexpr (OPT == SF_OPT_ADAM)
+        adam_element(ge, alpha, mo, ve, w);
+      else
+        adadelta_element(ge, mo, ve, w);
+      mom[k] = mo;
+      vel[k] = ve;
+      th[k] = w;
+    }
+    sTh[k] = w;
+  }
+  if ((mask & ASM_TRAIN_Z) != 0) {
+    for (int e0 = 0; e0 < nz; e0 += 256 * 4) {  // four elements per thread at once: their loads in flight together
+      double ge[4], mo[4], ve[4], x[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int e = min(e0 + 256 * u + tid, nz - 1);
+        ge[u] = -A[a.odZ + e];
+        mo[u] = mom[nt + e];
+        ve[u] = vel[nt + e];
+        x[u] = A[a.oZ + e];
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int e = e0 + 256 * u + tid;
+        if (e < nz) {
+          if constexpr (OPT == SF_OPT_ADAM)
+            adam_element(ge[u], alpha, mo[u], ve[u], x[u]);
+          else
+            adadelta_element(ge[u], mo[u], ve[u], x[u]);
+          mom[nt + e] = mo[u];
+          vel[nt + e] = ve[u];
+          A[a.oZ + e] = x[u];
+        }
+      }
+    }
+  }
+  if (tid == 255) {  // (a thread with no hyperparameter of its own)
+    const double elbo = sgpr_asm_elbo(nn, ad.yy[ad.units[cell]], variance, noise, sred);
+    double lp = 0.0;
+    {
+#pragma clang fp contract(off)
+      if (mask & ASM_TRAIN_VARIANCE) lp += px_ln_logpdf(variance);
+      if (mask & ASM_TRAIN_LENGTHSCALE)
+        for (int k = 0; k < ad.nlen; ++k) lp += px_ln_logpdf(ls[k]);
+      if (mask & ASM_TRAIN_NOISE) lp += px_ln_logpdf(noise);
+    }
+    const double loss = -(elbo + lp);
+    bool go = t < max_iter;
+    if constexpr (OPT == SF_OPT_ADAM) {
+      double best = ad.best[cell];
+      int stale = ad.stale[cell];
+      go = adam_keep_running(loss, best, stale) && go;
+      ad.best[cell] = best;
+      ad.stale[cell] = stale;
+    }
+    ad.loss[cell] = loss;
+    ad.n_evals[cell] += 1;
+    ad.tstep[cell] = t;
+    if (!go) ad.active[cell] = 0;
+    keep = go ? 1 : 0;
+  }
+  __syncthreads();  // (sTh and keep are complete; every read of this step's parameter row went through sPar)
+  if (keep == 0) return;
+  // ---- opens step t + 1: the parameter row of the updated variables (decode_theta's bits), the result words cleared; y stays in the
+  // cell block from the opening stage-in ----
+  if (tid < CELL_PAR) par[tid] = sf_par_from_theta(sTh, ad, cell, a.d, tid);
+  if (tid < a.res_doubles) res[tid] = 0.0;
+}
+
+hipError_t sgpr_launch_step(hipStream_t st, int opt, const SgprStep& a, const SfAdam& ad, int cells) {
+  if (opt == SF_OPT_ADAM)
+    hipLaunchKernelGGL((sgpr_step_kernel<SF_OPT_ADAM>), dim3(cells), dim3(256), 0, st, a, ad);
+  else if (opt == SF_OPT_ADADELTA)
+    hipLaunchKernelGGL((sgpr_step_kernel<SF_OPT_ADADELTA>), dim3(cells), dim3(256), 0, st, a, ad);
+  else
+    return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
+}  // namespace gprx

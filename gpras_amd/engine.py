@@ -154,10 +154,13 @@ class Engine:
 
     @_locked
     def adam_batch(self, units, thetas, mask: int, max_iter: int, zs=None):
-        """``_optimize_adam`` (gpr.py:147-173) for ``len(units)`` cells in lock step inside the library (``gprx_adam_batch``): one
-        batched evaluation per step, the update on the C side.  Returns ``(thetas, zs, n_evals, batches)`` -- the optimiser's
-        variables after the run (copies), evaluations per cell, batched evaluations made.  Raises as ``objective_batch`` does when
-        a cell stops being positive definite (the arrays of that step are attached to the exception as ``.state``)."""
+        """``_optimize_adam`` (gpr.py:147-173) for ``len(units)`` cells in lock step inside the library (``gprx_adam_batch``).  Sparse
+        models with d <= 64 run the loop resident on the device -- around the five fused launches for M <= 64, around the general
+        launch sequence with its step kernel otherwise (tuning key ``"sgpr_resident"`` = 0: never; ``last_optimizer_route()`` tells
+        which loop ran); other models take one batched evaluation per step, the update on the C side.  Returns ``(thetas, zs,
+        n_evals, batches)`` -- the optimiser's variables after the run (copies), evaluations per cell, batched evaluations made.
+        Raises as ``objective_batch`` does when a cell stops being positive definite (the arrays of that step are attached to the
+        exception as ``.state``)."""
         units = np.ascontiguousarray(units, dtype=np.int32)
         thetas = np.array(thetas, dtype=np.float64, order="C")
         if thetas.shape != (units.size, self.n_theta):
@@ -180,11 +183,20 @@ class Engine:
         return thetas, (zs if self.m != 0 else None), n_evals, batches.value
 
     @_locked
+    def last_optimizer_route(self):
+        """``(route, host_waits)`` of the last ``adam_batch`` / ``adadelta_batch`` call (``gprx_last_optimizer_route``): route 0
+        host-stepped, 1 resident around the fused launches, 2 resident around the general launch sequence; host_waits: how often that
+        call waited for the stream."""
+        route, waits = C.c_int(), C.c_int()
+        check(self._lib.gprx_last_optimizer_route(self._h, C.byref(route), C.byref(waits)), self._h)
+        return route.value, waits.value
+
+    @_locked
     def adadelta_batch(self, units, thetas, mask: int, max_iter: int, zs=None):
         """``_optimize_adadelta`` (gpr.py:176-192) for ``len(units)`` cells in lock step inside the library (``gprx_adadelta_batch``),
-        the twin of ``adam_batch``: exactly ``max_iter`` steps per cell.  Returns ``(thetas, zs, n_evals, batches, losses)`` --
-        ``losses`` holds each cell's last loss (NaN where no evaluation was made).  Raises as ``adam_batch`` does, with ``.state``
-        ``(thetas, zs, n_evals, batches)``."""
+        the twin of ``adam_batch`` (same routes, ``last_optimizer_route()``): exactly ``max_iter`` steps per cell.  Returns
+        ``(thetas, zs, n_evals, batches, losses)`` -- ``losses`` holds each cell's last loss (NaN where no evaluation was made).
+        Raises as ``adam_batch`` does, with ``.state`` ``(thetas, zs, n_evals, batches)``."""
         units = np.ascontiguousarray(units, dtype=np.int32)
         thetas = np.array(thetas, dtype=np.float64, order="C")
         if thetas.shape != (units.size, self.n_theta):

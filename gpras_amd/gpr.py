@@ -102,7 +102,7 @@ class GPRAS:
         if lockstep and not can_lockstep:
             raise ValueError("lockstep fitting needs several modes on one engine (workers=1)")
         if len(models) == 1 and len(self.engines) == 1 and lockstep is None and optimization_method in BATCHED_OPTIMIZERS and hasattr(self.engine, "adam_batch"):
-            # one mode with a batched driver: its Adam / Adadelta loops inside the library as well (sparse models with M <= 64: resident
+            # one mode with a batched driver: its Adam / Adadelta loops inside the library as well (sparse models: resident
             # on the device, no host round trip per step); same variables as the serial driver bit for bit (tests/test_gpu_gpras.py,
             # tests/test_gpu_drivers.py)
             stats1: dict[str, int] = {"batches": 0}

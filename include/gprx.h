@@ -302,7 +302,15 @@ int gprx_predict_batch_dev(gprx_handle h, int count, const int* units, const dou
  * (GPRX_ADAM_CHECK_EVERY): nothing else crosses the host link between the call's first upload and its last download.
  * GPRX_ADAM_HOST=1 selects the host-stepped loop below instead; both give the same variables bit for bit (the scalar tail of an
  * evaluation and the update are ONE source for host and device, csrc/sgpr_asm.h, on exp / log written out in IEEE operations,
- * csrc/px_math.h).  Other models: every step
+ * csrc/px_math.h).
+ * Every other sparse model with d <= 64 -- M > 64, or M <= 64 with "sgpr_fused" = 0 -- keeps the loop on the device as well, around
+ * the general launch sequence: a step is that sequence without its stage-in and stage-out launches, closed by ONE step kernel
+ * (csrc/sgpr_step.h) that forms the trace sums, the loss and the gradient, applies the update and the stop rule and writes the next
+ * step's parameter row; the step is captured into a linear graph per (cells, optimiser) and replayed, what changes between steps is
+ * read from device memory, the flags are read every 25 steps as above, and at a read where cells have stopped the batch shrinks to
+ * the running ones.  Same bits as the host-stepped loop.  "sgpr_resident" = 0 (gprx_set_tuning / gprx_set_handle_tuning) selects the
+ * host-stepped loop for every sparse model; gprx_last_optimizer_route reports which loop a call took.  Other models (exact ones,
+ * d > 64): every step
  * is ONE batched evaluation (gprx_objective_batch) of the cells still running, the update happens here on the host side of the
  * library -- no per-step round trip through the caller's language.  theta (count, n_theta) and z (count, m, d; NULL for exact
  * models) are the optimiser's variables, updated in place (elements outside `mask` stay as they are); n_evals[i] receives the
@@ -317,8 +325,9 @@ int gprx_adam_batch(gprx_handle h, int count, const int* units, double* theta, d
 /* The reference's Adadelta driver, _optimize_adadelta (gpr.py:176-192: tf.keras.optimizers.Adadelta() defaults -- learning rate 1e-3,
  * rho 0.95, epsilon 1e-7), for `count` cells in lock step: exactly max_iter steps for every cell, no early stop, fresh accumulators
  * per call.  The routes are those of gprx_adam_batch: sparse models with M <= 64 run the loop resident on the device (the same four
- * launches per step, the last one with this update; the error word is read every 25 steps), every other model -- and every model
- * under GPRX_ADAM_HOST=1 -- takes one batched evaluation per step with the update on the host side of the library; both give the
+ * launches per step, the last one with this update; the error word is read every 25 steps), the other sparse models with d <= 64
+ * run it resident around the general launch sequence (the same step kernel with this update), every other model -- and every model
+ * under GPRX_ADAM_HOST=1 or "sgpr_resident" = 0 -- takes one batched evaluation per step with the update on the host side of the library; both give the
  * same variables bit for bit (the update is one source for host and device, csrc/sgpr_asm.h adadelta_element: one rounding per
  * operation in the order of the NumPy statement in gpras_amd/optimizers.py).  theta, z, mask, n_evals and batches as in
  * gprx_adam_batch; a mask with nothing trainable returns at once.  losses (optional, count doubles) receives the loss of each
@@ -327,6 +336,14 @@ int gprx_adam_batch(gprx_handle h, int count, const int* units, double* theta, d
  * leaves them in that case. */
 int gprx_adadelta_batch(gprx_handle h, int count, const int* units, double* theta, double* z, int mask, int max_iter, double* losses,
                         int* n_evals, int* batches);
+
+/* Which loop the handle's last call of gprx_adam_batch (_optimize_adam, gpr.py:147-173) or of
+ * gprx_adadelta_batch (_optimize_adadelta, gpr.py:176-192) took, and how often that call waited for the stream.
+ * route: 0 host-stepped, 1 resident around the five fused launches, 2 resident around the general launch sequence.
+ * host_waits counts the loop's own waits.  A resident loop waits for its opening upload, once per window of 25 steps, for its
+ * closing download, and for one more round trip per shrink of the batch; the host-stepped loop waits once per step.  The
+ * allocation of a handle's buffers on its first call is not counted. */
+int gprx_last_optimizer_route(gprx_handle h, int* route, int* host_waits);
 
 /* ---- EOF (PCA) projection either side of the GP path: SURVEY.md section 8(f) row N1 ------------------- */
 /* One projector = the fitted state of a reference PreProcessor (gpras/preprocess.py:868-927): `dry` (n_cells bytes, 1 =
@@ -524,6 +541,8 @@ int gprx_gather_rows(int device, const double* field_dev, int64_t rows, int64_t 
  * "predict_path": 0 choose (default), 1 always the triangular GEMM against L^-1, 2 always blocked forward substitution.
  * "sgpr_fused": 1 (default) sparse models with M <= 64 take the five-launch evaluation and the device-resident Adam loop, 0: the
  * general launch sequence (gprx_objective_batch); a handle's cell blocks are rebuilt when its value changes.
+ * "sgpr_resident": 1 (default) the optimiser loops of sparse models with d <= 64 (gprx_adam_batch, gprx_adadelta_batch) stay on the
+ * device, 0: the host-stepped loop for every sparse model -- one process can run both routes (gprx_last_optimizer_route).
  * "sgpr_groups_from" (process-wide): the device-resident Adam loop runs a batch of at least this many cells (stated at N = 4096, i.e.
  * 16 chunks of 256 training points per cell: the criterion is cells x chunks > 16 (value - 1), a pass that needs a second round of the
  * CUs) as two groups of cells on two streams, one launch apart, so that one group's one-workgroup-per-cell launches overlap the

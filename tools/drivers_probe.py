@@ -1,10 +1,11 @@
-"""Time the optimiser drivers on one MI355X: GPRAS.fit on sparse models (RBF, N = 4096, d = 10, M = 50, 16 modes) with
+"""Time the optimiser drivers on one MI355X: GPRAS.fit on sparse models (RBF, N = 4096, d = 10, M = 50 or ``--m``, 16 modes) with
 ``three-stage``, ``adadelta``, ``diffential_evolution``, ``stochastic`` and, for scale, ``adam``.  Per driver one warm-up fit, then
 three timed fits (a host clock around the optimiser loop over the modes, GPRAS._run_optimizers, which ends in a synchronising
 download; the handle, the upload of the data and the k-means initialisation are outside the window); reported: best, the spread (min
-to max of the three) and the evaluation count.  Not a test and not bench.py.
+to max of the three) and the evaluation count.  Not a test and not bench.py.  Only the package's public interface is used, so the
+same file also times a checkout of an earlier commit (where the engine has no ``last_optimizer_route`` the route is reported as null).
 
-    python tools/drivers_probe.py [--out FILE.json] [--tiny]
+    python tools/drivers_probe.py [--out FILE.json] [--tiny] [--m M] [--drivers adam,adadelta]
 """
 import argparse
 import json
@@ -21,9 +22,11 @@ from gpras_amd.synth import make_regression  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--out", default=None)
 ap.add_argument("--tiny", action="store_true", help="a rehearsal of the script itself at toy sizes")
+ap.add_argument("--m", type=int, default=50, help="inducing points per model (M > 64 takes the general launch sequence)")
+ap.add_argument("--drivers", default=None, help="comma-separated subset of the drivers (default: all five)")
 args = ap.parse_args()
 
-n, d, m, modes = (4096, 10, 50, 16) if not args.tiny else (256, 3, 8, 3)
+n, d, m, modes = (4096, 10, args.m, 16) if not args.tiny else (256, 3, min(args.m, 8), 3)
 scale = 1 if not args.tiny else 50
 DRIVERS = [
     ("three-stage", lambda: {"max_iter": 100 // scale}),
@@ -32,6 +35,9 @@ DRIVERS = [
     ("stochastic", lambda: {"n_starts": max(2, 40 // scale), "iter_initial": max(2, 20 // scale), "iter_final": 10, "rng": np.random.default_rng(5)}),
     ("adam", lambda: {"max_iter": 1000 // scale}),
 ]
+
+if args.drivers:
+    DRIVERS = [dr for dr in DRIVERS if dr[0] in args.drivers.split(",")]
 
 x, y, _ = make_regression(n, d, n_outputs=modes, n_test=0, config=2, unit=0)
 result = {"kernel": "RBF", "n": n, "d": d, "m": m, "modes": modes, "drivers": {}}
@@ -46,12 +52,14 @@ for name, kwargs in DRIVERS:
         g._run_optimizers(g.models, name, None, kw)
         dt = time.perf_counter() - t0
         evals, stats = sum(mod.n_evals for mod in g.models), getattr(g, "lockstep_stats", None)
+        route = [list(eng.last_optimizer_route()) if hasattr(eng, "last_optimizer_route") else None for eng in g.engines]
         for eng in g.engines:
             eng.close()
         if rep > 0:
             times.append(dt)
     entry = {"kwargs": {k: v for k, v in kwargs().items() if k != "rng"}, "best_s": min(times), "min_s": min(times), "max_s": max(times),
-             "times_s": times, "evaluations": evals, "lockstep_stats": stats}
+             "times_s": times, "evaluations": evals, "lockstep_stats": stats,
+             "route_and_host_waits": route}
     if name in ("adam", "adadelta"):
         entry["per_step_us"] = 1e6 * min(times) / max(1, evals // modes)
     result["drivers"][name] = entry
