@@ -90,7 +90,7 @@ struct gprx_ctx {
   int last_route = 0, last_host_waits = 0;                // gprx_last_optimizer_route
   int host_waits = 0;                                     // stream waits of the running optimiser call (wait_stream and the loops' own)
   int sgpr_fused = 1;                                     // M <= 64: the five-launch evaluation of sgpr_fused.h ("sgpr_fused" tuning key)
-  Buf adam_dev;                                           // device state of the resident Adam loop (sgpr_adam_resident)
+  Buf adam_dev;                                           // device state of the resident optimiser loops (resident_state)
   double* adam_pin = nullptr;                             // pinned: stop flags of the cells + the error word, read every few steps
   size_t adam_pin_bytes = 0;
   unsigned long long* sf_stamps = nullptr;                // development aid (gprx_sf_stamps): phase stamps of the fused sparse kernels
@@ -1459,19 +1459,19 @@ int sgpr_predict_batch(gprx_handle h, int count, const double* xs_dev, int64_t n
   return GPRX_OK;
 }
 
-// gprx_adam_batch for sparse models with M <= 64: the loop RESIDENT on the device.  A step is FOUR launches (sgpr_fused.h: pass 1, mid,
-// pass 2, and sf_adam_prep_kernel = partial sums + loss + gradient + Keras's update + the stop rule of gpr.py:160-171, then Kuu, L, L^-1
-// of the updated variables with the positive transforms evaluated on the device); cells that have stopped return at once from every launch.  The host enqueues `check_every` steps, then reads
-// the stop flags (count + 1 ints through pinned memory) -- no gradient, loss or parameter crosses the host link during the run (round 4:
-// every step synchronised, downloaded the gradients, updated on the host and uploaded).  Same variables as the host-stepped loop, bit
-// for bit (sgpr_asm.h, px_math.h; tests/test_gpu_gpras.py).  A cell whose Kuu or B stops being positive definite ends the call with
-// GPRX_ENOTPD at the next check; the other cells may then be up to check_every - 1 steps past that evaluation.
-// kind = SF_OPT_ADADELTA (gprx_adadelta_batch): the same loop with Keras's Adadelta update (gpr.py:176-192) in the fourth launch -- no alpha
-// table, every cell runs max_iter steps; `losses` (optional) receives the loss of each cell's last evaluation.
-// The other groups' streams are joined into the handle's stream before EVERY return (SfJoin): after a failed HIP call inside the step
-// loop nothing may stay in flight on buffers the handle reuses.
-// The state block of both resident loops.  The captured steps of sgpr_resident_general (h->rgraphs) hold addresses inside it: whoever
-// reallocates it drops them (the stream is idle: every optimiser call ends with a synchronisation).
+// ---- what the two resident optimiser loops below share ------------------------------------------------------------------------------
+// steps between two reads of the stop flags
+int resident_check_every() {
+  static const int every = [] {
+    const char* e = getenv("GPRX_ADAM_CHECK_EVERY");
+    const int v = e ? atoi(e) : 0;
+    return v > 0 ? v : 25;
+  }();
+  return every;
+}
+
+// Grows the device state block of the resident loops.  The captured steps of sgpr_resident_general (h->rgraphs) hold addresses inside
+// it: whoever reallocates it drops them (the stream is idle: every optimiser call ends with a synchronisation).
 int ensure_adam_dev(gprx_handle h, size_t bytes) {
   if (h->adam_dev.bytes >= bytes) return GPRX_OK;
   for (auto& kv : h->rgraphs)
@@ -1480,6 +1480,134 @@ int ensure_adam_dev(gprx_handle h, size_t bytes) {
   return ensure(h, h->adam_dev, bytes);
 }
 
+// Grows the pinned block of the resident loops; a failed allocation leaves neither a block nor a size behind.
+int ensure_adam_pin(gprx_handle h, size_t bytes) {
+  if (h->adam_pin_bytes >= bytes) return GPRX_OK;
+  if (h->adam_pin) HIPCHK(h, hipHostFree(h->adam_pin));
+  h->adam_pin = nullptr;
+  h->adam_pin_bytes = 0;
+  HIPCHK(h, hipHostMalloc((void**)&h->adam_pin, bytes, hipHostMallocDefault));
+  h->adam_pin_bytes = bytes;
+  return GPRX_OK;
+}
+
+// The state of a residency of `cells` cells: one layout for both loops.  Device block (h->adam_dev), doubles first: theta, mom, vel, best,
+// loss (SfAdam), the window block, y.y of every unit; then ints: stale, active, n_evals, tstep, units, SF_MAX_GROUPS error words (one
+// per group of cells).  A window block is check_every alpha values (one window, not max_iter: a call "until the early stop" passes
+// max_iter = 2^31 - 1) and two doubles that carry the general route's control words (the fused route reads neither).  Pinned block
+// (h->adam_pin): a window block, then the stop flags of the cells and the error words as last read.
+struct ResidentState {
+  SfAdam ad;                                              // the pointers, nt, nlen, ard; mask, max_iter and the alpha window are the route's to set
+  double* win;                                            // the window block on the device
+  size_t n_dbl, n_int;                                    // doubles and ints of the device block (the ints start at ad.stale)
+  size_t o_mom, o_vel, o_best, o_loss, o_yy;              // where a host copy of the doubles holds each array (theta: 0)
+  size_t o_stale, o_active, o_n_evals, o_tstep, o_units;  // the same for the ints
+  double* hwin;                                           // pinned
+  int* hflags;                                            // pinned: [cells] stop flags, then the error words
+};
+static_assert(SGPR_CTL_WORDS * sizeof(int) == 2 * sizeof(double), "the control words travel as two doubles behind the alpha table");
+
+// lays the state of `cells` cells out and grows the two blocks to hold it
+int resident_state(gprx_handle h, int cells, int check_every, ResidentState* out) {
+  const size_t c = (size_t)cells, nt = (size_t)h->ntheta, gw = nt + (size_t)(h->m * h->d), win_dbl = (size_t)check_every + 2;
+  ResidentState rs{};
+  rs.o_mom = c * nt;
+  rs.o_vel = rs.o_mom + c * gw;
+  rs.o_best = rs.o_vel + c * gw;
+  rs.o_loss = rs.o_best + c;
+  const size_t o_win = rs.o_loss + c;
+  rs.o_yy = o_win + win_dbl;
+  rs.n_dbl = rs.o_yy + (size_t)h->n_units;
+  rs.o_stale = 0;
+  rs.o_active = c;
+  rs.o_n_evals = 2 * c;
+  rs.o_tstep = 3 * c;
+  rs.o_units = 4 * c;
+  rs.n_int = 5 * c + gprx_ctx::SF_MAX_GROUPS;
+  int rc;
+  if ((rc = ensure_adam_dev(h, sizeof(double) * rs.n_dbl + sizeof(int) * rs.n_int))) return rc;
+  if ((rc = ensure_adam_pin(h, sizeof(double) * win_dbl + sizeof(int) * (c + gprx_ctx::SF_MAX_GROUPS)))) return rc;
+  double* dp = h->adam_dev.p;
+  int* ip = reinterpret_cast<int*>(dp + rs.n_dbl);
+  rs.ad.theta = dp;
+  rs.ad.mom = dp + rs.o_mom;
+  rs.ad.vel = dp + rs.o_vel;
+  rs.ad.best = dp + rs.o_best;
+  rs.ad.loss = dp + rs.o_loss;
+  rs.win = dp + o_win;
+  rs.ad.yy = dp + rs.o_yy;
+  rs.ad.stale = ip + rs.o_stale;
+  rs.ad.active = ip + rs.o_active;
+  rs.ad.n_evals = ip + rs.o_n_evals;
+  rs.ad.tstep = ip + rs.o_tstep;
+  rs.ad.units = ip + rs.o_units;
+  rs.ad.error = ip + 5 * c;
+  rs.ad.nt = h->ntheta;
+  rs.ad.nlen = h->nlen;
+  rs.ad.ard = h->ard;
+  rs.hwin = h->adam_pin;
+  rs.hflags = reinterpret_cast<int*>(h->adam_pin + win_dbl);
+  *out = rs;
+  return GPRX_OK;
+}
+
+// the alpha values of the window of steps done + 1 .. done + k (every running cell is at the same step)
+void resident_fill_window(double* win, int done, int k) {
+  for (int i = 0; i < k; ++i) win[i] = adam_alpha((double)done + 1.0 + i);
+}
+
+// the stop flags of the `cells` cells and n_err error words -> rs.hflags, one wait for the stream; *running: how many cells still run
+int resident_read_flags(gprx_handle h, const ResidentState& rs, int cells, int n_err, int* running) {
+  HIPCHK(h, hipMemcpyAsync(rs.hflags, rs.ad.active, sizeof(int) * cells, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(rs.hflags + cells, rs.ad.error, sizeof(int) * n_err, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, wait_stream(h, h->stream));
+  *running = 0;
+  for (int c = 0; c < cells; ++c) *running += rs.hflags[c] != 0 ? 1 : 0;
+  return GPRX_OK;
+}
+
+// the end of a resident call: *batches = the most evaluations any cell took part in; bad_cell >= 0: that cell's Kuu or B was not
+// positive definite, the call fails
+int resident_finish(gprx_handle h, int count, const int* n_evals, int* batches, int bad_cell) {
+  if (batches) {
+    int mx = 0;
+    for (int c = 0; c < count; ++c) mx = std::max(mx, n_evals[c]);
+    *batches = mx;
+  }
+  if (bad_cell >= 0) {
+    char msg[160];
+    snprintf(msg, sizeof msg, "cell %d: Kuu or B not positive definite", bad_cell);
+    return fail(h, GPRX_ENOTPD, msg);
+  }
+  return GPRX_OK;
+}
+
+// the arguments of sgpr_step_kernel for the launch sequence's layout; ctl: the control words on the device
+SgprStep sgpr_step_params(gprx_handle h, const SgprLayout& L, const int* ctl) {
+  const int mp = (int)h->mp, np = (int)h->np;
+  SgprStep a{};
+  a.arena = h->sarena.p;
+  a.ss = L.ss;
+  a.oZ = L.oZ;
+  a.odZ = L.odZ;
+  a.oRed = L.oRed;
+  a.oPartP = L.oPart;
+  a.oPartQ = L.oPart + L.part_p;
+  a.nwg_p = (mp / KM_T) * (np / KM_T);
+  a.nwg_q = (mp / KM_T) * (mp / KM_T);
+  a.width = L.width;
+  a.n = (int)h->n;
+  a.m = (int)h->m;
+  a.d = h->d;
+  a.mp = mp;
+  a.cellpar = h->cellpar.p;
+  a.cellres = h->cellres.p;
+  a.res_doubles = CELL_RES;
+  a.ctl = ctl;
+  return a;
+}
+
+// joins the other groups' streams of the fused loop into the handle's stream: on request and when it goes out of scope
 struct SfJoin {
   gprx_handle h;
   hipStream_t st;
@@ -1493,73 +1621,46 @@ struct SfJoin {
   ~SfJoin() { join(); }
 };
 
-int sgpr_adam_resident(gprx_handle h, int kind, int count, const int* units, double* theta, double* z, int mask, int max_iter, double* losses,
-                       int* n_evals, int* batches) {
+// gprx_adam_batch for sparse models with M <= 64: the loop RESIDENT on the device.  A step is FOUR launches (sgpr_fused.h: pass 1, mid,
+// pass 2, and sf_adam_prep_kernel = partial sums + loss + gradient + Keras's update + the stop rule of gpr.py:160-171, then Kuu, L, L^-1
+// of the updated variables with the positive transforms evaluated on the device); cells that have stopped return at once from every
+// launch.  The host enqueues `check_every` steps, then reads the stop flags (count + 1 ints through pinned memory) -- no gradient, loss
+// or parameter crosses the host link during the run (round 4: every step synchronised, downloaded the gradients, updated on the host
+// and uploaded).  Same variables as the host-stepped loop, bit for bit (sgpr_asm.h, px_math.h; tests/test_gpu_gpras.py).  A cell whose
+// Kuu or B stops being positive definite ends the call with GPRX_ENOTPD at the next check; the other cells may then be up to
+// check_every - 1 steps past that evaluation.
+// kind = SF_OPT_ADADELTA (gprx_adadelta_batch): the same loop with Keras's Adadelta update (gpr.py:176-192) in the fourth launch -- no alpha
+// table, every cell runs max_iter steps; `losses` (optional) receives the loss of each cell's last evaluation.
+// The other groups' streams are joined into the handle's stream before EVERY return (SfJoin): after a failed HIP call inside the step
+// loop nothing may stay in flight on buffers the handle reuses.
+int sgpr_resident_fused(gprx_handle h, int kind, int count, const int* units, double* theta, double* z, int mask, int max_iter, double* losses,
+                        int* n_evals, int* batches) {
   const SgprLayout L = sgpr_batch_layout(h);
   int rc;
   if ((rc = ensure_sarena(h, count, L))) return rc;
   hipStream_t st = h->stream;
   const int nt = h->ntheta;
   const int64_t nz = h->m * h->d, gw = nt + nz;
-  static const int check_every = [] {
-    const char* e = getenv("GPRX_ADAM_CHECK_EVERY");
-    const int v = e ? atoi(e) : 0;
-    return v > 0 ? v : 25;
-  }();
-  // ---- device state: doubles first, then ints; the alpha table holds one window of check_every steps (not max_iter: a call "until
-  // the early stop" passes max_iter = 2^31 - 1) ----
-  const size_t n_dbl = (size_t)count * nt + 2 * (size_t)count * gw + 2 * (size_t)count + (size_t)check_every + (size_t)h->n_units;
-  const size_t n_int = 5 * (size_t)count + gprx_ctx::SF_MAX_GROUPS;  // (one error word per group of cells)
-  if ((rc = ensure_adam_dev(h, sizeof(double) * n_dbl + sizeof(int) * n_int))) return rc;
-  // pinned: the window's alpha values, then the stop flags of the cells and the error words
-  const size_t pin_need = sizeof(double) * (size_t)check_every + sizeof(int) * ((size_t)count + gprx_ctx::SF_MAX_GROUPS);
-  if (h->adam_pin_bytes < pin_need) {
-    if (h->adam_pin) HIPCHK(h, hipHostFree(h->adam_pin));
-    h->adam_pin = nullptr;
-    HIPCHK(h, hipHostMalloc((void**)&h->adam_pin, pin_need, hipHostMallocDefault));
-    h->adam_pin_bytes = pin_need;
-  }
-  SfAdam ad{};
-  double* dp = h->adam_dev.p;
-  ad.theta = dp;                 dp += (size_t)count * nt;
-  ad.mom = dp;                   dp += (size_t)count * gw;
-  ad.vel = dp;                   dp += (size_t)count * gw;
-  ad.best = dp;                  dp += count;
-  ad.loss = dp;                  dp += count;
-  double* d_alpha = dp;          dp += check_every;
-  double* d_yy = dp;             dp += h->n_units;
-  int* ip = reinterpret_cast<int*>(dp);
-  ad.stale = ip;                 ip += count;
-  ad.active = ip;                ip += count;
-  ad.n_evals = ip;               ip += count;
-  ad.tstep = ip;                 ip += count;
-  int* d_units = ip;             ip += count;
-  ad.error = ip;
-  ad.units = d_units;
+  const int check_every = resident_check_every();
+  ResidentState rs;
+  if ((rc = resident_state(h, count, check_every, &rs))) return rc;
+  SfAdam& ad = rs.ad;
   ad.alpha = nullptr;  // (set per window)
-  ad.yy = d_yy;
-  ad.nt = nt;
-  ad.nlen = h->nlen;
-  ad.ard = h->ard;
   ad.mask = mask;
   ad.max_iter = max_iter;
   // ---- initial state (host vectors live until the synchronisation below) ----
-  std::vector<double> hd(n_dbl, 0.0);
-  std::vector<int> hi(n_int, 0);
+  std::vector<double> hd(rs.n_dbl, 0.0);
+  std::vector<int> hi(rs.n_int, 0);
   std::memcpy(hd.data(), theta, sizeof(double) * (size_t)count * nt);
-  {
-    double* hbest = hd.data() + (ad.best - h->adam_dev.p);
-    double* hloss = hd.data() + (ad.loss - h->adam_dev.p);
-    for (int c = 0; c < count; ++c) hbest[c] = std::numeric_limits<double>::infinity();
-    for (int c = 0; c < count; ++c) hloss[c] = std::numeric_limits<double>::quiet_NaN();  // (no evaluation yet)
-    std::memcpy(hd.data() + (d_yy - h->adam_dev.p), h->yy.data(), sizeof(double) * h->n_units);
-    for (int c = 0; c < count; ++c) {
-      hi[(size_t)count + c] = 1;          // active
-      hi[4 * (size_t)count + c] = units[c];
-    }
+  std::memcpy(&hd[rs.o_yy], h->yy.data(), sizeof(double) * h->n_units);
+  for (int c = 0; c < count; ++c) {
+    hd[rs.o_best + c] = std::numeric_limits<double>::infinity();
+    hd[rs.o_loss + c] = std::numeric_limits<double>::quiet_NaN();  // (no evaluation yet)
+    hi[rs.o_active + c] = 1;
+    hi[rs.o_units + c] = units[c];
   }
-  HIPCHK(h, hipMemcpyAsync(h->adam_dev.p, hd.data(), sizeof(double) * n_dbl, hipMemcpyHostToDevice, st));
-  HIPCHK(h, hipMemcpyAsync(ad.stale, hi.data(), sizeof(int) * n_int, hipMemcpyHostToDevice, st));
+  HIPCHK(h, hipMemcpyAsync(h->adam_dev.p, hd.data(), sizeof(double) * rs.n_dbl, hipMemcpyHostToDevice, st));
+  HIPCHK(h, hipMemcpyAsync(ad.stale, hi.data(), sizeof(int) * rs.n_int, hipMemcpyHostToDevice, st));
   HIPCHK(h, hipMemcpy2DAsync(h->sarena.p + L.oZ, sizeof(double) * (size_t)L.ss, z, sizeof(double) * (size_t)nz, sizeof(double) * (size_t)nz, count,
                              hipMemcpyHostToDevice, st));
   ++h->host_waits;
@@ -1568,8 +1669,7 @@ int sgpr_adam_resident(gprx_handle h, int kind, int count, const int* units, dou
   p.active = ad.active;
   p.store_factors = 0;  // (nobody predicts from the cell blocks of a running optimisation)
   const int iso = (h->ard || h->dist_form) ? 0 : 1;
-  double* halpha = h->adam_pin;
-  int* flags = reinterpret_cast<int*>(h->adam_pin + check_every);
+  const int* flags = rs.hflags;
   int error_cell = 0;
   h->factorized = false;  // the cell blocks are overwritten
   // (large batches: two groups of cells on two streams, one launch apart -- sf_group_count)
@@ -1608,19 +1708,17 @@ int sgpr_adam_resident(gprx_handle h, int kind, int count, const int* units, dou
     HIPCHK(h, sf_launch_prep(sg_[g], h->kid, h->dist_form, pg[g], cells_g[g], nullptr, nullptr, h->cellpar.p + (size_t)cell0_g[g] * CELL_PAR, &adg[g]));  // opens step 1
   for (int done = 0; done < max_iter;) {
     const int k = std::min(check_every, max_iter - done);
-    // this window's alpha values (steps done + 1 .. done + k; every active cell is at the same step): the pinned block is free, the
-    // previous window's upload has completed before its stop flags were read
-    for (int i = 0; adam && i < k; ++i) {
-      const double t = (double)done + 1.0 + i;
-      halpha[i] = ADAM_LR * std::sqrt(1.0 - std::pow(ADAM_BETA2, t)) / (1.0 - std::pow(ADAM_BETA1, t));  // gprx_adam_batch's expression
+    // this window's alpha values: the pinned block is free, the previous window's upload has completed before its stop flags were read
+    if (adam) {
+      resident_fill_window(rs.hwin, done, k);
+      HIPCHK(h, hipMemcpyAsync(rs.win, rs.hwin, sizeof(double) * (size_t)k, hipMemcpyHostToDevice, st));
     }
-    if (adam) HIPCHK(h, hipMemcpyAsync(d_alpha, halpha, sizeof(double) * (size_t)k, hipMemcpyHostToDevice, st));
     if (adam && ngroups > 1) {
       HIPCHK(h, hipEventRecord(h->sf_evs[0], st));
       for (int g = 1; g < ngroups; ++g) HIPCHK(h, hipStreamWaitEvent(sg_[g], h->sf_evs[0], 0));
     }
     for (int g = 0; g < ngroups; ++g) {
-      adg[g].alpha = d_alpha;
+      adg[g].alpha = rs.win;
       adg[g].alpha_t1 = done + 1;
     }
     for (int i = 0; i < k; ++i) {
@@ -1642,15 +1740,12 @@ int sgpr_adam_resident(gprx_handle h, int kind, int count, const int* units, dou
       HIPCHK(h, hipEventRecord(h->sf_evs[g], sg_[g]));
       HIPCHK(h, hipStreamWaitEvent(st, h->sf_evs[g], 0));
     }
-    HIPCHK(h, hipMemcpyAsync(flags, ad.active, sizeof(int) * count, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(flags + count, ad.error, sizeof(int) * ngroups, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, wait_stream(h, st));
-    error_cell = 0;
+    int running = 0;
+    if ((rc = resident_read_flags(h, rs, count, ngroups, &running))) return rc;
+    error_cell = 0;  // (1 + the cell: a group's error word counts the group's own cells from 1)
     for (int g = ngroups - 1; g >= 0; --g)
       if (flags[count + g] != 0) error_cell = cell0_g[g] + flags[count + g];
-    bool any = false;
-    for (int c = 0; c < count; ++c) any = any || flags[c] != 0;
-    if (error_cell != 0 || !any) break;
+    if (error_cell != 0 || running == 0) break;
   }
   // ---- results ----
   joiner.join();  // (nothing of the other group's stream may outlive the call: max_iter = 0 enqueued its prep launch only)
@@ -1661,17 +1756,7 @@ int sgpr_adam_resident(gprx_handle h, int kind, int count, const int* units, dou
   if (losses) HIPCHK(h, hipMemcpyAsync(losses, ad.loss, sizeof(double) * count, hipMemcpyDeviceToHost, st));
   ++h->host_waits;
   HIPCHK(h, hipStreamSynchronize(st));
-  if (batches) {
-    int mx = 0;
-    for (int c = 0; c < count; ++c) mx = std::max(mx, n_evals[c]);
-    *batches = mx;
-  }
-  if (error_cell != 0) {
-    char msg[160];
-    snprintf(msg, sizeof msg, "cell %d: Kuu or B not positive definite", error_cell - 1);
-    return fail(h, GPRX_ENOTPD, msg);
-  }
-  return GPRX_OK;
+  return resident_finish(h, count, n_evals, batches, error_cell - 1);
 }
 
 // gprx_adam_batch / gprx_adadelta_batch for the sparse models that the fused route above does not take (M > 64, or M <= 64 with
@@ -1683,39 +1768,17 @@ int sgpr_adam_resident(gprx_handle h, int kind, int count, const int* units, dou
 // (step count, mask, max_iter, the window's alpha values and their first step) is read from device memory.  Every `check_every` steps
 // the host reads the stop flags and the error word.  Between two reads a stopped cell is still evaluated but the step kernel leaves it
 // alone; at a read where cells have stopped the residency is closed (state down) and reopened for the cells that still run (state up,
-// stage-in): a cell's bits depend neither on its slot nor on the batch size.  Failure: as sgpr_adam_resident.
+// stage-in): a cell's bits depend neither on its slot nor on the batch size.  Failure: as sgpr_resident_fused.
 int sgpr_resident_general(gprx_handle h, int kind, int count, const int* units, double* theta, double* z, int mask, int max_iter, double* losses,
                           int* n_evals, int* batches) {
   const SgprLayout L = sgpr_batch_layout(h);
   int rc;
   if ((rc = ensure_sarena(h, count, L))) return rc;
   hipStream_t st = h->stream;
-  const int nt = h->ntheta, mp = (int)h->mp, np = (int)h->np;
+  const int nt = h->ntheta;
   const int64_t nz = h->m * h->d, gw = nt + nz;
-  static const int check_every = [] {
-    const char* e = getenv("GPRX_ADAM_CHECK_EVERY");
-    const int v = e ? atoi(e) : 0;
-    return v > 0 ? v : 25;
-  }();
+  const int check_every = resident_check_every();
   const bool adam = kind == SF_OPT_ADAM;
-  // the window block (device and pinned): the alpha values of one window of check_every steps, then the control words
-  static_assert(SGPR_CTL_WORDS * sizeof(int) == 2 * sizeof(double), "the control words travel as two doubles behind the alpha table");
-  const size_t win_dbl = (size_t)check_every + 2;
-  auto dbl_of = [&](size_t cells) { return cells * nt + 2 * cells * gw + 2 * cells + win_dbl + (size_t)h->n_units; };
-  auto int_of = [&](size_t cells) { return 5 * cells + 1; };
-  if ((rc = ensure_adam_dev(h, sizeof(double) * dbl_of(count) + sizeof(int) * int_of(count)))) return rc;
-  const size_t pin_need = sizeof(double) * win_dbl + sizeof(int) * ((size_t)count + 1);
-  if (h->adam_pin_bytes < pin_need) {
-    if (h->adam_pin) HIPCHK(h, hipHostFree(h->adam_pin));
-    h->adam_pin = nullptr;
-    h->adam_pin_bytes = 0;
-    HIPCHK(h, hipHostMalloc((void**)&h->adam_pin, pin_need, hipHostMallocDefault));
-    h->adam_pin_bytes = pin_need;
-  }
-  double* hwin = h->adam_pin;
-  int* hctl = reinterpret_cast<int*>(hwin + check_every);
-  int* flags = reinterpret_cast<int*>(hwin + win_dbl);
-  for (int i = 0; i < check_every; ++i) hwin[i] = 0.0;  // (Adadelta reads no alpha)
   // ---- the optimiser's state of every cell on the host: what a residency is opened from and closed into ----
   std::vector<double> mom((size_t)count * gw, 0.0), vel((size_t)count * gw, 0.0), best(count, std::numeric_limits<double>::infinity()),
       loss(count, std::numeric_limits<double>::quiet_NaN());
@@ -1725,75 +1788,42 @@ int sgpr_resident_general(gprx_handle h, int kind, int count, const int* units, 
   h->factorized = false;                            // the cell blocks are overwritten
   int done = 0, error_cell = -1;
   while (!active.empty() && done < max_iter && error_cell < 0) {
-    // ---- open: state and staged inputs of the `na` running cells up, stage-in ----
+    // ---- open: state and staged inputs of the `na` running cells up, stage-in (the first residency is the largest: it sizes the
+    // blocks) ----
     const int na = (int)active.size();
-    const size_t n_dbl = dbl_of(na), n_int = int_of(na);
-    SfAdam ad{};
-    double* dp = h->adam_dev.p;
-    ad.theta = dp;                 dp += (size_t)na * nt;
-    ad.mom = dp;                   dp += (size_t)na * gw;
-    ad.vel = dp;                   dp += (size_t)na * gw;
-    ad.best = dp;                  dp += na;
-    ad.loss = dp;                  dp += na;
-    double* d_win = dp;            dp += win_dbl;
-    double* d_yy = dp;             dp += h->n_units;
-    int* ip = reinterpret_cast<int*>(dp);
-    ad.stale = ip;                 ip += na;
-    ad.active = ip;                ip += na;
-    ad.n_evals = ip;               ip += na;
-    ad.tstep = ip;                 ip += na;
-    int* d_units = ip;             ip += na;
-    ad.error = ip;
-    ad.units = d_units;
-    ad.alpha = d_win;
-    ad.yy = d_yy;
-    ad.nt = nt;
-    ad.nlen = h->nlen;
-    ad.ard = h->ard;
-    std::vector<double> hd(n_dbl, 0.0), zc((size_t)na * nz);
-    std::vector<int> hi(n_int, 0);
+    ResidentState rs;
+    if ((rc = resident_state(h, na, check_every, &rs))) return rc;
+    SfAdam& ad = rs.ad;
+    ad.alpha = rs.win;
+    int* hctl = reinterpret_cast<int*>(rs.hwin + check_every);
+    const int* flags = rs.hflags;
+    std::fill(rs.hwin, rs.hwin + check_every, 0.0);  // (Adadelta reads no alpha)
+    std::vector<double> hd(rs.n_dbl, 0.0), zc((size_t)na * nz);
+    std::vector<int> hi(rs.n_int, 0);
     const SgprStage sg = sgpr_stage(h, na, L);
     for (int j = 0; j < na; ++j) {
       const int i = active[j];
       std::memcpy(&hd[(size_t)j * nt], theta + (size_t)i * nt, sizeof(double) * nt);
-      std::memcpy(&hd[(ad.mom - h->adam_dev.p) + (size_t)j * gw], &mom[(size_t)i * gw], sizeof(double) * gw);
-      std::memcpy(&hd[(ad.vel - h->adam_dev.p) + (size_t)j * gw], &vel[(size_t)i * gw], sizeof(double) * gw);
-      hd[(ad.best - h->adam_dev.p) + j] = best[i];
-      hd[(ad.loss - h->adam_dev.p) + j] = loss[i];
-      hi[j] = stale[i];
-      hi[(size_t)na + j] = 1;  // active
-      hi[2 * (size_t)na + j] = n_evals[i];
-      hi[3 * (size_t)na + j] = done;
-      hi[4 * (size_t)na + j] = units[i];
+      std::memcpy(&hd[rs.o_mom + (size_t)j * gw], &mom[(size_t)i * gw], sizeof(double) * gw);
+      std::memcpy(&hd[rs.o_vel + (size_t)j * gw], &vel[(size_t)i * gw], sizeof(double) * gw);
+      hd[rs.o_best + j] = best[i];
+      hd[rs.o_loss + j] = loss[i];
+      hi[rs.o_stale + j] = stale[i];
+      hi[rs.o_active + j] = 1;
+      hi[rs.o_n_evals + j] = n_evals[i];
+      hi[rs.o_tstep + j] = done;
+      hi[rs.o_units + j] = units[i];
       sgpr_par_row(h, h->spin + sg.par + (size_t)j * CELL_PAR, units[i], decode_theta(h, theta + (size_t)i * nt));
       std::memcpy(h->spin + sg.z + (size_t)j * nz, z + (size_t)i * nz, sizeof(double) * nz);
     }
-    std::memcpy(&hd[d_yy - h->adam_dev.p], h->yy.data(), sizeof(double) * h->n_units);
-    HIPCHK(h, hipMemcpyAsync(h->adam_dev.p, hd.data(), sizeof(double) * n_dbl, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(ad.stale, hi.data(), sizeof(int) * n_int, hipMemcpyHostToDevice, st));
+    std::memcpy(&hd[rs.o_yy], h->yy.data(), sizeof(double) * h->n_units);
+    HIPCHK(h, hipMemcpyAsync(h->adam_dev.p, hd.data(), sizeof(double) * rs.n_dbl, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(ad.stale, hi.data(), sizeof(int) * rs.n_int, hipMemcpyHostToDevice, st));
     if ((rc = sgpr_stage_in_enqueue(h, na, L))) return rc;
     HIPCHK(h, hipGetLastError());
     ++h->host_waits;
     HIPCHK(h, hipStreamSynchronize(st));  // (the host vectors and the pinned rows are free again)
-    SgprStep sa{};
-    sa.arena = h->sarena.p;
-    sa.ss = L.ss;
-    sa.oZ = L.oZ;
-    sa.odZ = L.odZ;
-    sa.oRed = L.oRed;
-    sa.oPartP = L.oPart;
-    sa.oPartQ = L.oPart + L.part_p;
-    sa.nwg_p = (mp / KM_T) * (np / KM_T);
-    sa.nwg_q = (mp / KM_T) * (mp / KM_T);
-    sa.width = L.width;
-    sa.n = (int)h->n;
-    sa.m = (int)h->m;
-    sa.d = h->d;
-    sa.mp = mp;
-    sa.cellpar = h->cellpar.p;
-    sa.cellres = h->cellres.p;
-    sa.res_doubles = CELL_RES;
-    sa.ctl = reinterpret_cast<const int*>(d_win + check_every);
+    const SgprStep sa = sgpr_step_params(h, L, reinterpret_cast<const int*>(rs.win + check_every));
     auto step_enqueue = [&]() -> int {
       int erc;
       if ((erc = sgpr_body_enqueue(h, na, L, true, ps))) return erc;
@@ -1804,33 +1834,26 @@ int sgpr_resident_general(gprx_handle h, int kind, int count, const int* units, 
     int running = na;
     while (done < max_iter && running == na && error_cell < 0) {
       const int k = std::min(check_every, max_iter - done);
-      // this window's alpha values (steps done + 1 .. done + k; every running cell is at the same step) and the control words: the pinned
-      // block is free, the previous window's upload had completed before its stop flags were read
-      for (int i = 0; adam && i < k; ++i) {
-        const double t = (double)done + 1.0 + i;
-        hwin[i] = ADAM_LR * std::sqrt(1.0 - std::pow(ADAM_BETA2, t)) / (1.0 - std::pow(ADAM_BETA1, t));  // gprx_adam_batch's expression
-      }
+      // this window's alpha values and the control words: the pinned block is free, the previous window's upload had completed before
+      // its stop flags were read
+      if (adam) resident_fill_window(rs.hwin, done, k);
       hctl[SGPR_CTL_MASK] = mask;
       hctl[SGPR_CTL_MAX_ITER] = max_iter;
       hctl[SGPR_CTL_ALPHA_T1] = done + 1;
       hctl[3] = 0;
-      HIPCHK(h, hipMemcpyAsync(d_win, hwin, sizeof(double) * win_dbl, hipMemcpyHostToDevice, st));
+      HIPCHK(h, hipMemcpyAsync(rs.win, rs.hwin, sizeof(double) * ((size_t)check_every + 2), hipMemcpyHostToDevice, st));
       for (int i = 0; i < k; ++i) {
         bool replayed = false;
         if ((rc = sgpr_replay(h, h->rgraphs, {na, kind}, step_enqueue, &replayed))) return rc;
         if (!replayed && (rc = step_enqueue())) return rc;
       }
       done += k;
-      HIPCHK(h, hipMemcpyAsync(flags, ad.active, sizeof(int) * na, hipMemcpyDeviceToHost, st));
-      HIPCHK(h, hipMemcpyAsync(flags + na, ad.error, sizeof(int), hipMemcpyDeviceToHost, st));
-      HIPCHK(h, wait_stream(h, st));
+      if ((rc = resident_read_flags(h, rs, na, 1, &running))) return rc;
       if (flags[na] != 0) error_cell = active[flags[na] - 1];
-      running = 0;
-      for (int j = 0; j < na; ++j) running += flags[j] != 0 ? 1 : 0;
     }
     // ---- close: the state of the na cells down ----
-    HIPCHK(h, hipMemcpyAsync(hd.data(), h->adam_dev.p, sizeof(double) * n_dbl, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(hi.data(), ad.stale, sizeof(int) * n_int, hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(hd.data(), h->adam_dev.p, sizeof(double) * rs.n_dbl, hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(hi.data(), ad.stale, sizeof(int) * rs.n_int, hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipMemcpy2DAsync(zc.data(), sizeof(double) * (size_t)nz, h->sarena.p + L.oZ, sizeof(double) * (size_t)L.ss, sizeof(double) * (size_t)nz, na,
                                hipMemcpyDeviceToHost, st));
     ++h->host_waits;
@@ -1839,30 +1862,20 @@ int sgpr_resident_general(gprx_handle h, int kind, int count, const int* units, 
     for (int j = 0; j < na; ++j) {
       const int i = active[j];
       std::memcpy(theta + (size_t)i * nt, &hd[(size_t)j * nt], sizeof(double) * nt);
-      std::memcpy(&mom[(size_t)i * gw], &hd[(ad.mom - h->adam_dev.p) + (size_t)j * gw], sizeof(double) * gw);
-      std::memcpy(&vel[(size_t)i * gw], &hd[(ad.vel - h->adam_dev.p) + (size_t)j * gw], sizeof(double) * gw);
-      best[i] = hd[(ad.best - h->adam_dev.p) + j];
-      loss[i] = hd[(ad.loss - h->adam_dev.p) + j];
-      stale[i] = hi[j];
-      n_evals[i] = hi[2 * (size_t)na + j];
+      std::memcpy(&mom[(size_t)i * gw], &hd[rs.o_mom + (size_t)j * gw], sizeof(double) * gw);
+      std::memcpy(&vel[(size_t)i * gw], &hd[rs.o_vel + (size_t)j * gw], sizeof(double) * gw);
+      best[i] = hd[rs.o_best + j];
+      loss[i] = hd[rs.o_loss + j];
+      stale[i] = hi[rs.o_stale + j];
+      n_evals[i] = hi[rs.o_n_evals + j];
       std::memcpy(z + (size_t)i * nz, &zc[(size_t)j * nz], sizeof(double) * nz);
-      if (hi[(size_t)na + j] != 0) next.push_back(i);
+      if (hi[rs.o_active + j] != 0) next.push_back(i);
     }
     active.swap(next);
   }
   if (losses)
     for (int c = 0; c < count; ++c) losses[c] = loss[c];
-  if (batches) {
-    int mx = 0;
-    for (int c = 0; c < count; ++c) mx = std::max(mx, n_evals[c]);
-    *batches = mx;
-  }
-  if (error_cell >= 0) {
-    char msg[160];
-    snprintf(msg, sizeof msg, "cell %d: Kuu or B not positive definite", error_cell);
-    return fail(h, GPRX_ENOTPD, msg);
-  }
-  return GPRX_OK;
+  return resident_finish(h, count, n_evals, batches, error_cell);
 }
 
 int check_handle(gprx_handle h) {
@@ -2188,10 +2201,9 @@ static int optimizer_batch(gprx_handle h, int kind, int count, const int* units,
     for (int64_t e = 0; e < (int64_t)count * nz; ++e)
       if (!std::isfinite(z[e])) return fail(h, GPRX_EINVAL, "z is not finite");
     h->last_route = sgpr_five_launches(h) ? 1 : 2;
-    return (sgpr_five_launches(h) ? sgpr_adam_resident : sgpr_resident_general)(h, kind, count, units, theta, z, mask, max_iter, last_losses, n_evals,
-                                                                                  batches);
+    return (sgpr_five_launches(h) ? sgpr_resident_fused : sgpr_resident_general)(h, kind, count, units, theta, z, mask, max_iter, last_losses, n_evals,
+                                                                                   batches);
   }
-  const double lr = ADAM_LR, beta1 = ADAM_BETA1, beta2 = ADAM_BETA2;
   std::vector<double> mom((size_t)count * gw, 0.0), vel((size_t)count * gw, 0.0), best(count, std::numeric_limits<double>::infinity());
   std::vector<int> stale(count, 0), active(count);
   for (int i = 0; i < count; ++i) active[i] = i;
@@ -2211,7 +2223,7 @@ static int optimizer_batch(gprx_handle h, int kind, int count, const int* units,
     if (last_losses)  // (a failed cell holds NaN; after any other error the evaluation wrote no loss)
       for (int j = 0; j < na; ++j) last_losses[active[j]] = (rc == GPRX_OK || rc == GPRX_ENOTPD) ? losses[j] : std::numeric_limits<double>::quiet_NaN();
     if (rc) return rc;  // (GPRX_ENOTPD included: the reference's optimiser dies with the exception of that evaluation)
-    const double alpha = adam ? lr * std::sqrt(1.0 - std::pow(beta2, (double)t)) / (1.0 - std::pow(beta1, (double)t)) : 0.0;
+    const double alpha = adam ? adam_alpha((double)t) : 0.0;
     std::vector<int> next;
     next.reserve(na);
     for (int j = 0; j < na; ++j) {

@@ -1,5 +1,6 @@
 // Device code shared by the one-workgroup-per-cell launches of the fused sparse evaluation (sf_cell.hip: prep, mid, final; sf_adam.hip: the
-// merged Adam + prep launch of the resident optimiser).  Kernel-free.
+// merged Adam + prep launch of the resident optimiser), and the optimiser step that this launch shares with the step kernel of the
+// general launch sequence (sgpr_step.hip).  Kernel-free.
 #pragma once
 #include "sgpr_asm.h"
 #include "sgpr_fused_dev.h"
@@ -121,14 +122,86 @@ __device__ __forceinline__ void sf_reduce_sums(const SfParams& p, const double* 
   if (tid >= 128 && tid < 128 + width) sums[width + (tid - 128)] = 0.0;  // (the Kuu terms are inside the chunks' blocks since the slicing of pass 2)
 }
 
+// ---- one step of a resident optimiser loop for one cell: the parts that the fused route (sf_adam_body below) and the general launch
+// sequence (sgpr_step_kernel, sgpr_step.hip) share, so that both run the same operations in the same order.  The Z loops stay with
+// their routes: the gradient comes from the chunk sums in one and from the scaled dZ in the other. ---------------------------------
+// OPT (sgpr_asm.h): SF_OPT_ADAM runs Keras's Adam update with the step's alpha; SF_OPT_ADADELTA runs Keras's Adadelta update
+// (gpr.py:176-192) -- its two accumulators live in mo / ve, alpha is not read.
+template <int OPT>
+__device__ __forceinline__ void opt_element(double g, double alpha, double& mo, double& ve, double& x) {
+  if constexpr (OPT == SF_OPT_ADAM)
+    adam_element(g, alpha, mo, ve, x);
+  else
+    adadelta_element(g, mo, ve, x);
+}
+
+// thread k < ad.nt: the derivative w.r.t. hyperparameter k (mp: the padded M of the evaluation), the chain rule through softplus with the
+// prior, and the update of variable k in the cell's th / mom / vel rows when the mask trains it.  Returns the variable after the update.
+template <int OPT>
+__device__ __forceinline__ double opt_step_hyper(const SfAdam& ad, int k, int mask, double alpha, int d, int width, double nn, int mp,
+                                                 double variance, double noise, const double* ls, const double* sred, const double* shs,
+                                                 double* th, double* mom, double* vel) {
+  const double du = sgpr_asm_dparam(k, ad.nlen, ad.ard, d, width, nn, mp, variance, noise, sred, shs);
+  double u, w = th[k];
+  bool trainable;
+  if (k == 0) {
+    u = variance;
+    trainable = (mask & ASM_TRAIN_VARIANCE) != 0;
+  } else if (k < ad.nt - 1) {
+    u = ls[k - 1];
+    trainable = (mask & ASM_TRAIN_LENGTHSCALE) != 0;
+  } else {
+    u = noise;
+    trainable = (mask & ASM_TRAIN_NOISE) != 0;
+  }
+  const double ge = sgpr_asm_chain(du, u, w, trainable);
+  if (trainable) {
+    double mo = mom[k], ve = vel[k];
+    opt_element<OPT>(ge, alpha, mo, ve, w);
+    mom[k] = mo;
+    vel[k] = ve;
+    th[k] = w;
+  }
+  return w;
+}
+
+// thread 255: ELBO, the priors in log_prior's order, the loss, the stop rule (Adam; an Adadelta cell runs exactly max_iter steps: best /
+// stale stay untouched) and the counters of step t.  Returns whether the cell keeps running.
+template <int OPT>
+__device__ __forceinline__ bool opt_step_close(const SfAdam& ad, int cell, int t, int mask, int max_iter, double nn, double variance, double noise,
+                                               const double* ls, const double* sred) {
+  const double elbo = sgpr_asm_elbo(nn, ad.yy[ad.units[cell]], variance, noise, sred);
+  double lp = 0.0;
+  {
+#pragma clang fp contract(off)
+    if (mask & ASM_TRAIN_VARIANCE) lp += px_ln_logpdf(variance);
+    if (mask & ASM_TRAIN_LENGTHSCALE)
+      for (int k = 0; k < ad.nlen; ++k) lp += px_ln_logpdf(ls[k]);
+    if (mask & ASM_TRAIN_NOISE) lp += px_ln_logpdf(noise);
+  }
+  const double loss = -(elbo + lp);
+  bool go = t < max_iter;
+  if constexpr (OPT == SF_OPT_ADAM) {
+    double best = ad.best[cell];
+    int stale = ad.stale[cell];
+    go = adam_keep_running(loss, best, stale) && go;
+    ad.best[cell] = best;
+    ad.stale[cell] = stale;
+  }
+  ad.loss[cell] = loss;
+  ad.n_evals[cell] += 1;
+  ad.tstep[cell] = t;
+  if (!go) ad.active[cell] = 0;
+  return go;
+}
+
 // ---- one step of the resident Adam loop for one cell ---------------------------------------------------------------------------
 // What sgpr_objective_batch's host tail, chain_rule, log_prior and gprx_adam_batch's host loop do for one cell and one step, in their
 // order and with their arithmetic (sgpr_asm.h): the same variables after every step, bit for bit.  shs [2 width], sred [8]: LDS scratch.
 // sTh (nt) and sZnew (m d), when given, receive the variables after the update (LDS: the merged launch goes on to the next step's
 // Kuu from them).  Returns through *keep (LDS int, written by thread 255) whether the cell keeps running.  Every thread must call it;
 // it contains one __syncthreads().
-// OPT (sgpr_asm.h): SF_OPT_ADAM as above; SF_OPT_ADADELTA runs Keras's Adadelta update (gpr.py:176-192) instead -- its two accumulators
-// live in mom / vel, no alpha table is read, the cell runs exactly max_iter steps (best / stale stay untouched).
+// OPT: SF_OPT_ADAM as above; SF_OPT_ADADELTA reads no alpha table and keeps its two accumulators in mom / vel (opt_element, opt_step_close).
 template <int ISO, int OPT = SF_OPT_ADAM>
 __device__ __forceinline__ void sf_adam_body(const SfParams& p, const SfAdam& ad, int cell, int tid, double* __restrict__ shs, double* __restrict__ sred,
                                              double* __restrict__ sTh, double* __restrict__ sZnew, int* __restrict__ keep) {
@@ -151,32 +224,8 @@ __device__ __forceinline__ void sf_adam_body(const SfParams& p, const SfAdam& ad
   double* mom = ad.mom + (int64_t)cell * gw;
   double* vel = ad.vel + (int64_t)cell * gw;
   if (tid < nt) {
-    const int k = tid;
-    const double du = sgpr_asm_dparam(k, ad.nlen, ad.ard, p.d, width, nn, NB, variance, noise, sred, shs);
-    double u, w = th[k];
-    bool trainable;
-    if (k == 0) {
-      u = variance;
-      trainable = (ad.mask & ASM_TRAIN_VARIANCE) != 0;
-    } else if (k < nt - 1) {
-      u = ls[k - 1];
-      trainable = (ad.mask & ASM_TRAIN_LENGTHSCALE) != 0;
-    } else {
-      u = noise;
-      trainable = (ad.mask & ASM_TRAIN_NOISE) != 0;
-    }
-    const double ge = sgpr_asm_chain(du, u, w, trainable);
-    if (trainable) {
-      double mo = mom[k], ve = vel[k];
-      if constexpr (OPT == SF_OPT_ADAM)
-        adam_element(ge, alpha, mo, ve, w);
-      else
-        adadelta_element(ge, mo, ve, w);
-      mom[k] = mo;
-      vel[k] = ve;
-      th[k] = w;
-    }
-    if (sTh) sTh[k] = w;
+    const double w = opt_step_hyper<OPT>(ad, tid, ad.mask, alpha, p.d, width, nn, NB, variance, noise, ls, sred, shs, th, mom, vel);
+    if (sTh) sTh[tid] = w;
   }
   const bool train_z = (ad.mask & ASM_TRAIN_Z) != 0;
   if (train_z || sZnew) {
@@ -198,10 +247,7 @@ __device__ __forceinline__ void sf_adam_body(const SfParams& p, const SfAdam& ad
         if (e < nz) {
           if (train_z) {
             const double ge = -(acc[u] / ls[e % p.d]);
-            if constexpr (OPT == SF_OPT_ADAM)
-              adam_element(ge, alpha, mo[u], ve[u], x[u]);
-            else
-              adadelta_element(ge, mo[u], ve[u], x[u]);
+            opt_element<OPT>(ge, alpha, mo[u], ve[u], x[u]);
             mom[nt + e] = mo[u];
             vel[nt + e] = ve[u];
             A[p.oZ + e] = x[u];
@@ -212,28 +258,7 @@ __device__ __forceinline__ void sf_adam_body(const SfParams& p, const SfAdam& ad
     }
   }
   if (tid == 255) {  // (a thread with no hyperparameter of its own)
-    const double elbo = sgpr_asm_elbo(nn, ad.yy[ad.units[cell]], variance, noise, sred);
-    double lp = 0.0;
-    {
-#pragma clang fp contract(off)
-      if (ad.mask & ASM_TRAIN_VARIANCE) lp += px_ln_logpdf(variance);
-      if (ad.mask & ASM_TRAIN_LENGTHSCALE)
-        for (int k = 0; k < ad.nlen; ++k) lp += px_ln_logpdf(ls[k]);
-      if (ad.mask & ASM_TRAIN_NOISE) lp += px_ln_logpdf(noise);
-    }
-    const double loss = -(elbo + lp);
-    bool go = t < ad.max_iter;
-    if constexpr (OPT == SF_OPT_ADAM) {
-      double best = ad.best[cell];
-      int stale = ad.stale[cell];
-      go = adam_keep_running(loss, best, stale) && go;
-      ad.best[cell] = best;
-      ad.stale[cell] = stale;
-    }
-    ad.loss[cell] = loss;
-    ad.n_evals[cell] += 1;
-    ad.tstep[cell] = t;
-    if (!go) ad.active[cell] = 0;
+    const bool go = opt_step_close<OPT>(ad, cell, t, ad.mask, ad.max_iter, nn, variance, noise, ls, sred);
     if (keep) *keep = go ? 1 : 0;
   }
 }

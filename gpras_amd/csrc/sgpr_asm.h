@@ -49,6 +49,11 @@ GPRX_HD void adam_element(double ge, double alpha, double& mo, double& ve, doubl
   ve = ADAM_BETA2 * ve + ((1.0 - ADAM_BETA2) * ge) * ge;
   x = x - (alpha * mo) / (sqrt(ve) + ADAM_EPS);
 }
+// alpha of step t = 1, 2, ..: host only (its pow), the one expression behind the host-stepped loop and the resident loops' tables
+inline double adam_alpha(double t) {
+#pragma clang fp contract(off)
+  return ADAM_LR * std::sqrt(1.0 - std::pow(ADAM_BETA2, t)) / (1.0 - std::pow(ADAM_BETA1, t));
+}
 // the early-stop rule of gpr.py:160-171: returns whether the cell keeps running
 GPRX_HD bool adam_keep_running(double loss, double& best, int& stale) {
 #pragma clang fp contract(off)

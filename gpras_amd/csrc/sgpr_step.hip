@@ -1,8 +1,9 @@
 // Resident optimiser loop of the general sparse launch sequence: the step kernel (sgpr_step.h), one instantiation per optimiser.
 // Sibling of sf_adam_body (sf_cell_dev.h), which serves the fused evaluation: same thread assignment (thread k owns hyperparameter k,
-// thread 255 the loss and the stop rule, four Z elements per thread and pass), same functions in the same order.  What differs is where
-// the evaluation left its results: the trace sums come from the contraction partials (sgpr_trace_sums, shared with
-// sgpr_stage_out_kernel), dZ is already scaled (dz_kernel), and sgpr_asm_dparam gets the padded M of the launch sequence (mp).
+// thread 255 the loss and the stop rule, four Z elements per thread and pass), and the same code for both (opt_step_hyper,
+// opt_step_close, opt_element of sf_cell_dev.h).  What differs is where the evaluation left its results: the trace sums come from the
+// contraction partials (sgpr_trace_sums, shared with sgpr_stage_out_kernel), dZ is already scaled (dz_kernel), and sgpr_asm_dparam gets
+// the padded M of the launch sequence (mp).
 #include "sgpr_step.h"
 #include "sf_cell_dev.h"
 #include "sgpr_small_ops.h"
@@ -45,30 +46,7 @@ __global__ __launch_bounds__(256) void sgpr_step_kernel(SgprStep a, SfAdam ad) {
   double* vel = ad.vel + (int64_t)cell * gw;
   if (tid < nt) {
     const int k = tid;
-    const double du = sgpr_asm_dparam(k, ad.nlen, ad.ard, a.d, width, nn, a.mp, variance, noise, sred, shs);
-    double u, w = th[k];
-    bool trainable;
-    if (k == 0) {
-      u = variance;
-      trainable = (mask & ASM_TRAIN_VARIANCE) != 0;
-    } else if (k < nt - 1) {
-      u = ls[k - 1];
-      trainable = (mask & ASM_TRAIN_LENGTHSCALE) != 0;
-    } else {
-      u = noise;
-      trainable = (mask & ASM_TRAIN_NOISE) != 0;
-    }
-    const double ge = sgpr_asm_chain(du, u, w, trainable);
-    if (trainable) {
-      double mo = mom[k], ve = vel[k];
-      if constexpr (OPT == SF_OPT_ADAM)
-        adam_element(ge, alpha, mo, ve, w);
-      else
-        adadelta_element(ge, mo, ve, w);
-      mom[k] = mo;
-      vel[k] = ve;
-      th[k] = w;
-    }
+    const double w = opt_step_hyper<OPT>(ad, k, mask, alpha, a.d, width, nn, a.mp, variance, noise, ls, sred, shs, th, mom, vel);
     sTh[k] = w;
   }
   if ((mask & ASM_TRAIN_Z) != 0) {
@@ -86,10 +64,7 @@ __global__ __launch_bounds__(256) void sgpr_step_kernel(SgprStep a, SfAdam ad) {
       for (int u = 0; u < 4; ++u) {
         const int e = e0 + 256 * u + tid;
         if (e < nz) {
-          if constexpr (OPT == SF_OPT_ADAM)
-            adam_element(ge[u], alpha, mo[u], ve[u], x[u]);
-          else
-            adadelta_element(ge[u], mo[u], ve[u], x[u]);
+          opt_element<OPT>(ge[u], alpha, mo[u], ve[u], x[u]);
           mom[nt + e] = mo[u];
           vel[nt + e] = ve[u];
           A[a.oZ + e] = x[u];
@@ -97,31 +72,7 @@ __global__ __launch_bounds__(256) void sgpr_step_kernel(SgprStep a, SfAdam ad) {
       }
     }
   }
-  if (tid == 255) {  // (a thread with no hyperparameter of its own)
-    const double elbo = sgpr_asm_elbo(nn, ad.yy[ad.units[cell]], variance, noise, sred);
-    double lp = 0.0;
-    {
-#pragma clang fp contract(off)
-      if (mask & ASM_TRAIN_VARIANCE) lp += px_ln_logpdf(variance);
-      if (mask & ASM_TRAIN_LENGTHSCALE)
-        for (int k = 0; k < ad.nlen; ++k) lp += px_ln_logpdf(ls[k]);
-      if (mask & ASM_TRAIN_NOISE) lp += px_ln_logpdf(noise);
-    }
-    const double loss = -(elbo + lp);
-    bool go = t < max_iter;
-    if constexpr (OPT == SF_OPT_ADAM) {
-      double best = ad.best[cell];
-      int stale = ad.stale[cell];
-      go = adam_keep_running(loss, best, stale) && go;
-      ad.best[cell] = best;
-      ad.stale[cell] = stale;
-    }
-    ad.loss[cell] = loss;
-    ad.n_evals[cell] += 1;
-    ad.tstep[cell] = t;
-    if (!go) ad.active[cell] = 0;
-    keep = go ? 1 : 0;
-  }
+  if (tid == 255) keep = opt_step_close<OPT>(ad, cell, t, mask, max_iter, nn, variance, noise, ls, sred) ? 1 : 0;  // (a thread with no hyperparameter of its own)
   __syncthreads();  // (sTh and keep are complete; every read of this step's parameter row went through sPar)
   if (keep == 0) return;
   // ---- opens step t + 1: the parameter row of the updated variables (decode_theta's bits), the result words cleared; y stays in the

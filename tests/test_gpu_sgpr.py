@@ -276,7 +276,7 @@ def test_sparse_batch_failed_cell_is_isolated_and_leaves_no_trace(lib, m):
 
 
 def test_resident_adam_reports_a_cell_that_stops_being_positive_definite(lib):
-    """gprx_adam_batch on sparse models with M <= 64 runs resident on the device (gprx.hip sgpr_adam_resident); a cell whose Kuu is
+    """gprx_adam_batch on sparse models with M <= 64 runs resident on the device (gprx.hip sgpr_resident_fused); a cell whose Kuu is
     numerically singular from the first step on ends the call with GPRX_ENOTPD at the first read of the stop flags, names the cell,
     leaves the other cells' variables finite, and the handle serves a clean run afterwards (same result as a run that never failed)."""
     import ctypes as C

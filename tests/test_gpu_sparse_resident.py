@@ -184,6 +184,43 @@ def test_replayed_steps_equal_eager_and_captured_ones(lib, opt):
     assert not np.array_equal(out[0][1], thetas) and not np.array_equal(out[0][2], zs)
 
 
+# ---- 4b. both resident routes alternating on one handle ----------------------------------------------------------------------------
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("opt", ["adam", "adadelta"])
+def test_both_resident_routes_alternate_on_one_handle(lib, opt):
+    """The two resident loops share one state-block layout and one pinned block on a handle.  M = 17 with "sgpr_fused" = 0: three cells
+    twice on route 2 (the second call replays the captured step); "sgpr_fused" = 1: nineteen cells on route 1, a larger state block,
+    so it is reallocated and the captured steps are dropped; "sgpr_fused" = 0 again: the three cells on route 2.  The last route-2
+    result equals the first and the route-1 result equals the same call on a fresh handle, bit for bit."""
+    case = dict(ONE_TILE, cells=19)
+    x, y, thetas, zs, units, *_ = draw_inputs(case, units=3)
+    few = (units[:3].copy(), thetas[:3].copy(), zs[:3].copy())
+    h = make_handle(lib, case, x, y)
+    try:
+        check(lib.gprx_set_handle_tuning(h, b"sgpr_fused", 0), h)
+        general = [run_library(lib, h, opt, *few, ALL, 26) for _ in range(2)]
+        check(lib.gprx_set_handle_tuning(h, b"sgpr_fused", 1), h)
+        fused = run_library(lib, h, opt, units, thetas, zs, ALL, 26)
+        check(lib.gprx_set_handle_tuning(h, b"sgpr_fused", 0), h)
+        general.append(run_library(lib, h, opt, *few, ALL, 26))
+    finally:
+        lib.gprx_destroy(h)
+    h = make_handle(lib, case, x, y)
+    try:
+        fresh = run_library(lib, h, opt, units, thetas, zs, ALL, 26)
+    finally:
+        lib.gprx_destroy(h)
+    for r in general:
+        assert r[0] == _lib.GPRX_OK and r[6] == 2
+    for r in (fused, fresh):
+        assert r[0] == _lib.GPRX_OK and r[6] == 1
+    assert same_bits(general[0], general[1]) and same_bits(general[0], general[2])
+    assert same_bits(fused, fresh)
+    assert not np.array_equal(general[0][1], few[1]) and not np.array_equal(fused[2], zs)
+
+
 # ---- 5. a cell that is not positive definite ----------------------------------------------------------------------------------------
 
 
