@@ -123,6 +123,13 @@ PROTOTYPES = {
     "gprx_ps_surface_dev": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _vp, _i64]),
     "gprx_ps_synchronize": (C.c_int, [_vp]),
     "gprx_pca_slab_rows": (C.c_int, [_vp, C.POINTER(_i64)]),
+    "gprx_rs_create": (C.c_int, [C.c_int, _i64, _i64, C.c_int, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "gprx_rs_destroy": (C.c_int, [_vp]),
+    "gprx_rs_last_error": (C.c_char_p, [_vp]),
+    "gprx_rs_apply": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
+    "gprx_rs_apply_dev": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64]),
+    "gprx_rs_synchronize": (C.c_int, [_vp]),
+    "gprx_rs_timings": (C.c_int, [_vp, _dp]),
     "gprx_metrics": (C.c_int, [C.c_int, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_double, _vp, _vp, _vp, C.POINTER(C.c_uint64)]),
     "gprx_metrics_dev": (C.c_int, [C.c_int, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_double, _vp, _vp, _vp, C.POINTER(C.c_uint64)]),
     "gprx_kmeans_pp": (C.c_int, [C.c_int, _vp, _i64, C.c_int, _vp, C.c_int, C.c_int, _i64, _vp, _vp]),

@@ -64,6 +64,7 @@ typedef struct gprx_pca_ctx* gprx_pca_handle;
 typedef struct gprx_pcafit_ctx* gprx_pcafit_handle;
 typedef struct gprx_hms_ctx* gprx_hms_handle;
 typedef struct gprx_ps_ctx* gprx_ps_handle;
+typedef struct gprx_rs_ctx* gprx_rs_handle;
 typedef struct gprx_comm_ctx* gprx_comm;
 
 /* ---- library / device -------------------------------------------------------------- */
@@ -479,6 +480,36 @@ int gprx_ps_synchronize(gprx_ps_handle h);
 /* rows per device pass of gprx_pca_transform (the split-K plan of gprx_pca_transform_dev depends on the rows of a call, so a
  * caller of the _dev entry that wants the bits of gprx_pca_transform cuts its rows into the same slabs) */
 int gprx_pca_slab_rows(gprx_pca_handle p, int64_t* rows);
+
+/* ---- LF-to-HF mesh resampling: gpras/preprocess.py:163-174, :363-377, :433-451 ---------------------
+ * The low-fidelity field on the high-fidelity cells of the two "Upskill HEC-RAS" builders, from a (T, n_src) output block of the
+ * plan to (T, n_out).
+ *   n_vert = 1 (RasUpskillDataBuilder, :363-377; get_hf_plan_data's gather, :173): idx (n_out) = lf_resampler / hf_resampler,
+ *     out[t, j] = src[t, idx[j]]; with elev (n_out) = cell_elevations the result is floored, v < elev[j] ? elev[j] : v
+ *     (:375-376: a NaN value stays, a NaN elevation never wins); weights must be NULL.
+ *   n_vert = 3 (RasInterpolaterBuilder, :433-451): idx (n_out, 3) the vertices of the simplex that holds each point, as columns of
+ *     src, weights (n_out, 3) its barycentric coordinates c; acc = ((0.0 + c0 z0) + c1 z1) + c2 z2, the operations of scipy's
+ *     LinearNDInterpolator in their order.  With elev: out = (acc < elev || acc != acc) ? elev : acc (:449-450); without: acc.
+ *     A point outside the hull (find_simplex == -1) has idx (-1, -1, -1): its acc is NaN whatever the weights say.
+ * Every index lies in [0, n_src) or the call returns GPRX_EINVAL, as it does for another n_vert, n_src outside [1, 2^28] (a
+ * cell's byte offset in its row is a 32-bit number on the device), n_out outside [1, 2^31 - 1024) and weights that do not go
+ * with n_vert.  Not enough device memory: GPRX_ENOMEM before anything is allocated. */
+int gprx_rs_create(int device, int64_t n_src, int64_t n_out, int n_vert, const int32_t* idx, const double* weights, const double* elev,
+                   gprx_rs_handle* out);
+int gprx_rs_destroy(gprx_rs_handle h);
+const char* gprx_rs_last_error(gprx_rs_handle h);
+/* get_lf_plan_data (:363-377, :433-451) on host arrays: src (T, n_src) -> out (T, n_out), staged in row slabs (device memory
+ * does not grow with T).  src2 (T, n_src) or NULL: given, out = sqrt(vx vx + vy vy) of the two gathered operands, the velocity
+ * magnitude of :367-373, which has no floor: it needs an n_vert = 1 handle without elevations (GPRX_EINVAL otherwise). */
+int gprx_rs_apply(gprx_rs_handle h, const double* src, const double* src2, int64_t T, double* out);
+/* The same for `rows` rows on device buffers: src_dev / src2_dev (rows, lds), lds >= n_src; out_dev (rows, ldo), ldo >= n_out
+ * (GPRX_EINVAL otherwise, as for rows outside [0, 2^31 - 1024); the handle stays usable).  Columns [n_out, ldo) of out are set to 0, so that out_dev can be the padded
+ * input of gprx_pca_transform_dev.  out_dev must not overlap the sources.  Asynchronous on the handle's stream:
+ * gprx_rs_synchronize before another handle reads out_dev. */
+int gprx_rs_apply_dev(gprx_rs_handle h, int64_t rows, const double* src_dev, int64_t lds, const double* src2_dev, double* out_dev, int64_t ldo);
+int gprx_rs_synchronize(gprx_rs_handle h);
+/* device milliseconds of the kernel of the last gprx_rs_apply_dev (waits for the handle's stream); 0 when none has run */
+int gprx_rs_timings(gprx_rs_handle h, double* ms);
 
 /* ---- fused error metrics over two fields: SURVEY.md section 8(f) row N3 (gpras/metrics.py:85-318) ---------- */
 /* Two streaming passes over x (truth), y (prediction) and conf (may be NULL), each (rows, cells) row-major, yield every
