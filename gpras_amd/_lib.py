@@ -16,7 +16,7 @@ import os
 # (GPRX_LIBRARY: another build of the same library, e.g. an experiment compiled with -D flags -- development A/B runs only)
 LIB_PATH = Path(os.environ["GPRX_LIBRARY"]) if os.environ.get("GPRX_LIBRARY") else Path(__file__).resolve().parent / "libgprx.so"
 
-GPRX_OK, GPRX_EINVAL, GPRX_ENOTPD, GPRX_EHIP, GPRX_ENOMEM, GPRX_ESTATE, GPRX_ERCCL = range(7)
+GPRX_OK, GPRX_EINVAL, GPRX_ENOTPD, GPRX_EHIP, GPRX_ENOMEM, GPRX_ESTATE, GPRX_ERCCL, GPRX_ENOCONV = range(8)
 UNIQUE_ID_BYTES = 128
 TRAIN_VARIANCE, TRAIN_LENGTHSCALE, TRAIN_NOISE, TRAIN_Z = 1, 2, 4, 8
 GEMM_C_LOWER, GEMM_A_LOWER, GEMM_A_UPPER, GEMM_B_LOWER, GEMM_B_UPPER = 1, 2, 4, 8, 16
@@ -98,7 +98,16 @@ PROTOTYPES = {
     "gprx_pcafit_gram": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_i64)]),
     "gprx_pcafit_components": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
     "gprx_pcafit_timings": (C.c_int, [_vp, _dp]),
+    "gprx_pcafit_eig": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_i64), _ip]),
+    "gprx_pcafit_components_dev": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "gprx_pcafit_eig_ms": (C.c_int, [_vp, _dp]),
     "gprx_pcafit_destroy": (C.c_int, [_vp]),
+    "gprx_eigh_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(_vp)]),
+    "gprx_eigh": (C.c_int, [_vp, C.c_int, _vp, _i64, _vp, _vp]),
+    "gprx_eigh_dev": (C.c_int, [_vp, C.c_int, _vp, _i64, _vp, _vp, _i64]),
+    "gprx_eigh_info": (C.c_int, [_vp, _ip, _dp]),
+    "gprx_eigh_destroy": (C.c_int, [_vp]),
+    "gprx_eigh_last_error": (C.c_char_p, [_vp]),
     "gprx_pcafit_last_error": (C.c_char_p, [_vp]),
     "gprx_hms_create": (C.c_int, [C.c_int, _vp, _i64, _i64, _i64, C.c_int, _vp, _i64, _vp, _i64, _vp, C.POINTER(_vp)]),
     "gprx_hms_cov": (C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_int)]),
@@ -192,6 +201,8 @@ def check(rc: int, handle=None) -> None:
         raise ValueError(msg)
     if rc == GPRX_ENOTPD:
         raise np.linalg.LinAlgError(msg)  # tensorflow raises InvalidArgumentError from Cholesky here
+    if rc == GPRX_ENOCONV:
+        raise np.linalg.LinAlgError(msg)  # numpy.linalg.eigh: "Eigenvalues did not converge"
     if rc == GPRX_ENOMEM:
         raise MemoryError(msg)
     raise RuntimeError(f"libgprx error {rc}: {msg}")

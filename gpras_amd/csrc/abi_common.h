@@ -105,6 +105,14 @@ inline int64_t pca_chunk_doubles() {
 // dst (cols, rows) <- src (rows, cols)^T on `st` (pca.h transpose_small_kernel; defined in abi_eof.hip, the unit that holds pca.h)
 void launch_transpose_small(hipStream_t st, const double* src, int64_t rows, int64_t cols, double* dst);
 
+// The symmetric eigensolver (eig_jacobi.h; defined in abi_eig.hip, the unit that holds its kernels), all pointers on the device:
+// A (n, lda) symmetric, lower triangle read, overwritten; V (n, ldv) eigenvectors in columns; lam (n) ascending; workspace of
+// eig_jacobi_workspace_bytes(n).  Waits for `st` once per sweep.  GPRX_OK, GPRX_ENOCONV (30 sweeps, or a non-finite matrix) or a HIP
+// status, the text in *err.
+size_t eig_jacobi_workspace_bytes(int n);
+int eig_jacobi_run(hipStream_t st, int n, double* A, int64_t lda, double* V, int64_t ldv, double* lam, void* workspace, int* sweeps, double* off_rel,
+                   std::string* err);
+
 // Device temporaries of one call, named where they are declared.  When the scope ends, on every path: the stream that may still
 // read them is synchronised, then the non-null ones are freed.
 struct DevTemps {

@@ -239,6 +239,10 @@ struct gprx_pcafit_ctx {
   hipStream_t stream = nullptr;
   int64_t rows = 0, rows_p = 0, cells = 0, n_wet = 0, ldc = 0;  // ldc: leading dimension of the compacted matrices (multiple of 16)
   double *xc1 = nullptr, *xc2 = nullptr, *A = nullptr, *E = nullptr, *Z = nullptr;
+  double *G = nullptr;                                    // the Gram matrix, inside ws
+  double *U = nullptr, *lam = nullptr, *eig_ws = nullptr;  // device eigensolver: eigenvectors (rows, rows), ascending eigenvalues, workspace
+  std::vector<double> lam_h;                               // the eigenvalues, descending (empty before gprx_pcafit_eig)
+  double eig_ms = 0.0;
   Buf ws;  // split-K slabs, then their sum
   std::vector<unsigned char> cls;    // wetness class per cell
   std::vector<double> mean, gram;    // input_mean over the wet cells, G (rows, rows)
@@ -340,15 +344,13 @@ int pcafit_run(gprx_pcafit_handle f, const double* x, const double* elevations, 
   const int nsplit = (int)((ldc + kchunk - 1) / kchunk);
   int rc;
   if ((rc = ensure(f, f->ws, sizeof(double) * ((size_t)nsplit * rows * rows + (size_t)rows * rows)))) return rc;
-  double* G = f->ws.p + (size_t)nsplit * rows * rows;
+  double* G = f->G = f->ws.p + (size_t)nsplit * rows * rows;
   GemmArgs p{f->xc2, f->xc2, f->ws.p, ldc, ldc, (int64_t)n, n, n, (int)ldc, 1.0, 0.0, GEMM_C_LOWER, 0, 0, 0, 0, 0, 0, kchunk, (int64_t)n * n};
   HIPCHK(f, (launch_gemm_t<0, 1, 64, 64>(st, p, 1, nsplit)));
   hipLaunchKernelGGL(pcafit_gram_reduce_kernel, dim3((unsigned)(((int64_t)n * n + 255) / 256)), dim3(256), 0, st, (const double*)f->ws.p, nsplit, n, G);
   HIPCHK(f, hipGetLastError());
   HIPCHK(f, hipEventRecord(f->ev[5], st));
-  f->gram.resize((size_t)rows * rows);
-  HIPCHK(f, hipMemcpyAsync(f->gram.data(), G, sizeof(double) * rows * rows, hipMemcpyDeviceToHost, st));
-  HIPCHK(f, hipStreamSynchronize(st));
+  HIPCHK(f, hipStreamSynchronize(st));  // G stays on the device: gprx_pcafit_gram fetches it on its first call
   f->ms[0] = elapsed_ms(f->ev[0], f->ev[1]);
   f->ms[1] = elapsed_ms(f->ev[1], f->ev[2]);
   f->ms[2] = elapsed_ms(f->ev[3], f->ev[4]);
@@ -356,23 +358,22 @@ int pcafit_run(gprx_pcafit_handle f, const double* x, const double* elevations, 
   return GPRX_OK;
 }
 
-int pcafit_components(gprx_pcafit_handle f, int k, const double* u, const double* lam, double* eofs, double* z) {
-  const int64_t rows = f->rows, rp = f->rows_p, ldc = f->ldc;
-  hipStream_t st = f->stream;
-  // A = diag(lambda^-1/2) U_k^T, K padded to rows_p with zeros
-  std::vector<double> a((size_t)k * rp, 0.0);
-  for (int i = 0; i < k; ++i) {
-    const double s = 1.0 / std::sqrt(lam[i]);
-    for (int64_t t = 0; t < rows; ++t) a[(size_t)i * rp + t] = u[(size_t)t * k + i] * s;
-  }
+// the blocks of the components step: A (k, rows_p), E (k, ldc), Z (rows, k)
+int pcafit_components_alloc(gprx_pcafit_handle f, int k) {
   if (f->A) HIPCHK(f, hipFree(f->A));
   if (f->E) HIPCHK(f, hipFree(f->E));
   if (f->Z) HIPCHK(f, hipFree(f->Z));
   f->A = f->E = f->Z = nullptr;
-  HIPCHK(f, hipMalloc((void**)&f->A, sizeof(double) * a.size()));
-  HIPCHK(f, hipMalloc((void**)&f->E, sizeof(double) * (size_t)k * ldc));
-  HIPCHK(f, hipMalloc((void**)&f->Z, sizeof(double) * (size_t)rows * k));
-  HIPCHK(f, hipMemcpyAsync(f->A, a.data(), sizeof(double) * a.size(), hipMemcpyHostToDevice, st));
+  HIPCHK(f, hipMalloc((void**)&f->A, sizeof(double) * (size_t)k * f->rows_p));
+  HIPCHK(f, hipMalloc((void**)&f->E, sizeof(double) * (size_t)k * f->ldc));
+  HIPCHK(f, hipMalloc((void**)&f->Z, sizeof(double) * (size_t)f->rows * k));
+  return GPRX_OK;
+}
+
+// steps 5 and 6 from A = diag(lambda^-1/2) U_k^T on the device (K padded to rows_p with zeros)
+int pcafit_project(gprx_pcafit_handle f, int k, double* eofs, double* z) {
+  const int64_t rows = f->rows, rp = f->rows_p, ldc = f->ldc;
+  hipStream_t st = f->stream;
   const int tiles_m = (int)((rows + 63) / 64);
   const int kchunk = pcafit_kchunk(tiles_m * ((k + 63) / 64), ldc, rows * k);
   const int nsplit = (int)((ldc + kchunk - 1) / kchunk);
@@ -395,11 +396,48 @@ int pcafit_components(gprx_pcafit_handle f, int k, const double* u, const double
   f->ms[5] = elapsed_ms(f->ev[6], f->ev[7]);
   return GPRX_OK;
 }
+
+int pcafit_components(gprx_pcafit_handle f, int k, const double* u, const double* lam, double* eofs, double* z) {
+  const int64_t rows = f->rows, rp = f->rows_p;
+  // A = diag(lambda^-1/2) U_k^T, K padded to rows_p with zeros
+  std::vector<double> a((size_t)k * rp, 0.0);
+  for (int i = 0; i < k; ++i) {
+    const double s = 1.0 / std::sqrt(lam[i]);
+    for (int64_t t = 0; t < rows; ++t) a[(size_t)i * rp + t] = u[(size_t)t * k + i] * s;
+  }
+  int rc;
+  if ((rc = pcafit_components_alloc(f, k))) return rc;
+  HIPCHK(f, hipMemcpyAsync(f->A, a.data(), sizeof(double) * a.size(), hipMemcpyHostToDevice, f->stream));
+  return pcafit_project(f, k, eofs, z);
+}
+
+// step 4 on the device: G = U diag(lambda) U^T by the block Jacobi solver (eig_jacobi.h); G is overwritten
+int pcafit_eig(gprx_pcafit_handle f, int* sweeps) {
+  const int64_t rows = f->rows;
+  hipStream_t st = f->stream;
+  const size_t wsb = eig_jacobi_workspace_bytes((int)rows);
+  int rc;
+  if ((rc = need_device_bytes(f, 8.0 * ((double)rows * rows + rows) + (double)wsb, "the eigensolver"))) return rc;
+  HIPCHK(f, hipMalloc((void**)&f->U, sizeof(double) * rows * rows));
+  HIPCHK(f, hipMalloc((void**)&f->lam, sizeof(double) * rows));
+  HIPCHK(f, hipMalloc((void**)&f->eig_ws, wsb));
+  double off_rel = 0.0;
+  std::string msg;
+  HIPCHK(f, hipEventRecord(f->ev[6], st));
+  if ((rc = eig_jacobi_run(st, (int)rows, f->G, rows, f->U, rows, f->lam, f->eig_ws, sweeps, &off_rel, &msg))) return fail(f, rc, msg);
+  HIPCHK(f, hipEventRecord(f->ev[7], st));
+  std::vector<double> asc((size_t)rows);
+  HIPCHK(f, hipMemcpyAsync(asc.data(), f->lam, sizeof(double) * rows, hipMemcpyDeviceToHost, st));
+  HIPCHK(f, hipStreamSynchronize(st));
+  f->eig_ms = elapsed_ms(f->ev[6], f->ev[7]);
+  f->lam_h.assign(asc.rbegin(), asc.rend());
+  return GPRX_OK;
+}
 }  // namespace
 
 int gprx_pcafit_destroy(gprx_pcafit_handle f) {
   if (!f) return GPRX_OK;
-  release_handle(f->device, f->stream, {f->xc1, f->xc2, f->ws.p, f->A, f->E, f->Z}, f->ev, 8);
+  release_handle(f->device, f->stream, {f->xc1, f->xc2, f->ws.p, f->A, f->E, f->Z, f->U, f->lam, f->eig_ws}, f->ev, 8);
   delete f;
   return GPRX_OK;
 }
@@ -443,6 +481,22 @@ int gprx_pcafit_create(int device, const double* x, int64_t n_samples, int64_t n
 int gprx_pcafit_gram(gprx_pcafit_handle f, unsigned char* classes, double* input_mean, double* gram, int64_t* n_wet) {
   if (!f) return fail(f, GPRX_EINVAL, "null handle");
   if (!classes || !input_mean || !gram || !n_wet) return fail(f, GPRX_EINVAL, "null argument");
+  if (f->gram.empty()) {
+    if (f->U) return fail(f, GPRX_ESTATE, "the device eigensolver has overwritten the Gram matrix of this handle");
+    if (f->A) return fail(f, GPRX_ESTATE, "the components step has reused the block that held the Gram matrix");
+    try {
+      HIPCHK(f, hipSetDevice(f->device));
+      f->gram.resize((size_t)f->rows * f->rows);
+      const hipError_t e = hipMemcpyAsync(f->gram.data(), f->G, sizeof(double) * f->rows * f->rows, hipMemcpyDeviceToHost, f->stream);
+      const hipError_t e2 = e == hipSuccess ? hipStreamSynchronize(f->stream) : e;
+      if (e2 != hipSuccess) {
+        f->gram.clear();
+        return fail(f, GPRX_EHIP, std::string("download of the Gram matrix: ") + hipGetErrorString(e2));
+      }
+    } catch (const std::bad_alloc&) {
+      return fail(f, GPRX_ENOMEM, "host allocation failed");
+    }
+  }
   std::memcpy(classes, f->cls.data(), f->cls.size());
   std::memcpy(input_mean, f->mean.data(), sizeof(double) * f->mean.size());
   std::memcpy(gram, f->gram.data(), sizeof(double) * f->gram.size());
@@ -463,6 +517,49 @@ int gprx_pcafit_components(gprx_pcafit_handle f, int k, const double* u, const d
   } catch (const std::bad_alloc&) {
     return fail(f, GPRX_ENOMEM, "host allocation failed");
   }
+}
+
+int gprx_pcafit_eig(gprx_pcafit_handle f, unsigned char* classes, double* input_mean, double* lam, int64_t* n_wet, int* sweeps) {
+  if (!f) return fail(f, GPRX_EINVAL, "null handle");
+  if (!classes || !input_mean || !lam || !n_wet || !sweeps) return fail(f, GPRX_EINVAL, "null argument");
+  if (f->U) return fail(f, GPRX_ESTATE, "the eigensolver has run on this handle: it overwrites the Gram matrix");
+  if (f->A) return fail(f, GPRX_ESTATE, "the components step has reused the block that held the Gram matrix: call gprx_pcafit_eig before it");
+  try {
+    HIPCHK(f, hipSetDevice(f->device));
+    const int rc = pcafit_eig(f, sweeps);
+    if (rc) return rc;
+  } catch (const std::bad_alloc&) {
+    return fail(f, GPRX_ENOMEM, "host allocation failed");
+  }
+  std::memcpy(classes, f->cls.data(), f->cls.size());
+  std::memcpy(input_mean, f->mean.data(), sizeof(double) * f->mean.size());
+  std::memcpy(lam, f->lam_h.data(), sizeof(double) * f->lam_h.size());
+  *n_wet = f->n_wet;
+  return GPRX_OK;
+}
+
+int gprx_pcafit_components_dev(gprx_pcafit_handle f, int k, double* eofs, double* z) {
+  if (!f) return fail(f, GPRX_EINVAL, "null handle");
+  if (f->lam_h.empty()) return fail(f, GPRX_ESTATE, "gprx_pcafit_eig has not run on this handle");
+  if (k < 0 || k >= f->rows) return fail(f, GPRX_EINVAL, "need 0 <= k < n_samples (centring removes one direction)");
+  if (k == 0) return GPRX_OK;
+  if (!eofs || !z) return fail(f, GPRX_EINVAL, "null argument");
+  for (int i = 0; i < k; ++i)
+    if (!(f->lam_h[i] > 0.0)) return fail(f, GPRX_EINVAL, "retained eigenvalues must be positive");
+  HIPCHK(f, hipSetDevice(f->device));
+  int rc;
+  if ((rc = pcafit_components_alloc(f, k))) return rc;
+  const int64_t total = (int64_t)k * f->rows_p;
+  hipLaunchKernelGGL(pcafit_scale_u_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, f->stream, (const double*)f->U, (const double*)f->lam,
+                     f->rows, f->rows_p, k, f->A);
+  HIPCHK(f, hipGetLastError());
+  return pcafit_project(f, k, eofs, z);
+}
+
+int gprx_pcafit_eig_ms(gprx_pcafit_handle f, double* ms) {
+  if (!f || !ms) return fail(f, GPRX_EINVAL, "null argument");
+  *ms = f->eig_ms;
+  return GPRX_OK;
 }
 
 int gprx_pcafit_timings(gprx_pcafit_handle f, double* ms) {

@@ -10,7 +10,7 @@
 //                  IncrementalPCA's own centring Xc2 = Xc1 - colmean(Xc1) (partial_fit, first batch; the same pairwise
 //                  order), one thread per column.
 //   3. Gram:       G = Xc2 Xc2^T with the fp64 MFMA GEMM (lower triangle, split-K), slabs summed in a fixed order and mirrored.
-//   4. (host)      eigh(G) = U diag(lambda) U^T; the SVD of Xc2 is U diag(sqrt(lambda)) V^T.
+//   4. eigh(G) = U diag(lambda) U^T, on the host (numpy) or on the device (eig_jacobi.h); the SVD of Xc2 is U diag(sqrt(lambda)) V^T.
 //   5. components: E = diag(lambda^-1/2) U_k^T Xc2 (GEMM, K = n_samples), then svd_flip(u_based_decision=False): every row
 //                  is turned so that its entry of largest magnitude (lowest index on ties) is positive.
 //   6. projection: Z = Xc1 E^T (:1005 projects the matrix centred once).
@@ -158,6 +158,23 @@ __global__ __launch_bounds__(256) void pcafit_gram_reduce_kernel(const double* _
   for (int z = 0; z < nsplit; ++z) s += ws[(int64_t)z * n * n + e];
   G[(int64_t)i * n + j] = s;
   G[(int64_t)j * n + i] = s;
+}
+
+// A (k, rows_p) = diag(lambda^-1/2) U_k^T from the device eigenpairs: U (rows, rows) with eigenvectors in columns and lam ascending,
+// so row i of A takes column rows - 1 - i; the K padding [rows, rows_p) is zero.  The arithmetic of the host path: s = 1 / sqrt(lambda), u s.
+__global__ __launch_bounds__(256) void pcafit_scale_u_kernel(const double* __restrict__ U, const double* __restrict__ lam, int64_t rows, int64_t rows_p,
+                                                             int k, double* __restrict__ A) {
+#pragma clang fp contract(off)
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (int64_t)k * rows_p) return;
+  const int64_t i = e / rows_p, t = e % rows_p;
+  double v = 0.0;
+  if (t < rows) {
+    const int64_t c = rows - 1 - i;
+    const double s = 1.0 / sqrt(lam[c]);
+    v = U[t * rows + c] * s;
+  }
+  A[e] = v;
 }
 
 // svd_flip(u_based_decision=False) on the rows of E (k, lde), over the first `cols` entries: one workgroup per row finds the

@@ -3,8 +3,10 @@
 format, and ``compute_norths_rule`` (:1323-1353).
 
 ``PreProcessor.fit`` runs the fit on the device (``gprx_pcafit_*``: wetness classes, input mean, compaction, both centrings
-and the Gram matrix of the single-batch ``IncrementalPCA``, then the EOFs and the training projection); only the
-eigendecomposition of the small (n_samples x n_samples) Gram matrix and North's rule run on the host.
+and the Gram matrix of the single-batch ``IncrementalPCA``, then the EOFs and the training projection); the
+eigendecomposition of the small (n_samples x n_samples) Gram matrix runs on the host (``PreProcessor.eigensolver = "host"``, the
+default) or on the device (``"device"``: the Gram matrix is not downloaded, only its eigenvalues are), North's rule on the host
+(DESIGN.md section 3.12).
 ``EOFProjector`` holds a fitted state and runs the two projections through ``libgprx.so``; ``PreProcessor`` keeps one for
 ``transform`` / ``reverse_transform``.
 Difference from the reference: a ``PreProcessor`` fitted WITHOUT weights keeps ``weights = np.empty(0)``
@@ -178,6 +180,7 @@ class PreProcessor:
     format; ``fit``, ``transform``, ``reverse_transform`` and ``wse_2_depth`` on the device."""
 
     device = 0
+    eigensolver = "host"  # "host": numpy.linalg.eigh of the downloaded Gram matrix; "device": gprx_pcafit_eig (block Jacobi)
 
     def __init__(self, spatial_mode_count: int = 0, input_mean=None, wet_threshold: float = 0.03, elevations=None,
                  hydraulic_parameter: str = "wse", wetness_classes=None, weights=None, eofs=None, eigenvalues=None,
@@ -196,6 +199,7 @@ class PreProcessor:
         self.x_std = x_std if x_std is not None else np.empty(0, dtype=float)
         self._proj = None
         self.pca_ = None
+        self.last_eig_sweeps = None  # Jacobi sweeps of the last fit with eigensolver = "device" (None: host route, or no fit yet)
 
     @property
     def dry_indices(self) -> np.ndarray:
@@ -211,8 +215,12 @@ class PreProcessor:
 
     def fit(self, x, elevations, weights=None, spatial_mode_count: int | None = None) -> None:
         """PreProcessor.fit (preprocess.py:947-1007) on the device; North's rule picks the mode count when it is None."""
+        if self.eigensolver not in ("host", "device"):
+            raise ValueError(f"eigensolver must be 'host' or 'device', not {self.eigensolver!r}")
         x, elev, w = check_fit_args(x, elevations, weights, spatial_mode_count, self.hydraulic_parameter)
         n_s, n_cells = x.shape
+        on_device = self.eigensolver == "device"
+        self.last_eig_sweeps = None
         lib = _lib.load()
         mode = MODES.index(self.hydraulic_parameter)
         h = C.c_void_p()
@@ -221,23 +229,37 @@ class PreProcessor:
         try:
             codes = np.empty(n_cells, dtype=np.uint8)
             mean = np.empty(n_cells)
-            gram = np.empty((n_s, n_s))
             n_wet = C.c_int64()
-            check(lib.gprx_pcafit_gram(h, ptr(codes), ptr(mean), ptr(gram), C.byref(n_wet)))
-            n_wet = n_wet.value
             # the SVD of the twice-centred matrix from the eigendecomposition of its Gram matrix, largest first
-            lam, u = np.linalg.eigh(gram)
-            lam, u = np.maximum(lam[::-1], 0.0), u[:, ::-1]
+            if on_device:
+                lam = np.empty(n_s)
+                sweeps = C.c_int()
+                check(lib.gprx_pcafit_eig(h, ptr(codes), ptr(mean), ptr(lam), C.byref(n_wet), C.byref(sweeps)))
+                lam = np.maximum(lam, 0.0)
+            else:
+                gram = np.empty((n_s, n_s))
+                check(lib.gprx_pcafit_gram(h, ptr(codes), ptr(mean), ptr(gram), C.byref(n_wet)))
+                lam, u = np.linalg.eigh(gram)
+                lam, u = np.maximum(lam[::-1], 0.0), u[:, ::-1]
+            n_wet = n_wet.value
             pca = PCAFit(explained_variance_=lam / (n_s - 1), n_samples_seen_=n_s)
             k = compute_norths_rule(pca) if spatial_mode_count is None else int(spatial_mode_count)
             if k > n_s - 1 or (k > 0 and not lam[k - 1] > 0.0):
                 raise ValueError(f"{k} modes exceed the numerical rank of the centred data ({n_s} samples)")
             eofs = np.empty((k, n_wet))
             z = np.empty((n_s, k))
-            u_k = np.ascontiguousarray(u[:, :k])
-            lam_k = np.ascontiguousarray(lam[:k])
-            check(lib.gprx_pcafit_components(h, k, ptr(u_k), ptr(lam_k), ptr(eofs), ptr(z)))
+            if on_device:
+                check(lib.gprx_pcafit_components_dev(h, k, ptr(eofs), ptr(z)))
+            else:
+                u_k = np.ascontiguousarray(u[:, :k])
+                lam_k = np.ascontiguousarray(lam[:k])
+                check(lib.gprx_pcafit_components(h, k, ptr(u_k), ptr(lam_k), ptr(eofs), ptr(z)))
             self.last_timings_ms = self._timings(lib, h)
+            if on_device:
+                ms = C.c_double()
+                check(lib.gprx_pcafit_eig_ms(h, C.byref(ms)))
+                self.last_timings_ms["eigensolver"] = ms.value
+                self.last_eig_sweeps = sweeps.value
         finally:
             lib.gprx_pcafit_destroy(h)
         self.elevations = elevations if elev is None else elev

@@ -44,6 +44,7 @@ extern "C" {
 #define GPRX_ENOMEM 4  /* device allocation failed           -> MemoryError             */
 #define GPRX_ESTATE 5  /* call order violated (e.g. predict before factorize)           */
 #define GPRX_ERCCL 6   /* RCCL missing or a collective failed                -> RuntimeError */
+#define GPRX_ENOCONV 7 /* the eigensolver reached its sweep cap      -> numpy.linalg.LinAlgError */
 
 /* kernel ids: the five stationary kernels KERNEL_FACTORY (gpr.py:21-37) can construct
  * with kernel(variance=, lengthscales=) at gpr.py:298 */
@@ -63,6 +64,7 @@ typedef struct gprx_ctx* gprx_handle;
 typedef struct gprx_pca_ctx* gprx_pca_handle;
 typedef struct gprx_pcafit_ctx* gprx_pcafit_handle;
 typedef struct gprx_hms_ctx* gprx_hms_handle;
+typedef struct gprx_eigh_ctx* gprx_eigh_handle;
 typedef struct gprx_ps_ctx* gprx_ps_handle;
 typedef struct gprx_rs_ctx* gprx_rs_handle;
 typedef struct gprx_comm_ctx* gprx_comm;
@@ -393,7 +395,9 @@ int gprx_pca_transpose_dev(gprx_pca_handle p, const double* src_dev, int64_t row
 int gprx_pcafit_create(int device, const double* x, int64_t n_samples, int64_t n_cells, const double* elevations, const double* weights,
                        int mode, double wet_threshold, gprx_pcafit_handle* out);
 /* classes (n_cells): 0 = "" (maximum exactly at the threshold, or NaN), 1 = AD, 2 = TF, 3 = AF (:1128-1133);
- * input_mean (room for n_cells, the first n_wet are written: :980); gram (n_samples, n_samples); n_wet. */
+ * input_mean (room for n_cells, the first n_wet are written: :980); gram (n_samples, n_samples); n_wet.  G comes down from the
+ * device on the first call (create itself downloads nothing of size n_samples^2); GPRX_ESTATE when the first call comes after
+ * gprx_pcafit_eig or after a components call, which reuse the block that holds G. */
 int gprx_pcafit_gram(gprx_pcafit_handle f, unsigned char* classes, double* input_mean, double* gram, int64_t* n_wet);
 /* u (n_samples, k) row-major: the eigenvectors of G of the k largest eigenvalues lambda (k), all > 0, 0 <= k < n_samples.
  * eofs (k, n_wet) = diag(lambda^-1/2) u^T Xc with svd_flip(u_based_decision=False) applied (pca.components_[:k], :1000);
@@ -401,8 +405,40 @@ int gprx_pcafit_gram(gprx_pcafit_handle f, unsigned char* classes, double* input
 int gprx_pcafit_components(gprx_pcafit_handle f, int k, const double* u, const double* lam, double* eofs, double* z);
 /* device milliseconds of the last create / components: upload of x, statistics, centring, Gram, components, projection */
 int gprx_pcafit_timings(gprx_pcafit_handle f, double* ms);
+/* The same fit with the eigendecomposition on the device; the Gram matrix, its eigenvectors and its
+ * eigenvalues stay in device memory.  eig: classes, input_mean, n_wet as gprx_pcafit_gram returns them; lam: the n_samples
+ * eigenvalues of G, descending, unclamped (the caller clamps at 0 and divides by n_samples - 1: preprocess.py:988-1002 reads
+ * explained_variance_); sweeps: Jacobi sweeps taken.  GPRX_ENOCONV when the solver does not converge.  Call order: create, eig,
+ * components_dev.  GPRX_ESTATE on a second call of eig (the solver overwrites G) and when eig comes after gprx_pcafit_components
+ * or components_dev (they reuse the block that holds G).  components_dev: eofs and z as gprx_pcafit_components writes them, from the k leading
+ * eigenpairs held on the device; every one of those eigenvalues must be > 0, 0 <= k < n_samples; after eig only.  eig_ms: device
+ * milliseconds of the eigensolver (gprx_pcafit_timings keeps its six values). */
+int gprx_pcafit_eig(gprx_pcafit_handle f, unsigned char* classes, double* input_mean, double* lam, int64_t* n_wet, int* sweeps);
+int gprx_pcafit_components_dev(gprx_pcafit_handle f, int k, double* eofs, double* z);
+int gprx_pcafit_eig_ms(gprx_pcafit_handle f, double* ms);
 int gprx_pcafit_destroy(gprx_pcafit_handle f);
 const char* gprx_pcafit_last_error(gprx_pcafit_handle f);
+
+/* ---- symmetric eigensolver ------------------------------------------------------------------------
+ * Eigenvalues and eigenvectors of a real symmetric fp64 matrix by parallel two-sided block Jacobi on the device, with the
+ * conventions of numpy.linalg.eigh(a, UPLO="L"): only the lower triangle of the input is read, the eigenvalues ascend and column
+ * i of v belongs to lam[i].  Every eigenvector is turned so that its entry of largest magnitude (lowest index on ties) is positive.
+ * Two calls on the same input give the same bits.  Matrices are row-major.  Stop: off(A)_F <= n eps ||A||_F, tested before the
+ * first sweep and after every sweep; 30 sweeps without it, or a non-finite entry, return GPRX_ENOCONV and write no result.
+ *
+ * create: a handle for matrices up to n_max x n_max, 1 <= n_max <= 16384, with its own stream; three n_max x n_max blocks of
+ *   device memory (GPRX_ENOMEM before anything is allocated when they do not fit).
+ * eigh: a_host (n, lda) in, lam_host (n) and v_host (n, n; may be NULL) out, all host arrays; a_host is not changed.
+ * eigh_dev: the same on device buffers: a_dev (n, lda) IS OVERWRITTEN (its diagonal ends as the unsorted eigenvalues), lam_dev (n),
+ *   v_dev (n, ldv); returns when the result is complete.  The work runs on the handle's own non-blocking stream: whatever wrote
+ *   a_dev on another stream must have finished before the call.
+ * info: Jacobi sweeps of the last call (0: the matrix was diagonal to working accuracy) and off(A)_F / ||A||_F at its end. */
+int gprx_eigh_create(int device, int n_max, gprx_eigh_handle* out);
+int gprx_eigh(gprx_eigh_handle h, int n, const double* a_host, int64_t lda, double* lam_host, double* v_host);
+int gprx_eigh_dev(gprx_eigh_handle h, int n, double* a_dev, int64_t lda, double* lam_dev, double* v_dev, int64_t ldv);
+int gprx_eigh_info(gprx_eigh_handle h, int* sweeps, double* off_rel);
+int gprx_eigh_destroy(gprx_eigh_handle h);
+const char* gprx_eigh_last_error(gprx_eigh_handle h);
 
 /* ---- HmsPreProcessor: gpras/preprocess.py:1165-1320 ------------------------------------------------
  * create: x (rows, n_features), C order (fortran = 0: x[t * ld + c]) or F order (fortran = 1: x[c * ld + t]), goes up once and
