@@ -139,6 +139,14 @@ PROTOTYPES = {
     "gprx_rs_apply_dev": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64]),
     "gprx_rs_synchronize": (C.c_int, [_vp]),
     "gprx_rs_timings": (C.c_int, [_vp, _dp]),
+    "gprx_al_create": (C.c_int, [C.c_int, C.POINTER(_vp)]),
+    "gprx_al_destroy": (C.c_int, [_vp]),
+    "gprx_al_last_error": (C.c_char_p, [_vp]),
+    "gprx_al_synchronize": (C.c_int, [_vp]),
+    "gprx_al_cutoff_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _i64, C.c_double, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), _vp]),
+    "gprx_al_cutoff": (C.c_int, [_vp, _vp, _i64, _i64, C.c_double, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), _vp]),
+    "gprx_al_clip_dev": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _i64]),
+    "gprx_al_timings": (C.c_int, [_vp, _dp]),
     "gprx_metrics": (C.c_int, [C.c_int, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_double, _vp, _vp, _vp, C.POINTER(C.c_uint64)]),
     "gprx_metrics_dev": (C.c_int, [C.c_int, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_double, _vp, _vp, _vp, C.POINTER(C.c_uint64)]),
     "gprx_kmeans_pp": (C.c_int, [C.c_int, _vp, _i64, C.c_int, _vp, C.c_int, C.c_int, _i64, _vp, _vp]),

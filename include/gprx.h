@@ -67,6 +67,7 @@ typedef struct gprx_hms_ctx* gprx_hms_handle;
 typedef struct gprx_eigh_ctx* gprx_eigh_handle;
 typedef struct gprx_ps_ctx* gprx_ps_handle;
 typedef struct gprx_rs_ctx* gprx_rs_handle;
+typedef struct gprx_al_ctx* gprx_al_handle;
 typedef struct gprx_comm_ctx* gprx_comm;
 
 /* ---- library / device -------------------------------------------------------------- */
@@ -546,6 +547,44 @@ int gprx_rs_apply_dev(gprx_rs_handle h, int64_t rows, const double* src_dev, int
 int gprx_rs_synchronize(gprx_rs_handle h);
 /* device milliseconds of the kernel of the last gprx_rs_apply_dev (waits for the handle's stream); 0 when none has run */
 int gprx_rs_timings(gprx_rs_handle h, double* ms);
+
+/* ---- per-event temporal clipping: gpras/preprocess.py:89-155 ----------------------------------------
+ * DataBuilder.get_cutoff (preprocess.py:135-147) with _delta_cols_norm (preprocess.py:149-155), and the row slices that
+ * _align_datasets (preprocess.py:89-116) and aligned_ref_line_df (preprocess.py:125-133) take with its result.  `combo` is 1 to 4
+ * device blocks side by side that share `rows`: block b is (rows, cols[b]) with pitch ld[b] >= cols[b]; columns [cols[b], ld[b]) are
+ * never read and may hold anything.  The rule, quirks included:
+ *   rows before the first row that holds a NaN in any column are used (preprocess.py:138-140): T' of them;
+ *   dx = |diff(combo, axis=0)|, n_c = sum_t dx[t, c] with 0 -> 1, dx /= n_c (preprocess.py:151-154);
+ *   r_t = sum_c dx[t, c], r /= sum r, cum = cumsum(r) (preprocess.py:142-143);
+ *   stop = argmax(cum > threshold), start = argmax(cum > 10e-4) (preprocess.py:145-146): indices of DIFFERENCE rows, used unshifted
+ *   as row indices of the values; no crossing gives 0, an all-constant block (0 / 0) gives (0, 0).
+ * The sums run in a fixed order (csrc/align.h) that does not depend on how the columns are cut into blocks: the same input gives
+ * the same bits of the curve.  A handle owns a stream and its scratch, grown on demand (GPRX_ENOMEM before anything is allocated
+ * when it does not fit). */
+int gprx_al_create(int device, gprx_al_handle* out);
+int gprx_al_destroy(gprx_al_handle h);
+const char* gprx_al_last_error(gprx_al_handle h);
+int gprx_al_synchronize(gprx_al_handle h);
+/* get_cutoff (preprocess.py:135-147) over device blocks.  blocks_dev, cols, ld: host arrays of n_blocks entries (device pointers,
+ * columns, pitches).  Returns once *start, *stop and *rows_used (T'; may be NULL) are on the host; curve (host, room for rows - 1
+ * doubles) or NULL receives cum, T' - 1 values: what _plot_cutoff_diagnostic (preprocess.py:157-161) shows.  GPRX_EINVAL, the
+ * message saying which: n_blocks outside 1..4, cols < 1, ld < cols, rows < 1, a threshold that is not finite, fewer than 2 rows, or
+ * fewer than 2 rows left after the NaN trim (the reference raises ValueError from argmax of an empty sequence; *rows_used is set).
+ * The handle stays usable. */
+int gprx_al_cutoff_dev(gprx_al_handle h, int n_blocks, const double* const* blocks_dev, const int64_t* cols, const int64_t* ld, int64_t rows,
+                       double threshold, int64_t* start, int64_t* stop, int64_t* rows_used, double* curve);
+/* The same for one host matrix x (rows, cols), which is uploaded into the handle's scratch first. */
+int gprx_al_cutoff(gprx_al_handle h, const double* x, int64_t rows, int64_t cols, double threshold, int64_t* start, int64_t* stop,
+                   int64_t* rows_used, double* curve);
+/* values[start:stop, :] of _align_datasets (preprocess.py:110-112) and of aligned_ref_line_df (preprocess.py:132) for one block:
+ * dst_dev (stop - start, ldd) = rows [start, stop) of src_dev (., lds), columns [cols, ldd) set to 0.0 -- with ldd = cols rounded
+ * up to a multiple of 16 dst_dev is the input of gprx_pca_transform_dev.  stop <= start copies nothing (numpy's empty slice).  The
+ * caller keeps stop within the rows of src_dev.  Asynchronous on the handle's stream: gprx_al_synchronize before another handle
+ * reads dst_dev.  dst_dev must not overlap src_dev. */
+int gprx_al_clip_dev(gprx_al_handle h, const double* src_dev, int64_t lds, int64_t cols, int64_t start, int64_t stop, double* dst_dev, int64_t ldd);
+/* ms[4]: device milliseconds of the last cutoff call by stage -- the NaN scan, the column normalisers, the row sums (with the
+ * combination of the strips), the finish (waits for the handle's stream); zeros when none has run */
+int gprx_al_timings(gprx_al_handle h, double* ms);
 
 /* ---- fused error metrics over two fields: SURVEY.md section 8(f) row N3 (gpras/metrics.py:85-318) ---------- */
 /* Two streaming passes over x (truth), y (prediction) and conf (may be NULL), each (rows, cells) row-major, yield every
