@@ -20,6 +20,7 @@ GPRX_OK, GPRX_EINVAL, GPRX_ENOTPD, GPRX_EHIP, GPRX_ENOMEM, GPRX_ESTATE, GPRX_ERC
 UNIQUE_ID_BYTES = 128
 TRAIN_VARIANCE, TRAIN_LENGTHSCALE, TRAIN_NOISE, TRAIN_Z = 1, 2, 4, 8
 GEMM_C_LOWER, GEMM_A_LOWER, GEMM_A_UPPER, GEMM_B_LOWER, GEMM_B_UPPER = 1, 2, 4, 8, 16
+REDUCE_LOGDET_QUAD, REDUCE_COL, REDUCE_ROWSQ_FINAL, REDUCE_ROW = range(4)
 
 DISTANCE_FORMS = {"difference": 0, "expanded": 1}
 KERNEL_IDS = {"RBF": 0, "Matern12": 1, "Matern32": 2, "Matern52": 3, "Exponential": 4}
@@ -155,6 +156,17 @@ PROTOTYPES = {
     "gprx_kmat": (C.c_int, [C.c_int, C.c_int, _vp, _i64, _vp, _i64, C.c_int, _vp, C.c_double, C.c_double, _vp, _i64, _i64, _i64, C.c_int]),
     "gprx_gemm": (C.c_int, [C.c_int, C.c_int, C.c_int, _i64, _i64, _i64, C.c_double, _vp, _i64, _vp, _i64, C.c_double, _vp, _i64, C.c_int, C.c_int]),
     "gprx_potrf": (C.c_int, [C.c_int, _vp, _i64, _i64, _i64, _vp, _ip]),
+    "gprx_gemm_batched": (C.c_int, [C.c_int, C.c_int, C.c_int, _i64, _i64, _i64, C.c_double, _vp, _i64, _vp, _i64, C.c_double, _vp, _i64, C.c_int, C.c_int,
+                                    C.c_int, _i64, _i64, _i64, C.c_int, _i64, _i64, _i64, _vp, C.c_int, _vp, _i64]),
+    "gprx_gemm_splitk": (C.c_int, [C.c_int, C.c_int, C.c_int, _i64, _i64, _i64, C.c_double, _vp, _i64, _vp, _i64, C.c_double, _vp, _i64, _vp, C.c_int,
+                                   C.c_int, _i64, _i64, _i64, _i64, _vp, C.c_int]),
+    "gprx_trsv_lower": (C.c_int, [C.c_int, _vp, _i64, _vp, _vp, _i64, C.c_int, C.c_int, _i64, _vp]),
+    "gprx_trsm_lower_left": (C.c_int, [C.c_int, _vp, _i64, _vp, _vp, _i64, _i64, _i64, C.c_int, _i64, _vp]),
+    "gprx_trtri_lower": (C.c_int, [C.c_int, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, C.c_int, _i64, _i64, C.c_int]),
+    "gprx_transpose_inplace": (C.c_int, [C.c_int, _vp, _i64, _i64, C.c_int, _i64]),
+    "gprx_alpha_from_inverse": (C.c_int, [C.c_int, _vp, _i64, _vp, _vp, _vp, _i64, C.c_int, _i64, _i64, _i64]),
+    "gprx_reduce_probe": (C.c_int, [C.c_int, C.c_int, _vp, _i64, _vp, _i64, _i64, C.c_double, C.c_double, C.c_int, _vp, C.c_int, _vp, C.c_int, _i64, _i64,
+                                    _i64, _i64, _vp, _vp, C.c_int]),
     "gprx_set_tuning": (C.c_int, [C.c_char_p, C.c_int]),
     "gprx_set_handle_tuning": (C.c_int, [_vp, C.c_char_p, C.c_int]),
     "gprx_mfma_f64_peak": (C.c_int, [C.c_int, _dp]),

@@ -769,9 +769,10 @@ int exact_gradient_batch(gprx_handle h, int count, double* g, bool form_alpha = 
   double* T0 = h->garena.p + (int64_t)np * ld;
   double* K0 = h->arena.p;
   // (X needs no zeroing: scatter_inv_diag writes the diagonal blocks whole -- zeros above the diagonal included --, every tile
-  // below them is written with beta = 0 before it is read, and the triangular K ranges of the products never reach a tile above
-  // the diagonal; the 128 memsets of 134 MB were 1.5 % of a batched evaluation.  "poison_workspace" = 1 fills X with NaN patterns
-  // instead, for the test that proves it.)
+  // below them is written with beta = 0 before it is read.  The triangular K ranges of the products stay on or below the diagonal
+  // blocks at 64 x 64 tiles; a 128 x 128 tile also reads the block to the right of an even diagonal block, and scatter_inv_diag
+  // writes that one as zeros.  The 128 memsets of 134 MB were 1.5 % of a batched evaluation.  "poison_workspace" = 1 fills X
+  // with NaN patterns instead, for the test that proves it.)
   if (h->tune.poison_workspace)
     for (int c = 0; c < count; ++c) HIPCHK(h, hipMemsetAsync(X0 + (int64_t)c * gs, 0xff, sizeof(double) * h->np * ld, st));
   // 64 x 64 tiles throughout: with many cells per launch they beat the 128 x 128 tiles on these triangular products
@@ -2844,6 +2845,179 @@ int gprx_potrf(int device, double* a_dev, int64_t lda, int64_t np, int64_t extra
   HIPCHK(nullptr, e2);
   if (gave_up) return fail(nullptr, GPRX_EHIP, "tile-DAG factorisation: a dependency wait timed out");
   return *info_host ? fail(nullptr, GPRX_ENOTPD, "matrix not positive definite") : GPRX_OK;
+}
+
+// ---- probes of the GEMM dispatcher and of solve.h (the block tests call every variant directly) -------------------------------------
+// Each validates what its kernels cannot take and returns GPRX_EINVAL before any HIP call; then one launch sequence on util_stream().
+// What is refused is what a kernel reads with 16-byte vector loads or in fixed granules: odd leading dimensions and batch / cell
+// strides of the GEMM OPERANDS A and B, of L, inv_diag, the right-hand-side matrix, X and T, and of rowreduce's M; those pointers off
+// a 16-byte boundary; K or kchunk off a multiple of 16; np off a multiple of 64.  What is read and written element by element is
+// left free: ldc of a product (the vector form of the sparse path has ldc = 1), the vectors of trsv_lower, and everything of
+// alpha_from_inverse, logdet_quad and colreduce.
+namespace {
+inline bool off16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+inline bool odd(int64_t v) { return (v & 1) != 0; }
+const char* gemm_probe_invalid(int ta, int tb, int64_t m, int64_t n, int64_t k, const double* a, int64_t lda, const double* b, int64_t ldb,
+                               const double* c, int64_t ldc) {
+  if (!a || !b || !c) return "null argument";
+  if (!((ta == 0 && tb == 1) || (ta == 0 && tb == 0) || (ta == 1 && tb == 0))) return "unsupported transpose pair";
+  if (m <= 0 || n <= 0 || k <= 0 || m > (1 << 30) || n > (1 << 30) || k > (1 << 30)) return "sizes must be positive";
+  if (k % GEMM_BK) return "k must be a multiple of 16";
+  // (an m/n-contiguous operand of ONE column is read element by element: the vector form of the sparse path has ldb = 1)
+  if ((odd(lda) && !(ta == 1 && m == 1)) || (odd(ldb) && !(tb == 0 && n == 1))) return "leading dimensions must be even";
+  if (lda < (ta ? m : k) || ldb < (tb ? k : n) || ldc < n) return "leading dimension shorter than a row";
+  if (off16(a) || off16(b) || off16(c)) return "operands must be 16-byte aligned";
+  return nullptr;
+}
+const char* solve_probe_invalid(const double* L, int64_t lda, const double* inv_diag, int64_t np, int64_t count, int64_t cs) {
+  if (!L || !inv_diag) return "null argument";
+  if (np <= 0 || np % NB || np > (1 << 30)) return "np must be a positive multiple of 64";
+  if (lda < np || odd(lda)) return "leading dimension must be even and at least np";
+  if (count < 1 || odd(cs) || cs < 0) return "count must be positive, strides even";
+  if (off16(L) || off16(inv_diag)) return "operands must be 16-byte aligned";
+  return nullptr;
+}
+}  // namespace
+
+int gprx_gemm_batched(int device, int ta, int tb, int64_t m, int64_t n, int64_t k, double alpha, const double* a_dev, int64_t lda,
+                      const double* b_dev, int64_t ldb, double beta, double* c_dev, int64_t ldc, int flags, int tile, int batch,
+                      int64_t stride_a, int64_t stride_b, int64_t stride_c, int cells, int64_t cell_a, int64_t cell_b, int64_t cell_c,
+                      const double* alpha_tab_dev, int alpha_stride, double* rowsq_dev, int64_t rowsq_ld) {
+  if (const char* why = gemm_probe_invalid(ta, tb, m, n, k, a_dev, lda, b_dev, ldb, c_dev, ldc)) return fail(nullptr, GPRX_EINVAL, why);
+  if (tile != 0 && tile != 64 && tile != 128) return fail(nullptr, GPRX_EINVAL, "tile must be 0, 64 or 128");
+  if (flags < 0 || flags > 31) return fail(nullptr, GPRX_EINVAL, "unknown flag");
+  if (batch < 1 || cells < 1 || alpha_stride < 0) return fail(nullptr, GPRX_EINVAL, "batch and cells must be positive");
+  if (odd(stride_a) || odd(stride_b) || odd(stride_c) || odd(cell_a) || odd(cell_b) || odd(cell_c))
+    return fail(nullptr, GPRX_EINVAL, "batch and cell strides must be even");
+  if (stride_a < 0 || stride_b < 0 || stride_c < 0 || cell_a < 0 || cell_b < 0 || cell_c < 0) return fail(nullptr, GPRX_EINVAL, "negative stride");
+  // (rowsq: one product whose 2 * ceil(n / tile) slabs the caller sized for the tile it names)
+  if (rowsq_dev && (rowsq_ld < m || (tile != 64 && tile != 128) || batch != 1 || cells != 1))
+    return fail(nullptr, GPRX_EINVAL, "rowsq needs tile 64 or 128, one entry, one cell, rowsq_ld at least m");
+  HIPCHK(nullptr, hipSetDevice(device));
+  HIPCHK(nullptr, launch_gemm(util_stream(), ta, tb, (int)m, (int)n, (int)k, alpha, a_dev, lda, b_dev, ldb, beta, c_dev, ldc, flags, tile, batch,
+                              stride_a, stride_b, stride_c, cells, cell_a, cell_b, cell_c, alpha_tab_dev, alpha_stride, rowsq_dev, rowsq_ld));
+  HIPCHK(nullptr, hipStreamSynchronize(util_stream()));
+  return GPRX_OK;
+}
+
+int gprx_gemm_splitk(int device, int ta, int tb, int64_t m, int64_t n, int64_t k, double alpha, const double* a_dev, int64_t lda,
+                     const double* b_dev, int64_t ldb, double beta, double* c_dev, int64_t ldc, double* ws_dev, int kchunk, int cells,
+                     int64_t cell_a, int64_t cell_b, int64_t cell_c, int64_t ws_cell, const double* alpha_tab_dev, int alpha_stride) {
+  if (const char* why = gemm_probe_invalid(ta, tb, m, n, k, a_dev, lda, b_dev, ldb, c_dev, ldc)) return fail(nullptr, GPRX_EINVAL, why);
+  if (!ws_dev || off16(ws_dev)) return fail(nullptr, GPRX_EINVAL, "workspace must be given, 16-byte aligned");
+  if (kchunk <= 0 || kchunk % GEMM_BK) return fail(nullptr, GPRX_EINVAL, "kchunk must be a positive multiple of 16");
+  if (cells < 1 || alpha_stride < 0) return fail(nullptr, GPRX_EINVAL, "cells must be positive");
+  if (odd(cell_a) || odd(cell_b) || odd(cell_c) || odd(ws_cell) || cell_a < 0 || cell_b < 0 || cell_c < 0)
+    return fail(nullptr, GPRX_EINVAL, "cell strides must be even");
+  if (cells > 1 && ws_cell < (k + kchunk - 1) / kchunk * m * n) return fail(nullptr, GPRX_EINVAL, "ws_cell shorter than the slabs of one cell");
+  HIPCHK(nullptr, hipSetDevice(device));
+  HIPCHK(nullptr, launch_gemm_splitk(util_stream(), ta, tb, (int)m, (int)n, (int)k, alpha, a_dev, lda, b_dev, ldb, beta, c_dev, ldc, ws_dev, kchunk,
+                                     cells, cell_a, cell_b, cell_c, ws_cell, alpha_tab_dev, alpha_stride));
+  HIPCHK(nullptr, hipStreamSynchronize(util_stream()));
+  return GPRX_OK;
+}
+
+int gprx_trsv_lower(int device, const double* l_dev, int64_t lda, const double* inv_diag_dev, double* b_dev, int64_t np, int transpose,
+                    int batch, int64_t cs, double* work_dev) {
+  if (const char* why = solve_probe_invalid(l_dev, lda, inv_diag_dev, np, batch, cs)) return fail(nullptr, GPRX_EINVAL, why);
+  if (!b_dev || (work_dev && (!transpose || batch != 1))) return fail(nullptr, GPRX_EINVAL, "work is for the transposed solve of one system");
+  HIPCHK(nullptr, hipSetDevice(device));
+  HIPCHK(nullptr, trsv_lower(util_stream(), l_dev, lda, inv_diag_dev, b_dev, (int)np, transpose != 0, batch, cs, work_dev));
+  HIPCHK(nullptr, hipStreamSynchronize(util_stream()));
+  return GPRX_OK;
+}
+
+int gprx_trsm_lower_left(int device, const double* l_dev, int64_t lda, const double* inv_diag_dev, double* b_dev, int64_t ldb, int64_t n,
+                         int64_t ncols, int cells, int64_t cs, const double* src_dev) {
+  if (const char* why = solve_probe_invalid(l_dev, lda, inv_diag_dev, n, cells, cs)) return fail(nullptr, GPRX_EINVAL, why);
+  if (!b_dev || off16(b_dev) || (src_dev && off16(src_dev))) return fail(nullptr, GPRX_EINVAL, "right-hand side must be given, 16-byte aligned");
+  if (ncols <= 0 || ncols > (1 << 30) || ldb < ncols || odd(ldb)) return fail(nullptr, GPRX_EINVAL, "ldb must be even and at least ncols");
+  if (src_dev && n != NB) return fail(nullptr, GPRX_EINVAL, "src is for n == 64 only");
+  HIPCHK(nullptr, hipSetDevice(device));
+  HIPCHK(nullptr, trsm_lower_left(util_stream(), l_dev, lda, inv_diag_dev, b_dev, ldb, (int)n, (int)ncols, cells, cs, src_dev));
+  HIPCHK(nullptr, hipStreamSynchronize(util_stream()));
+  return GPRX_OK;
+}
+
+int gprx_trtri_lower(int device, const double* l_dev, int64_t lda, const double* inv_diag_dev, double* x_dev, int64_t ldx, double* t_dev,
+                     int64_t ldt, int64_t np, int cells, int64_t cs_l, int64_t cs_x, int tile) {
+  if (const char* why = solve_probe_invalid(l_dev, lda, inv_diag_dev, np, cells, cs_l)) return fail(nullptr, GPRX_EINVAL, why);
+  if (!x_dev || !t_dev || off16(x_dev) || off16(t_dev)) return fail(nullptr, GPRX_EINVAL, "X and T must be given, 16-byte aligned");
+  if (ldx < np || ldt < np || odd(ldx) || odd(ldt) || odd(cs_x) || cs_x < 0) return fail(nullptr, GPRX_EINVAL, "ldx, ldt, cs_x must be even, rows at least np");
+  if (tile != 0 && tile != 64 && tile != 128) return fail(nullptr, GPRX_EINVAL, "tile must be 0, 64 or 128");
+  HIPCHK(nullptr, hipSetDevice(device));
+  HIPCHK(nullptr, trtri_lower(util_stream(), l_dev, lda, inv_diag_dev, x_dev, ldx, t_dev, ldt, (int)np, cells, cs_l, cs_x, tile));
+  HIPCHK(nullptr, hipStreamSynchronize(util_stream()));
+  return GPRX_OK;
+}
+
+int gprx_transpose_inplace(int device, double* x_dev, int64_t ld, int64_t n, int cells, int64_t cs) {
+  if (!x_dev || off16(x_dev)) return fail(nullptr, GPRX_EINVAL, "X must be given, 16-byte aligned");
+  if (n <= 0 || n % 64 || n > (1 << 30) || ld < n || odd(ld) || cells < 1 || odd(cs) || cs < 0)
+    return fail(nullptr, GPRX_EINVAL, "n must be a positive multiple of 64, ld and cs even");
+  HIPCHK(nullptr, hipSetDevice(device));
+  HIPCHK(nullptr, transpose_inplace(util_stream(), x_dev, ld, (int)n, cells, cs));
+  HIPCHK(nullptr, hipStreamSynchronize(util_stream()));
+  return GPRX_OK;
+}
+
+int gprx_alpha_from_inverse(int device, const double* x_dev, int64_t ldx, const double* beta_dev, double* part_dev, double* alpha_dev, int64_t np,
+                            int cells, int64_t cs_x, int64_t cs_b, int64_t cs_a) {
+  if (!x_dev || !beta_dev || !part_dev || !alpha_dev) return fail(nullptr, GPRX_EINVAL, "null argument");
+  if (np <= 0 || np % NB || np > (1 << 30) || ldx < np || cells < 1 || cs_x < 0 || cs_b < 0 || cs_a < 0)
+    return fail(nullptr, GPRX_EINVAL, "np must be a positive multiple of 64");
+  HIPCHK(nullptr, hipSetDevice(device));
+  HIPCHK(nullptr, alpha_from_inverse(util_stream(), x_dev, ldx, beta_dev, part_dev, alpha_dev, (int)np, cells, cs_x, cs_b, cs_a));
+  HIPCHK(nullptr, hipStreamSynchronize(util_stream()));
+  return GPRX_OK;
+}
+
+int gprx_reduce_probe(int device, int op, const double* m_dev, int64_t ldm, const double* w_dev, int64_t nrows, int64_t ncols, double base,
+                      double scale, int accumulate, double* partial_dev, int rows_per_chunk, double* out_dev, int cells, int64_t m_cell,
+                      int64_t w_cell, int64_t p_cell, int64_t out_cell, const double* base_tab_dev, const double* base_tab2_dev, int base_stride) {
+  if (!m_dev || !out_dev) return fail(nullptr, GPRX_EINVAL, "null argument");
+  if (nrows <= 0 || ncols <= 0 || nrows > (1 << 30) || ncols > (1 << 30) || cells < 1) return fail(nullptr, GPRX_EINVAL, "sizes must be positive");
+  if (m_cell < 0 || w_cell < 0 || p_cell < 0 || out_cell < 0 || base_stride < 0) return fail(nullptr, GPRX_EINVAL, "negative stride");
+  hipStream_t st = nullptr;
+  switch (op) {
+    case GPRX_REDUCE_LOGDET_QUAD:  // M = L (nrows x nrows), w = v or null; out[cell * out_cell + {0, 1}]
+      if (ldm < nrows || ncols != nrows || out_cell > (1 << 30)) return fail(nullptr, GPRX_EINVAL, "logdet_quad: square matrix, ldm at least its order");
+      HIPCHK(nullptr, hipSetDevice(device));
+      st = util_stream();
+      hipLaunchKernelGGL(logdet_quad_kernel, dim3(cells), dim3(256), 0, st, m_dev, ldm, w_dev, (int)nrows, out_dev, m_cell, (int)out_cell);
+      break;
+    case GPRX_REDUCE_COL: {
+      if (ldm < ncols || !partial_dev || rows_per_chunk < 1) return fail(nullptr, GPRX_EINVAL, "colreduce: partial and rows_per_chunk needed");
+      const int nchunks = (int)((nrows + rows_per_chunk - 1) / rows_per_chunk);
+      if (cells > 1 && p_cell < (int64_t)nchunks * ncols) return fail(nullptr, GPRX_EINVAL, "colreduce: p_cell shorter than the partial sums of one cell");
+      HIPCHK(nullptr, hipSetDevice(device));
+      st = util_stream();
+      hipLaunchKernelGGL(colreduce_partial, dim3((unsigned)((ncols + 255) / 256), nchunks, cells), dim3(256), 0, st, m_dev, ldm, w_dev, (int)nrows,
+                         (int)ncols, rows_per_chunk, partial_dev, m_cell, w_cell, p_cell);
+      hipLaunchKernelGGL(colreduce_final, dim3((unsigned)((ncols + 255) / 256), cells), dim3(256), 0, st, (const double*)partial_dev, nchunks,
+                         (int)ncols, base, scale, accumulate, out_dev, p_cell, out_cell, base_tab_dev, base_tab2_dev, base_stride);
+      break;
+    }
+    case GPRX_REDUCE_ROWSQ_FINAL:  // M = the ncols slabs a rowsq GEMM left, ldm apart
+      if (ldm < nrows || cells != 1) return fail(nullptr, GPRX_EINVAL, "rowsq_final: one cell, ldm at least nrows");
+      HIPCHK(nullptr, hipSetDevice(device));
+      st = util_stream();
+      hipLaunchKernelGGL(rowsq_final_kernel, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, st, m_dev, (int)ncols, ldm, (int)nrows, base, out_dev);
+      break;
+    case GPRX_REDUCE_ROW:
+      if (ldm < ncols || odd(ldm) || odd(ncols) || off16(m_dev) || (w_dev && off16(w_dev)) || cells != 1)
+        return fail(nullptr, GPRX_EINVAL, "rowreduce: one cell, ncols and ldm even, M and w 16-byte aligned");
+      HIPCHK(nullptr, hipSetDevice(device));
+      st = util_stream();
+      hipLaunchKernelGGL(rowreduce_kernel, dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, st, m_dev, ldm, w_dev, (int)nrows, (int)ncols, base, scale,
+                         out_dev);
+      break;
+    default:
+      return fail(nullptr, GPRX_EINVAL, "unknown reduction");
+  }
+  HIPCHK(nullptr, hipGetLastError());
+  HIPCHK(nullptr, hipStreamSynchronize(st));
+  return GPRX_OK;
 }
 
 // development aid (GPRX_DAG_STAMPS=1): the stamps of the handle's last tile-DAG factorisation; returns the number of words

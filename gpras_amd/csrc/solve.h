@@ -277,20 +277,6 @@ inline hipError_t trsm_lower_left(hipStream_t st, const double* L, int64_t lda, 
                          ncols, cells, cs);
 }
 
-// L^T X = B (in place)
-inline hipError_t trsm_lower_left_t(hipStream_t st, const double* L, int64_t lda, const double* inv_diag, double* B, int64_t ldb,
-                                    int n, int ncols) {
-  if (n == NB) return launch_gemm(st, 1, 0, NB, ncols, NB, 1.0, inv_diag, NB, B, ldb, 0.0, B, ldb, GEMM_A_UPPER, 64);
-  const int n1 = (n / NB / 2) * NB, n2 = n - n1;
-  hipError_t e = trsm_lower_left_t(st, L + (int64_t)n1 * lda + n1, lda, inv_diag + (int64_t)(n1 / NB) * NB * NB,
-                                   B + (int64_t)n1 * ldb, ldb, n2, ncols);
-  if (e != hipSuccess) return e;
-  // B1 -= L21^T X2 : op(A) = L21^T with L21 stored (n2 x n1)
-  e = launch_gemm(st, 1, 0, n1, ncols, n2, -1.0, L + (int64_t)n1 * lda, lda, B + (int64_t)n1 * ldb, ldb, 1.0, B, ldb, 0);
-  if (e != hipSuccess) return e;
-  return trsm_lower_left_t(st, L, lda, inv_diag, B, ldb, n1, ncols);
-}
-
 // ---- inverse of the Cholesky factor: X = L^-1 (lower), recursive, two GEMMs per node ------------
 __global__ __launch_bounds__(256) void scatter_inv_diag(const double* __restrict__ inv_diag, double* __restrict__ X, int64_t ldx,
                                                         int64_t cs_in, int64_t cs_out) {
@@ -299,9 +285,14 @@ __global__ __launch_bounds__(256) void scatter_inv_diag(const double* __restrict
   X += (int64_t)blockIdx.y * cs_out;
   const double* src = inv_diag + (int64_t)blk * NB * NB;
   double* dst = X + (int64_t)blk * NB * ldx + blk * NB;
+  // A 128 x 128 GEMM tile clips its triangular K range at multiples of 128, so it reads the 64 x 64 block to the right of every EVEN
+  // diagonal block as part of a "triangular" operand (the products below at tile 128, and K^-1 = L^-T L^-1 after the in-place
+  // transpose): that block is written as zeros here, whatever the caller left in X.
+  const bool zero_right = (blk & 1) == 0 && blk + 1 < (int)gridDim.x;
   for (int e = threadIdx.x; e < NB * NB; e += 256) {
     const int r = e / NB, c = e % NB;
     dst[(int64_t)r * ldx + c] = src[e];
+    if (zero_right) dst[(int64_t)r * ldx + NB + c] = 0.0;
   }
 }
 

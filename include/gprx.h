@@ -280,6 +280,59 @@ int gprx_gemm(int device, int ta, int tb, int64_t m, int64_t n, int64_t k, doubl
  * the inverses of the diagonal blocks.  info_host: 0, or 1-based index of the failing pivot. */
 int gprx_potrf(int device, double* a_dev, int64_t lda, int64_t np, int64_t extra, double* inv_diag_dev, int* info_host);
 
+/* ---- probes: every argument of the GEMM dispatcher and the host drivers and reductions of the triangular solves, for the block
+ * tests.  All pointers are device pointers.  Each returns GPRX_EINVAL, before any device work, for what its kernels cannot take:
+ * odd leading dimensions or batch / cell strides of what is read with 16-byte loads (A and B of a product, L, inv_diag, a matrix
+ * right-hand side, X, T, the matrix of the row reduction), those pointers off a 16-byte boundary, k or kchunk not a multiple of 16,
+ * np not a multiple of 64.  ldc of a product may be odd (C is read and written element by element; the vector form has ldc = 1), and
+ * nothing is asked of the vectors of gprx_trsv_lower or of the operands of gprx_alpha_from_inverse, LOGDET_QUAD and COL, whose
+ * kernels use scalar loads. */
+
+/* gprx_gemm for batch x cells products: entry e of cell c reads A + c cell_a + e stride_a (B, C likewise) and uses
+ * alpha_tab[c * alpha_stride] when alpha_tab is given.  rowsq != NULL: C is not stored; the row sums of squares of alpha op(A) op(B)
+ * go to 2 * ceil(n / tile) slabs rowsq_ld apart; rowsq needs tile 64 or 128 and batch == cells == 1. */
+int gprx_gemm_batched(int device, int ta, int tb, int64_t m, int64_t n, int64_t k, double alpha, const double* a_dev, int64_t lda,
+                      const double* b_dev, int64_t ldb, double beta, double* c_dev, int64_t ldc, int flags, int tile, int batch,
+                      int64_t stride_a, int64_t stride_b, int64_t stride_c, int cells, int64_t cell_a, int64_t cell_b, int64_t cell_c,
+                      const double* alpha_tab_dev, int alpha_stride, double* rowsq_dev, int64_t rowsq_ld);
+
+/* The same product with K cut into slices of kchunk, summed in a fixed order; ws: ceil(k / kchunk) * m * n doubles per cell, ws_cell apart. */
+int gprx_gemm_splitk(int device, int ta, int tb, int64_t m, int64_t n, int64_t k, double alpha, const double* a_dev, int64_t lda,
+                     const double* b_dev, int64_t ldb, double beta, double* c_dev, int64_t ldc, double* ws_dev, int kchunk, int cells,
+                     int64_t cell_a, int64_t cell_b, int64_t cell_c, int64_t ws_cell, const double* alpha_tab_dev, int alpha_stride);
+
+/* L x = b (transpose 0) or L^T x = b (1) in place, L lower (np, np) with the inverses of its 64 x 64 diagonal blocks in inv_diag;
+ * batch systems whose L, inv_diag and b are all cs doubles apart.  work (transpose, batch 1): holds the right-hand side on entry and
+ * is used up, b only receives the solution. */
+int gprx_trsv_lower(int device, const double* l_dev, int64_t lda, const double* inv_diag_dev, double* b_dev, int64_t np, int transpose,
+                    int batch, int64_t cs, double* work_dev);
+
+/* L X = B in place, B (n, ncols); cells systems cs doubles apart.  src (n == 64): the right-hand side is read from there. */
+int gprx_trsm_lower_left(int device, const double* l_dev, int64_t lda, const double* inv_diag_dev, double* b_dev, int64_t ldb, int64_t n,
+                         int64_t ncols, int cells, int64_t cs, const double* src_dev);
+
+/* X = L^-1: the blocks on and below the block diagonal of X are written, T (np, np) is scratch. */
+int gprx_trtri_lower(int device, const double* l_dev, int64_t lda, const double* inv_diag_dev, double* x_dev, int64_t ldx, double* t_dev,
+                     int64_t ldt, int64_t np, int cells, int64_t cs_l, int64_t cs_x, int tile);
+
+int gprx_transpose_inplace(int device, double* x_dev, int64_t ld, int64_t n, int cells, int64_t cs);
+
+/* alpha_j = sum_{i >= j} X[i][j] beta_i; part: cells * ceil(np / 512) * np doubles. */
+int gprx_alpha_from_inverse(int device, const double* x_dev, int64_t ldx, const double* beta_dev, double* part_dev, double* alpha_dev, int64_t np,
+                            int cells, int64_t cs_x, int64_t cs_b, int64_t cs_a);
+
+/* The reductions of the solves.  LOGDET_QUAD: out[c * out_cell + {0, 1}] = sum log M[i][i], sum w[i]^2 (M square of order nrows).
+ * COL: out[t] = (accumulate ? out[t] : base) + scale * sum_r (w ? w[r] M[r][t] : M[r][t]^2), partial: ceil(nrows / rows_per_chunk) * ncols
+ * doubles per cell; base = base_tab[c * base_stride] (+ base_tab2[c * base_stride]) when given.  ROWSQ_FINAL: out[r] = base - the sum over
+ * the ncols slabs, ldm apart, of M[slab * ldm + r].  ROW: out[r] = base + scale * sum_c (w ? w[c] M[r][c] : M[r][c]^2). */
+#define GPRX_REDUCE_LOGDET_QUAD 0
+#define GPRX_REDUCE_COL 1
+#define GPRX_REDUCE_ROWSQ_FINAL 2
+#define GPRX_REDUCE_ROW 3
+int gprx_reduce_probe(int device, int op, const double* m_dev, int64_t ldm, const double* w_dev, int64_t nrows, int64_t ncols, double base,
+                      double scale, int accumulate, double* partial_dev, int rows_per_chunk, double* out_dev, int cells, int64_t m_cell,
+                      int64_t w_cell, int64_t p_cell, int64_t out_cell, const double* base_tab_dev, const double* base_tab2_dev, int base_stride);
+
 /* The whole predict loop of gpr.py:336-339 in one call: cell i = (units[i], thetas[i], z block i for sparse models) is
  * factorised (exact models: all cells by one batched launch sequence) and predicts at the shared xs (ns, d);
  * means / vars: (count, ns) row-major (the transpose of GPRAS.predict's (ns, K)). */

@@ -1,0 +1,77 @@
+"""The longdouble references of the block tests (blocks_reference.py) against mpmath at 50 digits, and the recorded bounds against
+their script.  CPU only."""
+
+import importlib.util
+import os
+
+import mpmath
+import numpy as np
+
+import blocks_reference as br
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+def _mp(a):
+    return mpmath.matrix([[mpmath.mpf(float(v)) for v in row] for row in np.atleast_2d(a)])
+
+
+def _worst(ref_ld, ref_mp, scale_mp):
+    """max |longdouble reference - mpmath| / scale, elementwise, evaluated in mpmath (a longdouble splits exactly into two doubles)."""
+    worst = mpmath.mpf(0)
+    for i in range(ref_ld.shape[0]):
+        for j in range(ref_ld.shape[1]):
+            hi = float(ref_ld[i, j])
+            lo = float(ref_ld[i, j] - br.LD(hi))
+            worst = max(worst, abs(mpmath.mpf(hi) + mpmath.mpf(lo) - ref_mp[i, j]) / scale_mp[i, j])
+    return float(worst)
+
+
+def test_longdouble_references_against_mpmath():
+    assert np.finfo(br.LD).eps < 1.1e-19
+    rng = np.random.default_rng(3)
+    with mpmath.workdps(50):
+        # one 64 x 48 x 32 product, with the update term
+        a, b, c0 = rng.standard_normal((64, 32)), rng.standard_normal((48, 32)), rng.standard_normal((64, 48))
+        ref, mag = br.gemm_ref(0, 1, 0.7, a, b, -1.3, c0)
+        exact = mpmath.mpf(0.7) * (_mp(a) * _mp(b).T) + mpmath.mpf(-1.3) * _mp(c0)
+        # K + 2 longdouble operations per element: (K + 2) eps_ld |.| is the textbook bound, ~1e-5 of the bound the kernels are held to
+        assert _worst(ref, exact, _mp(mag.astype(np.float64))) < 34 * np.finfo(br.LD).eps
+        # one 128 x 128 triangular solve (the factor the solve tests use), both orientations
+        low, _ = br.solve_inputs(128, br.NOISES[1])
+        rhs = br.rhs(128, 4, 0)
+        for transpose in (False, True):
+            x = br.solve_lower_ld(low, rhs, transpose)
+            lo_mp = _mp(low).T if transpose else _mp(low)
+            x_mp = _mp(rhs)
+            for i in (range(127, -1, -1) if transpose else range(128)):  # substitution at 50 digits
+                others = range(i + 1, 128) if transpose else range(i)
+                for j in range(4):
+                    x_mp[i, j] = (x_mp[i, j] - mpmath.fsum(lo_mp[i, m] * x_mp[m, j] for m in others)) / lo_mp[i, i]
+            # forward error of substitution: cond(L) n eps_ld at worst; cond(L) <= sqrt(n (1 + noise) / noise) = 1.2e4 for this factor
+            scale = mpmath.matrix(128, 4)
+            top = max(abs(x_mp[i, j]) for i in range(128) for j in range(4))
+            for i in range(128):
+                for j in range(4):
+                    scale[i, j] = top
+            assert _worst(x, x_mp, scale) < 1.2e4 * 128 * np.finfo(br.LD).eps
+        # the longdouble Cholesky factor: L L^T reproduces the matrix
+        k = rng.standard_normal((24, 30))
+        spd = k @ k.T + np.eye(24)
+        lo = br.chol_ld(spd)
+        back = (lo @ lo.T).astype(np.float64)
+        assert np.max(np.abs(back - spd)) <= 2 * np.finfo(np.float64).eps * np.max(np.abs(spd))
+
+
+def test_recorded_bounds_are_what_the_script_writes():
+    spec = importlib.util.spec_from_file_location("make_blocks_bounds", os.path.join(HERE, "golden", "make_blocks_bounds.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    with open(br.BOUNDS_PATH) as fh:
+        assert fh.read() == mod.render()
+
+
+def test_canary_is_a_nan_with_its_own_bits():
+    c = br.canary((3, 2))
+    assert np.all(np.isnan(c)) and np.all(br.is_canary(c))
+    assert not np.any(br.is_canary(np.array([np.nan, 0.0, np.inf])))

@@ -309,6 +309,34 @@ def test_gradient_does_not_depend_on_old_workspace_contents(lib, n):
     assert np.array_equal(out[0][2], out[1][2]) and np.array_equal(out[0][3], out[1][3])
 
 
+@pytest.mark.parametrize("n", [320, 1000])
+def test_gradient_at_128_tiles_does_not_depend_on_old_workspace_contents(lib, n):
+    """The same with "update_tile" = 128: a 128 x 128 tile clips its triangular K range at multiples of 128 and so reads the 64 x 64
+    block to the right of every even diagonal block of the L^-1 workspace (trtri_lower of the batched gradient, K^-1 = L^-T L^-1 of
+    both); scatter_inv_diag writes that block as zeros, so NaN patterns in the workspace change nothing."""
+    d = 4
+    x, y, _ = make_regression(n, d, n_outputs=3, n_test=8, config=1, unit=n)
+    theta = pack_theta(1.1, 0.8, 0.05)
+    out = {}
+    for poison in (0, 1):
+        h = make_handle(lib, n, d, "RBF", False, x, y)
+        try:
+            check(lib.gprx_set_handle_tuning(h, b"update_tile", 128), h)
+            check(lib.gprx_set_handle_tuning(h, b"poison_workspace", poison), h)
+            loss, grad = C.c_double(), np.zeros(theta.size)
+            check(lib.gprx_objective(h, 1, ptr(theta), None, ALL, C.byref(loss), ptr(grad)), h)
+            units = np.array([0, 1, 2, 1], dtype=np.int32)
+            thetas = np.ascontiguousarray(np.tile(theta, (4, 1)) + 0.01 * np.arange(4)[:, None])
+            losses, grads = np.zeros(4), np.zeros((4, theta.size))
+            check(lib.gprx_objective_batch(h, 4, ptr(units), ptr(thetas), None, ALL, ptr(losses), ptr(grads)), h)
+            out[poison] = (loss.value, grad, losses, grads)
+        finally:
+            lib.gprx_destroy(h)
+    assert np.all(np.isfinite(out[1][1])) and np.all(np.isfinite(out[1][3]))
+    assert out[0][0] == out[1][0] and np.array_equal(out[0][1], out[1][1])
+    assert np.array_equal(out[0][2], out[1][2]) and np.array_equal(out[0][3], out[1][3])
+
+
 @pytest.mark.parametrize("kernel,noise", [("RBF", 0.05), ("RBF", 2e-6), ("Matern32", 1e-4)])
 def test_alpha_from_the_gradients_inverse_agrees_with_backward_substitution(lib, kernel, noise):
     """An evaluation WITH a gradient forms alpha = X^T beta from the inverse it builds (solve.h alpha_from_inverse), a plain
