@@ -148,6 +148,16 @@ PROTOTYPES = {
     "gprx_al_cutoff": (C.c_int, [_vp, _vp, _i64, _i64, C.c_double, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), _vp]),
     "gprx_al_clip_dev": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _i64]),
     "gprx_al_timings": (C.c_int, [_vp, _dp]),
+    "gprx_dg_create": (C.c_int, [C.c_int, C.POINTER(_vp)]),
+    "gprx_dg_destroy": (C.c_int, [_vp]),
+    "gprx_dg_last_error": (C.c_char_p, [_vp]),
+    "gprx_dg_synchronize": (C.c_int, [_vp]),
+    "gprx_dg_sort_u64_dev": (C.c_int, [_vp, _vp, _i64, _vp]),
+    "gprx_dg_sort_abs_residual_dev": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
+    "gprx_dg_sort_info": (C.c_int, [_vp, _ip, _dp]),
+    "gprx_dg_gather_dev": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp]),
+    "gprx_dg_scatter_summary_dev": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
+    "gprx_dg_detect_dev": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, C.c_double, C.c_int, _vp, C.POINTER(_i64)]),
     "gprx_metrics": (C.c_int, [C.c_int, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_double, _vp, _vp, _vp, C.POINTER(C.c_uint64)]),
     "gprx_metrics_dev": (C.c_int, [C.c_int, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_double, _vp, _vp, _vp, C.POINTER(C.c_uint64)]),
     "gprx_kmeans_pp": (C.c_int, [C.c_int, _vp, _i64, C.c_int, _vp, C.c_int, C.c_int, _i64, _vp, _vp]),

@@ -12,6 +12,9 @@ The reference's chain is ``gpr.predict(x_test)`` (gpr.py:322-342) -> ``hf_reduce
 * ``gprx_pca_to_depth_dev`` / ``gprx_pca_sqrt_dev`` apply pipeline.py:262-277 and the ``np.sqrt(y_test_var)`` of :286 in place;
 * the truth field goes up once; one fused ``gprx_metrics_dev`` evaluation per event reads row ranges of the resident fields.
 
+* ``diagnostics`` computes the numbers inside the reference's diagnostic plots (``gen_plots``, pipeline.py:90-210: the residual CDF,
+  the scatter summaries, the detection categories) on the same resident fields (``gpras_amd/diagnostics.py``).
+
 Only the reductions the metric tables are made of (per-timestep and per-cell sums, peaks) and, on request, the fields
 themselves come back to the host.  The host chain (``GPRAS.predict`` -> ``EOFProjector.reverse_transform`` -> ``metrics``) stays
 available; tests/test_gpu_pipeline.py holds the two against each other.
@@ -200,3 +203,61 @@ class DevicePipeline:
         finally:
             truth.free()
         return fields
+
+    # ---- pipeline.py:90-210 (gen_plots) -----------------------------------------------------------------------------------------
+    def diagnostics(self, x_test, hf_test_data_df, lf_test_data=None, n_points: int = 2048, wet_threshold_depth: float = 0.0,
+                    include_correct_negative: bool = True) -> dict:
+        """The numbers inside ``performance_cdf``, ``performance_scatterplot`` (native space and depth) and ``map_detection_categories``
+        as ``gen_plots`` (pipeline.py:121-143, 171-180) draws them from what pipeline.py:260-277 computes, with every ``(T*, cells)`` field
+        resident: the prediction is ``predict_mean_field_dev(x_test)``, the truth ``hf_test_data_df`` (indexed by (event, timestep), one
+        column per cell) and the optional low-fidelity field ``lf_test_data`` (the ``ras_upskill`` case, resampled to the same cells) go
+        up once.  The CDF and the first scatter summary are taken in native space; then the three fields are converted in place by
+        ``gprx_pca_to_depth_dev`` (the elevations added to the prediction first for ``hydraulic_parameter == "depth"``, pipeline.py:266-267;
+        nothing for velocity) for the depth scatter summary and the per-event detection codes.  Returns a plain dict of small arrays:
+        ``n``, ``ranks``, ``pcts``, ``cdf_upskill`` and ``cdf_lf`` (``n_points`` values each; ``cdf_lf`` None without LF data), ``scatter`` and
+        ``scatter_depth`` ({"upskill": {ll, ur, rmse, sum_sq, n}, "lf": ...}), ``events``, ``detection_codes`` (E, cells) uint8 and
+        ``category_names``."""
+        from .diagnostics import CATEGORY_NAMES, FieldDiagnostics, cdf_ranks, event_ranges
+
+        pr = self.projector
+        cells = pr.n_cells
+        truth_host = as_f64(hf_test_data_df.values)
+        if truth_host.ndim != 2 or truth_host.shape != (np.shape(x_test)[0], cells):
+            raise ValueError(f"hf_test_data_df must have one row per row of x_test and {cells} columns")
+        lf_host = None if lf_test_data is None else as_f64(getattr(lf_test_data, "values", lf_test_data))
+        if lf_host is not None and lf_host.shape != truth_host.shape:
+            raise ValueError("lf_test_data must have the shape of hf_test_data_df")
+        names, ranges = event_ranges(hf_test_data_df.index)
+        to_depth = pr.hydraulic_parameter != "velocity"
+        if to_depth:
+            self._require_elevations()
+        dg = FieldDiagnostics(self.device)
+        bufs: list[DeviceBuffer] = []
+        try:
+            pred, ns = self.predict_mean_field_dev(x_test)
+            bufs.append(pred)
+            truth = DeviceBuffer.from_array(truth_host, self.device)
+            bufs.append(truth)
+            lf = None
+            if lf_host is not None:
+                lf = DeviceBuffer.from_array(lf_host, self.device)
+                bufs.append(lf)
+            n = ns * cells
+            sides = {"upskill": pred} if lf is None else {"lf": lf, "upskill": pred}
+            cdf_lf, cdf_upskill, pcts = dg.residual_cdf(lf, truth, pred, n_points, n=n)
+            scatter = {k: dg.scatter_summary(b, truth, n) for k, b in sides.items()}
+            if to_depth:
+                ph = pr.handle
+                check(self._lib.gprx_pca_to_depth_dev(ph, pred.ptr, ns, int(pr.hydraulic_parameter == "depth")))
+                check(self._lib.gprx_pca_to_depth_dev(ph, truth.ptr, ns, 0))
+                if lf is not None:
+                    check(self._lib.gprx_pca_to_depth_dev(ph, lf.ptr, ns, 0))
+                check(self._lib.gprx_pca_synchronize(ph))
+            scatter_depth = {k: dg.scatter_summary(b, truth, n) for k, b in sides.items()}
+            codes = dg.detection_categories_dev(truth, pred, ns, cells, ranges, wet_threshold_depth, include_correct_negative, names)
+        finally:
+            for b in bufs:
+                b.free()
+            dg.close()
+        return {"n": n, "ranks": cdf_ranks(n, n_points), "pcts": pcts, "cdf_lf": cdf_lf, "cdf_upskill": cdf_upskill, "scatter": scatter,
+                "scatter_depth": scatter_depth, "events": list(names), "detection_codes": codes, "category_names": CATEGORY_NAMES}

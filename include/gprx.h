@@ -68,6 +68,7 @@ typedef struct gprx_eigh_ctx* gprx_eigh_handle;
 typedef struct gprx_ps_ctx* gprx_ps_handle;
 typedef struct gprx_rs_ctx* gprx_rs_handle;
 typedef struct gprx_al_ctx* gprx_al_handle;
+typedef struct gprx_dg_ctx* gprx_dg_handle;
 typedef struct gprx_comm_ctx* gprx_comm;
 
 /* ---- library / device -------------------------------------------------------------- */
@@ -638,6 +639,46 @@ int gprx_al_clip_dev(gprx_al_handle h, const double* src_dev, int64_t lds, int64
 /* ms[4]: device milliseconds of the last cutoff call by stage -- the NaN scan, the column normalisers, the row sums (with the
  * combination of the strips), the finish (waits for the handle's stream); zeros when none has run */
 int gprx_al_timings(gprx_al_handle h, double* ms);
+
+/* ---- the numerics of the diagnostic plots: gpras/utils/plotting.py:155-233, 716-859 ------------------------
+ * What gen_plots (production/analysis/pipeline.py:90-210) computes inside its figures from the (T*, cells) fields that
+ * pipeline.py:260-277 hands it, on fields that stay in HBM:
+ *   performance_cdf (plotting.py:201-233): np.sort(np.abs(lf - hf).flatten()) (plotting.py:221-222), a device radix sort of fp64
+ *     keys (csrc/diag.h), equal to np.sort BIT FOR BIT: the sorted sequence of a multiset is unique; NaN sorts last, -0.0 becomes
+ *     +0.0, denormals survive;
+ *   performance_scatterplot (plotting.py:155-198): the joint min and max (plotting.py:183, 191) and the sum of squares behind the
+ *     rmse (plotting.py:185, 193), summed in an order fixed by n alone;
+ *   map_detection_categories (plotting.py:716-859): per event the column maxima (plotting.py:765-766), the check for negative values
+ *     (plotting.py:776-777), the wet threshold (plotting.py:780-781) and one category per cell (plotting.py:792-802).
+ * A handle owns a stream and its workspace (the second sort buffer, the histograms, the tile counts and offsets, the chunk sums),
+ * grown on demand and reused across calls.  Every call waits for its work.  Errors: GPRX_EINVAL with a message (null pointer,
+ * n < 1, E < 1, a rank or an event range out of bounds), GPRX_ENOMEM, a HIP status; the handle stays usable.  No C++ exception
+ * crosses the boundary (std::bad_alloc is GPRX_ENOMEM). */
+int gprx_dg_create(int device, gprx_dg_handle* out);
+int gprx_dg_destroy(gprx_dg_handle h);
+const char* gprx_dg_last_error(gprx_dg_handle h);
+int gprx_dg_synchronize(gprx_dg_handle h);
+/* out_dev (n) = np.sort of the n unsigned 64-bit keys keys_dev, which are left unchanged; the two must not overlap.  1 <= n <= 2^40.
+ * LSD radix sort, 8 bits per pass; a pass whose digit takes one value over all keys is skipped. */
+int gprx_dg_sort_u64_dev(gprx_dg_handle h, const uint64_t* keys_dev, int64_t n, uint64_t* out_dev);
+/* out_dev (n) = np.sort(np.abs(a - b).flatten()) (plotting.py:221-222) of two device arrays of n doubles, which are left
+ * unchanged: the key bits(fabs(a[i] - b[i])) is built where the sort reads it. */
+int gprx_dg_sort_abs_residual_dev(gprx_dg_handle h, const double* a_dev, const double* b_dev, int64_t n, double* out_dev);
+/* the last sort: bit p of *executed_mask set when pass p (byte p of the key) ran; ms[2]: device milliseconds of the histogram sweep
+ * and of the passes (either pointer may be NULL) */
+int gprx_dg_sort_info(gprx_dg_handle h, int* executed_mask, double* ms);
+/* out[j] = sorted_dev[ranks[j]], j < m: ranks and out are HOST arrays (a subsample of the curve of plotting.py:226-227); a rank
+ * outside [0, n) is GPRX_EINVAL */
+int gprx_dg_gather_dev(gprx_dg_handle h, const double* sorted_dev, int64_t n, const int64_t* ranks, int64_t m, double* out);
+/* out[4] (host): the min and the max over both arrays (NaN when either holds one, as ndarray.min / max; plotting.py:183, 191), the sum
+ * of (p - hf)^2 in the fixed order of csrc/diag.h, and n: rmse = sqrt(out[2] / out[3]) (plotting.py:185, 193) */
+int gprx_dg_scatter_summary_dev(gprx_dg_handle h, const double* p_dev, const double* hf_dev, int64_t n, double* out);
+/* truth_dev, pred_dev (rows, cells); event e is rows [ev_lo[e], ev_hi[e]) (host arrays, E of them).  codes_dev (E, cells) bytes:
+ * 1 Detected, 2 Miss, 3 False Alarm, 4 Correct Negative (0 unless include_cn), 0 where a NaN is compared (plotting.py:792-802), of
+ * the maxima over the event's rows ignoring NaN (plotting.py:765-766) with values below thr set to 0 (plotting.py:780-781).
+ * *first_negative_event: the first event with a negative maximum, where the reference raises ValueError (plotting.py:776-777), else -1. */
+int gprx_dg_detect_dev(gprx_dg_handle h, const double* truth_dev, const double* pred_dev, int64_t rows, int64_t cells, const int64_t* ev_lo,
+                       const int64_t* ev_hi, int64_t E, double thr, int include_cn, unsigned char* codes_dev, int64_t* first_negative_event);
 
 /* ---- fused error metrics over two fields: SURVEY.md section 8(f) row N3 (gpras/metrics.py:85-318) ---------- */
 /* Two streaming passes over x (truth), y (prediction) and conf (may be NULL), each (rows, cells) row-major, yield every
