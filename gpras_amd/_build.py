@@ -1,7 +1,7 @@
 """Build libgprx.so (HIP, gfx950 only) in-tree with hipcc.  No torch, no cmake.
 
 The library is several translation units (one object each, compiled in parallel, then linked): the C ABI by subsystem -- `gprx.hip`
-(the GP path and the raw kernel entry points), `abi_eof.hip` (EOF projection, its fit, HmsPreProcessor), `abi_pseudo.hip`, `abi_resample.hip` (LF-to-HF mesh resampling), `abi_align.hip` (per-event temporal clipping), `abi_diag.hip` (sort, scatter summary and detection codes of the diagnostic plots),
+(the GP path and the raw kernel entry points), `abi_eof.hip` (EOF projection, its fit, HmsPreProcessor), `abi_pseudo.hip`, `abi_resample.hip` (LF-to-HF mesh resampling), `abi_align.hip` (per-event temporal clipping), `abi_diag.hip` (sort, scatter summary and detection codes of the diagnostic plots), `abi_events.hip` (storm-event selection),
 `abi_fields.hip` (metrics, k-means, row gather), `abi_comm.hip` (RCCL), `abi_eig.hip` (symmetric eigensolver), all over the host toolkit of `abi_common.h` -- and the fused
 sparse evaluation, whose pass kernels are compiled once per kernel id (`-DSF_KID=k`) and whose resident-loop launch once per optimiser
 (`sf_adam.hip`, `sf_adadelta.hip` over `sf_adam_prep.h`), beside the step kernel of the resident loop of the general sparse launch
@@ -28,7 +28,7 @@ FLAGS += os.environ.get("GPRX_EXTRA_FLAGS", "").split()
 # (object name, source, extra defines)
 UNITS = (
     [("gprx", "gprx.hip", []), ("abi_eof", "abi_eof.hip", []), ("sf_cell", "sf_cell.hip", []), ("sf_adam", "sf_adam.hip", []), ("sf_adadelta", "sf_adadelta.hip", []), ("sgpr_step", "sgpr_step.hip", [])]
-    + [(n, f"{n}.hip", []) for n in ("abi_pseudo", "abi_resample", "abi_align", "abi_diag", "abi_fields", "abi_comm", "abi_eig")]
+    + [(n, f"{n}.hip", []) for n in ("abi_pseudo", "abi_resample", "abi_align", "abi_diag", "abi_events", "abi_fields", "abi_comm", "abi_eig")]
     + [(f"sf_pass1_k{k}", "sf_pass1.hip", [f"-DSF_KID={k}"]) for k in range(5)]
     + [(f"sf_pass2_k{k}", "sf_pass2.hip", [f"-DSF_KID={k}"]) for k in range(5)]
 )

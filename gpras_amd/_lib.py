@@ -158,6 +158,20 @@ PROTOTYPES = {
     "gprx_dg_gather_dev": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp]),
     "gprx_dg_scatter_summary_dev": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
     "gprx_dg_detect_dev": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, C.c_double, C.c_int, _vp, C.POINTER(_i64)]),
+    "gprx_ev_create": (C.c_int, [C.c_int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "gprx_ev_create_empty": (C.c_int, [C.c_int, C.POINTER(_vp)]),
+    "gprx_ev_destroy": (C.c_int, [_vp]),
+    "gprx_ev_last_error": (C.c_char_p, [_vp]),
+    "gprx_ev_synchronize": (C.c_int, [_vp]),
+    "gprx_ev_maxima": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "gprx_ev_return_periods": (C.c_int, [_vp, _i64, _vp, _vp, _vp]),
+    "gprx_ev_rp_eval": (C.c_int, [_vp, C.c_int, _vp, _i64, _vp]),
+    "gprx_ev_cov": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "gprx_ev_eigh": (C.c_int, [_vp, _vp, _vp, _ip]),
+    "gprx_ev_scores": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
+    "gprx_ev_standardise": (C.c_int, [_vp, _vp]),
+    "gprx_ev_farthest": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp, _i64, _i64, _vp, _vp]),
+    "gprx_ev_timings": (C.c_int, [_vp, _dp]),
     "gprx_metrics": (C.c_int, [C.c_int, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_double, _vp, _vp, _vp, C.POINTER(C.c_uint64)]),
     "gprx_metrics_dev": (C.c_int, [C.c_int, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_double, _vp, _vp, _vp, C.POINTER(C.c_uint64)]),
     "gprx_kmeans_pp": (C.c_int, [C.c_int, _vp, _i64, C.c_int, _vp, C.c_int, C.c_int, _i64, _vp, _vp]),

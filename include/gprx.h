@@ -69,6 +69,7 @@ typedef struct gprx_ps_ctx* gprx_ps_handle;
 typedef struct gprx_rs_ctx* gprx_rs_handle;
 typedef struct gprx_al_ctx* gprx_al_handle;
 typedef struct gprx_dg_ctx* gprx_dg_handle;
+typedef struct gprx_ev_ctx* gprx_ev_handle;
 typedef struct gprx_comm_ctx* gprx_comm;
 
 /* ---- library / device -------------------------------------------------------------- */
@@ -679,6 +680,57 @@ int gprx_dg_scatter_summary_dev(gprx_dg_handle h, const double* p_dev, const dou
  * *first_negative_event: the first event with a negative maximum, where the reference raises ValueError (plotting.py:776-777), else -1. */
 int gprx_dg_detect_dev(gprx_dg_handle h, const double* truth_dev, const double* pred_dev, int64_t rows, int64_t cells, const int64_t* ev_lo,
                        const int64_t* ev_hi, int64_t E, double thr, int include_cn, unsigned char* codes_dev, int64_t* first_negative_event);
+
+/* ---- storm-event selection: production/pre_processing/event_selection.py:13-257 -----------------------------
+ * The first stage of the reference's workflow, EventSelection, on a long frame of (event, hour) rows that stays in HBM:
+ *   _calculate_return_periods (event_selection.py:34-67): the per-event maxima of precip-cum and inflow, the block maxima over
+ *     arrival_rate consecutive events, their descending sort, first-occurrence unique, the (n_blocks + 1) / rank knots, and scipy's
+ *     linear interp1d with extrapolation at both ends -- every result equal to the reference's BIT FOR BIT;
+ *   _select_diverse_storms (event_selection.py:148-185): the two pivots with their zero fill, an exact PCA of each (column means in a
+ *     fixed order, Xc^T Xc and Xc V on the fp64 MFMA GEMM, eigh on the host or by gprx_ev_eigh), the standardised (E, 2k) score
+ *     matrix and the farthest-point loop, incrementally (one launch per pick, all enqueued at once), ties to the lowest row.
+ * The caller sorts once on the host: ev_rank[r] is the rank of row r's event id among the sorted unique ids, hour[r] its position inside
+ * its event (the reference's cumcount, event_selection.py:153-155); the three value columns arrive in their original row order.
+ * Domain: 1 <= n_events < 2^31, 1 <= n_hours <= 4096, n_events x (n_hours rounded up to 16) <= 2^28; finite values; the hours of an
+ * event exactly 0 .. len - 1, every (event, hour) once: otherwise GPRX_EINVAL with a message.  A handle owns a stream and all device
+ * memory; every call waits for its work.  No C++ exception crosses the boundary. */
+int gprx_ev_create(int device, int64_t rows, int64_t n_events, int64_t n_hours, const int32_t* ev_rank, const int32_t* hour, const double* precip_excess,
+                   const double* precip_cum, const double* inflow, gprx_ev_handle* out);
+/* a handle without a frame: it serves gprx_ev_farthest on a caller's score matrix only */
+int gprx_ev_create_empty(int device, gprx_ev_handle* out);
+int gprx_ev_destroy(gprx_ev_handle h);
+const char* gprx_ev_last_error(gprx_ev_handle h);
+int gprx_ev_synchronize(gprx_ev_handle h);
+/* host outputs, any of them NULL: the maxima over each event's own hours (the zero fill does not enter: a negative maximum survives)
+ * and the number of hours of each event */
+int gprx_ev_maxima(gprx_ev_handle h, double* max_precip_cum, double* max_inflow, int32_t* lengths);
+/* fits both return-period functions and evaluates each at its own maxima: rp_* (n_events) host outputs (may be NULL), n_knots[2] the
+ * numbers of distinct block maxima.  Fewer than two distinct block maxima: GPRX_EINVAL (interp1d needs two knots). */
+int gprx_ev_return_periods(gprx_ev_handle h, int64_t arrival_rate, double* rp_precip_cum, double* rp_inflow, int64_t* n_knots);
+/* out[i] = the fitted function `which` (0 precip-cum, 1 inflow) at values[i], n host doubles: scipy's interp1d._call_linear operation
+ * for operation, so values below the lowest and above the highest knot extrapolate as the reference does */
+int gprx_ev_rp_eval(gprx_ev_handle h, int which, const double* values, int64_t n, double* out);
+/* which: 0 the precip-excess pivot, 1 the inflow pivot.  mean (n_hours) and cov (n_hours, n_hours) = Xc^T Xc, not yet divided by
+ * n_events - 1: host outputs.  The covariance also stays on the device for one gprx_ev_eigh. */
+int gprx_ev_cov(gprx_ev_handle h, int which, double* mean, double* cov);
+/* eigh of the covariance of the last gprx_ev_cov by the device solver (gprx_eigh_dev's kernels): lam (n_hours) ascending, v (n_hours,
+ * n_hours) eigenvectors in columns, host outputs; *sweeps may be NULL.  GPRX_ENOCONV as gprx_eigh_dev. */
+int gprx_ev_eigh(gprx_ev_handle h, double* lam, double* v, int* sweeps);
+/* the scores Xc V of block `which`: components (k, n_hours) host, one component per row with its sign already chosen; 2k <= 64 */
+int gprx_ev_scores(gprx_ev_handle h, int which, int k, const double* components);
+/* both score blocks side by side, (n_events, 2k), each column standardised with the population standard deviation in a fixed order
+ * (scale 1 for a constant column); scores_out host, may be NULL.  The matrix stays on the device for gprx_ev_farthest. */
+int gprx_ev_standardise(gprx_ev_handle h, double* scores_out);
+/* The farthest-point loop on the rows of scores_dev (n, d) row-major on the device, or of the handle's standardised scores when it is
+ * NULL (then n = n_events, d = 2k).  selected: n_selected distinct rows (host); num picks, each the candidate whose squared distance
+ * to its nearest selected row (direct differences, summed over the columns in order) is largest, the lowest row on a tie.  picks
+ * (num) in pick order and pick_dist (num), the square root of that distance: host outputs.  2 <= n < 2^31, d <= 64,
+ * 1 <= n_selected, 1 <= num <= n - n_selected. */
+int gprx_ev_farthest(gprx_ev_handle h, const double* scores_dev, int64_t n, int d, const int32_t* selected, int64_t n_selected, int64_t num, int32_t* picks,
+                     double* pick_dist);
+/* ms[8], device milliseconds of the last call of each stage: upload + pivot + maxima, return periods, covariance of block 0 and of
+ * block 1, scores (both blocks), standardisation, selection, device eigh */
+int gprx_ev_timings(gprx_ev_handle h, double* ms);
 
 /* ---- fused error metrics over two fields: SURVEY.md section 8(f) row N3 (gpras/metrics.py:85-318) ---------- */
 /* Two streaming passes over x (truth), y (prediction) and conf (may be NULL), each (rows, cells) row-major, yield every
