@@ -25,7 +25,7 @@ __global__ __launch_bounds__(256) void sf_prep_kernel(SfParams p, const double* 
   const double* zsrc = z_src ? z_src + (int64_t)cell * nz : A + p.oZ;
   double parv = 0.0;
   if (ad.theta != nullptr) {
-    // resident optimiser: the row is formed here from the unconstrained variables (decode_theta of gprx.hip on the device: px_math.h
+    // resident optimiser: the row is formed here from the unconstrained variables (decode_theta_into of gp_ctx.h on the device: px_math.h
     // gives the host's bits)
     parv = sf_par_from_theta(ad.theta + (int64_t)cell * ad.nt, ad, cell, p.d, tid);
   } else if (tid < CELL_PAR) {

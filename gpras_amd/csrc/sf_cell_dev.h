@@ -7,7 +7,7 @@
 
 namespace gprx {
 
-// entry `tid` of a cell's parameter row (kfun.h CELL_PAR layout) from the unconstrained variables th[nt]: decode_theta of gprx.hip on
+// entry `tid` of a cell's parameter row (kfun.h CELL_PAR layout) from the unconstrained variables th[nt]: decode_theta_into of gp_ctx.h on
 // the device (px_math.h gives the host's bits); zero for the unused entries
 __device__ __forceinline__ double sf_par_from_theta(const double* __restrict__ th, const SfAdam& ad, int cell, int d, int tid) {
   double parv = 0.0;

@@ -1,4 +1,4 @@
-// Resident optimiser loop of the GENERAL sparse launch sequence (gprx.hip sgpr_batch_enqueue: M > 64, or M <= 64 with "sgpr_fused" = 0):
+// Resident optimiser loop of the GENERAL sparse launch sequence (gp_sparse.h sgpr_batch_enqueue: M > 64, or M <= 64 with "sgpr_fused" = 0):
 // the launch that closes step t and opens step t + 1 of every cell.  It does on the device what sgpr_stage_out_kernel, the host tail of
 // sgpr_objective_batch / gprx_objective_batch, the host update of the optimiser loop and sgpr_stage_in_kernel do between two host-stepped
 // evaluations -- with their arithmetic (sgpr_asm.h, px_math.h), so a cell ends with the same bits on either route.

@@ -117,7 +117,12 @@ int gprx_set_data(gprx_handle h, const double* x, const double* y, int n_units);
  * A sparse model (m > 0) is evaluated as a batch of ONE cell of gprx_objective_batch, for every M, d and tuning: the same launches,
  * the same bits as that cell inside any batch, and the same GPRX_ENOTPD text ("cell 0: Kuu or B not positive definite: pivot N").
  * d > 64 exceeds the lengthscale slots of a row of the cell-parameter table: the cell's hyperparameters then travel in the launch
- * arguments and the sequence is launched eagerly instead of replayed from a graph. */
+ * arguments and the sequence is launched eagerly instead of replayed from a graph.
+ * The per-cell arguments (unit, theta, z) of this and of every batched evaluation, optimiser and predict entry point below are
+ * checked before any device work, cell by cell, in this order: theta NULL, unit outside [0, n_units), a theta element that is not
+ * finite, z NULL (m > 0), a z element that is not finite -- GPRX_EINVAL, the first fault names the message, no output is written.
+ * (gprx_adam_batch / gprx_adadelta_batch clear n_evals, batches and losses first; a call that takes no step -- max_iter = 0, nothing
+ * trainable in mask -- returns GPRX_OK without looking at the cells.) */
 int gprx_objective(gprx_handle h, int unit, const double* theta, const double* z, int mask, double* loss, double* grad);
 
 /* Factorise only (kernel build + Cholesky + weights); what SGPR.predict_y recomputes on

@@ -276,7 +276,7 @@ def test_sparse_batch_failed_cell_is_isolated_and_leaves_no_trace(lib, m):
 
 
 def test_resident_adam_reports_a_cell_that_stops_being_positive_definite(lib):
-    """gprx_adam_batch on sparse models with M <= 64 runs resident on the device (gprx.hip sgpr_resident_fused); a cell whose Kuu is
+    """gprx_adam_batch on sparse models with M <= 64 runs resident on the device (gp_resident.h sgpr_resident_fused); a cell whose Kuu is
     numerically singular from the first step on ends the call with GPRX_ENOTPD at the first read of the stop flags, names the cell,
     leaves the other cells' variables finite, and the handle serves a clean run afterwards (same result as a run that never failed)."""
     import ctypes as C
@@ -325,7 +325,7 @@ def test_resident_adam_reports_a_cell_that_stops_being_positive_definite(lib):
 
 def test_resident_adam_in_two_groups_of_cells_equals_one_group(lib):
     """When a pass over the batch needs more than one round of the chip's CUs (17 cells at N = 4096) the resident Adam loop runs the batch
-    as two groups of cells on two streams, one launch apart (gprx.hip sf_group_count: one group's one-workgroup-per-cell launches beside
+    as two groups of cells on two streams, one launch apart (gp_sparse.h sf_group_count: one group's one-workgroup-per-cell launches beside
     the other's streamed passes).  Forced here on a small problem ("sgpr_groups_from" = 1: two groups whatever the size): same variables
     and evaluation counts bit for bit as with the grouping switched off (0); a cell of the SECOND group that is not positive definite is
     named by its index in the batch; a run of zero steps leaves nothing running."""

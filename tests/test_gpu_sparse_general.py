@@ -1,4 +1,4 @@
-"""Every branch of the sparse launch sequence for 64 < M <= 320 (gprx.hip sgpr_batch_enqueue -- a lone gprx_objective / gprx_factorize is
+"""Every branch of the sparse launch sequence for 64 < M <= 320 (gp_sparse.h sgpr_batch_enqueue -- a lone gprx_objective / gprx_factorize is
 a batch of one cell through it --, sgpr_predict_batch and the host-stepped Adam loop) against the oracle, and its bit-identity contracts:
 a cell's bits do not depend on its position in a batch or on the batch's size.
 
@@ -8,7 +8,7 @@ two cases per (kernel id, distance form, isotropy) instantiation of launch_kmat_
 and the cell count through them; ``test_case_table_covers_every_branch_and_edge`` (no GPU) checks that every size branch of the sequence
 is reached and that the inputs are well posed: it fails when a case is removed from the table.  One case beside the table has d = 70:
 more lengthscales than a row of the cell-parameter table holds, so its cells run one at a time with the hyperparameters in the launch
-arguments (gprx.hip SgprParSrc).
+arguments (gp_sparse.h SgprParSrc).
 
 Inputs as in the variants file: lengthscales sqrt(d) U(0.6, 1.6) keep Kuf away from underflow at d = 64, Z sits on data rows plus 1e-3
 noise.  RBF and Matern52 carry no d <= 8 (their Kuu is jitter-saturated there: cond 1e7 .. 2.6e8); Matern12, Matern32 and Exponential
@@ -42,15 +42,15 @@ HIGH_D = (9, 15, 16, 17, 32, 33, 50, 64)
 N_EDGES = (70, 255, 257, 960, 961, 1025, 1100, 2049)
 N_LARGE = 4097
 CELL_COUNTS = (1, 3, 7, 23, 24, 50)
-NB = 64  # gprx_common.h:12 -- mp = round_up(m, NB), np = round_up(n, NB) (gprx.hip:1627-1628)
-SPLITK_CHUNK = 256  # gprx.hip:874 -- B = A A^T and A y run split-K when np >= 4 * SPLITK_CHUNK (gprx.hip:1152, :1170)
-B_FINISH_MP = 128  # gprx.hip:1162 -- mp <= 128: sgpr_b_finish_kernel, above: add_diag / diag_sum / 2-D copy / 2-D memset
-SPLIT_PANEL_FROM = 24  # potrf.h:730 -- potrf_split_panel: batch >= 24 factorises with the split panel
-KM_DC = 8  # kmat.h:20 -- trace_body's p.d > KM_DC branch (grad.h:243)
-DZ_IG, DZ_DC = 4, 16  # grad.h:300 -- dz_kernel: groups of 4 inducing points, chunks of 16 dimensions (dz_grid, grad.h:366)
-MAX_D = 64  # kfun.h:11-12 -- CELL_PAR - CELL_PAR_LS lengthscales fit a row of the cell-parameter table
-SGPR_PRED_TILE = 4096  # gprx.hip:875 -- test points per pass of sgpr_predict_batch
-PRED_ROWS = 256  # gprx.hip:1377 -- rows per chunk of colreduce_partial
+NB = 64  # gprx_common.h NB -- mp = round_up(m, NB), np = round_up(n, NB) (gprx.hip gprx_create)
+SPLITK_CHUNK = 256  # gp_sparse.h SPLITK_CHUNK -- B = A A^T and A y run split-K when np >= 4 * SPLITK_CHUNK (gp_sparse.h sgpr_body_enqueue)
+B_FINISH_MP = 128  # gp_sparse.h sgpr_body_enqueue -- mp <= 128: sgpr_b_finish_kernel, above: add_diag / diag_sum / 2-D copy / 2-D memset
+SPLIT_PANEL_FROM = 24  # potrf.h potrf_split_panel: batch >= 24 factorises with the split panel
+KM_DC = 8  # kmat.h KM_DC -- the p.d > KM_DC branch of grad.h trace_body
+DZ_IG, DZ_DC = 4, 16  # grad.h dz_kernel: groups of 4 inducing points, chunks of 16 dimensions (grad.h dz_grid)
+MAX_D = 64  # kfun.h CELL_PAR, CELL_PAR_LS -- CELL_PAR - CELL_PAR_LS lengthscales fit a row of the cell-parameter table
+SGPR_PRED_TILE = 4096  # gp_sparse.h SGPR_PRED_TILE -- test points per pass of sgpr_predict_batch
+PRED_ROWS = 256  # gp_sparse.h sgpr_predict_batch rows_per_chunk -- rows per chunk of colreduce_partial
 HYPER = _lib.TRAIN_VARIANCE | _lib.TRAIN_LENGTHSCALE | _lib.TRAIN_NOISE
 ALL = HYPER | _lib.TRAIN_Z
 # Matern12 / Exponential in the expanded form (see NONSMOOTH_EXPANDED_TOL in test_gpu_sparse_variants.py: r^2 = |a|^2 + |b|^2 - 2 a.b
@@ -70,7 +70,7 @@ def mp_of(m):
 
 
 def splitk_of(n):
-    """gprx.hip:1152, :1170 -- np >= 4 * SPLITK_CHUNK (mp <= 512 holds for every M <= 320)."""
+    """gp_sparse.h sgpr_body_enqueue -- np >= 4 * SPLITK_CHUNK (mp <= 512 holds for every M <= 320)."""
     return mp_of(n) >= 4 * SPLITK_CHUNK
 
 

@@ -1,4 +1,4 @@
-"""GPU tests of the device-resident Adam and Adadelta loops around the GENERAL sparse launch sequence (gprx.hip sgpr_resident_general,
+"""GPU tests of the device-resident Adam and Adadelta loops around the GENERAL sparse launch sequence (gp_resident.h sgpr_resident_general,
 csrc/sgpr_step.hip): sparse models with M > 64, and M <= 64 with "sgpr_fused" = 0.  The contract is the host-stepped loop's: the same
 variables, evaluation counts and losses as a Python loop over gprx_objective_batch, bit for bit, whatever the window, the replay state
 of the step's graph or the size the batch has shrunk to.  gprx_last_optimizer_route tells which loop a call took (0 host-stepped,
@@ -20,7 +20,7 @@ from oracle import kernels as okn
 from oracle import transforms as otr
 
 Z_ONLY = _lib.TRAIN_Z
-CHECK_EVERY = 25  # gprx.hip sgpr_resident_general: steps between two reads of the stop flags (GPRX_ADAM_CHECK_EVERY)
+CHECK_EVERY = 25  # gp_resident.h resident_check_every: steps between two reads of the stop flags (GPRX_ADAM_CHECK_EVERY)
 
 # The smallest shapes that reach every branch of the step kernel and of the launch sequence around it (mp = M rounded up to 64).
 B_FINISH = dict(kernel="RBF", d=3, m=65, n=300, ard=False, form=0, cells=3, seed=401)  # mp 128: sgpr_b_finish_kernel, no split-K

@@ -1,7 +1,7 @@
 """Instruction mix and resources of one kernel from `hipcc -S --cuda-device-only` output (development aid).
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --cuda-device-only -o /tmp/gprx.s gpras_amd/csrc/gprx.hip
     python tools/isa_stats.py /tmp/gprx.s kmat_kernelILi0ELi0
-(the unit that launches the kernel: gprx.hip for the GP path, abi_eof.hip / abi_pseudo.hip / abi_fields.hip for the other rows, sf_*.hip)"""
+(the unit that launches the kernel: gprx.hip for the GP path -- gp_*.h are included into it --, abi_eof.hip / abi_pseudo.hip / abi_fields.hip for the other rows, sf_*.hip)"""
 import collections, re, sys
 lines = open(sys.argv[1]).read().split("\n")
 pat = sys.argv[2]
