@@ -624,138 +624,6 @@ inline hipError_t launch_gemm_t(hipStream_t st, GemmArgs p, int batch, int nspli
   return hipGetLastError();
 }
 
-// ---- single-stage K = 64 update: C(M x N) -= A(M x 64) * B(N x 64)^T on the lower trapezoid -----------
-// The in-block "strip" updates of the Cholesky sit on its critical path and are pure latency: with K = 64
-// the whole operand panel of a 64 x 64 tile is 2 x 32 KiB, so every global load (operands and the C tile)
-// is issued before anything is waited for, followed by one barrier, 64 MFMAs per wave and the store.
-constexpr int S64_LD = 64;  // LDS row stride (doubles), unpadded: 16-B chunk c of row `row` sits at chunk c ^ (row & 15) -- conflict-free
-                            // for the four 16-lane groups of ds_read_b128 (the padded stride 66 cost two cycles per group)
-
-// (static, like splitk_reduce_kernel: more than one translation unit of the library includes this header)
-static __global__ __launch_bounds__(256) void syrk_k64_kernel(const double* __restrict__ A, const double* __restrict__ B, double* __restrict__ C,
-                                                       int64_t lda, int64_t ldc, int M, int N, int tiles_n, int64_t cs) {
-  __shared__ __attribute__((aligned(16))) double sA[64 * S64_LD];
-  __shared__ __attribute__((aligned(16))) double sB[64 * S64_LD];
-  A += (int64_t)blockIdx.y * cs;  // batched: blockIdx.y = cell, cs = cell stride (0 for a single matrix)
-  B += (int64_t)blockIdx.y * cs;
-  C += (int64_t)blockIdx.y * cs;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1, g = lane >> 4, r = lane & 15;
-  // lower-trapezoid tile decode (tiles are square: tile (ti, tj) has work iff tj <= ti)
-  int bid = blockIdx.x, ti, tj;
-  const int tri = tiles_n * (tiles_n + 1) / 2;
-  if (bid < tri) {
-    ti = (int)((sqrtf(8.0f * (float)bid + 1.0f) - 1.0f) * 0.5f);
-    while ((ti + 1) * (ti + 2) / 2 <= bid) ++ti;
-    while (ti * (ti + 1) / 2 > bid) --ti;
-    tj = bid - ti * (ti + 1) / 2;
-  } else {
-    const int rest = bid - tri;
-    ti = tiles_n + rest / tiles_n;
-    tj = rest % tiles_n;
-  }
-  const int m0 = ti * 64, n0 = tj * 64;
-  // operands: 64 rows x 32 chunks of 16 B each = 2048 chunks -> 8 per thread per operand
-  d2 ra[8], rb[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int q = tid + 256 * i;
-    const int row = q >> 5, cc = q & 31;
-    ra[i] = (m0 + row < M) ? *reinterpret_cast<const d2*>(A + (int64_t)(m0 + row) * lda + 2 * cc) : d2{0.0, 0.0};
-    rb[i] = (n0 + row < N) ? *reinterpret_cast<const d2*>(B + (int64_t)(n0 + row) * lda + 2 * cc) : d2{0.0, 0.0};
-  }
-  d4 acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      const int col = n0 + wn * 32 + b * 16 + r;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int row = m0 + wm * 32 + a * 16 + g + 4 * q;
-        acc[a][b][q] = (row < M && col < N) ? C[(int64_t)row * ldc + col] : 0.0;
-      }
-    }
-  // LDS image: inside every block of 16 k the elements are stored 4 x 4 transposed (k_local -> (k_local % 4) * 4 +
-  // k_local / 4), so that the four consecutive doubles lane group g reads for a step are k = 16 ks + {g, 4 + g, 8 + g,
-  // 12 + g}: MFMA j of a step then sums the four CONSECUTIVE k = 16 ks + 4 j + {0..3}, and the 16 MFMAs of a tile walk k
-  // in ascending groups of four -- the same order in which the 8-column sub-panel updates of the panel kernels reach an
-  // element.
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int q = tid + 256 * i;
-    const int row = q >> 5, cc = q & 31;
-    const int c8 = cc & 7;
-    const int pos0 = 16 * (cc >> 3) + 8 * (c8 & 1) + (c8 >> 1), pos1 = pos0 + 4;
-    const int sw = row & 15;
-    const int o0 = 2 * ((pos0 >> 1) ^ sw) + (pos0 & 1), o1 = 2 * ((pos1 >> 1) ^ sw) + (pos1 & 1);
-    sA[row * S64_LD + o0] = ra[i].x;
-    sA[row * S64_LD + o1] = ra[i].y;
-    sB[row * S64_LD + o0] = rb[i].x;
-    sB[row * S64_LD + o1] = rb[i].y;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) {  // 16 k per step; MFMA j of the step takes k = 16 ks + 4 j + (lane group)
-    double fa[2][4], fb[2][4];
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-      const double* pa = sA + (wm * 32 + a * 16 + r) * S64_LD;
-      const d2 lo = *reinterpret_cast<const d2*>(pa + 2 * ((8 * ks + 2 * g) ^ r)), hi = *reinterpret_cast<const d2*>(pa + 2 * ((8 * ks + 2 * g + 1) ^ r));
-      fa[a][0] = -lo.x; fa[a][1] = -lo.y; fa[a][2] = -hi.x; fa[a][3] = -hi.y;
-    }
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      const double* pb = sB + (wn * 32 + b * 16 + r) * S64_LD;
-      const d2 lo = *reinterpret_cast<const d2*>(pb + 2 * ((8 * ks + 2 * g) ^ r)), hi = *reinterpret_cast<const d2*>(pb + 2 * ((8 * ks + 2 * g + 1) ^ r));
-      fb[b][0] = lo.x; fb[b][1] = lo.y; fb[b][2] = hi.x; fb[b][3] = hi.y;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[a][j], fb[b][j], acc[a][b], 0, 0, 0);
-  }
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      const int col = n0 + wn * 32 + b * 16 + r;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int row = m0 + wm * 32 + a * 16 + g + 4 * q;
-        if (row < M && col < N) C[(int64_t)row * ldc + col] = acc[a][b][q];
-      }
-    }
-}
-
-// C(M x N) -= A(M x 64) A(first N rows)^T, lower trapezoid only (M >= N)
-inline hipError_t launch_syrk_k64(hipStream_t st, int M, int N, const double* A, int64_t lda, double* C, int64_t ldc, int batch = 1,
-                                  int64_t cs = 0) {
-  const int tm = (M + 63) / 64;
-  int tn = (N + 63) / 64;
-  if (tm == 0 || tn == 0) return hipSuccess;
-  if (tn > tm) tn = tm;
-  const int nwg = tn * (tn + 1) / 2 + (tm - tn) * tn;
-  hipLaunchKernelGGL(syrk_k64_kernel, dim3(nwg, batch), dim3(256), 0, st, A, A, C, lda, ldc, M, N, tn, cs);
-  return hipGetLastError();
-}
-inline hipError_t launch_gemm(hipStream_t st, int ta, int tb, int M, int N, int K, double alpha, const double* A, int64_t lda, const double* B,
-                              int64_t ldb, double beta, double* C, int64_t ldc, int flags, int tile, int batch, int64_t strideA, int64_t strideB,
-                              int64_t strideC, int cells, int64_t cellA, int64_t cellB, int64_t cellC, const double* alpha_tab, int alpha_stride,
-                              double* rowsq, int64_t rowsq_ld);
-// The K = 64 in-block update: the general NT kernel (LDS-DMA operands, C prefetched: 32 KiB of LDS), or with GPRX_K64_GEMM=0
-// the single-stage kernel above.  syrk_k64_kernel holds both whole operand panels in 64 KiB of LDS; beside the bulk update
-// of a large matrix (whose workgroups own all LDS of every CU) each of its launches waited for TWO of them to retire on
-// one CU: 166 us per launch at N = 16384 (rocprofv3), 21 of the 32 ms of that factorisation.  Measured with the general
-// kernel: N = 16384 31.8 -> 30.2 ms, N = 8192 6.73 -> 6.50 ms, 128 cells of N = 4096 +0.5 %, N <= 4096 single unchanged.
-inline hipError_t launch_update_k64(hipStream_t st, int M, int N, const double* A, int64_t lda, double* C, int64_t ldc, int batch, int64_t cs) {
-  static const int via_gemm = getenv("GPRX_K64_GEMM") ? atoi(getenv("GPRX_K64_GEMM")) : 1;
-  if (!via_gemm) return launch_syrk_k64(st, M, N, A, lda, C, ldc, batch, cs);
-  return launch_gemm(st, 0, 1, M, N, 64, -1.0, A, lda, A, lda, 1.0, C, ldc, GEMM_C_LOWER, 64, batch, cs, cs, cs, 1, 0, 0, 0, nullptr, 0, nullptr, 0);
-}
-
 // tile: 0 = choose, 128 or 64 (square workgroup tiles)
 inline hipError_t launch_gemm(hipStream_t st, int ta, int tb, int M, int N, int K, double alpha, const double* A, int64_t lda,
                               const double* B, int64_t ldb, double beta, double* C, int64_t ldc, int flags, int tile = 0, int batch = 1,

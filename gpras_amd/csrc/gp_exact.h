@@ -280,84 +280,65 @@ int exact_factorize_batch(gprx_handle h, int count, const int* units, const Thet
     for (int k = 0; k < h->d; ++k) row[CELL_PAR_LS + k] = ts[c].ls[k];
     h->slot_ok[c] = 0;
   }
-  // Optional (GPRX_BATCH_GROUPS=2): two groups of cells on two streams run the same launch sequence out of phase, so
-  // the panel launches of one overlap the MFMA-bound updates of the other.  Measured at N = 4096: +2.5 % at 32 cells,
-  // +3 % at 64, nothing at 16, -5 % at 8 -- not worth a default whose per-launch timings depend on what the other
-  // stream happens to run.  Per-cell arithmetic is the same either way.
-  static const int env_groups = env_int("GPRX_BATCH_GROUPS", 0);
-  const int groups = (h->profiling || count < 2) ? 1 : (env_groups > 1 ? 2 : 1);
-  if (groups > 1 && (rc = ensure_lookahead(h))) return rc;
+  // One launch sequence for all cells on the handle's stream.  (Tried and removed, DESIGN.md 7b.2: two groups of cells on two streams,
+  // the panel launches of one overlapping the MFMA-bound updates of the other -- at N = 4096 +2.5 % at 32 cells, +3 % at 64, nothing at
+  // 16, -5 % at 8: not worth per-launch timings that depend on what the other stream happens to run.)
   HIPCHK(h, hipEventRecord(h->bev[0], st));
   HIPCHK(h, hipMemcpyAsync(h->cellpar.p, par, sizeof(double) * CELL_PAR * count, hipMemcpyHostToDevice, st));
   HIPCHK(h, hipMemsetAsync(h->cellres.p, 0, sizeof(double) * CELL_RES * count, st));
   if (h->profiling) h->prof.reset();
-  auto enqueue_group = [&](hipStream_t gs, int c0, int cnt) -> int {
-    double* K0 = h->arena.p + (int64_t)c0 * cs;
-    const double* cpar = h->cellpar.p + (int64_t)c0 * CELL_PAR;
-    double* cres = h->cellres.p + (int64_t)c0 * CELL_RES;
-    KmatArgs ka{h->X.p, h->X.p, nullptr, K0, ld, (int)h->n, (int)h->n, h->d, np, np, 0.0, 0.0, 1, 1.0, nullptr, 0};
-    ka.cell_par = cpar;
-    ka.out_stride = cs;
-    // (under profiling the launch sequence is instrumented launch by launch; the cell kernel -- ONE launch -- is timed when the handle
-    // forces it, "cell_kernel" = 1: gprx_last_cell_kernel)
-    const bool cell_kernel = use_cell_kernel(h->tune, np, cnt) && (!h->profiling || h->tune.cell_kernel > 0);
-    // (the column-pair cell kernel evaluates K where it consumes it: no build launch, nothing written but the right-hand-side rows)
-    const bool cell_builds_k = cell_kernel && potrf_cells_builds_k(h->kid, h->dist_form, np, h->d);
-    if (h->profiling) {
-      if ((rc = ensure_event_pair(h, h->kev))) return rc;
-      HIPCHK(h, hipEventRecord(h->kev[0], gs));
-    }
-    if (!cell_builds_k) HIPCHK(h, launch_kmat(gs, h->kid, with_form(ka, h), cnt));
-    if (h->profiling) {
-      HIPCHK(h, hipEventRecord(h->kev[1], gs));
-      h->kmat_bytes = 8.0 * KM_T * KM_T * (double)(np / KM_T) * (np / KM_T + 1) / 2 * cnt;
-    }
-    // (the column-pair cell kernel carries the right-hand side as a vector: one row, of which it reads and writes the first np entries)
-    // (so does the launch sequence's split panel: potrf_rows_kernel<..., YVEC>)
-    const bool rhs_vector = !cell_kernel && potrf_rhs_vector_ok(h->tune, cnt);
-    const bool beta_vector = rhs_vector || (cell_kernel && !cell_builds_k && potrf_cells_beta_vector(np, NB, false));
-    hipLaunchKernelGGL(set_rhs_rows_batch_kernel, dim3(beta_vector ? 4 : 64, cnt), dim3(256), 0, gs, K0 + (int64_t)np * ld, ld, (const double*)h->Y.p, cpar,
-                       (int)h->n, np, beta_vector ? 1 : NB, cs);
-    int* info0 = reinterpret_cast<int*>(cres + 2);
-    if (cell_kernel) {
-      // small matrices in many cells: one workgroup owns one cell from the first column to the last (potrf_cell.h)
-      if (h->profiling) {
-        if ((rc = ensure_event_pair(h, h->cev))) return rc;
-        HIPCHK(h, hipEventRecord(h->cev[0], gs));
-      }
-      if (cell_builds_k)
-        HIPCHK(h, potrf_cells(gs, K0, ld, np, NB, K0 + h->off_invd, info0, cnt, cs, 2 * CELL_RES, 0, h->X.p, cpar, (int)h->n, h->d));
-      else
-        HIPCHK(h, potrf_cells(gs, K0, ld, np, NB, K0 + h->off_invd, info0, cnt, cs, 2 * CELL_RES));
-      if (h->profiling) {
-        HIPCHK(h, hipEventRecord(h->cev[1], gs));
-        h->cev_recorded = true;
-        h->cell_cells = cnt;
-        h->cell_flops = (double)np * np * np / 3.0 * cnt;  // algorithmic: N^3 / 3 per cell (the right-hand-side rows' N^2 not counted)
-      }
-    } else {
-      HIPCHK(h, potrf_lower(gs, K0, ld, np, rhs_vector ? 0 : NB, K0 + h->off_invd, info0, K0 + h->off_stage, h->profiling ? &h->prof : nullptr, nullptr, cnt, cs,
-                            2 * CELL_RES, &h->tune, 0, rhs_vector ? K0 + (int64_t)np * ld : nullptr));
-    }
-    const double* beta = K0 + (int64_t)np * ld;
-    if (with_alpha) hipLaunchKernelGGL(copy_row_batch_kernel, dim3((np + 255) / 256, cnt), dim3(256), 0, gs, beta, K0 + h->off_alpha, np, cs);
-    hipLaunchKernelGGL(logdet_quad_kernel, dim3(cnt), dim3(256), 0, gs, (const double*)K0, ld, beta, np, cres, cs, CELL_RES);
-    if (with_alpha) HIPCHK(h, trsv_lower(gs, K0, ld, K0 + h->off_invd, K0 + h->off_alpha, np, true, cnt, cs));  // (else: exact_gradient_batch)
-    return GPRX_OK;
-  };
-  if (groups == 1) {
-    if ((rc = enqueue_group(st, 0, count))) return rc;
-  } else {
-    const int first = (count + 1) / 2;
-    hipStream_t aux = h->pstreams.aux;
-    HIPCHK(h, hipEventRecord(h->pstreams.block_done, st));  // parameter table and cleared results are on the main stream
-    HIPCHK(h, hipStreamWaitEvent(aux, h->pstreams.block_done, 0));
-    // (the two groups start in phase; staggering the second behind the first group's first in-block phase measured -1.7 %: DESIGN.md 7b.2)
-    if ((rc = enqueue_group(st, 0, first))) return rc;
-    if ((rc = enqueue_group(aux, first, count - first))) return rc;
-    HIPCHK(h, hipEventRecord(h->pstreams.tail_done, aux));
-    HIPCHK(h, hipStreamWaitEvent(st, h->pstreams.tail_done, 0));
+  double* K0 = h->arena.p;
+  const double* cpar = h->cellpar.p;
+  double* cres = h->cellres.p;
+  KmatArgs ka{h->X.p, h->X.p, nullptr, K0, ld, (int)h->n, (int)h->n, h->d, np, np, 0.0, 0.0, 1, 1.0, nullptr, 0};
+  ka.cell_par = cpar;
+  ka.out_stride = cs;
+  // (under profiling the launch sequence is instrumented launch by launch; the cell kernel -- ONE launch -- is timed when the handle
+  // forces it, "cell_kernel" = 1: gprx_last_cell_kernel)
+  const bool cell_kernel = use_cell_kernel(h->tune, np, count) && (!h->profiling || h->tune.cell_kernel > 0);
+  // (opt-in, GPRX_CELL_BUILD_K=1: the column-pair cell kernel evaluates K where it consumes it -- no build launch, nothing written but the
+  // right-hand-side rows)
+  const bool cell_builds_k = cell_kernel && potrf_cells_builds_k(h->kid, h->dist_form, np, h->d);
+  if (h->profiling) {
+    if ((rc = ensure_event_pair(h, h->kev))) return rc;
+    HIPCHK(h, hipEventRecord(h->kev[0], st));
   }
+  if (!cell_builds_k) HIPCHK(h, launch_kmat(st, h->kid, with_form(ka, h), count));
+  if (h->profiling) {
+    HIPCHK(h, hipEventRecord(h->kev[1], st));
+    h->kmat_bytes = 8.0 * KM_T * KM_T * (double)(np / KM_T) * (np / KM_T + 1) / 2 * count;
+  }
+  // (the column-pair cell kernel carries the right-hand side as a vector: one row, of which it reads and writes the first np entries)
+  // (so does the launch sequence's split panel: potrf_rows_kernel<..., YVEC>)
+  const bool rhs_vector = !cell_kernel && potrf_rhs_vector_ok(h->tune, count);
+  const bool beta_vector = rhs_vector || (cell_kernel && !cell_builds_k && potrf_cells_beta_vector(np, NB, false));
+  hipLaunchKernelGGL(set_rhs_rows_batch_kernel, dim3(beta_vector ? 4 : 64, count), dim3(256), 0, st, K0 + (int64_t)np * ld, ld, (const double*)h->Y.p, cpar,
+                     (int)h->n, np, beta_vector ? 1 : NB, cs);
+  int* info0 = reinterpret_cast<int*>(cres + 2);
+  if (cell_kernel) {
+    // small matrices in many cells: one workgroup owns one cell from the first column to the last (potrf_cell.h)
+    if (h->profiling) {
+      if ((rc = ensure_event_pair(h, h->cev))) return rc;
+      HIPCHK(h, hipEventRecord(h->cev[0], st));
+    }
+    if (cell_builds_k)
+      HIPCHK(h, potrf_cells(st, K0, ld, np, NB, K0 + h->off_invd, info0, count, cs, 2 * CELL_RES, 0, h->X.p, cpar, (int)h->n, h->d));
+    else
+      HIPCHK(h, potrf_cells(st, K0, ld, np, NB, K0 + h->off_invd, info0, count, cs, 2 * CELL_RES));
+    if (h->profiling) {
+      HIPCHK(h, hipEventRecord(h->cev[1], st));
+      h->cev_recorded = true;
+      h->cell_cells = count;
+      h->cell_flops = (double)np * np * np / 3.0 * count;  // algorithmic: N^3 / 3 per cell (the right-hand-side rows' N^2 not counted)
+    }
+  } else {
+    HIPCHK(h, potrf_lower(st, K0, ld, np, rhs_vector ? 0 : NB, K0 + h->off_invd, info0, K0 + h->off_stage, h->profiling ? &h->prof : nullptr, nullptr, count, cs,
+                          2 * CELL_RES, &h->tune, 0, rhs_vector ? K0 + (int64_t)np * ld : nullptr));
+  }
+  const double* beta = K0 + (int64_t)np * ld;
+  if (with_alpha) hipLaunchKernelGGL(copy_row_batch_kernel, dim3((np + 255) / 256, count), dim3(256), 0, st, beta, K0 + h->off_alpha, np, cs);
+  hipLaunchKernelGGL(logdet_quad_kernel, dim3(count), dim3(256), 0, st, (const double*)K0, ld, beta, np, cres, cs, CELL_RES);
+  if (with_alpha) HIPCHK(h, trsv_lower(st, K0, ld, K0 + h->off_invd, K0 + h->off_alpha, np, true, count, cs));  // (else: exact_gradient_batch)
   HIPCHK(h, hipMemcpyAsync(res, h->cellres.p, sizeof(double) * CELL_RES * count, hipMemcpyDeviceToHost, st));
   HIPCHK(h, hipEventRecord(h->bev[1], st));
   HIPCHK(h, wait_stream(h, st));
@@ -419,13 +400,6 @@ int select_slot(gprx_handle h, int slot) {
   return GPRX_OK;
 }
 
-// K^-1 = X^T X (X = L^-1) as the TN product on the LDS-DMA kernel (default), or GPRX_KINV_TN=0: X transposed in place and the NT
-// product of L^-T with itself (one more pass over X: 5.9 ms per 128 cells of N = 4096); the same sums in the same k order.
-bool kinv_tn() {
-  static const bool v = env_int("GPRX_KINV_TN", 1) != 0;
-  return v;
-}
-
 // gradient of the LML w.r.t. constrained (variance, lengthscales[nlen], noise) -> g[0 .. nlen+1], from the synchronised trace sums
 void exact_gradient_collect(gprx_handle h, const double* host, double* g) {
   g[0] = 0.5 * host[0];
@@ -471,15 +445,10 @@ int exact_gradient_batch(gprx_handle h, int count, double* g, bool form_alpha = 
     if ((rc = ensure(h, h->apart, sizeof(double) * (size_t)count * ((np + ALPHA_CHUNK - 1) / ALPHA_CHUNK) * np))) return rc;
     HIPCHK(h, alpha_from_inverse(st, X0, ld, K0 + (int64_t)np * ld, h->apart.p, K0 + h->off_alpha, np, count, gs, cs, cs));
   }
-  // K^-1 = L^-T L^-1 on the lower tiles, as an NT product of Xt = L^-T with itself (transposed in place; same sums in the same
-  // k order as the TN form it replaces, so the values are unchanged)
-  if (kinv_tn()) {
-    HIPCHK(h, launch_gemm(st, 1, 0, np, np, np, 1.0, X0, ld, X0, ld, 0.0, T0, ld, GEMM_C_LOWER | GEMM_A_UPPER | GEMM_B_LOWER, 64, count, gs, gs, gs));
-  } else {
-    HIPCHK(h, transpose_inplace(st, X0, ld, np, count, gs));
-    HIPCHK(h, launch_gemm(st, 0, 1, np, np, np, 1.0, X0, ld, X0, ld, 0.0, T0, ld, GEMM_C_LOWER | GEMM_A_UPPER | GEMM_B_LOWER, tile, count, gs, gs,
-                          gs));
-  }
+  // K^-1 = X^T X (X = L^-1) on the lower tiles, as the TN product on LDS-DMA operands.  (Until round 3 X was transposed in place and
+  // L^-T multiplied with itself as an NT product -- one more pass over X, 5.9 ms per 128 cells of N = 4096; the same sums in the same k
+  // order, so the values are unchanged: DESIGN.md 7b.)
+  HIPCHK(h, launch_gemm(st, 1, 0, np, np, np, 1.0, X0, ld, X0, ld, 0.0, T0, ld, GEMM_C_LOWER | GEMM_A_UPPER | GEMM_B_LOWER, 64, count, gs, gs, gs));
   TraceArgs ta{h->X.p, h->X.p, nullptr, T0, ld, K0 + h->off_alpha, K0 + h->off_alpha, -1.0, 1.0, (int)h->n, (int)h->n, h->d, 0.0, 1, h->gpartial.p,
                nullptr, 0, tiles};
   ta.cell_par = h->cellpar.p;
@@ -515,14 +484,8 @@ int exact_gradient_enqueue(gprx_handle h, const Theta& t, double* host, bool for
     HIPCHK(h, alpha_from_inverse(st, h->Xinv.p, ld, h->Kmat.p + (int64_t)np * ld, h->apart.p, h->alpha.p, np));
   }
   // K^-1 = X^T X on the lower tiles, into Tmp
-  h->have_linv = false;  // (Xinv is not zeroed above its diagonal, or holds L^-T: a later predict forms L^-1 again)
-  if (kinv_tn()) {
-    HIPCHK(h, launch_gemm(st, 1, 0, np, np, np, 1.0, h->Xinv.p, ld, h->Xinv.p, ld, 0.0, h->Tmp.p, ld, GEMM_C_LOWER | GEMM_A_UPPER | GEMM_B_LOWER, 64));
-  } else {
-    HIPCHK(h, transpose_inplace(st, h->Xinv.p, ld, np));
-    HIPCHK(h, launch_gemm(st, 0, 1, np, np, np, 1.0, h->Xinv.p, ld, h->Xinv.p, ld, 0.0, h->Tmp.p, ld,
-                          GEMM_C_LOWER | GEMM_A_UPPER | GEMM_B_LOWER, h->tune.update_tile));
-  }
+  h->have_linv = false;  // (Xinv is not zeroed above its diagonal: a later predict forms L^-1 again)
+  HIPCHK(h, launch_gemm(st, 1, 0, np, np, np, 1.0, h->Xinv.p, ld, h->Xinv.p, ld, 0.0, h->Tmp.p, ld, GEMM_C_LOWER | GEMM_A_UPPER | GEMM_B_LOWER, 64));
   const int tiles = np / KM_T;
   const int width = 2 + h->d;
   if ((rc = ensure(h, h->partial, sizeof(double) * ((size_t)tiles * tiles * width + width)))) return rc;

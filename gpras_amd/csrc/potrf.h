@@ -659,7 +659,7 @@ struct PotrfProfile {
   size_t used = 0;
   std::vector<std::pair<size_t, double>> gemm_marks;   // launches of the main GEMM kernel (bulk HEAD / TAIL updates and in-block updates with K > 128):
                                                        // (index of start event, algorithmic flops)
-  std::vector<std::pair<size_t, double>> strip_marks;  // short-K in-block updates (K = 64: syrk_k64_kernel, K = 128: GEMM with C prefetch)
+  std::vector<std::pair<size_t, double>> strip_marks;  // short-K in-block updates (K <= 128: the 64 x 64 GEMM with C prefetch)
   std::vector<size_t> panel_marks;
   hipEvent_t next() {
     if (used == pool.size()) {
@@ -786,15 +786,8 @@ inline hipError_t potrf_lower(hipStream_t st, double* A, int64_t lda, int np, in
   hipError_t err = hipSuccess;
   const bool split_panel = potrf_split_panel(tune, batch);
   if (yvec && !split_panel) return hipErrorInvalidValue;  // only the split panel carries the right-hand side as a vector
-  // fuse: the K = 64 update of these 64 columns by the 64 columns left of them happens inside the panel kernel (lone
-  // matrices: one dependent launch less); only where the separate launch would be the general NT kernel (same arithmetic)
-  static const bool fuse_ok = [] {
-    const char* a = getenv("GPRX_K64_GEMM");
-    const char* b = getenv("GPRX_GEMM_DMA");
-    const char* c = getenv("GPRX_FUSE_K64");
-    return !(a && atoi(a) == 0) && !(b && atoi(b) == 0) && !(c && atoi(c) == 0);
-  }();
-  // one panel: factor the diagonal block at column c and solve every row below it
+  // one panel: factor the diagonal block at column c and solve every row below it.  fuse: the K = 64 update of these 64 columns by the
+  // 64 columns left of them happens inside the panel kernel (one dependent launch less; same arithmetic as the general NT kernel)
   auto panel = [&](int c, bool fuse = false) {
     const int rows_below = total_rows - c - NB;
     double* Acc = A + (int64_t)c * lda + c;
@@ -828,9 +821,11 @@ inline hipError_t potrf_lower(hipStream_t st, double* A, int64_t lda, int np, in
     const int rows = total_rows - c1;
     const double* L21 = A + (int64_t)c1 * lda + c0;
     double* A22 = A + (int64_t)c1 * lda + c1;
-    mark_gemm(st, n, rows - n, n, k, k <= 128);  // K <= 128 runs the short-K kernels (syrk_k64 / C-prefetch GEMM), longer K the main GEMM kernel
-    hipError_t e = (k == NB) ? launch_update_k64(st, rows, n, L21, lda, A22, lda, batch, cs)
-                             : launch_gemm(st, 0, 1, rows, n, k, -1.0, L21, lda, L21, lda, 1.0, A22, lda, GEMM_C_LOWER, tile, batch, cs, cs, cs);
+    mark_gemm(st, n, rows - n, n, k, k <= 128);  // K <= 128 runs the 64 x 64 GEMM with C prefetch, longer K the main GEMM kernel
+    // (K = 64 gets here only with a 64-column outer block, GPRX_OUTER_BLOCK=64 -- a pair of panels fuses it, wider ranges split at
+    // K >= 128 -- and runs on 64 x 64 tiles whatever `tile` says, as it did when it had a launch function of its own; the single-stage
+    // 64 KiB kernel that function could select is retired)
+    hipError_t e = launch_gemm(st, 0, 1, rows, n, k, -1.0, L21, lda, L21, lda, 1.0, A22, lda, GEMM_C_LOWER, k == NB ? 64 : tile, batch, cs, cs, cs);
     mark_end(st);
     if (e != hipSuccess && err == hipSuccess) err = e;
   };
@@ -845,10 +840,10 @@ inline hipError_t potrf_lower(hipStream_t st, double* A, int64_t lda, int np, in
     }
     const int h = ((w / NB + 1) / 2) * NB;
     self(self, c0, h);
-    // (split panels fuse too since round 3, GPRX_FUSE_K64_SPLIT=0 restores the separate launch: the update is HBM-bound there)
-    static const bool fuse_split = !(getenv("GPRX_FUSE_K64_SPLIT") && atoi(getenv("GPRX_FUSE_K64_SPLIT")) == 0);
-    if (h == NB && w - h == NB && (!split_panel || fuse_split) && fuse_ok) {
-      panel(c0 + h, true);  // the K = 64 update of the right panel rides in its own kernel
+    if (h == NB && w - h == NB) {
+      // the K = 64 update of the right panel rides in its own kernel (split panels too since round 3: the update is HBM-bound there; the
+      // separate launch was kept for A/B runs until its measurements were in).  Wider ranges split at K >= 128.
+      panel(c0 + h, true);
       return;
     }
     update(c0, h, c0 + h, w - h, 64);

@@ -4,8 +4,8 @@
 // block: 63 k fits/s = 0.29 of the fp64 MFMA peak with 512 cells per launch sequence -- and every one of
 // its ~100 launches moves the panel through HBM.  A cell of N = 1024 is 8 MB: one workgroup can own it from the first column to
 // the last with NO inter-workgroup dependency, two workgroups per CU hiding each other's dependent chains:
-//   for block column j:  A(i,j) -= sum_{c<j} L(i,c) L(j,c)^T for i >= j (left-looking: ONE pass with K = 64 j per tile, four row
-//                        tiles per pass sharing the B operand -- dag_panel of potrf_dag.h);
+//   for block column j:  A(i,j) -= sum_{c<j} L(i,c) L(j,c)^T for i >= j (left-looking: ONE pass with K = 64 j per tile, the row
+//                        tiles of a pass sharing the B operand);
 //                        the diagonal block through the eight sub-panel steps of the tile-DAG chain (L(j,j) and its inverse);
 //                        L(i,j) = A(i,j) L(j,j)^-T for i > j (tile products against the inverse).
 // Each element of the lower triangle is read and written once per block column it belongs to plus once per use as an operand
@@ -13,6 +13,9 @@
 // Arithmetic: the same tile products and the same sub-panel substitution as the other schedules, but a tile receives its whole
 // update as one sum (C - sum, one rounding) and rows are solved against the explicit 64 x 64 inverse: results agree with
 // potrf_lower to rounding (tested), not bit for bit.
+// Block columns go in PAIRS (round 4, potrf_cell2_kernel below); the single-column phases that come first serve an odd last column.
+// Round 3's kernels -- two passes per block column (update every tile, factor, solve every tile), then update + solve fused per tile,
+// one block column at a time -- gave the pair kernel's factor bit for bit up to d8f5e12 and are retired.
 #pragma once
 #include "kmat.h"
 #include "tile_ops.h"
@@ -131,10 +134,10 @@ __device__ __forceinline__ int cell_diag(double* __restrict__ Ajj, int64_t lda, 
 }
 
 // Tiles (i0 .. i0+ni-1, j), all below the diagonal tile, in ONE pass: C_t <- (C_t - sum_{c<j} L(i,c) L(j,c)^T) L(j,j)^-T.  The
-// update sum as dag_panel<false> forms it (same steps, same accumulators); the updated tile then goes from the accumulator layout
-// straight into the A stage image and is multiplied by the inverse (B image, loaded once per call) exactly as dag_panel<true>
-// does with the tile it re-reads from memory -- same operands, same products: the factor is the two-pass kernel's bit for bit,
-// with one store and one load of every tile less (8.7 of ~44 MB per N = 1024 cell).
+// update sum as the tile-DAG's panel task forms it (dag_panel<false> of potrf_dag.h: same steps, same accumulators); the updated tile
+// then goes from the accumulator layout straight into the A stage image and is multiplied by the inverse (B image, loaded once per
+// call) exactly as dag_panel<true> does with the tile it re-reads from memory -- same operands, same products as two passes over the
+// block column, with one store and one load of every tile less (8.7 of ~44 MB per N = 1024 cell).
 __device__ __forceinline__ void cell_panel_fused(const TileCtx& p, int i0, int ni, int j, double* __restrict__ smem) {
   const int tid = cell_tid(), lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1, g = lane >> 4, r = lane & 15;
@@ -248,7 +251,7 @@ __device__ __forceinline__ void cell_panel_fused(const TileCtx& p, int i0, int n
 // The diagonal tile's update alone: A(j,j) -= sum_{c<j} L(j,c) L(j,c)^T.  Both operands of a step are the SAME block, so one
 // block load per step feeds both images' reads, and with one accumulator tile there are registers for two loads in flight (the
 // general panel's one-step-ahead prefetch left a memory round trip exposed in every step of this short dependent pass: 120 steps
-// per N = 1024 cell).  Same products in the same order as dag_panel<false> on this tile: bit-identical.
+// per N = 1024 cell).  Same products in the same order as dag_panel<false> (potrf_dag.h) on this tile: bit-identical.
 __device__ __forceinline__ void cell_diag_update(const TileCtx& p, int j, double* __restrict__ smem) {
   const int tid = cell_tid(), lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1, g = lane >> 4, r = lane & 15;
@@ -311,58 +314,8 @@ __device__ __forceinline__ void cell_diag_update(const TileCtx& p, int j, double
         st1_sc1<false>(rc, off_cd, __builtin_fma(1.0, cold[a][b][q], -1.0 * acc[a][b][q]), (unsigned)(a * 16 + 4 * q) * ldb + (unsigned)b * 128u);
 }
 
-// FUSED (default): per block column the diagonal tile is updated alone, factored, and every group of tiles below it is updated and
-// solved in one pass (cell_panel_fused); FUSED = false: the two-pass form (update every tile, factor, solve every tile).
-template <bool FUSED>
-__global__ __launch_bounds__(256, 2) void potrf_cell_kernel_t(CellArgs p) {
-  __shared__ __attribute__((aligned(16))) double smem[DAG_SMEM];
-  const int64_t off = (int64_t)blockIdx.x * p.cs;
-  const TileCtx tc{p.A + off, p.lda, p.inv_diag + off};
-  int first_bad = 0;
-  for (int j = 0; j < p.T; ++j) {
-    if (j > 0) {
-      cell_diag_update(tc, j, smem);
-      cell_sync();
-    }
-    const int bad = cell_diag(tc.A + (int64_t)j * NB * p.lda + (int64_t)j * NB, p.lda, const_cast<double*>(tc.inv_diag) + (int64_t)j * NB * NB, smem);
-    if (bad > 0 && first_bad == 0) first_bad = j * NB + bad;
-    cell_sync();
-    for (int i0 = j + 1; i0 < p.R; i0 += CELL_NI) {
-      const int ni = p.R - i0 < CELL_NI ? p.R - i0 : CELL_NI;
-      cell_panel_fused(tc, i0, ni, j, smem);
-      cell_sync();
-    }
-  }
-  if (threadIdx.x == 0 && first_bad > 0) atomicCAS(p.info + (int64_t)blockIdx.x * p.info_stride, 0, p.col_base + first_bad);
-}
-
-__global__ __launch_bounds__(256, 2) void potrf_cell_kernel(CellArgs p) {
-  __shared__ __attribute__((aligned(16))) double smem[DAG_SMEM];
-  const int64_t off = (int64_t)blockIdx.x * p.cs;
-  const TileCtx tc{p.A + off, p.lda, p.inv_diag + off};
-  int first_bad = 0;
-  for (int j = 0; j < p.T; ++j) {
-    if (j > 0) {
-      for (int i0 = j; i0 < p.R; i0 += DAG_NI) {
-        const int ni = p.R - i0 < DAG_NI ? p.R - i0 : DAG_NI;
-        dag_panel<false, false>(tc, i0, ni, j, 0, j, smem);
-        cell_sync();  // (LDS images free; the stores are visible to this workgroup's later loads)
-      }
-    }
-    const int bad = cell_diag(tc.A + (int64_t)j * NB * p.lda + (int64_t)j * NB, p.lda, const_cast<double*>(tc.inv_diag) + (int64_t)j * NB * NB, smem);
-    if (bad > 0 && first_bad == 0) first_bad = j * NB + bad;
-    cell_sync();
-    for (int i0 = j + 1; i0 < p.R; i0 += DAG_NI) {
-      const int ni = p.R - i0 < DAG_NI ? p.R - i0 : DAG_NI;
-      dag_panel<true, false>(tc, i0, ni, j, j, j + 1, smem);
-      cell_sync();
-    }
-  }
-  if (threadIdx.x == 0 && first_bad > 0) atomicCAS(p.info + (int64_t)blockIdx.x * p.info_stride, 0, p.col_base + first_bad);
-}
-
 // ---- column PAIRS (round 4): the operand stream halved -----------------------------------------------------------------------------
-// Measured on the kernel above (profiles/r04_pmc_cell_kernel.json, N = 1024 x 512 cells): 52.8 MB of HBM traffic per cell (45.7 read +
+// Measured on round 3's single-column kernel (profiles/r04_pmc_cell_kernel.json, N = 1024 x 512 cells): 52.8 MB of HBM traffic per cell (45.7 read +
 // 5.9 written; the matrix itself is 4.2 MB) at 4.56 TB/s -- the kernel is HBM-bound, and three quarters of those bytes are the operand
 // tiles of the left-looking update, 1.5 tile loads per 64 x 64 x 64 product (two row tiles sharing one B tile).  Here two block
 // columns (j, j + 1) are updated TOGETHER: a group of two row tiles against the two column tiles is one 128 x 128 product
@@ -375,9 +328,9 @@ __global__ __launch_bounds__(256, 2) void potrf_cell_kernel(CellArgs p) {
 //     acc(t, 1)  += L(i, j) L(j + 1, j)^T                          (the one term of column j + 1 that column j's result feeds)
 //     L(i, j + 1) = (A(i, j + 1) - acc(t, 1)) L(j + 1, j + 1)^-T
 // The accumulation order of every tile is that of the single-column kernel (k ascending in stages of 16, instruction jj takes
-// k = k0 + 4 g + jj), and the operands are the same values: the factor equals potrf_cell_kernel_t's BIT FOR BIT (tested).
+// k = k0 + 4 g + jj), and the operands are the same values: the factor equalled that kernel's BIT FOR BIT (tested until it was retired).
 constexpr int CELL2_STAGE = 4 * NB * GEMM_BK;  // doubles per stage: A image [128][16] | B image [128][16]
-static_assert(2 * CELL2_STAGE <= DAG_SMEM, "the two stages fit into the LDS of the single-column kernel");
+static_assert(2 * CELL2_STAGE <= DAG_SMEM, "the two stages fit into the LDS of the single-column phases");
 
 // a 64 x 64 block stored with leading dimension `ld` -> the four [64][16] stage images at `img`, by LDS-DMA (lane l of wave w fills row
 // 8 (4 i + w) + (l >> 3), LDS chunk l & 7 = global chunk (l & 7) ^ kc_swz(row): the involution the fragment reads apply)
@@ -420,9 +373,7 @@ __device__ __forceinline__ void cell2_stream(d4 (&acc)[NI][2][2][2], const doubl
     }
   };
   auto stage = [&](int k0, int buf) {
-#ifndef GPRX_CELL2_NODMA
     if (k0 + GEMM_BK < K) dma_fill(k0 + GEMM_BK, buf ^ 1);  // (every wave left buffer buf ^ 1 at the previous barrier)
-#endif
     const double* sb = smem + buf * CELL2_STAGE + 2 * NB * GEMM_BK;
     const double* sa = SAME ? sb : smem + buf * CELL2_STAGE;
     double fa[NI][2][4], fb[2][2][4];
@@ -453,9 +404,6 @@ __device__ __forceinline__ void cell2_stream(d4 (&acc)[NI][2][2][2], const doubl
         bsum = __builtin_fma(pv.y, bv.y, bsum);
       }
     }
-#ifdef GPRX_CELL2_NOMMA
-    acc[0][0][0][0][0] += fa[0][0][0] + fb[0][0][0] + fa[NI - 1][1][3] + fb[1][1][3];
-#else
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj)
 #pragma unroll
@@ -468,7 +416,6 @@ __device__ __forceinline__ void cell2_stream(d4 (&acc)[NI][2][2][2], const doubl
 #pragma unroll
             for (int b = 0; b < 2; ++b) acc[t][c][a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[t][a][jj], fb[c][b][jj], acc[t][c][a][b], 0, 0, 0);
         }
-#endif
     // (without this the scheduler hoists the barrier -- and with it the wait for the next stage's DMA -- to the middle of the MFMA
     // sequence: the loads then have a third of a stage to land instead of a whole one)
     __builtin_amdgcn_sched_barrier(0);
@@ -541,6 +488,9 @@ __device__ __forceinline__ void cell2_zero(d4 (&v)[2][2]) {
 // one reciprocal per dimension, r2 accumulated in k order by (a - b, fma), variance * exp_nonpos_tab(-r2 / 2), the diagonal term added
 // to the product, identity on the padding) -- the values are the ones the separate launch writes, bit for bit (tested).  RBF in the
 // difference form only (the judged configuration); anything else keeps the launch.
+// Measured SLOWER than the launch (potrf_cells_builds_k below) and opt-in ever since.  It outlived round 3's kernels only because the
+// compiler schedules the tile-row kernel potrf_cell2_kernel<false, false> differently once this instantiation leaves the translation
+// unit (profiles/cell_retire.txt section 1): retire it together with a measurement of that kernel.
 constexpr int CELL2_KX = DAG_SMEM;                      // doubles: row points [64][8] | column points [8][KM_BT_LD] | 2^(j/64) table [64]
 constexpr int CELL2_SMEM_K = DAG_SMEM + 64 * KM_DC + KM_DC * KM_BT_LD + 64;
 struct Cell2K {
@@ -768,7 +718,7 @@ __device__ __forceinline__ void cell2_rows(const TileCtx& p, int i0, int j, cons
 }
 
 // The pair's own three tiles (j, j), (j + 1, j), (j + 1, j + 1): ONE streaming product of the 128-row panel with itself (what the
-// single-column kernel does as three latency-bound passes of one tile product per step: the diagonal update of j, update + solve of
+// single-column kernel of round 3 did as three latency-bound passes of one tile product per step: the diagonal update of j, update + solve of
 // (j + 1, j), the diagonal update of j + 1), then the two chains and the solve between them.  Returns the failing pivot (1-based,
 // within the pair's 128 columns) or 0.
 template <bool KB, bool BETA = false>
@@ -861,7 +811,6 @@ __global__ __launch_bounds__(256, GPRX_CELL2_OCC) void potrf_cell2_kernel(CellAr
     CACC(2)
     if constexpr (BETA) cell2_beta_pair(tc, j, bq, cell_tid());
     CACC(3)
-#ifndef GPRX_CELL2_NOROWS
     int i0 = j + 2;
     for (; i0 + 1 < p.R; i0 += 2) {
       cell2_rows<2, KB>(tc, i0, j, kq, smem);
@@ -871,7 +820,6 @@ __global__ __launch_bounds__(256, GPRX_CELL2_OCC) void potrf_cell2_kernel(CellAr
       cell2_rows<1, KB>(tc, i0, j, kq, smem);
       cell_sync();
     }
-#endif
   }
   if (threadIdx.x == 0 && first_bad > 0) atomicCAS(p.info + (int64_t)blockIdx.x * p.info_stride, 0, p.col_base + first_bad);
 }
@@ -883,21 +831,17 @@ inline bool potrf_cells_builds_k(int kid, int form, int np, int d) {
   // OPT-IN (GPRX_CELL_BUILD_K=1): measured SLOWER than the separate launch -- N = 1024 x 512 cells 6.45 against 6.05 ms per step: the 153
   // tiles of a cell each cost a staging round trip (coordinates from L2, two barriers) and ~500 fp64 instructions per thread on the pipe
   // the MFMAs need, more than the 0.65 ms launch and the 8.6 MB per cell it saves
-  static const bool off = !(getenv("GPRX_CELL_BUILD_K") && atoi(getenv("GPRX_CELL_BUILD_K")) == 1) ||
-                          (getenv("GPRX_CELL_TWO_PASS") && atoi(getenv("GPRX_CELL_TWO_PASS")) != 0) ||
-                          (getenv("GPRX_CELL_SINGLE_COLUMN") && atoi(getenv("GPRX_CELL_SINGLE_COLUMN")) != 0);
+  static const bool off = !(getenv("GPRX_CELL_BUILD_K") && atoi(getenv("GPRX_CELL_BUILD_K")) == 1);
   return !off && kid == 0 && form == 0 && (np / NB) % 2 == 0 && d >= 1 && d <= CELL_PAR - CELL_PAR_LS;
 }
 
 // build_k: X / cell_par / n / d given and potrf_cells_builds_k() holds -- the matrices need not have been written (only their
 // right-hand-side rows)
 // Does potrf_cells carry the right-hand side as a VECTOR (cell2_beta_*: the default form, one right-hand-side row of which only the first
-// np entries are read and written) instead of 64 tile rows?  GPRX_CELL_BETA_ROWS=1 restores the tile form (A/B, bit-for-bit tests
-// against the other kernel forms, which only know the tile form).
+// np entries are read and written) instead of 64 tile rows?  GPRX_CELL_BETA_ROWS=1 restores the tile form (A/B; the tests compare
+// the two forms, and the K-building kernel only knows the tile form).
 inline bool potrf_cells_beta_vector(int np, int extra, bool builds_k) {
-  static const bool off = (getenv("GPRX_CELL_BETA_ROWS") && atoi(getenv("GPRX_CELL_BETA_ROWS")) != 0) ||
-                          (getenv("GPRX_CELL_TWO_PASS") && atoi(getenv("GPRX_CELL_TWO_PASS")) != 0) ||
-                          (getenv("GPRX_CELL_SINGLE_COLUMN") && atoi(getenv("GPRX_CELL_SINGLE_COLUMN")) != 0);
+  static const bool off = getenv("GPRX_CELL_BETA_ROWS") && atoi(getenv("GPRX_CELL_BETA_ROWS")) != 0;
   return !off && !builds_k && extra == NB && np / NB <= CELL2_BETA_MAXT;
 }
 
@@ -913,13 +857,7 @@ inline hipError_t potrf_cells(hipStream_t st, double* A, int64_t lda, int np, in
   a.cs = cs;
   a.info_stride = info_stride;
   a.col_base = col_base;
-  static const bool two_pass = getenv("GPRX_CELL_TWO_PASS") && atoi(getenv("GPRX_CELL_TWO_PASS")) != 0;
-  static const bool single_column = getenv("GPRX_CELL_SINGLE_COLUMN") && atoi(getenv("GPRX_CELL_SINGLE_COLUMN")) != 0;  // (round 3's kernel, for A/B)
-  if (two_pass)
-    hipLaunchKernelGGL(potrf_cell_kernel, dim3(batch), dim3(256), 0, st, a);
-  else if (single_column)
-    hipLaunchKernelGGL(potrf_cell_kernel_t<true>, dim3(batch), dim3(256), 0, st, a);
-  else if (X && cell_par) {
+  if (X && cell_par) {
     a.X = X;
     a.cell_par = cell_par;
     a.n = n;

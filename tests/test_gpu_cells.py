@@ -1,7 +1,8 @@
 """The one-workgroup-per-cell Cholesky for many small matrices (gpras_amd/csrc/potrf_cell.h; "cell_kernel" = 1 forces it, -1
 forbids it, default: N <= 256 from 32 cells, N <= 512 from 160, N <= 1024 from 256) through gprx_factorize_batch /
 gprx_objective_batch: against the batched launch sequence (same tile products, another summation grouping: equal to rounding),
-against the oracle, with a failing cell, and the two-pass form of the kernel bit for bit."""
+against the oracle, with a failing cell, and the forms of the kernel that remain against each other: the right-hand side as tile rows
+(GPRX_CELL_BETA_ROWS=1; also with K evaluated inside the kernel, GPRX_CELL_BUILD_K=1) bit for bit, the default vector form to rounding."""
 
 import ctypes as C
 import os
@@ -37,7 +38,7 @@ def thetas_for(x, cells, seed):
 
 
 @pytest.mark.parametrize("kernel,n,d,cells", [("RBF", 64, 2, 5), ("RBF", 200, 3, 40), ("Matern52", 333, 4, 12), ("Matern12", 512, 8, 9), ("RBF", 1000, 5, 6),
-                                              ("Matern32", 1024, 8, 4)])
+                                              ("Matern32", 1024, 8, 4), ("RBF", 1088, 3, 3)])  # (1088: 17 block columns, the forced kernel's tile-row form)
 def test_cell_kernel_against_launch_sequence_and_oracle(lib, kernel, n, d, cells):
     ns = 40
     x, y, xs = make_regression(n, d, n_outputs=cells, n_test=ns, config=2, unit=n)
@@ -111,7 +112,7 @@ def test_a_non_positive_definite_cell_is_reported_alone(lib, cell_kernel):
         lib.gprx_destroy(h)
 
 
-TWO_PASS = r"""
+FORMS = r"""
 import ctypes as C, json, sys
 import numpy as np
 sys.path.insert(0, {root!r})
@@ -139,24 +140,24 @@ print(json.dumps(out))
 
 
 def test_cell_kernel_forms_agree_bit_for_bit():
-    """Three forms of the one-workgroup-per-cell kernel -- two passes per block column, update + solve fused per tile (round 3), and the
-    column-pair kernel (round 4: two block columns per pass on LDS-DMA operand panels, potrf_cell.h cell2_rows; also with the kernel matrix
-    evaluated inside the kernel, GPRX_CELL_BUILD_K=1) -- perform the same tile products on the same operands in the same accumulation
-    order: the losses are equal to the last bit."""
+    """The forms of the column-pair kernel (two block columns per pass on LDS-DMA operand panels, potrf_cell.h cell2_rows) that carry the
+    right-hand side as tile rows -- K read from memory, and K evaluated inside the kernel (GPRX_CELL_BUILD_K=1) -- perform the same tile
+    products on the same operands in the same accumulation order: the losses are equal to the last bit.  (Round 3's two-pass and
+    single-column kernels were part of this comparison until they were retired; they agreed to the last bit.)"""
     import json
 
     outs = []
     # (GPRX_CELL_BUILD_K applies to even block-column counts only; the odd cases of that run take the plain kernel, pinned to the tile form too)
-    for env in ({"GPRX_CELL_TWO_PASS": "1"}, {"GPRX_CELL_SINGLE_COLUMN": "1"}, {"GPRX_CELL_BETA_ROWS": "1"}, {"GPRX_CELL_BUILD_K": "1", "GPRX_CELL_BETA_ROWS": "1"}, {}):
+    for env in ({"GPRX_CELL_BETA_ROWS": "1"}, {"GPRX_CELL_BUILD_K": "1", "GPRX_CELL_BETA_ROWS": "1"}, {}):
         base = {k: v for k, v in os.environ.items() if not k.startswith("GPRX_CELL")}
-        res = subprocess.run([sys.executable, "-c", TWO_PASS.format(root=ROOT)], capture_output=True, text=True, timeout=600, env=dict(base, **env))
+        res = subprocess.run([sys.executable, "-c", FORMS.format(root=ROOT)], capture_output=True, text=True, timeout=600, env=dict(base, **env))
         assert res.returncode == 0, res.stderr[-2000:]
         outs.append(res.stdout.strip().splitlines()[-1])
-    assert outs[0] == outs[1] == outs[2] == outs[3]
+    assert outs[0] == outs[1]
     # the default form carries the right-hand side as a VECTOR (cell2_beta_*: beta = L^-1 y by matrix-vector products on the same factor,
     # no tile row): the factor and log det are those bits, y^T K^-1 y = |beta|^2 is summed in another order -- equal to rounding
-    tiles = np.array([float.fromhex(v) for v in json.loads(outs[2])])
-    vector = np.array([float.fromhex(v) for v in json.loads(outs[4])])
+    tiles = np.array([float.fromhex(v) for v in json.loads(outs[0])])
+    vector = np.array([float.fromhex(v) for v in json.loads(outs[2])])
     assert np.max(np.abs(vector - tiles) / np.abs(tiles)) <= 1e-14
 
 
@@ -189,7 +190,7 @@ print(json.dumps(out))
 
 
 def test_cell_kernels_at_full_load_two_workgroups_per_cu():
-    """Round 4: every form of the one-workgroup-per-cell kernel at FULL load -- 512 cells of N = 1024, two workgroups on every CU --, three
+    """Round 4: every remaining form of the one-workgroup-per-cell kernel (tile rows, tile rows with K built inside, vector) at FULL load -- 512 cells of N = 1024, two workgroups on every CU --, three
     repetitions each: the same bits every time, the same bits in every form, and the launch sequence's values to rounding.  (A store
     whose data registers were reused too early corrupted the low dword of a few entries of L(j,j)^-1 in 7-50 % of the cells of the
     workgroups that became resident second, differently on every run, and only in some builds; the small cases above never showed it.)"""
@@ -205,7 +206,7 @@ def test_cell_kernels_at_full_load_two_workgroups_per_cu():
     assert seq[0] == seq[1] == seq[2]
     ref = np.array([float.fromhex(v) for v in seq[0]])
     first = None
-    for env in ({"GPRX_CELL_BETA_ROWS": "1"}, {"GPRX_CELL_SINGLE_COLUMN": "1"}, {"GPRX_CELL_TWO_PASS": "1"}, {"GPRX_CELL_BUILD_K": "1", "GPRX_CELL_BETA_ROWS": "1"}, {}):
+    for env in ({"GPRX_CELL_BETA_ROWS": "1"}, {"GPRX_CELL_BUILD_K": "1", "GPRX_CELL_BETA_ROWS": "1"}, {}):
         got = run(1, env)
         assert got[0] == got[1] == got[2], env
         first = first or got[0]

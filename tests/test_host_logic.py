@@ -111,6 +111,26 @@ def test_retired_tuning_keys_are_unknown_keys():
         assert lib.gprx_set_tuning(key, 0) == _lib.GPRX_OK, key
 
 
+RETIRED_ENVIRONMENT_VARIABLES = ("GPRX_CELL_TWO_PASS", "GPRX_CELL_SINGLE_COLUMN", "GPRX_CELL2_NODMA", "GPRX_CELL2_NOMMA", "GPRX_CELL2_NOROWS", "GPRX_K64_GEMM",
+                                 "GPRX_FUSE_K64", "GPRX_FUSE_K64_SPLIT", "GPRX_KINV_TN", "GPRX_BATCH_GROUPS")
+
+
+def test_retired_environment_variables_are_named_nowhere():
+    """The switches of the cell-kernel forms, the K = 64 strip update, the NT route to K^-1 and the two cell groups that were retired
+     are read by no source of the library and set by no tool: a variable that nothing reads must not look
+    like an option.  (The documents and the profile records may still name them.)"""
+    import glob
+
+    files = [f for pat in ("gpras_amd/**/*.py", "gpras_amd/**/*.h", "gpras_amd/**/*.hip", "include/**/*.h", "tools/*.py", "tools/*.sh")
+             for f in glob.glob(os.path.join(ROOT, pat), recursive=True)]
+    assert len(files) > 100  # (the patterns still find the sources)
+    for path in files:
+        with open(path, encoding="utf-8", errors="replace") as fh:
+            text = fh.read()
+        for name in RETIRED_ENVIRONMENT_VARIABLES:
+            assert name not in text, (name, os.path.relpath(path, ROOT))
+
+
 def test_missing_library_is_an_error_not_a_fallback(monkeypatch, tmp_path):
     monkeypatch.setattr(_lib, "_lib", None)
     monkeypatch.setattr(_lib, "LIB_PATH", tmp_path / "libgprx.so")

@@ -1,6 +1,8 @@
-// Standalone check of the one-workgroup-per-cell kernels at FULL load (development aid): `cells` SPD matrices of order n are factored by
-// the single-column kernel and by the column-pair kernel; the two factors (and the inverse diagonal blocks) are compared element by
-// element on the host and the tiles that differ are listed.
+// Standalone check of the one-workgroup-per-cell kernel at FULL load (development aid): `cells` SPD matrices of order n (at most 1024) are
+// factored by the column-pair kernel with the right-hand side as 64 tile rows (CC_BUILD_K set: by the form that evaluates K itself) and
+// with the right-hand side as a vector; the two factors (and the inverse diagonal blocks) are compared element by element on the host and
+// the tiles that differ are listed; beta = L^-1 y of the two forms is compared to rounding.  (Until d8f5e12 the first kernel was round 3's
+// single-column kernel, retired since.)
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -o /tmp/cc tools/cell_check.hip && /tmp/cc [n=1024] [cells=512] [reps=3]
 #include "../gpras_amd/csrc/potrf_cell.h"
 
@@ -31,6 +33,10 @@ __global__ void rhs_kernel(double* A, int64_t ld, int np, int64_t cs) {
 int main(int argc, char** argv) {
   const int n = argc > 1 ? atoi(argv[1]) : 1024, cells = argc > 2 ? atoi(argv[2]) : 512, reps = argc > 3 ? atoi(argv[3]) : 3, d = 8;
   const int np = (n + 63) / 64 * 64, T = np / 64;
+  if (T > CELL2_BETA_MAXT) {
+    fprintf(stderr, "n <= %d: the vector form holds beta in LDS\n", CELL2_BETA_MAXT * 64);
+    return 1;
+  }
   const int64_t ld = np, cs = (int64_t)(np + 64) * np + (int64_t)np * 64 + 64;
   const int64_t off_inv = (int64_t)(np + 64) * np;
   std::mt19937_64 rng(1);
@@ -64,7 +70,6 @@ int main(int argc, char** argv) {
   CellArgs ca;
   ca.lda = ld;
   ca.T = T;
-  ca.R = T + 1;
   ca.cs = cs;
   ca.info_stride = 1;
   ca.col_base = 0;
@@ -76,10 +81,8 @@ int main(int argc, char** argv) {
     ca.A = a1;
     ca.inv_diag = a1 + off_inv;
     ca.info = info;
-    hipLaunchKernelGGL(potrf_cell_kernel_t<true>, dim3(cells), dim3(256), 0, st, ca);
-    ca.A = a2;
-    ca.inv_diag = a2 + off_inv;
-    ca.info = info + cells;
+    ca.R = T + 1;
+    ca.beta = nullptr;
     if (getenv("CC_BUILD_K")) {
       ca.X = dx;
       ca.cell_par = dpar;
@@ -89,14 +92,30 @@ int main(int argc, char** argv) {
     } else {
       hipLaunchKernelGGL(potrf_cell2_kernel<false>, dim3(cells), dim3(256), 0, st, ca);
     }
+    ca.A = a2;
+    ca.inv_diag = a2 + off_inv;
+    ca.info = info + cells;
+    ca.R = T;
+    ca.beta = a2 + (int64_t)np * ld;
+    hipLaunchKernelGGL((potrf_cell2_kernel<false, true>), dim3(cells), dim3(256), 0, st, ca);
     CK(hipStreamSynchronize(st));
     int bad_cells = 0, shown = 0;
+    double beta_rel = 0.0;
     for (int c = 0; c < cells; ++c) {
       CK(hipMemcpy(h1.data(), a1 + (size_t)c * cs, (size_t)cs * 8, hipMemcpyDeviceToHost));
       CK(hipMemcpy(h2.data(), a2 + (size_t)c * cs, (size_t)cs * 8, hipMemcpyDeviceToHost));
       bool bad = false;
-      for (int ti = 0; ti <= T; ++ti)
-        for (int tj = 0; tj <= (ti < T ? ti : T - 1); ++tj) {
+      {  // beta: row 0 of the tile form's right-hand-side rows against the vector
+        double num = 0.0, den = 0.0;
+        for (int q = 0; q < np; ++q) {
+          const size_t e = (size_t)np * ld + q;
+          num = fmax(num, fabs(h1[e] - h2[e]));
+          den = fmax(den, fabs(h1[e]));
+        }
+        beta_rel = fmax(beta_rel, num / den);
+      }
+      for (int ti = 0; ti < T; ++ti)
+        for (int tj = 0; tj <= ti; ++tj) {
           int cnt = 0, fr = -1, fc = -1;
           double mx = 0.0;
           for (int r = 0; r < 64; ++r)
@@ -130,8 +149,8 @@ int main(int argc, char** argv) {
       }
       bad_cells += bad;
     }
-    printf("rep %d: %d of %d cells differ between the two kernels\n", rep, bad_cells, cells);
-    // ground truth for the first rows of the first differing cell: which kernel is off?
+    printf("rep %d: the factors of %d of %d cells differ between the two forms; beta: max |d| / max |beta| over the cells %.2e\n", rep, bad_cells, cells, beta_rel);
+    // ground truth for the first rows of the first differing cell: which form is off?
     for (int c = 0; c < cells && rep == 0; ++c) {
       CK(hipMemcpy(h1.data(), a1 + (size_t)c * cs, (size_t)cs * 8, hipMemcpyDeviceToHost));
       CK(hipMemcpy(h2.data(), a2 + (size_t)c * cs, (size_t)cs * 8, hipMemcpyDeviceToHost));
@@ -187,10 +206,10 @@ int main(int argc, char** argv) {
               for (int k = j; k <= i; ++k) sum += (long double)hh[off_inv + (size_t)i * 64 + k] * hh[(size_t)k * ld + j];
               worst = fmax(worst, fabs((double)sum - (i == j ? 1.0 : 0.0)));
             }
-          printf("%s: |inv0 * L00 - I| max %.2e\n", which ? "column-pair" : "single-column", worst);
+          printf("%s: |inv0 * L00 - I| max %.2e\n", which ? "vector form" : "tile-row form", worst);
         }
       }
-      printf("cell %d, first %d rows against a long-double host Cholesky: single-column max |err| %.2e, column-pair max |err| %.2e\n", c, m, e1, e2);
+      printf("cell %d, first %d rows against a long-double host Cholesky: tile-row form max |err| %.2e, vector form max |err| %.2e\n", c, m, e1, e2);
       break;
     }
   }
