@@ -188,6 +188,21 @@ def dot64(a, b):
     return acc.reshape((a.shape[0],) + b.shape[1:])
 
 
+def log_ld(x):
+    """log in longdouble by +, -, *, / alone (the x87 instruction behind logl differs between CPU vendors in the last bits, and a
+    recorded ratio must come out the same everywhere): x = 2^k m with sqrt(1/2) <= m < sqrt(2), log m = 2 atanh(t) =
+    2 t sum t^2j / (2j + 1) with t = (m - 1) / (m + 1), |t| < 0.172; k ln 2 with ln 2 in two parts."""
+    m, k = np.frexp(np.asarray(x, dtype=LD))
+    low = m < np.sqrt(LD(0.5))
+    m, k = np.where(low, m + m, m), (k - low).astype(LD)
+    t = (m - LD(1)) / (m + LD(1))
+    t2 = t * t
+    s = np.zeros_like(t)
+    for j in range(14, -1, -1):  # (0.172^30 / 31 < 1e-24)
+        s = LD(1) / LD(2 * j + 1) + t2 * s
+    return (LD(2) * t * s + k * LD("1.9082149292705878161442656807550013e-10")) + k * LD(0.6931471803691238)
+
+
 def sum64(x, axis=0):
     """Sequential float64 sum along an axis (np.sum's pairwise blocking is an implementation detail)."""
     return np.take(np.cumsum(np.asarray(x, np.float64), axis=axis), -1, axis=axis)
@@ -302,7 +317,7 @@ def compute_bounds() -> dict:
         for n in LOGDET_N:
             low, _ = solve_inputs(max(SIZES), NOISES[0], seed)
             d, v = np.diag(low)[:n], vec(n, seed)
-            lg = np.log(d.astype(LD))  # (each term rounded from longdouble: numpy's double log is not the same on every CPU)
+            lg = log_ld(d)  # (each term rounded from longdouble: numpy's double log is not the same on every CPU, nor is its longdouble log)
             out[f"logdet/n{n}/seed{seed}"] = sum_ratio(sum64(lg.astype(np.float64)), np.sum(lg), np.sum(np.abs(lg)))
             out[f"quad/n{n}/seed{seed}"] = sum_ratio(sum64(v * v), np.sum(v.astype(LD) ** 2), np.sum(v.astype(LD) ** 2))
         for nr, nc in COLREDUCE_SHAPES:

@@ -63,6 +63,19 @@ def test_longdouble_references_against_mpmath():
         assert np.max(np.abs(back - spd)) <= 2 * np.finfo(np.float64).eps * np.max(np.abs(spd))
 
 
+def test_spelled_out_log_against_mpmath():
+    """log_ld uses no libm (the recorded log-determinant ratios must not depend on the host's): a few longdouble ulp of the value,
+    absolutely below 1e-3 of it near x = 1."""
+    x = np.concatenate([np.random.default_rng(0).uniform(1e-3, 5.0, 300), [1.0, 0.5, 2.0, 0.70710678, 1.41421356]])
+    got = br.log_ld(x)
+    assert got[300] == 0
+    with mpmath.workdps(50):
+        for g, v in zip(got, x):
+            hi = float(g)
+            exact = mpmath.log(mpmath.mpf(float(v)))
+            assert abs(mpmath.mpf(hi) + mpmath.mpf(float(g - br.LD(hi))) - exact) <= 4 * float(np.finfo(br.LD).eps) * max(abs(exact), mpmath.mpf("1e-3"))
+
+
 def test_recorded_bounds_are_what_the_script_writes():
     spec = importlib.util.spec_from_file_location("make_blocks_bounds", os.path.join(HERE, "golden", "make_blocks_bounds.py"))
     mod = importlib.util.module_from_spec(spec)

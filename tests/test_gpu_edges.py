@@ -61,8 +61,9 @@ def test_ragged_sizes_exact_and_sparse(lib, n, d, m):
 
 
 def test_predict_tiling_and_latent_variance(lib):
-    """More test points than one 8192-column pass; include_noise = 0 gives predict_f."""
-    n, d, ns = 300, 3, 8192 + 8192 + 77
+    """More test points than one pass -- 32768 points at N <= 1024 (pred_tile_for) --, the second pass ragged; include_noise = 0
+    gives predict_f."""
+    n, d, ns = 300, 3, 32768 + 8192 + 77
     x, y, xs = make_regression(n, d, n_outputs=1, n_test=ns, config=5, unit=1)
     h = C.c_void_p()
     check(lib.gprx_create(0, n, d, 0, 0, 0, C.byref(h)))
@@ -83,8 +84,8 @@ def test_predict_tiling_and_latent_variance(lib):
 
 
 def test_predict_inverse_path_matches_substitution(lib):
-    """N* >= 2 N switches predict to one triangular GEMM against the explicit inverse of L; N* < 2 N uses blocked
-    substitution.  Both must agree with the oracle (and hence with each other) on an ill-conditioned-ish K."""
+    """One triangular GEMM against the explicit inverse of L ("predict_path" = 1) and blocked substitution ("predict_path" = 2; left
+    alone, every N <= 4096 takes the inverse).  Both must agree with the oracle (and hence with each other) on an ill-conditioned-ish K."""
     n, d = 640, 4
     x, y, xs = make_regression(n, d, n_outputs=1, n_test=2 * n + 50, config=5, unit=4)
     h = C.c_void_p()
@@ -97,8 +98,10 @@ def test_predict_inverse_path_matches_substitution(lib):
         check(lib.gprx_factorize(h, 0, ptr(theta), None, 7, C.byref(loss)), h)
         ns = xs.shape[0]
         m_big, v_big = np.zeros(ns), np.zeros(ns)
+        check(lib.gprx_set_handle_tuning(h, b"predict_path", 1), h)
         check(lib.gprx_predict(h, ptr(xs), ns, ptr(m_big), ptr(v_big), 1), h)  # inverse path
         m_small, v_small = np.zeros(100), np.zeros(100)
+        check(lib.gprx_set_handle_tuning(h, b"predict_path", 2), h)
         check(lib.gprx_predict(h, ptr(xs), 100, ptr(m_small), ptr(v_small), 1), h)  # substitution path
         ref_m, ref_v = oex.predict("RBF", x, y[:, 0], variance, ls, noise, xs, True)
         assert np.max(np.abs(m_big - ref_m)) <= 1e-8 * np.max(np.abs(ref_m))
