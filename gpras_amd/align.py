@@ -15,29 +15,15 @@ numbers per plan down.
 from __future__ import annotations
 
 import ctypes as C
-import time
 
 import numpy as np
 
 from . import _lib
+from ._device import DeviceHandle, StageTimer, slab_rows
 from ._lib import DeviceBuffer, as_f64, check, ptr
 
 FILE_FORMAT = "gpras_amd-align-1"
 MAX_BLOCKS = 4  # csrc/align.h: AL_MAX_BLOCKS
-
-
-class _Laps:
-    """Host milliseconds by stage (every stage ends with a synchronisation of its stream) and the bytes over the host link."""
-
-    def __init__(self, keys):
-        self.ms = dict.fromkeys(keys, 0.0)
-        self.start = self.mark = time.perf_counter()
-        self.link_bytes = 0
-
-    def lap(self, key):
-        now = time.perf_counter()
-        self.ms[key] += (now - self.mark) * 1e3
-        self.mark = now
 
 
 class _Slab:
@@ -47,9 +33,7 @@ class _Slab:
     def __init__(self, aligner, projector, n_cells, cells_p, most_rows, laps):
         self.al, self.proj, self.n_cells, self.cells_p, self.laps = aligner, projector, n_cells, cells_p, laps
         self.k, self.fill, self.buf, self.out = projector.spatial_mode_count, 0, None, []
-        rows = C.c_int64()
-        check(_lib.load().gprx_pca_slab_rows(projector.handle, C.byref(rows)))
-        self.rows = max(1, int(rows.value) if most_rows is None else min(int(rows.value), most_rows))
+        self.rows = slab_rows(projector, most_rows)
 
     def take(self, field, start, stop):
         """Rows [start, stop) of ``field`` (., cells_p) go into the slab."""
@@ -96,11 +80,13 @@ def _pair(block):
     return tuple(block) if isinstance(block, (tuple, list)) else (block, None)
 
 
-class EventAligner:
+class EventAligner(DeviceHandle):
     """``flow_convergence_threshold`` and ``cutoffs`` of ``DataBuilder`` (:70-71, :85), and the clipping they drive."""
 
+    destroy_symbol = "gprx_al_destroy"
+
     def __init__(self, flow_convergence_threshold: float = 0.95, cutoffs=None, device: int = 0):
-        self._h = C.c_void_p()
+        super().__init__()
         threshold = float(flow_convergence_threshold)
         if not np.isfinite(threshold):
             raise ValueError("flow_convergence_threshold must be finite")
@@ -119,23 +105,8 @@ class EventAligner:
         return int(c[0]), int(c[1])
 
     # ---- device state -------------------------------------------------------------------------------------------------------------
-    @property
-    def handle(self):
-        """The device state, created at its first use (building and storing an aligner needs no device)."""
-        if not self._h.value:
-            check(_lib.load().gprx_al_create(self.device, C.byref(self._h)))
-        return self._h
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            _lib.load().gprx_al_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _create(self):
+        check(_lib.load().gprx_al_create(self.device, C.byref(self._h)))
 
     @staticmethod
     def _two_rows(T: int) -> None:
@@ -246,7 +217,7 @@ class EventAligner:
         n_cells = hf_gather.n_out
         if lf_resampler.n_out != n_cells or hf_projector.n_cells != n_cells or lf_projector.n_cells != n_cells:
             raise ValueError(f"the resamplers and the projectors must cover the same {n_cells} cells")
-        laps = _Laps(("upload", "resample", "cutoff", "clip", "transform", "download"))
+        laps = StageTimer(("upload", "resample", "cutoff", "clip", "transform", "download"))
         cells_p = -(-n_cells // 16) * 16
         most_rows = sum(int(np.shape(_pair(hf)[0])[0]) for _, hf, _ in plan_rows) if hasattr(plan_rows, "__len__") else None
         runs, ts = [], []
@@ -299,10 +270,7 @@ class EventAligner:
         if not ts:
             raise ValueError("no plans")
         y, x = slabs[0].features(), slabs[1].features()
-        ms = laps.ms
-        ms["total"] = (time.perf_counter() - laps.start) * 1e3
-        ms["host_link_bytes"] = laps.link_bytes  # the raw rows up; the features, and two integers per computed cutoff, down
-        self.last_timings_ms = ms
+        self.last_timings_ms = laps.finish()  # the link bytes: the raw rows up; the features, and two integers per computed cutoff, down
         return x, y, np.array(runs), np.concatenate(ts)
 
     def stage_timings_ms(self) -> dict[str, float]:
@@ -313,7 +281,7 @@ class EventAligner:
 
     # ---- storage --------------------------------------------------------------------------------------------------------------------
     def to_dict(self) -> dict[str, np.ndarray]:
-        """Plain arrays (what ``np.savez`` stores) plus the format string.  Plans are stored by name: a plan key that is not a string
+        """Plain arrays (what an ``.npz`` stores) plus the format string.  Plans are stored by name: a plan key that is not a string
         would come back as another key (and its cutoff be computed again), so it is refused here."""
         plans = list(self.cutoffs)
         if not all(isinstance(p, str) for p in plans):

@@ -16,6 +16,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._device import DeviceHandle
 from ._lib import DeviceBuffer, as_f64, check, ptr
 
 DG_TILE = 4096  # csrc/diag.h: DG_TILE, the keys of one workgroup per sort pass
@@ -103,29 +104,16 @@ class _Held:
             self.buf.free()
 
 
-class FieldDiagnostics:
+class FieldDiagnostics(DeviceHandle):
+    destroy_symbol = "gprx_dg_destroy"
+
     def __init__(self, device: int = 0):
-        self._h = C.c_void_p()
+        super().__init__()
         self.device = device
 
-    # ---- device state ---------------------------------------------------------------------------------------------------------------
-    @property
-    def handle(self):
-        """The device state (a stream and the sort's workspace, reused across calls), created at its first use."""
-        if not self._h.value:
-            check(_lib.load().gprx_dg_create(self.device, C.byref(self._h)))
-        return self._h
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            _lib.load().gprx_dg_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _create(self):
+        """The device state: a stream and the sort's workspace, reused across calls."""
+        check(_lib.load().gprx_dg_create(self.device, C.byref(self._h)))
 
     def _pair(self, a, b, n=None):
         held = []

@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._device import DeviceHandle
 from ._lib import check, ptr
 
 N_MAX = 16384
@@ -28,8 +29,11 @@ def _check_matrix(a) -> np.ndarray:
     return a
 
 
-class SymmetricEigensolver:
+class SymmetricEigensolver(DeviceHandle):
     """Owns one ``gprx_eigh`` handle (device buffers for matrices up to ``n_max``) for repeated calls."""
+
+    destroy_symbol = "gprx_eigh_destroy"
+    create_on_use = False
 
     def __init__(self, n_max: int, device: int = 0):
         if int(n_max) != n_max or not 1 <= n_max <= N_MAX:
@@ -37,8 +41,10 @@ class SymmetricEigensolver:
         self.n_max = int(n_max)
         self.device = device
         self._lib = _lib.load()
-        self._h = C.c_void_p()
-        check(self._lib.gprx_eigh_create(device, self.n_max, C.byref(self._h)))
+        super().__init__()
+
+    def _create(self):
+        check(self._lib.gprx_eigh_create(self.device, self.n_max, C.byref(self._h)))
 
     def eigh(self, a, eigenvectors: bool = True):
         """(lam, v) of the symmetric matrix given by the lower triangle of ``a``; ``a`` is not changed.  ``eigenvectors=False``
@@ -65,23 +71,6 @@ class SymmetricEigensolver:
         sweeps, off = C.c_int(), C.c_double()
         check(self._lib.gprx_eigh_info(self._h, C.byref(sweeps), C.byref(off)))
         return sweeps.value, off.value
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.gprx_eigh_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def eigh(a, device: int = 0):

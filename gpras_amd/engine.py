@@ -13,6 +13,7 @@ import threading
 import numpy as np
 
 from . import _lib
+from ._device import DeviceHandle
 from ._lib import KERNEL_IDS, as_f64, check, ptr
 
 
@@ -28,17 +29,20 @@ def _locked(method):
     return wrapper
 
 
-class Engine:
+class Engine(DeviceHandle):
     """Owns the device copy of ``x (N, d)``, ``y (N, K)`` and all factorisation workspaces.
 
     ``n_inducing = 0`` selects the exact GP; otherwise the sparse model with that many inducing points
     (``SGPR`` at ``/root/reference/gpras/gpr.py:299``).
     """
 
+    destroy_symbol = "gprx_destroy"
+    create_on_use = False
+
     def __init__(self, kernel: str, x, y, n_inducing: int = 0, ard: bool = False, device: int = 0, distance_form: str = "difference"):
         self._lib = _lib.load()
         self.kernel = kernel
-        kernel_id = KERNEL_IDS[kernel]  # KeyError for unknown names, as gpr.py:230
+        self._kernel_id = KERNEL_IDS[kernel]  # KeyError for unknown names, as gpr.py:230
         x = as_f64(x)
         y = as_f64(y)
         if x.ndim != 2 or y.ndim != 2 or x.shape[0] != y.shape[0]:
@@ -52,8 +56,7 @@ class Engine:
         self.n_theta = 2 + self.n_len
         self.device = device
         self._lock = threading.RLock()
-        self._h = C.c_void_p()
-        check(self._lib.gprx_create(device, self.n, self.d, self.m, kernel_id, int(self.ard), C.byref(self._h)))
+        super().__init__()
         check(self._lib.gprx_set_data(self._h, ptr(x), ptr(y), self.n_units), self._h)
         self.distance_form = "difference"
         if distance_form != "difference":
@@ -66,17 +69,8 @@ class Engine:
         check(self._lib.gprx_set_distance_form(self._h, _lib.DISTANCE_FORMS[form]), self._h)
         self.distance_form = form
 
-    # -- lifetime -------------------------------------------------------------------------------
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.gprx_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _create(self):
+        check(self._lib.gprx_create(self.device, self.n, self.d, self.m, self._kernel_id, int(self.ard), C.byref(self._h)))
 
     # -- evaluations -----------------------------------------------------------------------------
     def _z_ptr(self, z):
@@ -332,7 +326,3 @@ class Engine:
         ms = (C.c_double * 4)()
         self._lib.gprx_last_timings(self._h, ms)
         return {"kernel_build_ms": ms[0], "cholesky_ms": ms[1], "solves_ms": ms[2], "gradient_ms": ms[3]}
-
-    @property
-    def handle(self):
-        return self._h

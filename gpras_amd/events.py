@@ -23,6 +23,7 @@ import numpy as np
 import pandas as pd
 
 from . import _lib
+from ._device import DeviceHandle
 from ._lib import check, ptr
 
 MAX_HOURS = 4096  # csrc/abi_events.hip: EV_MAX_H
@@ -80,12 +81,14 @@ def sign_convention(components: np.ndarray) -> np.ndarray:
     return components * signs[:, None]
 
 
-class EventSelector:
+class EventSelector(DeviceHandle):
     """``EventSelection`` of the reference on five long-format columns; see the module text."""
+
+    destroy_symbol = "gprx_ev_destroy"
 
     def __init__(self, event_id, datetime, precip_excess, precip_cum, inflow, arrival_rate: int = 10, window_ratio: float = 0.2, test_rp_range=None,
                  tol: float = 0.15, device: int = 0, eigensolver: str = "host"):
-        self._h = C.c_void_p()
+        super().__init__()
         self._set_parameters(arrival_rate, window_ratio, test_rp_range, tol, device, eigensolver)
         t0 = time.perf_counter()
         datetime = pd.to_datetime(pd.Series(np.asarray(datetime))).to_numpy()
@@ -143,7 +146,7 @@ class EventSelector:
         """Around a given ``event_max`` table (columns ``event_id, precip-cum, inflow, RP_precip-cum, RP_inflow``): ``select_aep`` and
         ``select_test`` work, nothing touches the device, the methods that need the long frame raise."""
         self = cls.__new__(cls)
-        self._h = C.c_void_p()
+        DeviceHandle.__init__(self)
         self._set_parameters(arrival_rate, window_ratio, test_rp_range, tol, 0, "host")
         need = ["event_id", "precip-cum", "inflow", "RP_precip-cum", "RP_inflow"]
         missing = [c for c in need if c not in frame.columns]
@@ -159,37 +162,19 @@ class EventSelector:
         return self
 
     # ---- device state -----------------------------------------------------------------------------------------------------------------
-    @property
-    def handle(self):
-        """The device state, created at its first use: the columns go up in their original row order and are pivoted there."""
-        if not self._h.value:
-            if self._cols is None:
-                raise RuntimeError("this EventSelector was built from an event_max table: it has no long frame")
-            t0 = time.perf_counter()
-            check(_lib.load().gprx_ev_create(self.device, self._rank.size, self.n_events, self.n_hours, ptr(self._rank), ptr(self._hour), ptr(self._cols[0]),
-                                             ptr(self._cols[1]), ptr(self._cols[2]), C.byref(self._h)))
-            self.upload_pivot_wall_ms = 1e3 * (time.perf_counter() - t0)
-        return self._h
+    def _create(self):
+        """The columns go up in their original row order and are pivoted on the device."""
+        if self._cols is None:
+            raise RuntimeError("this EventSelector was built from an event_max table: it has no long frame")
+        t0 = time.perf_counter()
+        check(_lib.load().gprx_ev_create(self.device, self._rank.size, self.n_events, self.n_hours, ptr(self._rank), ptr(self._hour), ptr(self._cols[0]),
+                                         ptr(self._cols[1]), ptr(self._cols[2]), C.byref(self._h)))
+        self.upload_pivot_wall_ms = 1e3 * (time.perf_counter() - t0)
 
-    def close(self):
-        """Releases the device memory; ``event_max`` stays, the scores (whose device copy the selection reads) are computed again when
-        they are next needed."""
-        if getattr(self, "_h", None) is not None and self._h.value:
-            _lib.load().gprx_ev_destroy(self._h)
-            self._h = C.c_void_p()
-            self._scores = {}
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _released(self):
+        """``close()`` releases the device memory; ``event_max`` stays, the scores (whose device copy the selection reads) are computed
+        again when they are next needed."""
+        self._scores = {}
 
     def stage_timings_ms(self) -> dict[str, float]:
         """Device milliseconds of the last call of each stage (``gprx_ev_timings``)."""

@@ -24,14 +24,19 @@ from typing import Any
 import numpy as np
 
 from . import _lib
+from ._device import DeviceHandle, scoped_handle
 from ._lib import as_f64, check, ptr
 
 
-class EOFProjector:
+class EOFProjector(DeviceHandle):
+    destroy_symbol = "gprx_pca_destroy"
+    create_on_use = False
+
     def __init__(self, dry_indices, elevations, input_mean, weights, eofs, x_mean, x_std, hydraulic_parameter: str = "wse", device: int = 0):
         if hydraulic_parameter not in ("wse", "depth", "velocity"):
             raise ValueError(f"unknown hydraulic_parameter {hydraulic_parameter!r}")
         self._lib = _lib.load()
+        self.device = device
         self.hydraulic_parameter = hydraulic_parameter
         self.dry_indices = np.ascontiguousarray(dry_indices, dtype=bool)
         self.elevations = None if elevations is None or np.size(elevations) == 0 else as_f64(elevations)
@@ -51,13 +56,15 @@ class EOFProjector:
             raise ValueError("x_mean and x_std must be (k,)")
         if self.elevations is not None and self.elevations.shape != (self.n_cells,):
             raise ValueError("elevations must be (n_cells,)")
+        super().__init__()
+
+    def _create(self):
         dry_u8 = np.ascontiguousarray(self.dry_indices, dtype=np.uint8)
-        self._h = C.c_void_p()
         check(
             self._lib.gprx_pca_create(
-                device, self.n_cells, self.spatial_mode_count, ptr(dry_u8), None if self.elevations is None else ptr(self.elevations),
+                self.device, self.n_cells, self.spatial_mode_count, ptr(dry_u8), None if self.elevations is None else ptr(self.elevations),
                 ptr(self.input_mean), None if self.weights is None else ptr(self.weights), ptr(self.eofs), ptr(self.x_mean), ptr(self.x_std),
-                int(hydraulic_parameter == "depth"), C.byref(self._h),
+                int(self.hydraulic_parameter == "depth"), C.byref(self._h),
             )
         )
 
@@ -65,17 +72,6 @@ class EOFProjector:
     def from_preprocessor(cls, pre: Any, device: int = 0) -> "EOFProjector":
         """Take the fitted state of a reference ``PreProcessor`` (attribute names of preprocess.py:868-927)."""
         return cls(pre.dry_indices, pre.elevations, pre.input_mean, pre.weights, pre.eofs, pre.x_mean, pre.x_std, pre.hydraulic_parameter, device=device)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.gprx_pca_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def transform(self, x):
         """(samples, cells) -> EOF space (samples, spatial_mode_count)  (preprocess.py:1009-1038)."""
@@ -101,10 +97,6 @@ class EOFProjector:
         var_full = np.empty_like(full)
         check(self._lib.gprx_pca_reverse(self._h, ptr(mean), ptr(var), mean.shape[0], ptr(full), ptr(var_full)))
         return full, var_full
-
-    @property
-    def handle(self):
-        return self._h
 
 
 # ---- fitting (preprocess.py:947-1007) -------------------------------------------------------------------------------------
@@ -223,10 +215,8 @@ class PreProcessor:
         self.last_eig_sweeps = None
         lib = _lib.load()
         mode = MODES.index(self.hydraulic_parameter)
-        h = C.c_void_p()
-        check(lib.gprx_pcafit_create(self.device, ptr(x), n_s, n_cells, None if elev is None else ptr(elev), None if w is None else ptr(w),
-                                     mode, float(self.wet_threshold), C.byref(h)))
-        try:
+        with scoped_handle(lib.gprx_pcafit_create, "gprx_pcafit_destroy", self.device, ptr(x), n_s, n_cells, None if elev is None else ptr(elev),
+                           None if w is None else ptr(w), mode, float(self.wet_threshold)) as h:
             codes = np.empty(n_cells, dtype=np.uint8)
             mean = np.empty(n_cells)
             n_wet = C.c_int64()
@@ -260,8 +250,6 @@ class PreProcessor:
                 check(lib.gprx_pcafit_eig_ms(h, C.byref(ms)))
                 self.last_timings_ms["eigensolver"] = ms.value
                 self.last_eig_sweeps = sweeps.value
-        finally:
-            lib.gprx_pcafit_destroy(h)
         self.elevations = elevations if elev is None else elev
         self.wetness_classes = CLASS_NAMES[codes]
         self.input_mean = mean[:n_wet].copy()
@@ -453,9 +441,7 @@ class HmsPreProcessor:
         n_s, n_f = x.shape
         p = pc.size
         lib = _lib.load()
-        h = C.c_void_p()
-        check(lib.gprx_hms_create(self.device, ptr(x), n_s, ld, n_f, fortran, ptr(bc), bc.size, ptr(pc), p, None, C.byref(h)))
-        try:
+        with scoped_handle(lib.gprx_hms_create, "gprx_hms_destroy", self.device, ptr(x), n_s, ld, n_f, fortran, ptr(bc), bc.size, ptr(pc), p, None) as h:
             input_mean = np.empty(n_f)
             route = C.c_int()
             n_cov = p if n_s >= p else n_s
@@ -486,8 +472,6 @@ class HmsPreProcessor:
             check(lib.gprx_hms_features(h, ke, ptr(e_c), ptr(w1), w1.size, ptr(w2), w2.size, ptr(x_mean), ptr(x_std), 1, None))
             self.last_timings_ms = self._timings(lib, h)
             self.last_timings_ms["host_eigh"] = eigh_ms
-        finally:
-            lib.gprx_hms_destroy(h)
         self.input_mean = input_mean
         self.bc_mask = bc_mask
         self.precip_mask = precip_mask
@@ -528,15 +512,12 @@ class HmsPreProcessor:
         if n_s < 1:
             raise ValueError("x has no rows")
         lib = _lib.load()
-        h = C.c_void_p()
-        check(lib.gprx_hms_create(self.device, ptr(x), n_s, ld, n_f, fortran, ptr(bc), bc.size, ptr(pc), pc.size, ptr(mean), C.byref(h)))
-        try:
+        with scoped_handle(lib.gprx_hms_create, "gprx_hms_destroy", self.device, ptr(x), n_s, ld, n_f, fortran, ptr(bc), bc.size, ptr(pc), pc.size,
+                           ptr(mean)) as h:
             w1, w2 = api_weights(0.85, n_s), api_weights(1, n_s)
             out = np.empty((n_s, nf))
             check(lib.gprx_hms_features(h, ke, ptr(eofs), ptr(w1), w1.size, ptr(w2), w2.size, ptr(x_mean), ptr(x_std), 0, ptr(out)))
             self.last_timings_ms = self._timings(lib, h)
-        finally:
-            lib.gprx_hms_destroy(h)
         return out
 
     def calc_antecedent_precipitation_index(self, x, k: float = 0.85, window: int | None = None):

@@ -17,12 +17,12 @@ without moving anything of size ``T x n_cells`` over the host link.
 from __future__ import annotations
 
 import ctypes as C
-import time
 from typing import Any
 
 import numpy as np
 
 from . import _lib
+from ._device import DeviceHandle, StageTimer, load_npz, save_npz, slab_rows
 from ._lib import DeviceBuffer, as_f64, check, ptr
 
 MAX_KNOTS = 64  # interior knots the device evaluation is sized for
@@ -118,12 +118,14 @@ def _series(a, name: str) -> np.ndarray:
     return np.ascontiguousarray(a)
 
 
-class PseudoSurface:
+class PseudoSurface(DeviceHandle):
     """The numeric state of ``PseudoSurfaceDataBuilder`` on the device."""
+
+    destroy_symbol = "gprx_ps_destroy"
 
     def __init__(self, cell_elevations, cell_interpolater, us_rating_curve: RatingCurve | None, ds_rating_curve: RatingCurve | None,
                  cl_interpolater=None, device: int = 0, n_centerline: int | None = None):
-        self._h = C.c_void_p()
+        super().__init__()
         self.device = device
         self.cell_elevations = as_f64(cell_elevations)
         ci = np.asarray(cell_interpolater)
@@ -148,29 +150,14 @@ class PseudoSurface:
         self.us_rating_curve, self.ds_rating_curve = us_rating_curve, ds_rating_curve
         self.last_timings_ms: dict[str, float] = {}
 
-    @property
-    def handle(self):
-        """The device state, created at its first use (building and storing an estimator needs no device)."""
-        if not self._h.value:
-            us, ds = self.us_rating_curve, self.ds_rating_curve
-            check(_lib.load().gprx_ps_create(
-                self.device, self.n_cells, ptr(self.cell_elevations), ptr(self.cell_interpolater), self.n_centerline,
-                None if self.cl_interpolater is None else ptr(self.cl_interpolater),
-                None if us is None else ptr(us.knots), 0 if us is None else len(us.knots), None if us is None else ptr(us.coefficients),
-                None if ds is None else ptr(ds.knots), 0 if ds is None else len(ds.knots), None if ds is None else ptr(ds.coefficients),
-                C.byref(self._h)))
-        return self._h
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            _lib.load().gprx_ps_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _create(self):
+        us, ds = self.us_rating_curve, self.ds_rating_curve
+        check(_lib.load().gprx_ps_create(
+            self.device, self.n_cells, ptr(self.cell_elevations), ptr(self.cell_interpolater), self.n_centerline,
+            None if self.cl_interpolater is None else ptr(self.cl_interpolater),
+            None if us is None else ptr(us.knots), 0 if us is None else len(us.knots), None if us is None else ptr(us.coefficients),
+            None if ds is None else ptr(ds.knots), 0 if ds is None else len(ds.knots), None if ds is None else ptr(ds.coefficients),
+            C.byref(self._h)))
 
     # ---- preprocess.py:643-667 ----------------------------------------------------------------------------------------------
     def fit_centerline(self, us_wse, ds_wse, us_q, ds_q, centerline_wse) -> np.ndarray:
@@ -268,23 +255,12 @@ class PseudoSurface:
         if projector.n_cells != self.n_cells or (fluvial_projector is not None and fluvial_projector.n_cells != self.n_cells):
             raise ValueError(f"the projectors must cover the {self.n_cells} cells of the surface")
         lib = _lib.load()
-        ms = dict.fromkeys(("rating", "predict", "reverse", "surface", "transform", "download"), 0.0)
-        clock = time.perf_counter
-        t_start = t_mark = clock()
-
-        def lap(key):  # every stage below ends with a synchronisation of its stream
-            nonlocal t_mark
-            now = clock()
-            ms[key] += (now - t_mark) * 1e3
-            t_mark = now
-
+        timer = StageTimer(("rating", "predict", "reverse", "surface", "transform", "download"))
         T, _, _ = self._rating(us_q, ds_q)
-        lap("rating")
+        timer.lap("rating")
         k = projector.spatial_mode_count
         cells, cells_p = self.n_cells, -(-self.n_cells // 16) * 16
-        slab = C.c_int64()
-        check(lib.gprx_pca_slab_rows(projector.handle, C.byref(slab)))
-        slab_rows = min(int(slab.value), T)
+        slab = slab_rows(projector, T)
         bufs: list[DeviceBuffer] = []
         try:
             modes = None
@@ -297,30 +273,29 @@ class PseudoSurface:
                 var.free()
                 bufs.append(modes)
                 kf = fluvial_projector.spatial_mode_count
-                fl = DeviceBuffer(8 * slab_rows * cells, self.device)
+                fl = DeviceBuffer(8 * slab * cells, self.device)
                 bufs.append(fl)
-                lap("predict")
-            field = DeviceBuffer(8 * slab_rows * cells_p, self.device)
+                timer.lap("predict")
+            field = DeviceBuffer(8 * slab * cells_p, self.device)
             z = DeviceBuffer(8 * T * k, self.device)
             bufs += [field, z]
-            for t0 in range(0, T, slab_rows):
-                nr = min(slab_rows, T - t0)
+            for t0 in range(0, T, slab):
+                nr = min(slab, T - t0)
                 if modes is not None:
                     check(lib.gprx_pca_reverse_dev(fluvial_projector.handle, modes.at(t0 * kf), None, nr, fl.ptr, None))
                     check(lib.gprx_pca_synchronize(fluvial_projector.handle))
-                    lap("reverse")
+                    timer.lap("reverse")
                 check(lib.gprx_ps_surface_dev(self.handle, t0, nr, None if modes is None else fl.ptr, cells, field.ptr, cells_p))
                 check(lib.gprx_ps_synchronize(self.handle))
-                lap("surface")
+                timer.lap("surface")
                 check(lib.gprx_pca_transform_dev(projector.handle, field.ptr, nr, z.at(t0 * k)))
                 check(lib.gprx_pca_synchronize(projector.handle))
-                lap("transform")
+                timer.lap("transform")
             out = z.to_array((T, k))
-            lap("download")
-            ms["total"] = (clock() - t_start) * 1e3
+            timer.lap("download")
             # what crossed the host link: the flows and the fluvial model's inputs up, the features down
-            ms["host_link_bytes"] = 8 * (2 * T + (np.size(fluvial_x) if modes is not None else 0) + T * k)
-            self.last_timings_ms = ms
+            timer.link_bytes = 8 * (2 * T + (np.size(fluvial_x) if modes is not None else 0) + T * k)
+            self.last_timings_ms = timer.finish()
             return out
         finally:
             for b in bufs:
@@ -328,7 +303,7 @@ class PseudoSurface:
 
     # ---- storage ------------------------------------------------------------------------------------------------------------
     def to_dict(self) -> dict[str, np.ndarray]:
-        """Plain arrays (what ``np.savez`` stores)."""
+        """Plain arrays (what ``to_file`` stores)."""
         d = {"cell_elevations": self.cell_elevations, "cell_interpolater": self.cell_interpolater, "n_centerline": np.array(self.n_centerline)}
         if self.cl_interpolater is not None:
             d["cl_interpolater"] = self.cl_interpolater
@@ -344,14 +319,9 @@ class PseudoSurface:
                    n_centerline=int(d["n_centerline"]), device=device)
 
     def to_file(self, out_path) -> None:
-        """``to_dict`` as an ``.npz`` in the convention of ``modelfile``'s portable container: plain arrays and one ``format`` string,
-        read back with ``allow_pickle=False``; the caller's path is kept as given."""
-        with open(out_path, "wb") as f:
-            np.savez(f, format=np.array(FILE_FORMAT), **self.to_dict())
+        """``to_dict`` as an ``.npz`` (``_device.save_npz``); the caller's path is kept as given."""
+        save_npz(out_path, FILE_FORMAT, self.to_dict())
 
     @classmethod
     def from_file(cls, in_path, device: int = 0) -> "PseudoSurface":
-        with np.load(in_path, allow_pickle=False) as z:
-            if "format" not in z.files or str(z["format"]) != FILE_FORMAT:
-                raise ValueError(f"{in_path}: not a pseudo-surface file")
-            return cls.from_dict({k: z[k] for k in z.files if k != "format"}, device=device)
+        return cls.from_dict(load_npz(in_path, FILE_FORMAT, "pseudo-surface"), device=device)

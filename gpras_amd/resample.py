@@ -17,11 +17,11 @@ there, so only ``T x n_lf`` numbers go up and ``T x k`` come down.
 from __future__ import annotations
 
 import ctypes as C
-import time
 
 import numpy as np
 
 from . import _lib
+from ._device import DeviceHandle, StageTimer, load_npz, save_npz, slab_rows
 from ._lib import DeviceBuffer, as_f64, check, ptr
 
 FILE_FORMAT = "gpras_amd-resample-1"
@@ -52,11 +52,13 @@ def barycentric_weights(transform, simplex, points) -> np.ndarray:
     return c
 
 
-class MeshResampler:
+class MeshResampler(DeviceHandle):
     """Index (and weight) arrays that turn ``(T, n_lf)`` rows of a plan's output block into the ``(T, n_hf)`` field, on the device."""
 
+    destroy_symbol = "gprx_rs_destroy"
+
     def __init__(self, n_src: int, idx, weights=None, cell_elevations=None, hydraulic_parameter: str = "wse", device: int = 0):
-        self._h = C.c_void_p()
+        super().__init__()
         self.device = device
         ix = np.asarray(idx)
         if ix.size == 0 or not np.issubdtype(ix.dtype, np.integer) or ix.ndim not in (1, 2) or (ix.ndim == 2 and ix.shape[1] != 3):
@@ -128,25 +130,10 @@ class MeshResampler:
         return cls(n_lf, idx, weights, cell_elevations, "wse", device)
 
     # ---- device state -------------------------------------------------------------------------------------------------------------
-    @property
-    def handle(self):
-        """The device state, created at its first use (building and storing a resampler needs no device)."""
-        if not self._h.value:
-            check(_lib.load().gprx_rs_create(
-                self.device, self.n_src, self.n_out, self.n_vert, ptr(self.idx), None if self.weights is None else ptr(self.weights),
-                None if self.cell_elevations is None else ptr(self.cell_elevations), C.byref(self._h)))
-        return self._h
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            _lib.load().gprx_rs_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _create(self):
+        check(_lib.load().gprx_rs_create(
+            self.device, self.n_src, self.n_out, self.n_vert, ptr(self.idx), None if self.weights is None else ptr(self.weights),
+            None if self.cell_elevations is None else ptr(self.cell_elevations), C.byref(self._h)))
 
     def _sources(self, z, vy):
         z = as_f64(z)
@@ -184,43 +171,31 @@ class MeshResampler:
         if projector.n_cells != self.n_out:
             raise ValueError(f"the projector must cover the {self.n_out} cells of the resampler")
         lib = _lib.load()
-        ms = dict.fromkeys(("upload", "resample", "transform", "download"), 0.0)
-        clock = time.perf_counter
-        t_start = t_mark = clock()
-
-        def lap(key):  # every stage below ends with a synchronisation of its stream
-            nonlocal t_mark
-            now = clock()
-            ms[key] += (now - t_mark) * 1e3
-            t_mark = now
-
+        timer = StageTimer(("upload", "resample", "transform", "download"))
         T, k = z.shape[0], projector.spatial_mode_count
         cells_p = -(-self.n_out // 16) * 16
-        slab = C.c_int64()
-        check(lib.gprx_pca_slab_rows(projector.handle, C.byref(slab)))
-        slab_rows = max(1, min(int(slab.value), T))
+        slab = slab_rows(projector, T)
         bufs: list[DeviceBuffer] = []
         try:
-            srcs = [DeviceBuffer(8 * slab_rows * self.n_src, self.device) for _ in range(1 if vy is None else 2)]
-            field = DeviceBuffer(8 * slab_rows * cells_p, self.device)
+            srcs = [DeviceBuffer(8 * slab * self.n_src, self.device) for _ in range(1 if vy is None else 2)]
+            field = DeviceBuffer(8 * slab * cells_p, self.device)
             feat = DeviceBuffer(8 * max(T * k, 1), self.device)
             bufs += srcs + [field, feat]
-            for t0 in range(0, T, slab_rows):
-                nr = min(slab_rows, T - t0)
+            for t0 in range(0, T, slab):
+                nr = min(slab, T - t0)
                 for buf, a in zip(srcs, (z, vy)):
                     check(lib.gprx_memcpy_h2d(self.device, buf.ptr, ptr(a[t0 : t0 + nr]), 8 * nr * self.n_src))
-                lap("upload")
+                timer.lap("upload")
                 check(lib.gprx_rs_apply_dev(self.handle, nr, srcs[0].ptr, self.n_src, None if vy is None else srcs[1].ptr, field.ptr, cells_p))
                 check(lib.gprx_rs_synchronize(self.handle))
-                lap("resample")
+                timer.lap("resample")
                 check(lib.gprx_pca_transform_dev(projector.handle, field.ptr, nr, feat.at(t0 * k)))
                 check(lib.gprx_pca_synchronize(projector.handle))
-                lap("transform")
+                timer.lap("transform")
             out = feat.to_array((T, k))
-            lap("download")
-            ms["total"] = (clock() - t_start) * 1e3
-            ms["host_link_bytes"] = 8 * (T * self.n_src * len(srcs) + T * k)  # the LF rows up, the features down
-            self.last_timings_ms = ms
+            timer.lap("download")
+            timer.link_bytes = 8 * (T * self.n_src * len(srcs) + T * k)  # the LF rows up, the features down
+            self.last_timings_ms = timer.finish()
             return out
         finally:
             for b in bufs:
@@ -228,7 +203,7 @@ class MeshResampler:
 
     # ---- storage --------------------------------------------------------------------------------------------------------------------
     def to_dict(self) -> dict[str, np.ndarray]:
-        """Plain arrays (what ``np.savez`` stores)."""
+        """Plain arrays (what ``to_file`` stores)."""
         d = {"n_src": np.array(self.n_src), "idx": self.idx, "hydraulic_parameter": np.array(self.hydraulic_parameter)}
         if self.weights is not None:
             d["weights"] = self.weights
@@ -242,14 +217,9 @@ class MeshResampler:
                    d["cell_elevations"] if "cell_elevations" in d else None, str(d["hydraulic_parameter"]), device)
 
     def to_file(self, out_path) -> None:
-        """``to_dict`` as an ``.npz`` in the convention of ``modelfile``'s portable container: plain arrays and one ``format`` string,
-        read back with ``allow_pickle=False``; the caller's path is kept as given."""
-        with open(out_path, "wb") as f:
-            np.savez(f, format=np.array(FILE_FORMAT), **self.to_dict())
+        """``to_dict`` as an ``.npz`` (``_device.save_npz``); the caller's path is kept as given."""
+        save_npz(out_path, FILE_FORMAT, self.to_dict())
 
     @classmethod
     def from_file(cls, in_path, device: int = 0) -> "MeshResampler":
-        with np.load(in_path, allow_pickle=False) as z:
-            if "format" not in z.files or str(z["format"]) != FILE_FORMAT:
-                raise ValueError(f"{in_path}: not a mesh-resampler file")
-            return cls.from_dict({k: z[k] for k in z.files if k != "format"}, device=device)
+        return cls.from_dict(load_npz(in_path, FILE_FORMAT, "mesh-resampler"), device=device)

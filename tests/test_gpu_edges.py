@@ -279,3 +279,63 @@ def test_engine_objective_with_gradient_then_predict(lib, m):
             assert np.max(np.abs(mean - ref_mean)) <= 1e-8 * np.max(np.abs(ref_mean)) and np.max(np.abs(var - ref_var) / ref_var) <= 1e-8
     finally:
         eng.close()
+
+
+def test_a_closed_wrapper_recreates_its_handle_and_computes_the_same_bits(lib):
+    """Each class that creates its handle at the first use, at a toy size: a result, ``close()``, the same result through the handle made
+    anew.  The two classes that are closed for good by leaving their ``with`` block answer "null handle" afterwards."""
+    import pandas as pd
+
+    from gpras_amd.align import EventAligner
+    from gpras_amd.diagnostics import FieldDiagnostics
+    from gpras_amd.eigh import SymmetricEigensolver
+    from gpras_amd.events import EventSelector
+    from gpras_amd.preprocess import EOFProjector
+    from gpras_amd.pseudo_surface import PseudoSurface
+    from gpras_amd.resample import MeshResampler
+
+    rng = np.random.default_rng(11)
+    z = rng.standard_normal((3, 5))
+    field = np.cumsum(rng.random((6, 4)), axis=0)
+    keys = rng.integers(0, 2**63, size=9, dtype=np.uint64)
+    us, ds = 10.0 + rng.random(4), 8.0 + rng.random(4)
+    hours = pd.Timestamp("2000-01-01") + pd.to_timedelta(np.tile(np.arange(5), 4), unit="h")
+    cols = rng.random((3, 20))
+
+    def maxima(sel):
+        out = np.empty((2, 4))
+        check(lib.gprx_ev_maxima(sel.handle, ptr(out[0]), ptr(out[1]), None))
+        return out
+
+    cases = [
+        (MeshResampler.nearest(np.array([4, 0, 2, 2, 1, 3, 0]), 5), lambda o: o.lf_plan_data(z)),
+        (EventAligner(), lambda o: np.append(o.cutoff_curve(field), o.get_cutoff(field))),
+        (FieldDiagnostics(), lambda o: o.sort_u64(keys)),
+        (PseudoSurface(rng.random(6), np.array([0, 1, 2, 2, 1, 0]), None, None, cl_interpolater=np.array([0.0, 0.4, 1.0])), lambda o: o.surface_from_wse(us, ds)),
+        (EventSelector(np.repeat(np.arange(4), 5), hours, cols[0], cols[1], cols[2], arrival_rate=2), maxima),
+    ]
+    for obj, compute in cases:
+        assert obj._h.value is None
+        first = compute(obj)
+        assert obj._h.value is not None
+        obj.close()
+        assert obj._h.value is None
+        again = compute(obj)
+        assert obj._h.value is not None and first.dtype == again.dtype and first.tobytes() == again.tobytes(), type(obj).__name__
+        obj.close()
+
+    a = rng.standard_normal((4, 4))
+    with SymmetricEigensolver(4) as solver:
+        lam, _ = solver.eigh(a + a.T)
+        assert np.all(np.diff(lam) >= 0)
+    assert solver._h.value is None
+    with pytest.raises(ValueError):
+        solver.eigh(a + a.T)
+
+    eofs = np.linalg.qr(rng.standard_normal((16, 2)))[0].T
+    x = rng.standard_normal((3, 16))
+    with EOFProjector(np.zeros(16, dtype=bool), np.zeros(16), np.zeros(16), None, eofs, np.zeros(2), np.ones(2)) as proj:
+        assert proj.transform(x).shape == (3, 2)
+    assert proj._h.value is None
+    with pytest.raises(ValueError):
+        proj.transform(x)
