@@ -66,6 +66,8 @@ PROTOTYPES = {
     "gprx_adam_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp]),
     "gprx_adadelta_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "gprx_last_optimizer_route": (C.c_int, [_vp, _ip, _ip]),
+    "gprx_loeo_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "gprx_last_loeo": (C.c_int, [_vp, _ip, _vp]),
     "gprx_comm_runtime_check": (C.c_int, [C.c_int]),
     "gprx_comm_unique_id": (C.c_int, [_vp]),
     "gprx_comm_init": (C.c_int, [C.c_int, C.c_int, C.c_int, _vp, C.POINTER(_vp)]),

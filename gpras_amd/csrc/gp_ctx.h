@@ -36,6 +36,8 @@ struct gprx_ctx {
   std::map<std::pair<int, int>, hipGraphExec_t> rgraphs;  // (cells, optimiser) -> captured step of the resident loop of the launch sequence
   int sgpr_resident = 1;                                  // sparse models: the optimiser loops stay on the device ("sgpr_resident" tuning key)
   int last_route = 0, last_host_waits = 0;                // gprx_last_optimizer_route
+  int last_loeo = 0;                                      // gprx_last_loeo: the last gprx_loeo_batch ran its downdate kernel
+  double loeo_ms[4] = {0, 0, 0, 0};                       // ... and its stage times (gprx.h)
   int host_waits = 0;                                     // stream waits of the running optimiser call (wait_stream and the loops' own)
   int sgpr_fused = 1;                                     // M <= 64: the five-launch evaluation of sgpr_fused.h ("sgpr_fused" tuning key)
   Buf adam_dev;                                           // device state of the resident optimiser loops (resident_state)

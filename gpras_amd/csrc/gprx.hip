@@ -1,6 +1,6 @@
 // libgprx: the C boundary (include/gprx.h) of the GP path and of the raw kernel entry points -- handle life cycle, thin wrappers over
 // gp_*.h, the building-block probes, the development stamps and the tuning keys.  The GP path itself is host orchestration in six
-// headers, included below in dependency order into THIS unit (one instantiation of the GEMM, Cholesky, solve and kernel-matrix
+// headers (and gp_loeo.h, the leave-one-event-out sequence on top of the predict), included below in dependency order into THIS unit (one instantiation of the GEMM, Cholesky, solve and kernel-matrix
 // kernels that the exact path, the sparse path and the probes all launch).  No CPU fallback exists for any device stage.
 #include "abi_common.h"
 
@@ -27,6 +27,7 @@
 #include "sgpr.h"
 #include "sgpr_asm.h"
 #include "sgpr_fused.h"
+#include "sf_loeo.h"
 #include "sgpr_step.h"
 #include "solve.h"
 
@@ -62,6 +63,7 @@ hipStream_t util_stream() {
 #include "gp_resident.h"
 #include "gp_objective.h"
 #include "gp_predict.h"
+#include "gp_loeo.h"
 
 namespace {
 
@@ -362,6 +364,22 @@ int gprx_predict_batch_t(gprx_handle h, int count, const int* units, const doubl
                          double* means_t, double* vars_t, int include_noise) {
   return predict_batch_slabs(h, count, units, thetas, z, xs, ns, means_t, vars_t, include_noise, true, (int64_t)1 << 26,
                              env_int("GPRX_PREDICT_SLAB", NO_FORCED_SLAB));
+}
+
+int gprx_loeo_batch(gprx_handle h, int count, const int* units, const double* thetas, const double* z, int n_events, const int64_t* ev_lo,
+                    const int64_t* ev_hi, double* means, double* vars, int include_noise, int* status) {
+  try {
+    return loeo_batch(h, count, units, thetas, z, n_events, ev_lo, ev_hi, means, vars, include_noise, status);
+  } catch (const std::bad_alloc&) {  // (no C++ exception may cross the C ABI)
+    return fail(h, GPRX_ENOMEM, "host allocation failed");
+  }
+}
+
+int gprx_last_loeo(gprx_handle h, int* ran, double* stage_ms) {
+  if (!h || !ran) return fail(h, GPRX_EINVAL, "null argument");
+  *ran = h->last_loeo;
+  if (stage_ms) std::copy(h->loeo_ms, h->loeo_ms + 4, stage_ms);
+  return GPRX_OK;
 }
 
 int gprx_mem_info(int device, int64_t* free_bytes, int64_t* total_bytes) {

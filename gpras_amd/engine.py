@@ -292,6 +292,39 @@ class Engine(DeviceHandle):
         return means, variances
 
     @_locked
+    def loeo_batch(self, units, thetas, zs, ranges, include_noise: bool = True):
+        """Leave-one-event-out predictions of fitted sparse models with M <= 64 on the engine's own rows (``gprx_loeo_batch``): for every
+        event ``(lo, hi)`` of ``ranges`` -- sorted, disjoint row ranges -- and every cell, ``predict_y`` at ``x[lo:hi]`` of the model on all
+        other rows at the same hyperparameters and inducing points, from ONE factorisation per cell.  Returns ``(means, variances,
+        status)``: ``(cells, N)`` each, NaN at rows of no event, and ``(cells, events)`` int32, 0 or the pivot at which an event's
+        downdated factor failed (its rows are NaN).  Raises ``ValueError`` for models and ranges the kernel does not take."""
+        from .loeo import check_event_ranges
+
+        units = np.ascontiguousarray(units, dtype=np.int32)
+        thetas = as_f64(thetas)
+        if thetas.shape != (units.size, self.n_theta):
+            raise ValueError(f"thetas must be ({units.size}, {self.n_theta})")
+        lo, hi = check_event_ranges(ranges, self.n)
+        zs = as_f64(zs) if self.m != 0 else None
+        if zs is not None and zs.shape != (units.size, self.m, self.d):
+            raise ValueError(f"zs must be ({units.size}, {self.m}, {self.d})")
+        means = np.full((units.size, self.n), np.nan)
+        variances = np.full((units.size, self.n), np.nan)
+        status = np.zeros((units.size, lo.size), dtype=np.int32)
+        check(self._lib.gprx_loeo_batch(self._h, units.size, ptr(units), ptr(thetas), None if zs is None else ptr(zs), lo.size, ptr(lo), ptr(hi),
+                                        ptr(means), ptr(variances), int(include_noise), ptr(status)), self._h)
+        return means, variances, status
+
+    @_locked
+    def last_loeo(self):
+        """``(ran, stage_ms)`` of the last ``loeo_batch`` call (``gprx_last_loeo``): whether the downdate kernel ran to the end, and the
+        times of the batched factorisation (host clock), of the first tile's predict head and downdate kernel and of all tiles (device)."""
+        ran = C.c_int()
+        ms = (C.c_double * 4)()
+        check(self._lib.gprx_last_loeo(self._h, C.byref(ran), ms), self._h)
+        return bool(ran.value), {"factorize_ms": ms[0], "head_ms": ms[1], "downdate_ms": ms[2], "tiles_ms": ms[3]}
+
+    @_locked
     def predict_batch_dev(self, units, thetas, xs_dev, ns: int, means_dev, vars_dev, zs=None, include_noise: bool = True, wait: bool = True):
         """``predict_batch`` with the test points and the ``(cells, N*)`` results in device memory (``gprx_predict_batch_dev``)."""
         units = np.ascontiguousarray(units, dtype=np.int32)

@@ -409,6 +409,27 @@ int gprx_adadelta_batch(gprx_handle h, int count, const int* units, double* thet
  * allocation of a handle's buffers on its first call is not counted. */
 int gprx_last_optimizer_route(gprx_handle h, int* route, int* host_waits);
 
+/* Leave-one-event-out predictions of fitted sparse models on their own training rows (model selection: the held-out score of every
+ * training event of production/analysis/cross_validation.py without one refit per event).  Cell i = (units[i], thetas[i], z block i)
+ * is factorised once; for every event e = rows [ev_lo[e], ev_hi[e]) of the handle's x the call returns, at those rows, SGPR predict_y
+ * of the model built on ALL OTHER rows at the SAME hyperparameters and inducing points -- nothing is re-optimised per fold.  With
+ * t1 = L^-1 k(Z, X[lo:hi]) and t2 = LB^-1 t1 (the predict path's tmp1 / tmp2):
+ *   H = I - t2 t2^T / s,  Lh = chol(H),  c' = Lh^-1 (c - t2 y[lo:hi] / s),  W = Lh^-1 t2,
+ *   mean_j = W[:, j]^T c',  var_j = v - colsum(t1^2)_j + colsum(W^2)_j  (+ s with include_noise)
+ * one workgroup per (event, cell) after the head of the batched predict on tiles of consecutive events; a (cell, event) result has
+ * the same bits whatever else is in the batch or in the event list.
+ * means / vars: (count, N) row-major; rows that belong to no event come back NaN.  status: (count, n_events), 0 or the 1-based pivot
+ * at which chol(H) failed (that event's rows are then NaN in that cell; the call still returns GPRX_OK).
+ * GPRX_EINVAL, before any device work: an exact handle, more than 64 inducing points, d > 64, ranges that are unsorted, overlapping,
+ * empty or outside [0, N], an event longer than one predict tile (4096 rows).  GPRX_ENOTPD: a cell's own factorisation failed. */
+int gprx_loeo_batch(gprx_handle h, int count, const int* units, const double* thetas, const double* z, int n_events, const int64_t* ev_lo,
+                    const int64_t* ev_hi, double* means, double* vars, int include_noise, int* status);
+
+/* ran: 1 when the handle's last gprx_loeo_batch ran its downdate kernel to the end, 0 when it returned an error (or none was made).
+ * stage_ms (optional, 4 doubles) of that call: [0] the batched factorisation (host clock, its wait included), [1] the predict head of
+ * the first tile, [2] the downdate kernel of the first tile, [3] everything between the first tile's start and the copies out (device). */
+int gprx_last_loeo(gprx_handle h, int* ran, double* stage_ms);
+
 /* ---- EOF (PCA) projection either side of the GP path: SURVEY.md section 8(f) row N1 ------------------- */
 /* One projector = the fitted state of a reference PreProcessor (gpras/preprocess.py:868-927): `dry` (n_cells bytes, 1 =
  * always-dry cell, may be NULL = none), `elevations` (n_cells, needed for depth mode and for filling dry cells in wse mode),
