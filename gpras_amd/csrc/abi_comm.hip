@@ -38,48 +38,43 @@ static int comm_runtime_ready() {
 }
 
 int gprx_comm_runtime_check(int device) {
-  HIPCHK(nullptr, hipSetDevice(device));
-  return comm_runtime_ready();
+  return guarded(nullptr, [&]() -> int { HIPCHK(nullptr, hipSetDevice(device)); return comm_runtime_ready(); });
 }
 
 int gprx_comm_unique_id(unsigned char* id128) {
-  if (!id128) return fail(nullptr, GPRX_EINVAL, "null argument");
-  int rc0;
-  if ((rc0 = comm_runtime_ready())) return rc0;
-  ncclUniqueId id;
-  COMMNCCL(nullptr, rccl().GetUniqueId(&id));
-  static_assert(sizeof(id) == GPRX_UNIQUE_ID_BYTES, "ncclUniqueId size");
-  std::memcpy(id128, &id, sizeof(id));
-  return GPRX_OK;
+  return guarded(nullptr, [&]() -> int {
+    if (!id128) return fail(nullptr, GPRX_EINVAL, "null argument");
+    int rc0;
+    if ((rc0 = comm_runtime_ready())) return rc0;
+    ncclUniqueId id;
+    COMMNCCL(nullptr, rccl().GetUniqueId(&id));
+    static_assert(sizeof(id) == GPRX_UNIQUE_ID_BYTES, "ncclUniqueId size");
+    std::memcpy(id128, &id, sizeof(id));
+    return GPRX_OK;
+  });
 }
 
 int gprx_comm_init(int device, int rank, int world, const unsigned char* id128, gprx_comm* out) {
   if (!out) return fail(nullptr, GPRX_EINVAL, "out is null");
   *out = nullptr;
   if (!id128 || world <= 0 || rank < 0 || rank >= world) return fail(nullptr, GPRX_EINVAL, "bad rank / world / id");
-  HIPCHK(nullptr, hipSetDevice(device));
-  int rc0;
-  if ((rc0 = comm_runtime_ready())) return rc0;
-  gprx_comm c = new gprx_comm_ctx();
-  c->device = device;
-  c->rank = rank;
-  c->world = world;
-  hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-  if (e != hipSuccess) {
-    delete c;
-    return fail(nullptr, GPRX_EHIP, std::string("hipStreamCreate: ") + hipGetErrorString(e));
-  }
-  ncclUniqueId id;
-  std::memcpy(&id, id128, sizeof(id));
-  ncclResult_t r = rccl().CommInitRank(&c->comm, world, id, rank);  // collective: every rank of the job calls it
-  if (r != ncclSuccess) {
-    const std::string msg = std::string("ncclCommInitRank: ") + rccl().GetErrorString(r);
-    hipStreamDestroy(c->stream);
-    delete c;
-    return fail(nullptr, GPRX_ERCCL, msg);
-  }
-  *out = c;
-  return GPRX_OK;
+  gprx_comm c = nullptr;
+  const int rc = guarded(nullptr, [&]() -> int {
+    HIPCHK(nullptr, hipSetDevice(device));
+    int rc;
+    if ((rc = comm_runtime_ready())) return rc;
+    c = new gprx_comm_ctx();
+    c->rank = rank;
+    c->world = world;
+    if ((rc = open_handle(c, device))) return rc;
+    ncclUniqueId id;
+    std::memcpy(&id, id128, sizeof(id));
+    const ncclResult_t r = rccl().CommInitRank(&c->comm, world, id, rank);  // collective: every rank of the job calls it
+    return r == ncclSuccess ? GPRX_OK : fail(nullptr, GPRX_ERCCL, std::string("ncclCommInitRank: ") + rccl().GetErrorString(r));
+  });
+  if (rc) gprx_comm_destroy(c);
+  else *out = c;
+  return rc;
 }
 
 int gprx_comm_destroy(gprx_comm c) {
@@ -96,86 +91,96 @@ int gprx_comm_destroy(gprx_comm c) {
 const char* gprx_comm_last_error(gprx_comm c) { return c ? c->err.c_str() : last_error().c_str(); }
 
 int gprx_comm_rank(gprx_comm c, int* rank, int* world) {
-  if (!c || !rank || !world) return fail(c, GPRX_EINVAL, "null argument");
-  *rank = c->rank;
-  *world = c->world;
-  // what RCCL itself reports for this communicator (ncclCommUserRank / ncclCommCount), so that "did RCCL see N ranks" does not rest
-  // on the numbers the caller passed to gprx_comm_init
-  if (rccl().CommUserRank) COMMNCCL(c, rccl().CommUserRank(c->comm, rank));
-  if (rccl().CommCount) COMMNCCL(c, rccl().CommCount(c->comm, world));
-  return GPRX_OK;
+  return guarded(c, [&]() -> int {
+    if (!c || !rank || !world) return fail(c, GPRX_EINVAL, "null argument");
+    *rank = c->rank;
+    *world = c->world;
+    // what RCCL itself reports for this communicator (ncclCommUserRank / ncclCommCount), so that "did RCCL see N ranks" does not rest
+    // on the numbers the caller passed to gprx_comm_init
+    if (rccl().CommUserRank) COMMNCCL(c, rccl().CommUserRank(c->comm, rank));
+    if (rccl().CommCount) COMMNCCL(c, rccl().CommCount(c->comm, world));
+    return GPRX_OK;
+  });
 }
 
 int gprx_comm_synchronize(gprx_comm c) {
   if (!c) return fail(c, GPRX_EINVAL, "null communicator");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return GPRX_OK;
+  return guarded(c, [&]() -> int { HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, hipStreamSynchronize(c->stream)); return GPRX_OK; });
 }
 
 int gprx_comm_all_gather(gprx_comm c, const double* send_dev, double* recv_dev, int64_t count) {
-  if (!c || count < 0 || (count > 0 && (!send_dev || !recv_dev))) return fail(c, GPRX_EINVAL, "null argument");
-  if (count == 0) return GPRX_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  COMMNCCL(c, rccl().AllGather(send_dev, recv_dev, (size_t)count, ncclDouble, c->comm, c->stream));
-  return GPRX_OK;
+  return guarded(c, [&]() -> int {
+    if (!c || count < 0 || (count > 0 && (!send_dev || !recv_dev))) return fail(c, GPRX_EINVAL, "null argument");
+    if (count == 0) return GPRX_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    COMMNCCL(c, rccl().AllGather(send_dev, recv_dev, (size_t)count, ncclDouble, c->comm, c->stream));
+    return GPRX_OK;
+  });
 }
 
 int gprx_comm_gather(gprx_comm c, const double* send_dev, double* recv_dev, int64_t count, int root) {
-  if (!c || count < 0 || root < 0 || root >= c->world || (count > 0 && !send_dev)) return fail(c, GPRX_EINVAL, "bad argument");
-  if (c->rank == root && count > 0 && !recv_dev) return fail(c, GPRX_EINVAL, "recv_dev is null on the root");
-  if (count == 0) return GPRX_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  // one group: the root posts world - 1 receives (its own block is a device copy), every other rank one send; inside a
-  // node all inbound xGMI links of the root are busy at once
-  COMMNCCL(c, rccl().GroupStart());
-  ncclResult_t r = ncclSuccess;
-  if (c->rank == root) {
-    for (int p = 0; p < c->world && r == ncclSuccess; ++p)
-      if (p != root) r = rccl().Recv(recv_dev + (int64_t)p * count, (size_t)count, ncclDouble, p, c->comm, c->stream);
-  } else {
-    r = rccl().Send(send_dev, (size_t)count, ncclDouble, root, c->comm, c->stream);
-  }
-  const ncclResult_t r2 = rccl().GroupEnd();
-  COMMNCCL(c, r);
-  COMMNCCL(c, r2);
-  if (c->rank == root && recv_dev + (int64_t)root * count != send_dev)
-    HIPCHK(c, hipMemcpyAsync(recv_dev + (int64_t)root * count, send_dev, sizeof(double) * count, hipMemcpyDeviceToDevice, c->stream));
-  return GPRX_OK;
+  return guarded(c, [&]() -> int {
+    if (!c || count < 0 || root < 0 || root >= c->world || (count > 0 && !send_dev)) return fail(c, GPRX_EINVAL, "bad argument");
+    if (c->rank == root && count > 0 && !recv_dev) return fail(c, GPRX_EINVAL, "recv_dev is null on the root");
+    if (count == 0) return GPRX_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    // one group: the root posts world - 1 receives (its own block is a device copy), every other rank one send; inside a
+    // node all inbound xGMI links of the root are busy at once
+    COMMNCCL(c, rccl().GroupStart());
+    ncclResult_t r = ncclSuccess;
+    if (c->rank == root) {
+      for (int p = 0; p < c->world && r == ncclSuccess; ++p)
+        if (p != root) r = rccl().Recv(recv_dev + (int64_t)p * count, (size_t)count, ncclDouble, p, c->comm, c->stream);
+    } else {
+      r = rccl().Send(send_dev, (size_t)count, ncclDouble, root, c->comm, c->stream);
+    }
+    const ncclResult_t r2 = rccl().GroupEnd();
+    COMMNCCL(c, r);
+    COMMNCCL(c, r2);
+    if (c->rank == root && recv_dev + (int64_t)root * count != send_dev)
+      HIPCHK(c, hipMemcpyAsync(recv_dev + (int64_t)root * count, send_dev, sizeof(double) * count, hipMemcpyDeviceToDevice, c->stream));
+    return GPRX_OK;
+  });
 }
 
 int gprx_comm_all_reduce_max(gprx_comm c, double* buf_dev, int64_t count) {
-  if (!c || count < 0 || (count > 0 && !buf_dev)) return fail(c, GPRX_EINVAL, "null argument");
-  if (count == 0) return GPRX_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  COMMNCCL(c, rccl().AllReduce(buf_dev, buf_dev, (size_t)count, ncclDouble, ncclMax, c->comm, c->stream));
-  return GPRX_OK;
+  return guarded(c, [&]() -> int {
+    if (!c || count < 0 || (count > 0 && !buf_dev)) return fail(c, GPRX_EINVAL, "null argument");
+    if (count == 0) return GPRX_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    COMMNCCL(c, rccl().AllReduce(buf_dev, buf_dev, (size_t)count, ncclDouble, ncclMax, c->comm, c->stream));
+    return GPRX_OK;
+  });
 }
 
 int gprx_comm_all_gather_host(gprx_comm c, const double* send, double* recv, int64_t count) {
-  if (!c || count < 0 || (count > 0 && (!send || !recv))) return fail(c, GPRX_EINVAL, "null argument");
-  if (count == 0) return GPRX_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  int rc;
-  if ((rc = ensure(c, c->scratch, sizeof(double) * (size_t)count * (c->world + 1)))) return rc;
-  double* dsend = c->scratch.p;
-  double* drecv = c->scratch.p + count;
-  HIPCHK(c, hipMemcpyAsync(dsend, send, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
-  if ((rc = gprx_comm_all_gather(c, dsend, drecv, count))) return rc;
-  HIPCHK(c, hipMemcpyAsync(recv, drecv, sizeof(double) * count * c->world, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return GPRX_OK;
+  return guarded(c, [&]() -> int {
+    if (!c || count < 0 || (count > 0 && (!send || !recv))) return fail(c, GPRX_EINVAL, "null argument");
+    if (count == 0) return GPRX_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensure(c, c->scratch, sizeof(double) * (size_t)count * (c->world + 1)))) return rc;
+    double* dsend = c->scratch.p;
+    double* drecv = c->scratch.p + count;
+    HIPCHK(c, hipMemcpyAsync(dsend, send, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
+    if ((rc = gprx_comm_all_gather(c, dsend, drecv, count))) return rc;
+    HIPCHK(c, hipMemcpyAsync(recv, drecv, sizeof(double) * count * c->world, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return GPRX_OK;
+  });
 }
 
 int gprx_comm_barrier(gprx_comm c) {
-  if (!c) return fail(c, GPRX_EINVAL, "null communicator");
-  int rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  if ((rc = ensure(c, c->scratch, sizeof(double) * (size_t)(c->world + 1)))) return rc;
-  HIPCHK(c, hipMemsetAsync(c->scratch.p, 0, sizeof(double), c->stream));
-  if ((rc = gprx_comm_all_reduce_max(c, c->scratch.p, 1))) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return GPRX_OK;
+  return guarded(c, [&]() -> int {
+    if (!c) return fail(c, GPRX_EINVAL, "null communicator");
+    int rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = ensure(c, c->scratch, sizeof(double) * (size_t)(c->world + 1)))) return rc;
+    HIPCHK(c, hipMemsetAsync(c->scratch.p, 0, sizeof(double), c->stream));
+    if ((rc = gprx_comm_all_reduce_max(c, c->scratch.p, 1))) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return GPRX_OK;
+  });
 }
 
 }  // extern "C"

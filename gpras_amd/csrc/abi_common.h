@@ -1,5 +1,6 @@
-// Host plumbing shared by the C ABI units (gprx.hip, abi_*.hip): the last-error string, the status check, device buffers,
-// the free-memory check, event timing, the utility stream and the owners of a call's temporaries and a handle's blocks.
+// Host plumbing shared by the C ABI units (gprx.hip, abi_*.hip): the last-error string, the exception guard, the status check, device
+// buffers, the free-memory check, event timing, the utility stream, the split-K plan, the opener of a stream-owning handle and the
+// owners of a call's temporaries and a handle's blocks.
 // Host code only: no kernel lives here, so any unit may include it.
 #pragma once
 
@@ -7,8 +8,11 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdlib>
+#include <exception>
 #include <initializer_list>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -27,6 +31,21 @@ int fail(Ctx* c, int code, const std::string& msg) {
 inline int fail(std::nullptr_t, int code, const std::string& msg) {
   last_error() = msg;
   return code;
+}
+
+// No C++ exception crosses the C boundary: every extern "C" entry point whose body can allocate on the host (new, std::vector,
+// std::string, a concatenated message) runs it as `return guarded(ctx, [&]() -> int { ... });`.  `c`: as for fail.
+template <class Ctx, class F>
+int guarded(Ctx c, F&& body) {
+  try {
+    return body();
+  } catch (const std::bad_alloc&) {
+    return fail(c, GPRX_ENOMEM, "host allocation failed");
+  } catch (const std::exception& e) {
+    return fail(c, GPRX_EHIP, std::string("unexpected exception: ") + e.what());
+  } catch (...) {
+    return fail(c, GPRX_EHIP, "unexpected exception");
+  }
 }
 
 #define HIPCHK(c, expr)                                                                            \
@@ -126,6 +145,30 @@ struct DevTemps {
       if (*q) hipFree(*q);
   }
 };
+
+// Split-K plan of a product with `tiles` output tiles of 64 x 64 and K = kdim: a few thousand workgroups, slices of at least 256 and
+// a multiple of 16, the slabs (slab_doubles each; 1: no cap) held to 256 MiB in all.
+struct SplitK {
+  int kchunk, nsplit;
+};
+inline SplitK splitk_plan(int64_t tiles, int64_t kdim, int64_t slab_doubles) {
+  int64_t nsplit = std::max<int64_t>(1, 2048 / std::max<int64_t>(tiles, 1));
+  nsplit = std::min<int64_t>(nsplit, std::max<int64_t>(1, ((int64_t)1 << 25) / std::max<int64_t>(slab_doubles, 1)));
+  const int64_t kchunk = std::max<int64_t>(((kdim + nsplit - 1) / nsplit + 15) / 16 * 16, 256);
+  return {(int)kchunk, (int)((kdim + kchunk - 1) / kchunk)};
+}
+
+// What the *_create of a stream-owning handle does first, in this order: set the device and store it, create the non-blocking
+// stream, create the events.  On failure the caller destroys the handle (release_handle skips what was not created).
+template <class Ctx>
+static int open_handle(Ctx* h, int device, hipEvent_t* ev = nullptr, int n_ev = 0) {
+  h->device = device;
+  HIPCHK(nullptr, hipSetDevice(device));
+  hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+  for (int i = 0; i < n_ev && e == hipSuccess; ++i) e = hipEventCreate(&ev[i]);
+  if (e != hipSuccess) return fail(nullptr, GPRX_EHIP, std::string("hipStreamCreate / hipEventCreate: ") + hipGetErrorString(e));
+  return GPRX_OK;
+}
 
 // What the *_destroy of a stream-owning handle does, in this order: wait for the stream, free the device blocks, destroy the
 // events, destroy the stream.

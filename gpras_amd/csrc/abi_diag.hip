@@ -39,20 +39,6 @@ constexpr int64_t DG_MAX_N = (int64_t)1 << 40;                          // 32-bi
 constexpr size_t DG_HIST_BYTES = sizeof(unsigned long long) * DG_PASSES * DG_BINS;
 constexpr size_t DG_FIXED_BYTES = DG_HIST_BYTES + 64;                   // + res[4] doubles, the first negative event
 
-// no C++ exception crosses the boundary
-template <class F>
-int guarded(gprx_dg_handle h, F&& body) {
-  try {
-    return body();
-  } catch (const std::bad_alloc&) {
-    return fail(h, GPRX_ENOMEM, "out of host memory");
-  } catch (const std::exception& e) {
-    return fail(h, GPRX_EHIP, std::string("unexpected exception: ") + e.what());
-  } catch (...) {
-    return fail(h, GPRX_EHIP, "unexpected exception");
-  }
-}
-
 // (n <= 2^40: every size here fits a size_t; ensure() answers GPRX_ENOMEM before it allocates what does not fit the device)
 int dg_ensure(gprx_dg_handle h, Buf& b, double bytes, const char* what) { return ensure(h, b, (size_t)bytes, what); }
 
@@ -139,23 +125,15 @@ extern "C" {
 int gprx_dg_create(int device, gprx_dg_handle* out) {
   if (!out) return fail(nullptr, GPRX_EINVAL, "out is null");
   *out = nullptr;
-  return guarded(nullptr, [&]() -> int {
-    HIPCHK(nullptr, hipSetDevice(device));
-    gprx_dg_handle h = new gprx_dg_ctx();
-    h->device = device;
-    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    for (hipEvent_t& ev : h->ev)
-      if (e == hipSuccess) e = hipEventCreate(&ev);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->fixed.p, DG_FIXED_BYTES);
-    if (e != hipSuccess) {
-      h->fixed.p = nullptr;
-      gprx_dg_destroy(h);
-      return fail(nullptr, e == hipErrorOutOfMemory ? GPRX_ENOMEM : GPRX_EHIP, std::string("creating the diagnostics handle: ") + hipGetErrorString(e));
-    }
-    h->fixed.bytes = DG_FIXED_BYTES;
-    *out = h;
-    return GPRX_OK;
+  gprx_dg_handle h = nullptr;
+  const int rc = guarded(nullptr, [&]() -> int {
+    h = new gprx_dg_ctx();
+    const int rc = open_handle(h, device, h->ev, 3);
+    return rc ? rc : ensure(nullptr, h->fixed, DG_FIXED_BYTES);
   });
+  if (rc) gprx_dg_destroy(h);
+  else *out = h;
+  return rc;
 }
 
 // np.sort of n unsigned 64-bit keys: out_dev (n) <- keys_dev (n), which is left unchanged.  The buffers must not overlap.
@@ -169,17 +147,19 @@ int gprx_dg_sort_abs_residual_dev(gprx_dg_handle h, const double* a_dev, const d
 }
 
 int gprx_dg_sort_info(gprx_dg_handle h, int* executed_mask, double* ms) {
-  if (!h) return fail(h, GPRX_EINVAL, "null handle");
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (executed_mask) *executed_mask = h->last_mask;
-  if (ms)
-    for (int i = 0; i < 2; ++i) {
-      float v = 0.f;
-      if (h->timed) HIPCHK(h, hipEventElapsedTime(&v, h->ev[i], h->ev[i + 1]));
-      ms[i] = v;
-    }
-  return GPRX_OK;
+  return guarded(h, [&]() -> int {
+    if (!h) return fail(h, GPRX_EINVAL, "null handle");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (executed_mask) *executed_mask = h->last_mask;
+    if (ms)
+      for (int i = 0; i < 2; ++i) {
+        float v = 0.f;
+        if (h->timed) HIPCHK(h, hipEventElapsedTime(&v, h->ev[i], h->ev[i + 1]));
+        ms[i] = v;
+      }
+    return GPRX_OK;
+  });
 }
 
 // out[j] = sorted_dev[ranks[j]], j < m: ranks and out on the host, only m numbers cross the link each way
@@ -264,8 +244,7 @@ int gprx_dg_detect_dev(gprx_dg_handle h, const double* truth_dev, const double* 
 
 int gprx_dg_synchronize(gprx_dg_handle h) {
   if (!h) return fail(h, GPRX_EINVAL, "null handle");
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return GPRX_OK;
+  return guarded(h, [&]() -> int { HIPCHK(h, hipStreamSynchronize(h->stream)); return GPRX_OK; });
 }
 
 const char* gprx_dg_last_error(gprx_dg_handle h) { return h ? h->err.c_str() : last_error().c_str(); }

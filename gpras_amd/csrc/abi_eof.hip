@@ -30,6 +30,63 @@ void gprx::launch_transpose_small(hipStream_t st, const double* src, int64_t row
   hipLaunchKernelGGL(transpose_small_kernel, dim3((unsigned)std::min<int64_t>((rows * cols + 255) / 256, 4096)), dim3(256), 0, st, src, rows, cols, dst);
 }
 
+// ---- shared by the fit and HmsPreProcessor: the lower-triangle Gram stage and the components stage ----------------------------------
+namespace {
+// split-K plan of the lower-triangle product of n x n with K = kdim
+SplitK gram_plan(int64_t n, int64_t kdim) {
+  const int64_t tiles = (n + 63) / 64;
+  return splitk_plan(tiles * (tiles + 1) / 2, kdim, n * n);
+}
+
+// *out (n, n) = X X^T of X (n, kdim), leading dimension ld: lower-triangle tiles, split-K slabs summed in a fixed order.  `ws` holds
+// the slabs, then their sum, where *out points.
+template <class Ctx>
+int gram_lower(Ctx* c, hipStream_t st, const double* X, int64_t ld, int64_t n, int64_t kdim, Buf& ws, double** out) {
+  const SplitK sk = gram_plan(n, kdim);
+  int rc;
+  if ((rc = ensure(c, ws, sizeof(double) * (size_t)(sk.nsplit + 1) * n * n))) return rc;
+  *out = ws.p + (size_t)sk.nsplit * n * n;
+  GemmArgs g{X, X, ws.p, ld, ld, n, (int)n, (int)n, (int)kdim, 1.0, 0.0, GEMM_C_LOWER, 0, 0, 0, 0, 0, 0, sk.kchunk, n * n};
+  HIPCHK(c, (launch_gemm_t<0, 1, 64, 64>(st, g, 1, sk.nsplit)));
+  hipLaunchKernelGGL(pcafit_gram_reduce_kernel, dim3((unsigned)((n * n + 255) / 256)), dim3(256), 0, st, (const double*)ws.p, sk.nsplit, (int)n, *out);
+  HIPCHK(c, hipGetLastError());
+  return GPRX_OK;
+}
+
+// the argument checks of a components step, of the fit and of HmsPreProcessor (k == 0 passes them: the caller has nothing to do)
+template <class Ctx>
+int check_components(Ctx* c, int k, int64_t rows, const char* rows_name, bool null_argument, const double* lam) {
+  if (k < 0 || k >= rows) return fail(c, GPRX_EINVAL, std::string("need 0 <= k < ") + rows_name + " (centring removes one direction)");
+  if (k == 0) return GPRX_OK;
+  if (null_argument) return fail(c, GPRX_EINVAL, "null argument");
+  for (int i = 0; i < k; ++i)
+    if (!(lam[i] > 0.0)) return fail(c, GPRX_EINVAL, "retained eigenvalues must be positive");
+  return GPRX_OK;
+}
+
+// A (k, rows_p) on the device = diag(lambda^-1/2) U_k^T from u (rows, k) on the host, K padded to rows_p with zeros.  `a` stages
+// it on the host: the caller keeps it until it has waited for `st`.
+template <class Ctx>
+int upload_scaled_ut(Ctx* c, hipStream_t st, const double* u, const double* lam, int k, int64_t rows, int64_t rows_p, std::vector<double>& a, double* A) {
+  a.assign((size_t)k * rows_p, 0.0);
+  for (int i = 0; i < k; ++i) {
+    const double s = 1.0 / std::sqrt(lam[i]);
+    for (int64_t t = 0; t < rows; ++t) a[(size_t)i * rows_p + t] = u[(size_t)t * k + i] * s;
+  }
+  HIPCHK(c, hipMemcpyAsync(A, a.data(), sizeof(double) * a.size(), hipMemcpyHostToDevice, st));
+  return GPRX_OK;
+}
+
+// E (k, ld) = A X2 (NN, K = rows_p; X2 has rows_p rows, zero beyond the samples), then svd_flip on the first `cols` entries of its rows
+template <class Ctx>
+int components_gemm(Ctx* c, hipStream_t st, int k, const double* A, int64_t rows_p, const double* X2, int64_t ld, int64_t cols, double* E) {
+  HIPCHK(c, launch_gemm(st, 0, 0, k, (int)ld, (int)rows_p, 1.0, A, rows_p, X2, ld, 0.0, E, ld, 0));
+  hipLaunchKernelGGL(pcafit_sign_flip_kernel, dim3((unsigned)k), dim3(256), 0, st, E, ld, cols);
+  HIPCHK(c, hipGetLastError());
+  return GPRX_OK;
+}
+}  // namespace
+
 extern "C" {
 
 // ---- EOF projection either side of the GP path ------------------------------
@@ -54,44 +111,41 @@ int gprx_pca_create(int device, int64_t n_cells, int k, const unsigned char* dry
     for (int64_t c = 0; c < n_cells; ++c) n_dry += dry[c] != 0;
   if (depth_mode && !elevations) return fail(nullptr, GPRX_EINVAL, "depth mode needs the cell elevations");
   if (!depth_mode && n_dry > 0 && !elevations) return fail(nullptr, GPRX_EINVAL, "always-dry cells are filled with their elevations: elevations is null");
-  HIPCHK(nullptr, hipSetDevice(device));
-  gprx_pca_handle p = new gprx_pca_ctx();
-  p->device = device;
-  p->cells = n_cells;
-  p->cells_p = round_up(n_cells, 16);
-  p->k = k;
-  p->depth = depth_mode ? 1 : 0;
-  const int64_t n_wet = n_cells - n_dry, cp = p->cells_p;
-  // expand the wet-cell parameters to the full cell axis: dry cells get weight 0 (forward) / 1 (reverse), E = 0 and the fill value
-  std::vector<double> mu(cp, 0.0), wf(cp, 0.0), wr(cp, 1.0), el(cp, 0.0), base(cp, 0.0), E((size_t)k * cp, 0.0);
-  int64_t j = 0;
-  for (int64_t c = 0; c < n_cells; ++c) {
-    if (elevations) el[c] = elevations[c];
-    if (dry && dry[c]) {
-      base[c] = depth_mode ? 0.0 : elevations[c];
-      continue;
+  gprx_pca_handle p = nullptr;
+  const int rc = guarded(nullptr, [&]() -> int {
+    p = new gprx_pca_ctx();
+    int rc = open_handle(p, device);
+    if (rc) return rc;
+    p->cells = n_cells;
+    p->cells_p = round_up(n_cells, 16);
+    p->k = k;
+    p->depth = depth_mode ? 1 : 0;
+    const int64_t n_wet = n_cells - n_dry, cp = p->cells_p;
+    // expand the wet-cell parameters to the full cell axis: dry cells get weight 0 (forward) / 1 (reverse), E = 0 and the fill value
+    std::vector<double> mu(cp, 0.0), wf(cp, 0.0), wr(cp, 1.0), el(cp, 0.0), base(cp, 0.0), E((size_t)k * cp, 0.0);
+    int64_t j = 0;
+    for (int64_t c = 0; c < n_cells; ++c) {
+      if (elevations) el[c] = elevations[c];
+      if (dry && dry[c]) {
+        base[c] = depth_mode ? 0.0 : elevations[c];
+        continue;
+      }
+      mu[c] = input_mean[j];
+      wf[c] = weights ? weights[j] : 1.0;
+      wr[c] = wf[c];
+      base[c] = input_mean[j];
+      for (int kk = 0; kk < k; ++kk) E[(size_t)kk * cp + c] = eofs[(size_t)kk * n_wet + j];
+      ++j;
     }
-    mu[c] = input_mean[j];
-    wf[c] = weights ? weights[j] : 1.0;
-    wr[c] = wf[c];
-    base[c] = input_mean[j];
-    for (int kk = 0; kk < k; ++kk) E[(size_t)kk * cp + c] = eofs[(size_t)kk * n_wet + j];
-    ++j;
-  }
-  int rc = GPRX_OK;
-  hipError_t e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
-  if (e != hipSuccess) {
-    delete p;
-    return fail(nullptr, GPRX_EHIP, std::string("hipStreamCreate: ") + hipGetErrorString(e));
-  }
-  std::vector<double> xm(x_mean, x_mean + k), xs(x_std, x_std + k);
-  if ((rc = pupload(p, p->mu, mu)) || (rc = pupload(p, p->wfwd, wf)) || (rc = pupload(p, p->wrev, wr)) || (rc = pupload(p, p->elev, el)) ||
-      (rc = pupload(p, p->base, base)) || (rc = pupload(p, p->E, E)) || (rc = pupload(p, p->xm, xm)) || (rc = pupload(p, p->xs, xs))) {
-    gprx_pca_destroy(p);
-    return rc;
-  }
-  *out = p;
-  return GPRX_OK;
+    std::vector<double> xm(x_mean, x_mean + k), xs(x_std, x_std + k);
+    if ((rc = pupload(p, p->mu, mu)) || (rc = pupload(p, p->wfwd, wf)) || (rc = pupload(p, p->wrev, wr)) || (rc = pupload(p, p->elev, el)) ||
+        (rc = pupload(p, p->base, base)) || (rc = pupload(p, p->E, E)) || (rc = pupload(p, p->xm, xm)) || (rc = pupload(p, p->xs, xs)))
+      return rc;
+    return GPRX_OK;
+  });
+  if (rc) gprx_pca_destroy(p);
+  else *out = p;
+  return rc;
 }
 
 int gprx_pca_destroy(gprx_pca_handle p) {
@@ -104,125 +158,134 @@ int gprx_pca_destroy(gprx_pca_handle p) {
 
 // x_dev: (rows, ld) with ld = cells_p (padding columns may hold anything finite: their weight is 0); z_dev: (rows, k)
 int gprx_pca_transform_dev(gprx_pca_handle p, const double* x_dev, int64_t rows, double* z_dev) {
-  if (!p) return fail(p, GPRX_EINVAL, "null handle");
-  if (rows < 0 || (rows > 0 && (!x_dev || !z_dev))) return fail(p, GPRX_EINVAL, "null argument");
-  if (rows == 0) return GPRX_OK;
-  if (rows > (1 << 30)) return fail(p, GPRX_EINVAL, "too many rows in one call");
-  HIPCHK(p, hipSetDevice(p->device));
-  hipStream_t st = p->stream;
-  const int64_t cp = p->cells_p;
-  // Z = ((g(X) - mu) w) E^T in ONE pass over X: the centring / weighting runs inside the GEMM's operand load
-  // (gemm_f64_kernel AXF); M = rows, N = k, K = cells_p cut into slices so that a few thousand workgroups exist
-  const int tiles_m = (int)((rows + 63) / 64);
-  int nsplit = std::max(1, 2048 / tiles_m);
-  int kchunk = (int)round_up((cp + nsplit - 1) / nsplit, 16);
-  if (kchunk < 256) kchunk = 256;
-  nsplit = (int)((cp + kchunk - 1) / kchunk);
-  int rc;
-  if ((rc = ensure(p, p->ws, sizeof(double) * (size_t)nsplit * rows * p->k))) return rc;
-  HIPCHK(p, launch_gemm_splitk_axf(st, (int)rows, p->k, (int)cp, x_dev, cp, p->E.p, cp, z_dev, p->k, p->ws.p, kchunk, p->mu.p, p->wfwd.p,
-                                   p->depth ? p->elev.p : nullptr));
-  hipLaunchKernelGGL(pca_standardize_kernel, dim3((unsigned)((rows * p->k + 255) / 256)), dim3(256), 0, st, z_dev, rows, p->k,
-                     (const double*)p->xm.p, (const double*)p->xs.p);
-  HIPCHK(p, hipGetLastError());
-  return GPRX_OK;
+  return guarded(p, [&]() -> int {
+    if (!p) return fail(p, GPRX_EINVAL, "null handle");
+    if (rows < 0 || (rows > 0 && (!x_dev || !z_dev))) return fail(p, GPRX_EINVAL, "null argument");
+    if (rows == 0) return GPRX_OK;
+    if (rows > (1 << 30)) return fail(p, GPRX_EINVAL, "too many rows in one call");
+    HIPCHK(p, hipSetDevice(p->device));
+    hipStream_t st = p->stream;
+    const int64_t cp = p->cells_p;
+    // Z = ((g(X) - mu) w) E^T in ONE pass over X: the centring / weighting runs inside the GEMM's operand load
+    // (gemm_f64_kernel AXF); M = rows, N = k, K = cells_p cut into slices so that a few thousand workgroups exist
+    const SplitK sk = splitk_plan((rows + 63) / 64, cp, 1);
+    int rc;
+    if ((rc = ensure(p, p->ws, sizeof(double) * (size_t)sk.nsplit * rows * p->k))) return rc;
+    HIPCHK(p, launch_gemm_splitk_axf(st, (int)rows, p->k, (int)cp, x_dev, cp, p->E.p, cp, z_dev, p->k, p->ws.p, sk.kchunk, p->mu.p, p->wfwd.p,
+                                     p->depth ? p->elev.p : nullptr));
+    hipLaunchKernelGGL(pca_standardize_kernel, dim3((unsigned)((rows * p->k + 255) / 256)), dim3(256), 0, st, z_dev, rows, p->k,
+                       (const double*)p->xm.p, (const double*)p->xs.p);
+    HIPCHK(p, hipGetLastError());
+    return GPRX_OK;
+  });
 }
 
 int gprx_pca_reverse_dev(gprx_pca_handle p, const double* mean_dev, const double* var_dev, int64_t rows, double* full_dev, double* vfull_dev) {
-  if (!p) return fail(p, GPRX_EINVAL, "null handle");
-  if (rows < 0 || (rows > 0 && (!mean_dev || !full_dev))) return fail(p, GPRX_EINVAL, "null argument");
-  if ((var_dev == nullptr) != (vfull_dev == nullptr)) return fail(p, GPRX_EINVAL, "var and var_full must both be given or both be null");
-  if (rows == 0) return GPRX_OK;
-  HIPCHK(p, hipSetDevice(p->device));
-  dim3 grid((unsigned)((p->cells + 255) / 256), (unsigned)std::min<int64_t>((rows + PCA_RB - 1) / PCA_RB, 64));
-  if (p->k <= 16)
-    hipLaunchKernelGGL(pca_reverse_kernel<16>, grid, dim3(256), 0, p->stream, mean_dev, var_dev, rows, p->k, p->cells, (const double*)p->E.p, p->cells_p,
-                       (const double*)p->wrev.p, (const double*)p->base.p, (const double*)p->xm.p, (const double*)p->xs.p, full_dev, vfull_dev);
-  else
-    hipLaunchKernelGGL(pca_reverse_kernel<64>, grid, dim3(256), 0, p->stream, mean_dev, var_dev, rows, p->k, p->cells, (const double*)p->E.p, p->cells_p,
-                       (const double*)p->wrev.p, (const double*)p->base.p, (const double*)p->xm.p, (const double*)p->xs.p, full_dev, vfull_dev);
-  HIPCHK(p, hipGetLastError());
-  return GPRX_OK;
+  return guarded(p, [&]() -> int {
+    if (!p) return fail(p, GPRX_EINVAL, "null handle");
+    if (rows < 0 || (rows > 0 && (!mean_dev || !full_dev))) return fail(p, GPRX_EINVAL, "null argument");
+    if ((var_dev == nullptr) != (vfull_dev == nullptr)) return fail(p, GPRX_EINVAL, "var and var_full must both be given or both be null");
+    if (rows == 0) return GPRX_OK;
+    HIPCHK(p, hipSetDevice(p->device));
+    dim3 grid((unsigned)((p->cells + 255) / 256), (unsigned)std::min<int64_t>((rows + PCA_RB - 1) / PCA_RB, 64));
+    if (p->k <= 16)
+      hipLaunchKernelGGL(pca_reverse_kernel<16>, grid, dim3(256), 0, p->stream, mean_dev, var_dev, rows, p->k, p->cells, (const double*)p->E.p, p->cells_p,
+                         (const double*)p->wrev.p, (const double*)p->base.p, (const double*)p->xm.p, (const double*)p->xs.p, full_dev, vfull_dev);
+    else
+      hipLaunchKernelGGL(pca_reverse_kernel<64>, grid, dim3(256), 0, p->stream, mean_dev, var_dev, rows, p->k, p->cells, (const double*)p->E.p, p->cells_p,
+                         (const double*)p->wrev.p, (const double*)p->base.p, (const double*)p->xm.p, (const double*)p->xs.p, full_dev, vfull_dev);
+    HIPCHK(p, hipGetLastError());
+    return GPRX_OK;
+  });
 }
 
 int gprx_pca_to_depth_dev(gprx_pca_handle p, double* field_dev, int64_t rows, int add_elevations_first) {
-  if (!p) return fail(p, GPRX_EINVAL, "null handle");
-  if (rows < 0 || (rows > 0 && !field_dev)) return fail(p, GPRX_EINVAL, "null argument");
-  if (rows == 0) return GPRX_OK;
-  HIPCHK(p, hipSetDevice(p->device));
-  hipLaunchKernelGGL(field_to_depth_kernel, dim3(4096), dim3(256), 0, p->stream, field_dev, rows, p->cells, (const double*)p->elev.p,
-                     add_elevations_first ? 1 : 0);
-  HIPCHK(p, hipGetLastError());
-  return GPRX_OK;
+  return guarded(p, [&]() -> int {
+    if (!p) return fail(p, GPRX_EINVAL, "null handle");
+    if (rows < 0 || (rows > 0 && !field_dev)) return fail(p, GPRX_EINVAL, "null argument");
+    if (rows == 0) return GPRX_OK;
+    HIPCHK(p, hipSetDevice(p->device));
+    hipLaunchKernelGGL(field_to_depth_kernel, dim3(4096), dim3(256), 0, p->stream, field_dev, rows, p->cells, (const double*)p->elev.p,
+                       add_elevations_first ? 1 : 0);
+    HIPCHK(p, hipGetLastError());
+    return GPRX_OK;
+  });
 }
 
 int gprx_pca_sqrt_dev(gprx_pca_handle p, double* field_dev, int64_t count) {
-  if (!p) return fail(p, GPRX_EINVAL, "null handle");
-  if (count < 0 || (count > 0 && !field_dev)) return fail(p, GPRX_EINVAL, "null argument");
-  if (count == 0) return GPRX_OK;
-  HIPCHK(p, hipSetDevice(p->device));
-  hipLaunchKernelGGL(field_sqrt_kernel, dim3(4096), dim3(256), 0, p->stream, field_dev, count);
-  HIPCHK(p, hipGetLastError());
-  return GPRX_OK;
+  return guarded(p, [&]() -> int {
+    if (!p) return fail(p, GPRX_EINVAL, "null handle");
+    if (count < 0 || (count > 0 && !field_dev)) return fail(p, GPRX_EINVAL, "null argument");
+    if (count == 0) return GPRX_OK;
+    HIPCHK(p, hipSetDevice(p->device));
+    hipLaunchKernelGGL(field_sqrt_kernel, dim3(4096), dim3(256), 0, p->stream, field_dev, count);
+    HIPCHK(p, hipGetLastError());
+    return GPRX_OK;
+  });
 }
 
 int gprx_pca_transpose_dev(gprx_pca_handle p, const double* src_dev, int64_t rows, int64_t cols, double* dst_dev) {
-  if (!p) return fail(p, GPRX_EINVAL, "null handle");
-  if (rows < 0 || cols < 0 || (rows * cols > 0 && (!src_dev || !dst_dev))) return fail(p, GPRX_EINVAL, "null argument");
-  if (rows * cols == 0) return GPRX_OK;
-  HIPCHK(p, hipSetDevice(p->device));
-  launch_transpose_small(p->stream, src_dev, rows, cols, dst_dev);
-  HIPCHK(p, hipGetLastError());
-  return GPRX_OK;
+  return guarded(p, [&]() -> int {
+    if (!p) return fail(p, GPRX_EINVAL, "null handle");
+    if (rows < 0 || cols < 0 || (rows * cols > 0 && (!src_dev || !dst_dev))) return fail(p, GPRX_EINVAL, "null argument");
+    if (rows * cols == 0) return GPRX_OK;
+    HIPCHK(p, hipSetDevice(p->device));
+    launch_transpose_small(p->stream, src_dev, rows, cols, dst_dev);
+    HIPCHK(p, hipGetLastError());
+    return GPRX_OK;
+  });
 }
 
 int gprx_pca_synchronize(gprx_pca_handle p) {
   if (!p) return fail(p, GPRX_EINVAL, "null handle");
-  HIPCHK(p, hipStreamSynchronize(p->stream));
-  return GPRX_OK;
+  return guarded(p, [&]() -> int { HIPCHK(p, hipStreamSynchronize(p->stream)); return GPRX_OK; });
 }
 
 int gprx_pca_transform(gprx_pca_handle p, const double* x, int64_t rows, double* z) {
-  if (!p) return fail(p, GPRX_EINVAL, "null handle");
-  if (rows < 0 || (rows > 0 && (!x || !z))) return fail(p, GPRX_EINVAL, "null argument");
-  HIPCHK(p, hipSetDevice(p->device));
-  const int64_t cp = p->cells_p, chunk = std::max<int64_t>(64, pca_chunk_doubles() / cp);
-  int rc;
-  for (int64_t t0 = 0; t0 < rows; t0 += chunk) {
-    const int64_t nr = std::min(chunk, rows - t0);
-    if ((rc = ensure(p, p->dX, sizeof(double) * (size_t)nr * cp)) || (rc = ensure(p, p->dZ, sizeof(double) * (size_t)nr * p->k))) return rc;
-    if (cp > p->cells)  // padding columns must be finite (their weight is 0, and 0 * NaN is not)
-      HIPCHK(p, hipMemset2DAsync(p->dX.p + p->cells, sizeof(double) * cp, 0, sizeof(double) * (cp - p->cells), nr, p->stream));
-    HIPCHK(p, hipMemcpy2DAsync(p->dX.p, sizeof(double) * cp, x + t0 * p->cells, sizeof(double) * p->cells, sizeof(double) * p->cells, nr,
-                               hipMemcpyHostToDevice, p->stream));
-    if ((rc = gprx_pca_transform_dev(p, p->dX.p, nr, p->dZ.p))) return rc;
-    HIPCHK(p, hipMemcpyAsync(z + t0 * p->k, p->dZ.p, sizeof(double) * nr * p->k, hipMemcpyDeviceToHost, p->stream));
-    HIPCHK(p, hipStreamSynchronize(p->stream));
-  }
-  return GPRX_OK;
+  return guarded(p, [&]() -> int {
+    if (!p) return fail(p, GPRX_EINVAL, "null handle");
+    if (rows < 0 || (rows > 0 && (!x || !z))) return fail(p, GPRX_EINVAL, "null argument");
+    HIPCHK(p, hipSetDevice(p->device));
+    const int64_t cp = p->cells_p, chunk = std::max<int64_t>(64, pca_chunk_doubles() / cp);
+    int rc;
+    for (int64_t t0 = 0; t0 < rows; t0 += chunk) {
+      const int64_t nr = std::min(chunk, rows - t0);
+      if ((rc = ensure(p, p->dX, sizeof(double) * (size_t)nr * cp)) || (rc = ensure(p, p->dZ, sizeof(double) * (size_t)nr * p->k))) return rc;
+      if (cp > p->cells)  // padding columns must be finite (their weight is 0, and 0 * NaN is not)
+        HIPCHK(p, hipMemset2DAsync(p->dX.p + p->cells, sizeof(double) * cp, 0, sizeof(double) * (cp - p->cells), nr, p->stream));
+      HIPCHK(p, hipMemcpy2DAsync(p->dX.p, sizeof(double) * cp, x + t0 * p->cells, sizeof(double) * p->cells, sizeof(double) * p->cells, nr,
+                                 hipMemcpyHostToDevice, p->stream));
+      if ((rc = gprx_pca_transform_dev(p, p->dX.p, nr, p->dZ.p))) return rc;
+      HIPCHK(p, hipMemcpyAsync(z + t0 * p->k, p->dZ.p, sizeof(double) * nr * p->k, hipMemcpyDeviceToHost, p->stream));
+      HIPCHK(p, hipStreamSynchronize(p->stream));
+    }
+    return GPRX_OK;
+  });
 }
 
 int gprx_pca_reverse(gprx_pca_handle p, const double* mean, const double* var, int64_t rows, double* full, double* var_full) {
-  if (!p) return fail(p, GPRX_EINVAL, "null handle");
-  if (rows < 0 || (rows > 0 && (!mean || !full))) return fail(p, GPRX_EINVAL, "null argument");
-  if ((var == nullptr) != (var_full == nullptr)) return fail(p, GPRX_EINVAL, "var and var_full must both be given or both be null");
-  HIPCHK(p, hipSetDevice(p->device));
-  const int64_t chunk = std::max<int64_t>(64, pca_chunk_doubles() / p->cells);
-  int rc;
-  for (int64_t t0 = 0; t0 < rows; t0 += chunk) {
-    const int64_t nr = std::min(chunk, rows - t0);
-    if ((rc = ensure(p, p->dMean, sizeof(double) * (size_t)nr * p->k)) || (rc = ensure(p, p->dFull, sizeof(double) * (size_t)nr * p->cells))) return rc;
-    HIPCHK(p, hipMemcpyAsync(p->dMean.p, mean + t0 * p->k, sizeof(double) * nr * p->k, hipMemcpyHostToDevice, p->stream));
-    if (var) {
-      if ((rc = ensure(p, p->dVar, sizeof(double) * (size_t)nr * p->k)) || (rc = ensure(p, p->dVfull, sizeof(double) * (size_t)nr * p->cells))) return rc;
-      HIPCHK(p, hipMemcpyAsync(p->dVar.p, var + t0 * p->k, sizeof(double) * nr * p->k, hipMemcpyHostToDevice, p->stream));
+  return guarded(p, [&]() -> int {
+    if (!p) return fail(p, GPRX_EINVAL, "null handle");
+    if (rows < 0 || (rows > 0 && (!mean || !full))) return fail(p, GPRX_EINVAL, "null argument");
+    if ((var == nullptr) != (var_full == nullptr)) return fail(p, GPRX_EINVAL, "var and var_full must both be given or both be null");
+    HIPCHK(p, hipSetDevice(p->device));
+    const int64_t chunk = std::max<int64_t>(64, pca_chunk_doubles() / p->cells);
+    int rc;
+    for (int64_t t0 = 0; t0 < rows; t0 += chunk) {
+      const int64_t nr = std::min(chunk, rows - t0);
+      if ((rc = ensure(p, p->dMean, sizeof(double) * (size_t)nr * p->k)) || (rc = ensure(p, p->dFull, sizeof(double) * (size_t)nr * p->cells))) return rc;
+      HIPCHK(p, hipMemcpyAsync(p->dMean.p, mean + t0 * p->k, sizeof(double) * nr * p->k, hipMemcpyHostToDevice, p->stream));
+      if (var) {
+        if ((rc = ensure(p, p->dVar, sizeof(double) * (size_t)nr * p->k)) || (rc = ensure(p, p->dVfull, sizeof(double) * (size_t)nr * p->cells))) return rc;
+        HIPCHK(p, hipMemcpyAsync(p->dVar.p, var + t0 * p->k, sizeof(double) * nr * p->k, hipMemcpyHostToDevice, p->stream));
+      }
+      if ((rc = gprx_pca_reverse_dev(p, p->dMean.p, var ? p->dVar.p : nullptr, nr, p->dFull.p, var ? p->dVfull.p : nullptr))) return rc;
+      HIPCHK(p, hipMemcpyAsync(full + t0 * p->cells, p->dFull.p, sizeof(double) * nr * p->cells, hipMemcpyDeviceToHost, p->stream));
+      if (var) HIPCHK(p, hipMemcpyAsync(var_full + t0 * p->cells, p->dVfull.p, sizeof(double) * nr * p->cells, hipMemcpyDeviceToHost, p->stream));
+      HIPCHK(p, hipStreamSynchronize(p->stream));
     }
-    if ((rc = gprx_pca_reverse_dev(p, p->dMean.p, var ? p->dVar.p : nullptr, nr, p->dFull.p, var ? p->dVfull.p : nullptr))) return rc;
-    HIPCHK(p, hipMemcpyAsync(full + t0 * p->cells, p->dFull.p, sizeof(double) * nr * p->cells, hipMemcpyDeviceToHost, p->stream));
-    if (var) HIPCHK(p, hipMemcpyAsync(var_full + t0 * p->cells, p->dVfull.p, sizeof(double) * nr * p->cells, hipMemcpyDeviceToHost, p->stream));
-    HIPCHK(p, hipStreamSynchronize(p->stream));
-  }
-  return GPRX_OK;
+    return GPRX_OK;
+  });
 }
 
 int gprx_pca_slab_rows(gprx_pca_handle p, int64_t* rows) {
@@ -252,14 +315,6 @@ struct gprx_pcafit_ctx {
 };
 
 namespace {
-// split-K plan of a product with `tiles` output tiles of 64 x 64 and K = kdim: a few thousand workgroups, slabs capped at 256 MiB
-int pcafit_kchunk(int64_t tiles, int64_t kdim, int64_t slab_doubles) {
-  int64_t nsplit = std::max<int64_t>(1, 2048 / std::max<int64_t>(tiles, 1));
-  nsplit = std::min<int64_t>(nsplit, std::max<int64_t>(1, ((int64_t)1 << 25) / std::max<int64_t>(slab_doubles, 1)));
-  int64_t kchunk = round_up((kdim + nsplit - 1) / nsplit, 16);
-  return (int)std::max<int64_t>(kchunk, 256);
-}
-
 // steps 1-3: upload, column statistics + classes, compaction + both centrings, Gram matrix
 int pcafit_run(gprx_pcafit_handle f, const double* x, const double* elevations, const double* weights, double thr) {
   const int64_t rows = f->rows, cells = f->cells;
@@ -268,8 +323,7 @@ int pcafit_run(gprx_pcafit_handle f, const double* x, const double* elevations, 
   // device memory of the whole fit, before anything is allocated: x, per-cell vectors, both compacted matrices, Gram slabs
   {
     const int64_t ldc_max = round_up(cells, 16);
-    const int64_t tiles = (rows + 63) / 64, ltiles = tiles * (tiles + 1) / 2;
-    const int64_t nsplit = (ldc_max + pcafit_kchunk(ltiles, ldc_max, rows * rows) - 1) / pcafit_kchunk(ltiles, ldc_max, rows * rows);
+    const int64_t nsplit = gram_plan(rows, ldc_max).nsplit;
     const double need = (double)xb + 8.0 * (4.0 * cells + (double)(rows + f->rows_p) * ldc_max + (double)(nsplit + 1) * rows * rows) + cells;
     int rc0;
     if ((rc0 = need_device_bytes(f, need, "the fit"))) return rc0;
@@ -338,17 +392,8 @@ int pcafit_run(gprx_pcafit_handle f, const double* x, const double* elevations, 
   HIPCHK(f, hipGetLastError());
   HIPCHK(f, hipEventRecord(f->ev[4], st));
   // 3. G = Xc2 Xc2^T: lower-triangle tiles, split-K slabs summed in a fixed order
-  const int n = (int)rows;
-  const int64_t tiles = (rows + 63) / 64, ltiles = tiles * (tiles + 1) / 2;
-  const int kchunk = pcafit_kchunk(ltiles, ldc, rows * rows);
-  const int nsplit = (int)((ldc + kchunk - 1) / kchunk);
   int rc;
-  if ((rc = ensure(f, f->ws, sizeof(double) * ((size_t)nsplit * rows * rows + (size_t)rows * rows)))) return rc;
-  double* G = f->G = f->ws.p + (size_t)nsplit * rows * rows;
-  GemmArgs p{f->xc2, f->xc2, f->ws.p, ldc, ldc, (int64_t)n, n, n, (int)ldc, 1.0, 0.0, GEMM_C_LOWER, 0, 0, 0, 0, 0, 0, kchunk, (int64_t)n * n};
-  HIPCHK(f, (launch_gemm_t<0, 1, 64, 64>(st, p, 1, nsplit)));
-  hipLaunchKernelGGL(pcafit_gram_reduce_kernel, dim3((unsigned)(((int64_t)n * n + 255) / 256)), dim3(256), 0, st, (const double*)f->ws.p, nsplit, n, G);
-  HIPCHK(f, hipGetLastError());
+  if ((rc = gram_lower(f, st, f->xc2, ldc, rows, ldc, f->ws, &f->G))) return rc;
   HIPCHK(f, hipEventRecord(f->ev[5], st));
   HIPCHK(f, hipStreamSynchronize(st));  // G stays on the device: gprx_pcafit_gram fetches it on its first call
   f->ms[0] = elapsed_ms(f->ev[0], f->ev[1]);
@@ -374,19 +419,15 @@ int pcafit_components_alloc(gprx_pcafit_handle f, int k) {
 int pcafit_project(gprx_pcafit_handle f, int k, double* eofs, double* z) {
   const int64_t rows = f->rows, rp = f->rows_p, ldc = f->ldc;
   hipStream_t st = f->stream;
-  const int tiles_m = (int)((rows + 63) / 64);
-  const int kchunk = pcafit_kchunk(tiles_m * ((k + 63) / 64), ldc, rows * k);
-  const int nsplit = (int)((ldc + kchunk - 1) / kchunk);
+  const SplitK sk = splitk_plan((rows + 63) / 64 * ((k + 63) / 64), ldc, rows * k);
   int rc;
-  if ((rc = ensure(f, f->ws, sizeof(double) * (size_t)nsplit * rows * k))) return rc;
-  // 5. E = A Xc2 (NN, K = rows_p), then svd_flip on its rows
+  if ((rc = ensure(f, f->ws, sizeof(double) * (size_t)sk.nsplit * rows * k))) return rc;
+  // 5. E = A Xc2, then svd_flip on its rows
   HIPCHK(f, hipEventRecord(f->ev[5], st));
-  HIPCHK(f, launch_gemm(st, 0, 0, k, (int)ldc, (int)rp, 1.0, f->A, rp, f->xc2, ldc, 0.0, f->E, ldc, 0));
-  hipLaunchKernelGGL(pcafit_sign_flip_kernel, dim3((unsigned)k), dim3(256), 0, st, f->E, ldc, f->n_wet);
-  HIPCHK(f, hipGetLastError());
+  if ((rc = components_gemm(f, st, k, f->A, rp, f->xc2, ldc, f->n_wet, f->E))) return rc;
   HIPCHK(f, hipEventRecord(f->ev[6], st));
   // 6. Z = Xc1 E^T (split-K NT; the padding columns of both operands are zero)
-  HIPCHK(f, launch_gemm_splitk(st, 0, 1, (int)rows, k, (int)ldc, 1.0, f->xc1, ldc, f->E, ldc, 0.0, f->Z, k, f->ws.p, kchunk));
+  HIPCHK(f, launch_gemm_splitk(st, 0, 1, (int)rows, k, (int)ldc, 1.0, f->xc1, ldc, f->E, ldc, 0.0, f->Z, k, f->ws.p, sk.kchunk));
   HIPCHK(f, hipEventRecord(f->ev[7], st));
   HIPCHK(f, hipMemcpy2DAsync(eofs, sizeof(double) * f->n_wet, f->E, sizeof(double) * ldc, sizeof(double) * f->n_wet, (size_t)k,
                              hipMemcpyDeviceToHost, st));
@@ -395,20 +436,6 @@ int pcafit_project(gprx_pcafit_handle f, int k, double* eofs, double* z) {
   f->ms[4] = elapsed_ms(f->ev[5], f->ev[6]);
   f->ms[5] = elapsed_ms(f->ev[6], f->ev[7]);
   return GPRX_OK;
-}
-
-int pcafit_components(gprx_pcafit_handle f, int k, const double* u, const double* lam, double* eofs, double* z) {
-  const int64_t rows = f->rows, rp = f->rows_p;
-  // A = diag(lambda^-1/2) U_k^T, K padded to rows_p with zeros
-  std::vector<double> a((size_t)k * rp, 0.0);
-  for (int i = 0; i < k; ++i) {
-    const double s = 1.0 / std::sqrt(lam[i]);
-    for (int64_t t = 0; t < rows; ++t) a[(size_t)i * rp + t] = u[(size_t)t * k + i] * s;
-  }
-  int rc;
-  if ((rc = pcafit_components_alloc(f, k))) return rc;
-  HIPCHK(f, hipMemcpyAsync(f->A, a.data(), sizeof(double) * a.size(), hipMemcpyHostToDevice, f->stream));
-  return pcafit_project(f, k, eofs, z);
 }
 
 // step 4 on the device: G = U diag(lambda) U^T by the block Jacobi solver (eig_jacobi.h); G is overwritten
@@ -452,30 +479,18 @@ int gprx_pcafit_create(int device, const double* x, int64_t n_samples, int64_t n
   if (n_samples < 2 || n_cells < n_samples || n_samples > 16384)
     return fail(nullptr, GPRX_EINVAL, "need 2 <= n_samples <= min(n_cells, 16384)");
   gprx_pcafit_handle f = nullptr;
-  try {
-    HIPCHK(nullptr, hipSetDevice(device));
+  const int rc = guarded(nullptr, [&]() -> int {
     f = new gprx_pcafit_ctx();
-    f->device = device;
     f->mode = mode;
     f->rows = n_samples;
     f->rows_p = round_up(n_samples, 16);
     f->cells = n_cells;
-    int rc = GPRX_OK;
-    hipError_t e = hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking);
-    for (hipEvent_t& ev : f->ev)
-      if (e == hipSuccess) e = hipEventCreate(&ev);
-    if (e != hipSuccess) rc = fail(nullptr, GPRX_EHIP, std::string("hipStreamCreate / hipEventCreate: ") + hipGetErrorString(e));
-    if (!rc) rc = pcafit_run(f, x, elevations, weights, wet_threshold);
-    if (rc) {
-      gprx_pcafit_destroy(f);
-      return rc;
-    }
-  } catch (const std::bad_alloc&) {
-    gprx_pcafit_destroy(f);
-    return fail(nullptr, GPRX_ENOMEM, "host allocation failed");
-  }
-  *out = f;
-  return GPRX_OK;
+    const int rc = open_handle(f, device, f->ev, 8);
+    return rc ? rc : pcafit_run(f, x, elevations, weights, wet_threshold);
+  });
+  if (rc) gprx_pcafit_destroy(f);
+  else *out = f;
+  return rc;
 }
 
 int gprx_pcafit_gram(gprx_pcafit_handle f, unsigned char* classes, double* input_mean, double* gram, int64_t* n_wet) {
@@ -484,7 +499,7 @@ int gprx_pcafit_gram(gprx_pcafit_handle f, unsigned char* classes, double* input
   if (f->gram.empty()) {
     if (f->U) return fail(f, GPRX_ESTATE, "the device eigensolver has overwritten the Gram matrix of this handle");
     if (f->A) return fail(f, GPRX_ESTATE, "the components step has reused the block that held the Gram matrix");
-    try {
+    const int rc = guarded(f, [&]() -> int {
       HIPCHK(f, hipSetDevice(f->device));
       f->gram.resize((size_t)f->rows * f->rows);
       const hipError_t e = hipMemcpyAsync(f->gram.data(), f->G, sizeof(double) * f->rows * f->rows, hipMemcpyDeviceToHost, f->stream);
@@ -493,9 +508,9 @@ int gprx_pcafit_gram(gprx_pcafit_handle f, unsigned char* classes, double* input
         f->gram.clear();
         return fail(f, GPRX_EHIP, std::string("download of the Gram matrix: ") + hipGetErrorString(e2));
       }
-    } catch (const std::bad_alloc&) {
-      return fail(f, GPRX_ENOMEM, "host allocation failed");
-    }
+      return GPRX_OK;
+    });
+    if (rc) return rc;
   }
   std::memcpy(classes, f->cls.data(), f->cls.size());
   std::memcpy(input_mean, f->mean.data(), sizeof(double) * f->mean.size());
@@ -506,17 +521,14 @@ int gprx_pcafit_gram(gprx_pcafit_handle f, unsigned char* classes, double* input
 
 int gprx_pcafit_components(gprx_pcafit_handle f, int k, const double* u, const double* lam, double* eofs, double* z) {
   if (!f) return fail(f, GPRX_EINVAL, "null handle");
-  if (k < 0 || k >= f->rows) return fail(f, GPRX_EINVAL, "need 0 <= k < n_samples (centring removes one direction)");
-  if (k == 0) return GPRX_OK;
-  if (!u || !lam || !eofs || !z) return fail(f, GPRX_EINVAL, "null argument");
-  for (int i = 0; i < k; ++i)
-    if (!(lam[i] > 0.0)) return fail(f, GPRX_EINVAL, "retained eigenvalues must be positive");
-  try {
+  return guarded(f, [&]() -> int {
+    int rc;
+    if ((rc = check_components(f, k, f->rows, "n_samples", !u || !lam || !eofs || !z, lam)) || k == 0) return rc;
     HIPCHK(f, hipSetDevice(f->device));
-    return pcafit_components(f, k, u, lam, eofs, z);
-  } catch (const std::bad_alloc&) {
-    return fail(f, GPRX_ENOMEM, "host allocation failed");
-  }
+    std::vector<double> a;  // read by the upload until pcafit_project has waited for the stream
+    if ((rc = pcafit_components_alloc(f, k)) || (rc = upload_scaled_ut(f, f->stream, u, lam, k, f->rows, f->rows_p, a, f->A))) return rc;
+    return pcafit_project(f, k, eofs, z);
+  });
 }
 
 int gprx_pcafit_eig(gprx_pcafit_handle f, unsigned char* classes, double* input_mean, double* lam, int64_t* n_wet, int* sweeps) {
@@ -524,13 +536,8 @@ int gprx_pcafit_eig(gprx_pcafit_handle f, unsigned char* classes, double* input_
   if (!classes || !input_mean || !lam || !n_wet || !sweeps) return fail(f, GPRX_EINVAL, "null argument");
   if (f->U) return fail(f, GPRX_ESTATE, "the eigensolver has run on this handle: it overwrites the Gram matrix");
   if (f->A) return fail(f, GPRX_ESTATE, "the components step has reused the block that held the Gram matrix: call gprx_pcafit_eig before it");
-  try {
-    HIPCHK(f, hipSetDevice(f->device));
-    const int rc = pcafit_eig(f, sweeps);
-    if (rc) return rc;
-  } catch (const std::bad_alloc&) {
-    return fail(f, GPRX_ENOMEM, "host allocation failed");
-  }
+  const int rc = guarded(f, [&]() -> int { HIPCHK(f, hipSetDevice(f->device)); return pcafit_eig(f, sweeps); });
+  if (rc) return rc;
   std::memcpy(classes, f->cls.data(), f->cls.size());
   std::memcpy(input_mean, f->mean.data(), sizeof(double) * f->mean.size());
   std::memcpy(lam, f->lam_h.data(), sizeof(double) * f->lam_h.size());
@@ -541,19 +548,17 @@ int gprx_pcafit_eig(gprx_pcafit_handle f, unsigned char* classes, double* input_
 int gprx_pcafit_components_dev(gprx_pcafit_handle f, int k, double* eofs, double* z) {
   if (!f) return fail(f, GPRX_EINVAL, "null handle");
   if (f->lam_h.empty()) return fail(f, GPRX_ESTATE, "gprx_pcafit_eig has not run on this handle");
-  if (k < 0 || k >= f->rows) return fail(f, GPRX_EINVAL, "need 0 <= k < n_samples (centring removes one direction)");
-  if (k == 0) return GPRX_OK;
-  if (!eofs || !z) return fail(f, GPRX_EINVAL, "null argument");
-  for (int i = 0; i < k; ++i)
-    if (!(f->lam_h[i] > 0.0)) return fail(f, GPRX_EINVAL, "retained eigenvalues must be positive");
-  HIPCHK(f, hipSetDevice(f->device));
-  int rc;
-  if ((rc = pcafit_components_alloc(f, k))) return rc;
-  const int64_t total = (int64_t)k * f->rows_p;
-  hipLaunchKernelGGL(pcafit_scale_u_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, f->stream, (const double*)f->U, (const double*)f->lam,
-                     f->rows, f->rows_p, k, f->A);
-  HIPCHK(f, hipGetLastError());
-  return pcafit_project(f, k, eofs, z);
+  return guarded(f, [&]() -> int {
+    int rc;
+    if ((rc = check_components(f, k, f->rows, "n_samples", !eofs || !z, f->lam_h.data())) || k == 0) return rc;
+    HIPCHK(f, hipSetDevice(f->device));
+    if ((rc = pcafit_components_alloc(f, k))) return rc;
+    const int64_t total = (int64_t)k * f->rows_p;
+    hipLaunchKernelGGL(pcafit_scale_u_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, f->stream, (const double*)f->U, (const double*)f->lam,
+                       f->rows, f->rows_p, k, f->A);
+    HIPCHK(f, hipGetLastError());
+    return pcafit_project(f, k, eofs, z);
+  });
 }
 
 int gprx_pcafit_eig_ms(gprx_pcafit_handle f, double* ms) {
@@ -586,13 +591,6 @@ struct gprx_hms_ctx {
 };
 
 namespace {
-// split-K plan of the lower-triangle product of n x n with K = kdim (as the Gram of pcafit_run)
-void hms_split(int64_t n, int64_t kdim, int& kchunk, int& nsplit) {
-  const int64_t tiles = (n + 63) / 64, ltiles = tiles * (tiles + 1) / 2;
-  kchunk = pcafit_kchunk(ltiles, kdim, n * n);
-  nsplit = (int)((kdim + kchunk - 1) / kchunk);
-}
-
 // x goes up once and is kept column-major: an F-order x is copied as it is, a C-order x in row chunks through a staging buffer
 int hms_upload(gprx_hms_handle h, const double* x, int64_t ld, int fortran) {
   const int64_t rows = h->rows, nf = h->nfeat;
@@ -630,10 +628,8 @@ int hms_cov(gprx_hms_handle h, double* cov) {
   const int route = rows >= p ? HMS_COV : HMS_GRAM;
   const int64_t n = route == HMS_COV ? p : rows;
   const int64_t ld2 = round_up(route == HMS_COV ? rows : p, 16), r2 = round_up(n, 16);
-  int kchunk = 0, nsplit = 0;
-  hms_split(n, ld2, kchunk, nsplit);
   int rc;
-  if ((rc = need_device_bytes(h, 8.0 * ((double)r2 * ld2 + (double)(nsplit + 1) * n * n + p), "the covariance"))) return rc;
+  if ((rc = need_device_bytes(h, 8.0 * ((double)r2 * ld2 + (double)(gram_plan(n, ld2).nsplit + 1) * n * n + p), "the covariance"))) return rc;
   double* m2 = nullptr;
   DevTemps tmp(st, {(void**)&m2});
   HIPCHK(h, hipMalloc((void**)&m2, sizeof(double) * p));
@@ -650,12 +646,8 @@ int hms_cov(gprx_hms_handle h, double* cov) {
                      (const double*)h->X, rows, rows, (const int64_t*)h->pc, p, (const double*)h->mu, (const double*)m2, route, h->X2, ld2);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipEventRecord(h->ev[3], st));
-  if ((rc = ensure(h, h->ws, sizeof(double) * ((size_t)nsplit * n * n + (size_t)n * n)))) return rc;
-  double* C = h->ws.p + (size_t)nsplit * n * n;
-  GemmArgs g{h->X2, h->X2, h->ws.p, ld2, ld2, n, (int)n, (int)n, (int)ld2, 1.0, 0.0, GEMM_C_LOWER, 0, 0, 0, 0, 0, 0, kchunk, n * n};
-  HIPCHK(h, (launch_gemm_t<0, 1, 64, 64>(st, g, 1, nsplit)));
-  hipLaunchKernelGGL(pcafit_gram_reduce_kernel, dim3((unsigned)((n * n + 255) / 256)), dim3(256), 0, st, (const double*)h->ws.p, nsplit, (int)n, C);
-  HIPCHK(h, hipGetLastError());
+  double* C = nullptr;
+  if ((rc = gram_lower(h, st, h->X2, ld2, n, ld2, h->ws, &C))) return rc;
   HIPCHK(h, hipEventRecord(h->ev[4], st));
   h->mu_h.resize((size_t)h->nfeat);
   HIPCHK(h, hipMemcpyAsync(h->mu_h.data(), h->mu, sizeof(double) * h->nfeat, hipMemcpyDeviceToHost, st));
@@ -670,22 +662,16 @@ int hms_cov(gprx_hms_handle h, double* cov) {
 int hms_components(gprx_hms_handle h, int k, const double* u, const double* lam, double* eofs) {
   const int64_t rows = h->rows, rp = round_up(rows, 16), ld2 = h->ld2;
   hipStream_t st = h->stream;
-  std::vector<double> a((size_t)k * rp, 0.0);
-  for (int i = 0; i < k; ++i) {
-    const double s = 1.0 / std::sqrt(lam[i]);
-    for (int64_t t = 0; t < rows; ++t) a[(size_t)i * rp + t] = u[(size_t)t * k + i] * s;
-  }
   int rc;
-  if ((rc = need_device_bytes(h, 8.0 * ((double)a.size() + (double)k * ld2), "the components"))) return rc;
+  if ((rc = need_device_bytes(h, 8.0 * ((double)k * rp + (double)k * ld2), "the components"))) return rc;
+  std::vector<double> a;  // declared before tmp: it outlives the wait for the stream that reads it
   double *A = nullptr, *E = nullptr;
   DevTemps tmp(st, {(void**)&A, (void**)&E});
-  HIPCHK(h, hipMalloc((void**)&A, sizeof(double) * a.size()));
+  HIPCHK(h, hipMalloc((void**)&A, sizeof(double) * (size_t)k * rp));
   HIPCHK(h, hipMalloc((void**)&E, sizeof(double) * (size_t)k * ld2));
-  HIPCHK(h, hipMemcpyAsync(A, a.data(), sizeof(double) * a.size(), hipMemcpyHostToDevice, st));
+  if ((rc = upload_scaled_ut(h, st, u, lam, k, rows, rp, a, A))) return rc;
   HIPCHK(h, hipEventRecord(h->ev[4], st));
-  HIPCHK(h, launch_gemm(st, 0, 0, k, (int)ld2, (int)rp, 1.0, A, rp, h->X2, ld2, 0.0, E, ld2, 0));
-  hipLaunchKernelGGL(pcafit_sign_flip_kernel, dim3((unsigned)k), dim3(256), 0, st, E, ld2, h->p);
-  HIPCHK(h, hipGetLastError());
+  if ((rc = components_gemm(h, st, k, A, rp, h->X2, ld2, h->p, E))) return rc;
   HIPCHK(h, hipEventRecord(h->ev[5], st));
   HIPCHK(h, hipMemcpy2DAsync(eofs, sizeof(double) * h->p, E, sizeof(double) * ld2, sizeof(double) * h->p, (size_t)k, hipMemcpyDeviceToHost, st));
   HIPCHK(h, hipStreamSynchronize(st));
@@ -791,51 +777,35 @@ int gprx_hms_create(int device, const double* x, int64_t rows, int64_t ld, int64
     if (bc_idx[j] < 0 || bc_idx[j] >= n_features) return fail(nullptr, GPRX_EINVAL, "bc column out of range");
   if (std::min(rows, n_precip) > 16384) return fail(nullptr, GPRX_EINVAL, "min(rows, precip columns) must be <= 16384 (host eigh)");
   gprx_hms_handle h = nullptr;
-  try {
-    HIPCHK(nullptr, hipSetDevice(device));
+  const int rc = guarded(nullptr, [&]() -> int {
     h = new gprx_hms_ctx();
-    h->device = device;
     h->rows = rows;
     h->nfeat = n_features;
     h->n_bc = n_bc;
     h->p = n_precip;
     h->bc_h.assign(bc_idx, bc_idx + n_bc);
     h->pc_h.assign(precip_idx, precip_idx + n_precip);
-    int rc = GPRX_OK;
-    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    for (hipEvent_t& ev : h->ev)
-      if (e == hipSuccess) e = hipEventCreate(&ev);
-    if (e != hipSuccess) rc = fail(nullptr, GPRX_EHIP, std::string("hipStreamCreate / hipEventCreate: ") + hipGetErrorString(e));
+    int rc = open_handle(h, device, h->ev, 8);
     const double staged = fortran ? 0.0 : (double)std::min<int64_t>(rows, std::max<int64_t>(32, ((int64_t)1 << 22) / n_features)) * n_features;
-    if (!rc) rc = need_device_bytes(h, 8.0 * ((double)rows * n_features + staged + n_features + n_bc + n_precip), "x");
-    auto setup = [&]() -> int {
-      HIPCHK(h, hipMalloc((void**)&h->X, sizeof(double) * (size_t)rows * n_features));
-      HIPCHK(h, hipMalloc((void**)&h->mu, sizeof(double) * n_features));
-      HIPCHK(h, hipMalloc((void**)&h->pc, sizeof(int64_t) * n_precip));
-      HIPCHK(h, hipMalloc((void**)&h->bc, sizeof(int64_t) * std::max<int64_t>(n_bc, 1)));
-      HIPCHK(h, hipMemcpyAsync(h->pc, precip_idx, sizeof(int64_t) * n_precip, hipMemcpyHostToDevice, h->stream));
-      if (n_bc) HIPCHK(h, hipMemcpyAsync(h->bc, bc_idx, sizeof(int64_t) * n_bc, hipMemcpyHostToDevice, h->stream));
-      if (input_mean) {
-        h->mu_h.assign(input_mean, input_mean + n_features);
-        HIPCHK(h, hipMemcpyAsync(h->mu, input_mean, sizeof(double) * n_features, hipMemcpyHostToDevice, h->stream));
-      }
-      int rc2 = hms_upload(h, x, ld, fortran);
-      if (rc2) return rc2;
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      h->ms[0] = elapsed_ms(h->ev[0], h->ev[1]);
-      return GPRX_OK;
-    };
-    if (!rc) rc = setup();
-    if (rc) {
-      gprx_hms_destroy(h);
-      return rc;
+    if (rc || (rc = need_device_bytes(h, 8.0 * ((double)rows * n_features + staged + n_features + n_bc + n_precip), "x"))) return rc;
+    HIPCHK(h, hipMalloc((void**)&h->X, sizeof(double) * (size_t)rows * n_features));
+    HIPCHK(h, hipMalloc((void**)&h->mu, sizeof(double) * n_features));
+    HIPCHK(h, hipMalloc((void**)&h->pc, sizeof(int64_t) * n_precip));
+    HIPCHK(h, hipMalloc((void**)&h->bc, sizeof(int64_t) * std::max<int64_t>(n_bc, 1)));
+    HIPCHK(h, hipMemcpyAsync(h->pc, precip_idx, sizeof(int64_t) * n_precip, hipMemcpyHostToDevice, h->stream));
+    if (n_bc) HIPCHK(h, hipMemcpyAsync(h->bc, bc_idx, sizeof(int64_t) * n_bc, hipMemcpyHostToDevice, h->stream));
+    if (input_mean) {
+      h->mu_h.assign(input_mean, input_mean + n_features);
+      HIPCHK(h, hipMemcpyAsync(h->mu, input_mean, sizeof(double) * n_features, hipMemcpyHostToDevice, h->stream));
     }
-  } catch (const std::bad_alloc&) {
-    gprx_hms_destroy(h);
-    return fail(nullptr, GPRX_ENOMEM, "host allocation failed");
-  }
-  *out = h;
-  return GPRX_OK;
+    if ((rc = hms_upload(h, x, ld, fortran))) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->ms[0] = elapsed_ms(h->ev[0], h->ev[1]);
+    return GPRX_OK;
+  });
+  if (rc) gprx_hms_destroy(h);
+  else *out = h;
+  return rc;
 }
 
 int gprx_hms_cov(gprx_hms_handle h, double* input_mean, double* cov, int* route) {
@@ -843,13 +813,8 @@ int gprx_hms_cov(gprx_hms_handle h, double* input_mean, double* cov, int* route)
   if (!input_mean || !cov || !route) return fail(h, GPRX_EINVAL, "null argument");
   if (h->route >= 0 || !h->mu_h.empty()) return fail(h, GPRX_ESTATE, "the covariance is computed once, by a handle created without input_mean");
   if (h->rows < 2) return fail(h, GPRX_EINVAL, "the fit needs rows >= 2");
-  try {
-    HIPCHK(h, hipSetDevice(h->device));
-    const int rc = hms_cov(h, cov);
-    if (rc) return rc;
-  } catch (const std::bad_alloc&) {
-    return fail(h, GPRX_ENOMEM, "host allocation failed");
-  }
+  const int rc = guarded(h, [&]() -> int { HIPCHK(h, hipSetDevice(h->device)); return hms_cov(h, cov); });
+  if (rc) return rc;
   std::memcpy(input_mean, h->mu_h.data(), sizeof(double) * h->nfeat);
   *route = h->route;
   return GPRX_OK;
@@ -858,17 +823,12 @@ int gprx_hms_cov(gprx_hms_handle h, double* input_mean, double* cov, int* route)
 int gprx_hms_components(gprx_hms_handle h, int k, const double* u, const double* lam, double* eofs) {
   if (!h) return fail(h, GPRX_EINVAL, "null handle");
   if (h->route != HMS_GRAM) return fail(h, GPRX_ESTATE, "components are formed on the device only on the Gram route (rows < precip columns)");
-  if (k < 0 || k >= h->rows) return fail(h, GPRX_EINVAL, "need 0 <= k < rows (centring removes one direction)");
-  if (k == 0) return GPRX_OK;
-  if (!u || !lam || !eofs) return fail(h, GPRX_EINVAL, "null argument");
-  for (int i = 0; i < k; ++i)
-    if (!(lam[i] > 0.0)) return fail(h, GPRX_EINVAL, "retained eigenvalues must be positive");
-  try {
+  return guarded(h, [&]() -> int {
+    int rc;
+    if ((rc = check_components(h, k, h->rows, "rows", !u || !lam || !eofs, lam)) || k == 0) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     return hms_components(h, k, u, lam, eofs);
-  } catch (const std::bad_alloc&) {
-    return fail(h, GPRX_ENOMEM, "host allocation failed");
-  }
+  });
 }
 
 int gprx_hms_features(gprx_hms_handle h, int k, const double* eofs, const double* w1, int64_t n1, const double* w2, int64_t n2, double* x_mean,
@@ -877,12 +837,7 @@ int gprx_hms_features(gprx_hms_handle h, int k, const double* eofs, const double
   if (k < 0 || n1 < 0 || n2 < 0 || (k > 0 && !eofs) || (n1 > 0 && !w1) || (n2 > 0 && !w2) || !x_mean || !x_std || (!fit && !out))
     return fail(h, GPRX_EINVAL, "null or negative argument");
   if (h->mu_h.empty()) return fail(h, GPRX_ESTATE, "input_mean is not known: run gprx_hms_cov first or pass it to gprx_hms_create");
-  try {
-    HIPCHK(h, hipSetDevice(h->device));
-    return hms_features(h, k, eofs, w1, n1, w2, n2, x_mean, x_std, fit, out);
-  } catch (const std::bad_alloc&) {
-    return fail(h, GPRX_ENOMEM, "host allocation failed");
-  }
+  return guarded(h, [&]() -> int { HIPCHK(h, hipSetDevice(h->device)); return hms_features(h, k, eofs, w1, n1, w2, n2, x_mean, x_std, fit, out); });
 }
 
 int gprx_hms_timings(gprx_hms_handle h, double* ms) {
@@ -892,28 +847,30 @@ int gprx_hms_timings(gprx_hms_handle h, double* ms) {
 }
 
 int gprx_api(int device, const double* a, int64_t n, const double* w, int64_t n_w, int64_t window, double* out) {
-  if (n < 1 || window < 1) return fail(nullptr, GPRX_EINVAL, "the series and the window must not be empty");
-  if (n_w < 0 || n_w > window || !a || !out || (n_w > 0 && !w)) return fail(nullptr, GPRX_EINVAL, "need 0 <= n_w <= window and non-null arrays");
-  for (int64_t i = 0; i < n_w; ++i)
-    if (!std::isfinite(w[i])) return fail(nullptr, GPRX_EINVAL, "the weights must be finite");
-  bool finite = true;
-  for (int64_t t = 0; t < n && finite; ++t) finite = std::isfinite(a[t]);
-  const int64_t lags = std::min(finite ? n_w : window, n);
-  HIPCHK(nullptr, hipSetDevice(device));
-  const int rc0 = need_device_bytes(nullptr, 8.0 * (2.0 * n + std::max<int64_t>(n_w, 1)), "the API");
-  if (rc0) return rc0;
-  hipStream_t st = util_stream();
-  double *A = nullptr, *W = nullptr, *O = nullptr;
-  DevTemps tmp(st, {(void**)&A, (void**)&W, (void**)&O});
-  HIPCHK(nullptr, hipMalloc((void**)&A, sizeof(double) * n));
-  HIPCHK(nullptr, hipMalloc((void**)&O, sizeof(double) * n));
-  HIPCHK(nullptr, hipMalloc((void**)&W, sizeof(double) * std::max<int64_t>(n_w, 1)));
-  HIPCHK(nullptr, hipMemcpyAsync(A, a, sizeof(double) * n, hipMemcpyHostToDevice, st));
-  if (n_w) HIPCHK(nullptr, hipMemcpyAsync(W, w, sizeof(double) * n_w, hipMemcpyHostToDevice, st));
-  HIPCHK(nullptr, hms_api_launch(st, A, n, W, n_w, lags, O));
-  HIPCHK(nullptr, hipMemcpyAsync(out, O, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-  HIPCHK(nullptr, hipStreamSynchronize(st));
-  return GPRX_OK;
+  return guarded(nullptr, [&]() -> int {
+    if (n < 1 || window < 1) return fail(nullptr, GPRX_EINVAL, "the series and the window must not be empty");
+    if (n_w < 0 || n_w > window || !a || !out || (n_w > 0 && !w)) return fail(nullptr, GPRX_EINVAL, "need 0 <= n_w <= window and non-null arrays");
+    for (int64_t i = 0; i < n_w; ++i)
+      if (!std::isfinite(w[i])) return fail(nullptr, GPRX_EINVAL, "the weights must be finite");
+    bool finite = true;
+    for (int64_t t = 0; t < n && finite; ++t) finite = std::isfinite(a[t]);
+    const int64_t lags = std::min(finite ? n_w : window, n);
+    HIPCHK(nullptr, hipSetDevice(device));
+    const int rc0 = need_device_bytes(nullptr, 8.0 * (2.0 * n + std::max<int64_t>(n_w, 1)), "the API");
+    if (rc0) return rc0;
+    hipStream_t st = util_stream();
+    double *A = nullptr, *W = nullptr, *O = nullptr;
+    DevTemps tmp(st, {(void**)&A, (void**)&W, (void**)&O});
+    HIPCHK(nullptr, hipMalloc((void**)&A, sizeof(double) * n));
+    HIPCHK(nullptr, hipMalloc((void**)&O, sizeof(double) * n));
+    HIPCHK(nullptr, hipMalloc((void**)&W, sizeof(double) * std::max<int64_t>(n_w, 1)));
+    HIPCHK(nullptr, hipMemcpyAsync(A, a, sizeof(double) * n, hipMemcpyHostToDevice, st));
+    if (n_w) HIPCHK(nullptr, hipMemcpyAsync(W, w, sizeof(double) * n_w, hipMemcpyHostToDevice, st));
+    HIPCHK(nullptr, hms_api_launch(st, A, n, W, n_w, lags, O));
+    HIPCHK(nullptr, hipMemcpyAsync(out, O, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    HIPCHK(nullptr, hipStreamSynchronize(st));
+    return GPRX_OK;
+  });
 }
 
 const char* gprx_hms_last_error(gprx_hms_handle h) { return h ? h->err.c_str() : last_error().c_str(); }

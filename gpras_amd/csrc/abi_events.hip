@@ -63,19 +63,6 @@ constexpr int64_t EV_MAX_H = 4096;                // hours per event
 constexpr int64_t EV_MAX_CELLS = (int64_t)1 << 28;  // E x ld: 2 GiB per pivot
 constexpr int64_t EV_MAX_E = ((int64_t)1 << 31) - 1;
 
-template <class F>
-int guarded(gprx_ev_handle h, F&& body) {
-  try {
-    return body();
-  } catch (const std::bad_alloc&) {
-    return fail(h, GPRX_ENOMEM, "out of host memory");
-  } catch (const std::exception& e) {
-    return fail(h, GPRX_EHIP, std::string("unexpected exception: ") + e.what());
-  } catch (...) {
-    return fail(h, GPRX_EHIP, "unexpected exception");
-  }
-}
-
 template <class T>
 int ev_alloc(gprx_ev_handle h, T*& p, double count, const char* what) {
   if (p) return GPRX_OK;
@@ -103,18 +90,11 @@ int finish(gprx_ev_handle h, int slot, bool add = false) {
 }
 
 int new_handle(int device, gprx_ev_handle* out) {
-  HIPCHK(nullptr, hipSetDevice(device));
   gprx_ev_handle h = new gprx_ev_ctx();
-  h->device = device;
-  hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  for (hipEvent_t& ev : h->ev)
-    if (e == hipSuccess) e = hipEventCreate(&ev);
-  if (e != hipSuccess) {
-    gprx_ev_destroy(h);
-    return fail(nullptr, GPRX_EHIP, std::string("creating the event-selection handle: ") + hipGetErrorString(e));
-  }
-  *out = h;
-  return GPRX_OK;
+  const int rc = open_handle(h, device, h->ev, 2);
+  if (rc) gprx_ev_destroy(h);
+  else *out = h;
+  return rc;
 }
 
 // column means (as_scale 0, shift null) or scales of X (n, ncol) with row stride ld, in the fixed order of events.h
@@ -513,8 +493,7 @@ int gprx_ev_farthest(gprx_ev_handle h, const double* scores_dev, int64_t n, int 
 
 int gprx_ev_synchronize(gprx_ev_handle h) {
   if (!h) return fail(h, GPRX_EINVAL, "null handle");
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return GPRX_OK;
+  return guarded(h, [&]() -> int { HIPCHK(h, hipStreamSynchronize(h->stream)); return GPRX_OK; });
 }
 
 int gprx_ev_timings(gprx_ev_handle h, double* ms) {

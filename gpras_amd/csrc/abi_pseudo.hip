@@ -94,74 +94,61 @@ int gprx_ps_create(int device, int64_t n_cells, const double* elev, const int32_
   const double* kn[2] = {us_knots, ds_knots};
   const double* co[2] = {us_coef, ds_coef};
   const int nts[2] = {us_nt, ds_nt};
-  int rc = GPRX_OK;
-  for (int s = 0; s < 2; ++s)
-    if (nts[s] != 0 && (rc = ps_check_spline(nullptr, kn[s], nts[s], co[s]))) return rc;
   gprx_ps_handle h = nullptr;
-  try {
-    HIPCHK(nullptr, hipSetDevice(device));
+  std::vector<double> el, tc[2];  // staged until the stream is idle, on the failure path too (gprx_ps_destroy waits for it)
+  std::vector<int> ix;
+  const int rc = guarded(nullptr, [&]() -> int {
+    int rc;
+    for (int s = 0; s < 2; ++s)
+      if (nts[s] != 0 && (rc = ps_check_spline(nullptr, kn[s], nts[s], co[s]))) return rc;
     h = new gprx_ps_ctx();
-    h->device = device;
     h->cells = n_cells;
     h->C = n_centerline;
     const int64_t ce = round_up(n_cells, 2);  // the surface kernel reads idx and elev in pairs
-    std::vector<double> el(ce, 0.0);
-    std::vector<int> ix(ce, 0);
+    el.assign(ce, 0.0);
+    ix.assign(ce, 0);
     std::copy(elev, elev + n_cells, el.begin());
     std::copy(idx, idx + n_cells, ix.begin());
-    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    for (hipEvent_t& ev : h->ev)
-      if (e == hipSuccess) e = hipEventCreate(&ev);
-    if (e != hipSuccess) rc = fail(nullptr, GPRX_EHIP, std::string("hipStreamCreate / hipEventCreate: ") + hipGetErrorString(e));
-    if (!rc) rc = need_device_bytes(h, 12.0 * ce + 8.0 * n_centerline + 32.0 * PS_MAX_KNOTS, "the pseudo-surface state");
-    std::vector<double> tc[2];  // staged until the stream is idle, on the failure path too (gprx_ps_destroy waits for it)
-    auto setup = [&]() -> int {
-      HIPCHK(h, hipMalloc((void**)&h->elev, sizeof(double) * ce));
-      HIPCHK(h, hipMalloc((void**)&h->idx, sizeof(int) * ce));
-      HIPCHK(h, hipMalloc((void**)&h->w, sizeof(double) * n_centerline));
-      HIPCHK(h, hipMemcpyAsync(h->elev, el.data(), sizeof(double) * ce, hipMemcpyHostToDevice, h->stream));
-      HIPCHK(h, hipMemcpyAsync(h->idx, ix.data(), sizeof(int) * ce, hipMemcpyHostToDevice, h->stream));
-      if (w) {
-        HIPCHK(h, hipMemcpyAsync(h->w, w, sizeof(double) * n_centerline, hipMemcpyHostToDevice, h->stream));
-        h->have_w = true;
-      }
-      for (int s = 0; s < 2; ++s) {
-        if (!nts[s]) continue;
-        tc[s].assign(2 * PS_MAX_KNOTS, 0.0);
-        std::copy(kn[s], kn[s] + nts[s], tc[s].begin());
-        std::copy(co[s], co[s] + nts[s] - 4, tc[s].begin() + PS_MAX_KNOTS);
-        HIPCHK(h, hipMalloc((void**)&h->spl[s], sizeof(double) * 2 * PS_MAX_KNOTS));
-        HIPCHK(h, hipMemcpyAsync(h->spl[s], tc[s].data(), sizeof(double) * 2 * PS_MAX_KNOTS, hipMemcpyHostToDevice, h->stream));
-        h->nt[s] = nts[s];
-      }
-      HIPCHK(h, hipStreamSynchronize(h->stream));  // the host vectors above are read until here
-      return GPRX_OK;
-    };
-    if (!rc) rc = setup();
-    if (rc) {
-      gprx_ps_destroy(h);
+    if ((rc = open_handle(h, device, h->ev, 4)) || (rc = need_device_bytes(h, 12.0 * ce + 8.0 * n_centerline + 32.0 * PS_MAX_KNOTS, "the pseudo-surface state")))
       return rc;
+    HIPCHK(h, hipMalloc((void**)&h->elev, sizeof(double) * ce));
+    HIPCHK(h, hipMalloc((void**)&h->idx, sizeof(int) * ce));
+    HIPCHK(h, hipMalloc((void**)&h->w, sizeof(double) * n_centerline));
+    HIPCHK(h, hipMemcpyAsync(h->elev, el.data(), sizeof(double) * ce, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->idx, ix.data(), sizeof(int) * ce, hipMemcpyHostToDevice, h->stream));
+    if (w) {
+      HIPCHK(h, hipMemcpyAsync(h->w, w, sizeof(double) * n_centerline, hipMemcpyHostToDevice, h->stream));
+      h->have_w = true;
     }
-  } catch (const std::bad_alloc&) {
-    gprx_ps_destroy(h);
-    return fail(nullptr, GPRX_ENOMEM, "host allocation failed");
-  }
-  *out = h;
-  return GPRX_OK;
+    for (int s = 0; s < 2; ++s) {
+      if (!nts[s]) continue;
+      tc[s].assign(2 * PS_MAX_KNOTS, 0.0);
+      std::copy(kn[s], kn[s] + nts[s], tc[s].begin());
+      std::copy(co[s], co[s] + nts[s] - 4, tc[s].begin() + PS_MAX_KNOTS);
+      HIPCHK(h, hipMalloc((void**)&h->spl[s], sizeof(double) * 2 * PS_MAX_KNOTS));
+      HIPCHK(h, hipMemcpyAsync(h->spl[s], tc[s].data(), sizeof(double) * 2 * PS_MAX_KNOTS, hipMemcpyHostToDevice, h->stream));
+      h->nt[s] = nts[s];
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));  // the host vectors above are read until here
+    return GPRX_OK;
+  });
+  if (rc) gprx_ps_destroy(h);
+  else *out = h;
+  return rc;
 }
 
 int gprx_spline_eval(int device, const double* knots, int nt, const double* coef, const double* x, int64_t n, double* out) {
-  int rc = ps_check_spline(nullptr, knots, nt, coef);
-  if (rc) return rc;
-  if (n < 0 || (n > 0 && (!x || !out))) return fail(nullptr, GPRX_EINVAL, "null argument");
-  if (n == 0) return GPRX_OK;
-  HIPCHK(nullptr, hipSetDevice(device));
-  if ((rc = need_device_bytes(nullptr, 16.0 * n + 16.0 * PS_MAX_KNOTS, "the spline evaluation"))) return rc;
-  hipStream_t st = util_stream();
-  double *X = nullptr, *O = nullptr, *TC = nullptr;
-  std::vector<double> tc;  // read by the stream until `tmp` has synchronised it
-  DevTemps tmp(st, {(void**)&X, (void**)&O, (void**)&TC});
-  auto run = [&]() -> int {
+  return guarded(nullptr, [&]() -> int {
+    int rc = ps_check_spline(nullptr, knots, nt, coef);
+    if (rc) return rc;
+    if (n < 0 || (n > 0 && (!x || !out))) return fail(nullptr, GPRX_EINVAL, "null argument");
+    if (n == 0) return GPRX_OK;
+    HIPCHK(nullptr, hipSetDevice(device));
+    if ((rc = need_device_bytes(nullptr, 16.0 * n + 16.0 * PS_MAX_KNOTS, "the spline evaluation"))) return rc;
+    hipStream_t st = util_stream();
+    double *X = nullptr, *O = nullptr, *TC = nullptr;
+    std::vector<double> tc;  // read by the stream until `tmp` has synchronised it
+    DevTemps tmp(st, {(void**)&X, (void**)&O, (void**)&TC});
     tc.assign(2 * PS_MAX_KNOTS, 0.0);
     std::copy(knots, knots + nt, tc.begin());
     std::copy(coef, coef + nt - 4, tc.begin() + PS_MAX_KNOTS);
@@ -174,23 +161,19 @@ int gprx_spline_eval(int device, const double* knots, int nt, const double* coef
     HIPCHK(nullptr, hipMemcpyAsync(out, O, sizeof(double) * n, hipMemcpyDeviceToHost, st));
     HIPCHK(nullptr, hipStreamSynchronize(st));
     return GPRX_OK;
-  };
-  try {
-    rc = run();
-  } catch (const std::bad_alloc&) {
-    rc = fail(nullptr, GPRX_ENOMEM, "host allocation failed");
-  }
-  return rc;
+  });
 }
 
 int gprx_ps_set_weights(gprx_ps_handle h, const double* w) {
-  if (!h) return fail(h, GPRX_EINVAL, "null handle");
-  if (!w) return fail(h, GPRX_EINVAL, "null argument");
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipMemcpyAsync(h->w, w, sizeof(double) * h->C, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->have_w = true;
-  return GPRX_OK;
+  return guarded(h, [&]() -> int {
+    if (!h) return fail(h, GPRX_EINVAL, "null handle");
+    if (!w) return fail(h, GPRX_EINVAL, "null argument");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipMemcpyAsync(h->w, w, sizeof(double) * h->C, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->have_w = true;
+    return GPRX_OK;
+  });
 }
 
 int gprx_ps_fit_centerline(gprx_ps_handle h, const double* us_wse, const double* ds_wse, const double* us_q, const double* ds_q,
@@ -198,13 +181,13 @@ int gprx_ps_fit_centerline(gprx_ps_handle h, const double* us_wse, const double*
   if (!h) return fail(h, GPRX_EINVAL, "null handle");
   if (!us_wse || !ds_wse || !us_q || !ds_q || !centerline_wse || !w) return fail(h, GPRX_EINVAL, "null argument");
   if (rows < 1 || rows > ((int64_t)1 << 31) - 1024) return fail(h, GPRX_EINVAL, "need 1 <= rows < 2^31");
-  HIPCHK(h, hipSetDevice(h->device));
-  double *W = nullptr, *B = nullptr;
-  unsigned char* K = nullptr;
-  const int64_t C = h->C;
-  std::vector<unsigned char> keep;  // read by the stream until `tmp` has synchronised it
-  DevTemps tmp(h->stream, {(void**)&W, (void**)&B, (void**)&K});
-  auto run = [&]() -> int {
+  return guarded(h, [&]() -> int {
+    HIPCHK(h, hipSetDevice(h->device));
+    double *W = nullptr, *B = nullptr;
+    unsigned char* K = nullptr;
+    const int64_t C = h->C;
+    std::vector<unsigned char> keep;  // read by the stream until `tmp` has synchronised it
+    DevTemps tmp(h->stream, {(void**)&W, (void**)&B, (void**)&K});
     keep.assign(rows, 0);
     int64_t n_keep = 0;
     for (int64_t r = 0; r < rows; ++r) n_keep += (keep[r] = (us_q[r] > 0 || ds_q[r] > 0) ? 1 : 0);
@@ -228,137 +211,143 @@ int gprx_ps_fit_centerline(gprx_ps_handle h, const double* us_wse, const double*
     h->fit_timed = true;
     h->have_w = true;
     return GPRX_OK;
-  };
-  int rc;
-  try {
-    rc = run();
-  } catch (const std::bad_alloc&) {
-    rc = fail(h, GPRX_ENOMEM, "host allocation failed");
-  }
-  return rc;
+  });
 }
 
 int gprx_ps_timings(gprx_ps_handle h, double* ms) {
-  if (!h || !ms) return fail(h, GPRX_EINVAL, "null argument");
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  float v[2] = {0.f, 0.f};
-  if (h->fit_timed) HIPCHK(h, hipEventElapsedTime(&v[0], h->ev[0], h->ev[1]));
-  if (h->surface_timed) HIPCHK(h, hipEventElapsedTime(&v[1], h->ev[2], h->ev[3]));
-  ms[0] = v[0];
-  ms[1] = v[1];
-  return GPRX_OK;
+  return guarded(h, [&]() -> int {
+    if (!h || !ms) return fail(h, GPRX_EINVAL, "null argument");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    float v[2] = {0.f, 0.f};
+    if (h->fit_timed) HIPCHK(h, hipEventElapsedTime(&v[0], h->ev[0], h->ev[1]));
+    if (h->surface_timed) HIPCHK(h, hipEventElapsedTime(&v[1], h->ev[2], h->ev[3]));
+    ms[0] = v[0];
+    ms[1] = v[1];
+    return GPRX_OK;
+  });
 }
 
 int gprx_ps_rating(gprx_ps_handle h, const double* us_q, const double* ds_q, int64_t T, double* us_wse, double* ds_wse) {
-  if (!h) return fail(h, GPRX_EINVAL, "null handle");
-  if (!us_q || !ds_q) return fail(h, GPRX_EINVAL, "null argument");
-  if (!h->nt[0] || !h->nt[1]) return fail(h, GPRX_ESTATE, "the handle was created without rating curves");
-  HIPCHK(h, hipSetDevice(h->device));
-  int rc = ps_boundary_buffers(h, T);
-  if (rc) return rc;
-  if ((rc = ensure(h, h->q, sizeof(double) * 2 * (size_t)T, "the flows"))) return rc;
-  HIPCHK(h, hipMemcpyAsync(h->q.p, us_q, sizeof(double) * T, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(h->q.p + T, ds_q, sizeof(double) * T, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, ps_spline_launch(h->stream, h->q.p, T, h->spl[0], h->nt[0], h->us.p));
-  HIPCHK(h, ps_spline_launch(h->stream, h->q.p + T, T, h->spl[1], h->nt[1], h->ds));
-  if (us_wse) HIPCHK(h, hipMemcpyAsync(us_wse, h->us.p, sizeof(double) * T, hipMemcpyDeviceToHost, h->stream));
-  if (ds_wse) HIPCHK(h, hipMemcpyAsync(ds_wse, h->ds, sizeof(double) * T, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return GPRX_OK;
+  return guarded(h, [&]() -> int {
+    if (!h) return fail(h, GPRX_EINVAL, "null handle");
+    if (!us_q || !ds_q) return fail(h, GPRX_EINVAL, "null argument");
+    if (!h->nt[0] || !h->nt[1]) return fail(h, GPRX_ESTATE, "the handle was created without rating curves");
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = ps_boundary_buffers(h, T);
+    if (rc) return rc;
+    if ((rc = ensure(h, h->q, sizeof(double) * 2 * (size_t)T, "the flows"))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->q.p, us_q, sizeof(double) * T, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->q.p + T, ds_q, sizeof(double) * T, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, ps_spline_launch(h->stream, h->q.p, T, h->spl[0], h->nt[0], h->us.p));
+    HIPCHK(h, ps_spline_launch(h->stream, h->q.p + T, T, h->spl[1], h->nt[1], h->ds));
+    if (us_wse) HIPCHK(h, hipMemcpyAsync(us_wse, h->us.p, sizeof(double) * T, hipMemcpyDeviceToHost, h->stream));
+    if (ds_wse) HIPCHK(h, hipMemcpyAsync(ds_wse, h->ds, sizeof(double) * T, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return GPRX_OK;
+  });
 }
 
 int gprx_ps_set_boundaries(gprx_ps_handle h, const double* us_wse, const double* ds_wse, int64_t T) {
-  if (!h) return fail(h, GPRX_EINVAL, "null handle");
-  if (!us_wse || !ds_wse) return fail(h, GPRX_EINVAL, "null argument");
-  HIPCHK(h, hipSetDevice(h->device));
-  int rc = ps_boundary_buffers(h, T);
-  if (rc) return rc;
-  HIPCHK(h, hipMemcpyAsync(h->us.p, us_wse, sizeof(double) * T, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(h->ds, ds_wse, sizeof(double) * T, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return GPRX_OK;
+  return guarded(h, [&]() -> int {
+    if (!h) return fail(h, GPRX_EINVAL, "null handle");
+    if (!us_wse || !ds_wse) return fail(h, GPRX_EINVAL, "null argument");
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = ps_boundary_buffers(h, T);
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->us.p, us_wse, sizeof(double) * T, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->ds, ds_wse, sizeof(double) * T, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return GPRX_OK;
+  });
 }
 
 int gprx_ps_surface_dev(gprx_ps_handle h, int64_t t0, int64_t rows, const double* fluvial_dev, int64_t ldf, double* out_dev, int64_t ldo) {
-  if (!h) return fail(h, GPRX_EINVAL, "null handle");
-  if (rows == 0) return GPRX_OK;
-  if (!out_dev) return fail(h, GPRX_EINVAL, "null argument");
-  if (!h->have_w) return fail(h, GPRX_ESTATE, "the centerline interpolater is not set: fit it or pass it to gprx_ps_create");
-  if (h->T == 0) return fail(h, GPRX_ESTATE, "no boundary series: call gprx_ps_rating or gprx_ps_set_boundaries first");
-  if (t0 < 0 || rows < 0 || t0 + rows > h->T) return fail(h, GPRX_EINVAL, "rows [t0, t0 + rows) lie outside the boundary series");
-  if (ldo < h->cells || (fluvial_dev && ldf < h->cells)) return fail(h, GPRX_EINVAL, "a leading dimension is smaller than n_cells");
-  if (fluvial_dev == out_dev && ldf != ldo) return fail(h, GPRX_EINVAL, "in place needs equal leading dimensions");
-  HIPCHK(h, hipSetDevice(h->device));
-  PsSurfaceArgs a{h->us.p + t0, h->ds + t0, h->w, nullptr, h->idx, h->elev, fluvial_dev, out_dev, rows, h->cells, h->C, ldf, ldo};
-  HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
-  HIPCHK(h, ps_surface_launch(h->stream, a));
-  HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
-  h->surface_timed = true;
-  return GPRX_OK;
+  return guarded(h, [&]() -> int {
+    if (!h) return fail(h, GPRX_EINVAL, "null handle");
+    if (rows == 0) return GPRX_OK;
+    if (!out_dev) return fail(h, GPRX_EINVAL, "null argument");
+    if (!h->have_w) return fail(h, GPRX_ESTATE, "the centerline interpolater is not set: fit it or pass it to gprx_ps_create");
+    if (h->T == 0) return fail(h, GPRX_ESTATE, "no boundary series: call gprx_ps_rating or gprx_ps_set_boundaries first");
+    if (t0 < 0 || rows < 0 || t0 + rows > h->T) return fail(h, GPRX_EINVAL, "rows [t0, t0 + rows) lie outside the boundary series");
+    if (ldo < h->cells || (fluvial_dev && ldf < h->cells)) return fail(h, GPRX_EINVAL, "a leading dimension is smaller than n_cells");
+    if (fluvial_dev == out_dev && ldf != ldo) return fail(h, GPRX_EINVAL, "in place needs equal leading dimensions");
+    HIPCHK(h, hipSetDevice(h->device));
+    PsSurfaceArgs a{h->us.p + t0, h->ds + t0, h->w, nullptr, h->idx, h->elev, fluvial_dev, out_dev, rows, h->cells, h->C, ldf, ldo};
+    HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
+    HIPCHK(h, ps_surface_launch(h->stream, a));
+    HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
+    h->surface_timed = true;
+    return GPRX_OK;
+  });
 }
 
 int gprx_ps_synchronize(gprx_ps_handle h) {
   if (!h) return fail(h, GPRX_EINVAL, "null handle");
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return GPRX_OK;
+  return guarded(h, [&]() -> int { HIPCHK(h, hipStreamSynchronize(h->stream)); return GPRX_OK; });
 }
 
 int gprx_ps_surface(gprx_ps_handle h, const double* fluvial, double* out) {
-  if (!h) return fail(h, GPRX_EINVAL, "null handle");
-  if (!out) return fail(h, GPRX_EINVAL, "null argument");
-  if (h->T == 0) return fail(h, GPRX_ESTATE, "no boundary series: call gprx_ps_rating or gprx_ps_set_boundaries first");
-  HIPCHK(h, hipSetDevice(h->device));
-  const int64_t cells = h->cells, chunk = std::max<int64_t>(64, pca_chunk_doubles() / cells);
-  int rc;
-  for (int64_t t0 = 0; t0 < h->T; t0 += chunk) {
-    const int64_t nr = std::min(chunk, h->T - t0);
-    if ((rc = ensure(h, h->slab, sizeof(double) * (size_t)nr * cells, "a slab of the surface"))) return rc;
-    if (fluvial) HIPCHK(h, hipMemcpyAsync(h->slab.p, fluvial + t0 * cells, sizeof(double) * nr * cells, hipMemcpyHostToDevice, h->stream));
-    if ((rc = gprx_ps_surface_dev(h, t0, nr, fluvial ? h->slab.p : nullptr, cells, h->slab.p, cells))) return rc;  // in place
-    HIPCHK(h, hipMemcpyAsync(out + t0 * cells, h->slab.p, sizeof(double) * nr * cells, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
-  return GPRX_OK;
+  return guarded(h, [&]() -> int {
+    if (!h) return fail(h, GPRX_EINVAL, "null handle");
+    if (!out) return fail(h, GPRX_EINVAL, "null argument");
+    if (h->T == 0) return fail(h, GPRX_ESTATE, "no boundary series: call gprx_ps_rating or gprx_ps_set_boundaries first");
+    HIPCHK(h, hipSetDevice(h->device));
+    const int64_t cells = h->cells, chunk = std::max<int64_t>(64, pca_chunk_doubles() / cells);
+    int rc;
+    for (int64_t t0 = 0; t0 < h->T; t0 += chunk) {
+      const int64_t nr = std::min(chunk, h->T - t0);
+      if ((rc = ensure(h, h->slab, sizeof(double) * (size_t)nr * cells, "a slab of the surface"))) return rc;
+      if (fluvial) HIPCHK(h, hipMemcpyAsync(h->slab.p, fluvial + t0 * cells, sizeof(double) * nr * cells, hipMemcpyHostToDevice, h->stream));
+      if ((rc = gprx_ps_surface_dev(h, t0, nr, fluvial ? h->slab.p : nullptr, cells, h->slab.p, cells))) return rc;  // in place
+      HIPCHK(h, hipMemcpyAsync(out + t0 * cells, h->slab.p, sizeof(double) * nr * cells, hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return GPRX_OK;
+  });
 }
 
 int gprx_ps_centerline(gprx_ps_handle h, double* out) {
-  if (!h) return fail(h, GPRX_EINVAL, "null handle");
-  if (!out) return fail(h, GPRX_EINVAL, "null argument");
-  if (!h->have_w) return fail(h, GPRX_ESTATE, "the centerline interpolater is not set: fit it or pass it to gprx_ps_create");
-  if (h->T == 0) return fail(h, GPRX_ESTATE, "no boundary series: call gprx_ps_rating or gprx_ps_set_boundaries first");
-  HIPCHK(h, hipSetDevice(h->device));
-  const int64_t C = h->C, chunk = std::max<int64_t>(64, pca_chunk_doubles() / C);
-  int rc;
-  for (int64_t t0 = 0; t0 < h->T; t0 += chunk) {
-    const int64_t nr = std::min(chunk, h->T - t0);
-    if ((rc = ensure(h, h->slab, sizeof(double) * (size_t)nr * C, "a slab of the centerline"))) return rc;
-    PsSurfaceArgs a{h->us.p + t0, h->ds + t0, h->w, nullptr, nullptr, nullptr, nullptr, h->slab.p, nr, C, C, C, C};
-    HIPCHK(h, ps_surface_launch(h->stream, a));
-    HIPCHK(h, hipMemcpyAsync(out + t0 * C, h->slab.p, sizeof(double) * nr * C, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
-  return GPRX_OK;
+  return guarded(h, [&]() -> int {
+    if (!h) return fail(h, GPRX_EINVAL, "null handle");
+    if (!out) return fail(h, GPRX_EINVAL, "null argument");
+    if (!h->have_w) return fail(h, GPRX_ESTATE, "the centerline interpolater is not set: fit it or pass it to gprx_ps_create");
+    if (h->T == 0) return fail(h, GPRX_ESTATE, "no boundary series: call gprx_ps_rating or gprx_ps_set_boundaries first");
+    HIPCHK(h, hipSetDevice(h->device));
+    const int64_t C = h->C, chunk = std::max<int64_t>(64, pca_chunk_doubles() / C);
+    int rc;
+    for (int64_t t0 = 0; t0 < h->T; t0 += chunk) {
+      const int64_t nr = std::min(chunk, h->T - t0);
+      if ((rc = ensure(h, h->slab, sizeof(double) * (size_t)nr * C, "a slab of the centerline"))) return rc;
+      PsSurfaceArgs a{h->us.p + t0, h->ds + t0, h->w, nullptr, nullptr, nullptr, nullptr, h->slab.p, nr, C, C, C, C};
+      HIPCHK(h, ps_surface_launch(h->stream, a));
+      HIPCHK(h, hipMemcpyAsync(out + t0 * C, h->slab.p, sizeof(double) * nr * C, hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return GPRX_OK;
+  });
 }
 
 int gprx_ps_gather(gprx_ps_handle h, const double* centerline, int64_t rows, double* out) {
-  if (!h) return fail(h, GPRX_EINVAL, "null handle");
-  if (rows < 0 || (rows > 0 && (!centerline || !out))) return fail(h, GPRX_EINVAL, "null argument");
-  HIPCHK(h, hipSetDevice(h->device));
-  const int64_t C = h->C, cells = h->cells, chunk = std::max<int64_t>(64, pca_chunk_doubles() / cells);
-  int rc;
-  for (int64_t t0 = 0; t0 < rows; t0 += chunk) {
-    const int64_t nr = std::min(chunk, rows - t0);
-    if ((rc = ensure(h, h->slab, sizeof(double) * (size_t)nr * cells, "a slab of the surface")) ||
-        (rc = ensure(h, h->cl, sizeof(double) * (size_t)nr * C, "a slab of the centerline")))
-      return rc;
-    HIPCHK(h, hipMemcpyAsync(h->cl.p, centerline + t0 * C, sizeof(double) * nr * C, hipMemcpyHostToDevice, h->stream));
-    PsSurfaceArgs a{nullptr, nullptr, nullptr, h->cl.p, h->idx, nullptr, nullptr, h->slab.p, nr, cells, C, cells, cells};
-    HIPCHK(h, ps_surface_launch(h->stream, a));
-    HIPCHK(h, hipMemcpyAsync(out + t0 * cells, h->slab.p, sizeof(double) * nr * cells, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
-  return GPRX_OK;
+  return guarded(h, [&]() -> int {
+    if (!h) return fail(h, GPRX_EINVAL, "null handle");
+    if (rows < 0 || (rows > 0 && (!centerline || !out))) return fail(h, GPRX_EINVAL, "null argument");
+    HIPCHK(h, hipSetDevice(h->device));
+    const int64_t C = h->C, cells = h->cells, chunk = std::max<int64_t>(64, pca_chunk_doubles() / cells);
+    int rc;
+    for (int64_t t0 = 0; t0 < rows; t0 += chunk) {
+      const int64_t nr = std::min(chunk, rows - t0);
+      if ((rc = ensure(h, h->slab, sizeof(double) * (size_t)nr * cells, "a slab of the surface")) ||
+          (rc = ensure(h, h->cl, sizeof(double) * (size_t)nr * C, "a slab of the centerline")))
+        return rc;
+      HIPCHK(h, hipMemcpyAsync(h->cl.p, centerline + t0 * C, sizeof(double) * nr * C, hipMemcpyHostToDevice, h->stream));
+      PsSurfaceArgs a{nullptr, nullptr, nullptr, h->cl.p, h->idx, nullptr, nullptr, h->slab.p, nr, cells, C, cells, cells};
+      HIPCHK(h, ps_surface_launch(h->stream, a));
+      HIPCHK(h, hipMemcpyAsync(out + t0 * cells, h->slab.p, sizeof(double) * nr * cells, hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return GPRX_OK;
+  });
 }
 
 const char* gprx_ps_last_error(gprx_ps_handle h) { return h ? h->err.c_str() : last_error().c_str(); }

@@ -70,25 +70,26 @@ int gprx_rs_create(int device, int64_t n_src, int64_t n_out, int n_vert, const i
   if ((n_vert == 3) != (weights != nullptr)) return fail(nullptr, GPRX_EINVAL, "weights go with n_vert = 3 and with nothing else");
   if (n_src < 1 || n_out < 1 || n_src > RS_MAX_SRC || n_out > ((int64_t)1 << 31) - 1024)
     return fail(nullptr, GPRX_EINVAL, "need 1 <= n_src <= 2^28 and 1 <= n_out < 2^31");
-  for (int64_t j = 0; j < n_out; ++j) {
-    const int32_t* t = idx + j * n_vert;
-    if (n_vert == 3 && t[0] == -1 && t[1] == -1 && t[2] == -1) continue;  // outside the hull
-    for (int v = 0; v < n_vert; ++v)
-      if (t[v] < 0 || t[v] >= n_src)
-        return fail(nullptr, GPRX_EINVAL, "idx holds an index outside [0, n_src)" + std::string(n_vert == 3 ? " that is not the outside marker (-1, -1, -1)" : ""));
-  }
   gprx_rs_handle h = nullptr;
-  try {
-    HIPCHK(nullptr, hipSetDevice(device));
+  std::vector<int> ix;  // staged until the stream is idle, on the failure path too (gprx_rs_destroy waits for it)
+  std::vector<double> ww, el;
+  const int rc = guarded(nullptr, [&]() -> int {
+    for (int64_t j = 0; j < n_out; ++j) {
+      const int32_t* t = idx + j * n_vert;
+      if (n_vert == 3 && t[0] == -1 && t[1] == -1 && t[2] == -1) continue;  // outside the hull
+      for (int v = 0; v < n_vert; ++v)
+        if (t[v] < 0 || t[v] >= n_src)
+          return fail(nullptr, GPRX_EINVAL, "idx holds an index outside [0, n_src)" + std::string(n_vert == 3 ? " that is not the outside marker (-1, -1, -1)" : ""));
+    }
     h = new gprx_rs_ctx();
-    h->device = device;
     h->n_src = n_src;
     h->n_out = n_out;
     h->nv = n_vert;
     const int64_t ce = h->ce = round_up(n_out, 2);  // the kernel reads the per-cell arrays in pairs
     // planes per vertex; an outside point becomes vertices (0, 0, 0) with NaN weights, so the kernel reads in range and yields NaN
-    std::vector<int> ix((size_t)ce * n_vert, 0);
-    std::vector<double> ww(weights ? (size_t)ce * 3 : 0, 0.0), el(elev ? (size_t)ce : 0, 0.0);
+    ix.assign((size_t)ce * n_vert, 0);
+    ww.assign(weights ? (size_t)ce * 3 : 0, 0.0);
+    el.assign(elev ? (size_t)ce : 0, 0.0);
     const double nan = std::numeric_limits<double>::quiet_NaN();
     for (int64_t j = 0; j < n_out; ++j) {
       const bool outside = idx[j * n_vert] < 0;
@@ -98,94 +99,88 @@ int gprx_rs_create(int device, int64_t n_src, int64_t n_out, int n_vert, const i
       }
     }
     if (elev) std::copy(elev, elev + n_out, el.begin());
-    int rc = GPRX_OK;
-    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    for (hipEvent_t& ev : h->ev)
-      if (e == hipSuccess) e = hipEventCreate(&ev);
-    if (e != hipSuccess) rc = fail(nullptr, GPRX_EHIP, std::string("hipStreamCreate / hipEventCreate: ") + hipGetErrorString(e));
-    if (!rc) rc = need_device_bytes(h, (4.0 * n_vert + (weights ? 24.0 : 0.0) + (elev ? 8.0 : 0.0)) * ce, "the resampler state");
-    auto setup = [&]() -> int {
-      HIPCHK(h, hipMalloc((void**)&h->idx, sizeof(int) * ix.size()));
-      HIPCHK(h, hipMemcpyAsync(h->idx, ix.data(), sizeof(int) * ix.size(), hipMemcpyHostToDevice, h->stream));
-      if (weights) {
-        HIPCHK(h, hipMalloc((void**)&h->w, sizeof(double) * ww.size()));
-        HIPCHK(h, hipMemcpyAsync(h->w, ww.data(), sizeof(double) * ww.size(), hipMemcpyHostToDevice, h->stream));
-      }
-      if (elev) {
-        HIPCHK(h, hipMalloc((void**)&h->elev, sizeof(double) * el.size()));
-        HIPCHK(h, hipMemcpyAsync(h->elev, el.data(), sizeof(double) * el.size(), hipMemcpyHostToDevice, h->stream));
-      }
-      HIPCHK(h, hipStreamSynchronize(h->stream));  // the host vectors above are read until here
-      return GPRX_OK;
-    };
-    if (!rc) rc = setup();
-    if (rc) {
-      gprx_rs_destroy(h);  // waits for the stream before the vectors go
+    int rc;
+    if ((rc = open_handle(h, device, h->ev, 2)) ||
+        (rc = need_device_bytes(h, (4.0 * n_vert + (weights ? 24.0 : 0.0) + (elev ? 8.0 : 0.0)) * ce, "the resampler state")))
       return rc;
+    HIPCHK(h, hipMalloc((void**)&h->idx, sizeof(int) * ix.size()));
+    HIPCHK(h, hipMemcpyAsync(h->idx, ix.data(), sizeof(int) * ix.size(), hipMemcpyHostToDevice, h->stream));
+    if (weights) {
+      HIPCHK(h, hipMalloc((void**)&h->w, sizeof(double) * ww.size()));
+      HIPCHK(h, hipMemcpyAsync(h->w, ww.data(), sizeof(double) * ww.size(), hipMemcpyHostToDevice, h->stream));
     }
-  } catch (const std::bad_alloc&) {
-    gprx_rs_destroy(h);
-    return fail(nullptr, GPRX_ENOMEM, "host allocation failed");
-  }
-  *out = h;
-  return GPRX_OK;
+    if (elev) {
+      HIPCHK(h, hipMalloc((void**)&h->elev, sizeof(double) * el.size()));
+      HIPCHK(h, hipMemcpyAsync(h->elev, el.data(), sizeof(double) * el.size(), hipMemcpyHostToDevice, h->stream));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));  // the host vectors above are read until here
+    return GPRX_OK;
+  });
+  if (rc) gprx_rs_destroy(h);
+  else *out = h;
+  return rc;
 }
 
 // get_lf_plan_data of either builder (:363-377, :433-451) or get_hf_plan_data's gather (:163-174) on device buffers.
 int gprx_rs_apply_dev(gprx_rs_handle h, int64_t rows, const double* src_dev, int64_t lds, const double* src2_dev, double* out_dev, int64_t ldo) {
-  if (!h) return fail(h, GPRX_EINVAL, "null handle");
-  if (rows < 0 || rows > ((int64_t)1 << 31) - 1024) return fail(h, GPRX_EINVAL, "need 0 <= rows < 2^31");
-  if (src2_dev && (h->nv != 1 || h->elev)) return fail(h, GPRX_EINVAL, "a second operand (velocity) needs a nearest handle without elevations");
-  if (lds < h->n_src) return fail(h, GPRX_EINVAL, "lds is smaller than n_src");
-  if (ldo < h->n_out) return fail(h, GPRX_EINVAL, "ldo is smaller than n_out");
-  if (rows == 0) return GPRX_OK;
-  if (!src_dev || !out_dev) return fail(h, GPRX_EINVAL, "null argument");
-  HIPCHK(h, hipSetDevice(h->device));
-  RsArgs a{src_dev, src2_dev, h->idx, h->w, h->elev, out_dev, rows, h->n_out, h->ce, lds, ldo};
-  HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-  HIPCHK(h, rs_launch(h->stream, h->nv, a));
-  HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
-  h->timed = true;
-  return GPRX_OK;
+  return guarded(h, [&]() -> int {
+    if (!h) return fail(h, GPRX_EINVAL, "null handle");
+    if (rows < 0 || rows > ((int64_t)1 << 31) - 1024) return fail(h, GPRX_EINVAL, "need 0 <= rows < 2^31");
+    if (src2_dev && (h->nv != 1 || h->elev)) return fail(h, GPRX_EINVAL, "a second operand (velocity) needs a nearest handle without elevations");
+    if (lds < h->n_src) return fail(h, GPRX_EINVAL, "lds is smaller than n_src");
+    if (ldo < h->n_out) return fail(h, GPRX_EINVAL, "ldo is smaller than n_out");
+    if (rows == 0) return GPRX_OK;
+    if (!src_dev || !out_dev) return fail(h, GPRX_EINVAL, "null argument");
+    HIPCHK(h, hipSetDevice(h->device));
+    RsArgs a{src_dev, src2_dev, h->idx, h->w, h->elev, out_dev, rows, h->n_out, h->ce, lds, ldo};
+    HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
+    HIPCHK(h, rs_launch(h->stream, h->nv, a));
+    HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
+    h->timed = true;
+    return GPRX_OK;
+  });
 }
 
 // The same on host arrays, src / src2 (T, n_src), out (T, n_out), in row slabs: device memory does not grow with T.
 int gprx_rs_apply(gprx_rs_handle h, const double* src, const double* src2, int64_t T, double* out) {
-  if (!h) return fail(h, GPRX_EINVAL, "null handle");
-  if (T < 0 || (T > 0 && (!src || !out))) return fail(h, GPRX_EINVAL, "null argument");
-  if (src2 && (h->nv != 1 || h->elev)) return fail(h, GPRX_EINVAL, "a second operand (velocity) needs a nearest handle without elevations");
-  HIPCHK(h, hipSetDevice(h->device));
-  const int64_t ns = h->n_src, no = h->n_out, chunk = std::max<int64_t>(64, pca_chunk_doubles() / std::max(ns, no));
-  int rc;
-  for (int64_t t0 = 0; t0 < T; t0 += chunk) {
-    const int64_t nr = std::min(chunk, T - t0);
-    if ((rc = ensure(h, h->src, sizeof(double) * (size_t)nr * ns, "a slab of the source rows")) ||
-        (src2 && (rc = ensure(h, h->src2, sizeof(double) * (size_t)nr * ns, "a slab of the second operand"))) ||
-        (rc = ensure(h, h->slab, sizeof(double) * (size_t)nr * no, "a slab of the resampled field")))
-      return rc;
-    HIPCHK(h, hipMemcpyAsync(h->src.p, src + t0 * ns, sizeof(double) * nr * ns, hipMemcpyHostToDevice, h->stream));
-    if (src2) HIPCHK(h, hipMemcpyAsync(h->src2.p, src2 + t0 * ns, sizeof(double) * nr * ns, hipMemcpyHostToDevice, h->stream));
-    if ((rc = gprx_rs_apply_dev(h, nr, h->src.p, ns, src2 ? h->src2.p : nullptr, h->slab.p, no))) return rc;
-    HIPCHK(h, hipMemcpyAsync(out + t0 * no, h->slab.p, sizeof(double) * nr * no, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
-  return GPRX_OK;
+  return guarded(h, [&]() -> int {
+    if (!h) return fail(h, GPRX_EINVAL, "null handle");
+    if (T < 0 || (T > 0 && (!src || !out))) return fail(h, GPRX_EINVAL, "null argument");
+    if (src2 && (h->nv != 1 || h->elev)) return fail(h, GPRX_EINVAL, "a second operand (velocity) needs a nearest handle without elevations");
+    HIPCHK(h, hipSetDevice(h->device));
+    const int64_t ns = h->n_src, no = h->n_out, chunk = std::max<int64_t>(64, pca_chunk_doubles() / std::max(ns, no));
+    int rc;
+    for (int64_t t0 = 0; t0 < T; t0 += chunk) {
+      const int64_t nr = std::min(chunk, T - t0);
+      if ((rc = ensure(h, h->src, sizeof(double) * (size_t)nr * ns, "a slab of the source rows")) ||
+          (src2 && (rc = ensure(h, h->src2, sizeof(double) * (size_t)nr * ns, "a slab of the second operand"))) ||
+          (rc = ensure(h, h->slab, sizeof(double) * (size_t)nr * no, "a slab of the resampled field")))
+        return rc;
+      HIPCHK(h, hipMemcpyAsync(h->src.p, src + t0 * ns, sizeof(double) * nr * ns, hipMemcpyHostToDevice, h->stream));
+      if (src2) HIPCHK(h, hipMemcpyAsync(h->src2.p, src2 + t0 * ns, sizeof(double) * nr * ns, hipMemcpyHostToDevice, h->stream));
+      if ((rc = gprx_rs_apply_dev(h, nr, h->src.p, ns, src2 ? h->src2.p : nullptr, h->slab.p, no))) return rc;
+      HIPCHK(h, hipMemcpyAsync(out + t0 * no, h->slab.p, sizeof(double) * nr * no, hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return GPRX_OK;
+  });
 }
 
 int gprx_rs_timings(gprx_rs_handle h, double* ms) {
-  if (!h || !ms) return fail(h, GPRX_EINVAL, "null argument");
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  float v = 0.f;
-  if (h->timed) HIPCHK(h, hipEventElapsedTime(&v, h->ev[0], h->ev[1]));
-  ms[0] = v;
-  return GPRX_OK;
+  return guarded(h, [&]() -> int {
+    if (!h || !ms) return fail(h, GPRX_EINVAL, "null argument");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    float v = 0.f;
+    if (h->timed) HIPCHK(h, hipEventElapsedTime(&v, h->ev[0], h->ev[1]));
+    ms[0] = v;
+    return GPRX_OK;
+  });
 }
 
 int gprx_rs_synchronize(gprx_rs_handle h) {
   if (!h) return fail(h, GPRX_EINVAL, "null handle");
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return GPRX_OK;
+  return guarded(h, [&]() -> int { HIPCHK(h, hipStreamSynchronize(h->stream)); return GPRX_OK; });
 }
 
 const char* gprx_rs_last_error(gprx_rs_handle h) { return h ? h->err.c_str() : last_error().c_str(); }

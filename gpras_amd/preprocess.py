@@ -464,7 +464,8 @@ class HmsPreProcessor:
                 if k > n_s - 1 or (k > 0 and not lam[k - 1] > 0.0):
                     raise ValueError(f"{k} modes exceed the numerical rank of the centred precip block ({n_s} samples)")
                 eofs = np.empty((k, p))
-                check(lib.gprx_hms_components(h, k, ptr(np.ascontiguousarray(v[:, :k])), ptr(np.ascontiguousarray(lam[:k])), ptr(eofs)))
+                u_k, lam_k = np.ascontiguousarray(v[:, :k]), np.ascontiguousarray(lam[:k])  # named: ptr() keeps no reference
+                check(lib.gprx_hms_components(h, k, ptr(u_k), ptr(lam_k), ptr(eofs)))
             ke = eofs.shape[0]
             e_c = np.ascontiguousarray(eofs)
             w1, w2 = api_weights(0.85, n_s), api_weights(1, n_s)

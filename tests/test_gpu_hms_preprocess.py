@@ -126,6 +126,80 @@ def test_k_beyond_the_component_count():
         HmsPreProcessor().fit(c["x"], c["bc_mask"], c["precip_mask"], c["x"].shape[0])
 
 
+def _raw_hms(rows, n_bc, n_precip, n_other=0, with_mean=False):
+    """A gprx_hms handle over random x: columns [bc | precip | unused], created with or without input_mean."""
+    import ctypes as C
+
+    from gpras_amd import _lib
+    from gpras_amd._lib import ptr
+
+    lib = _lib.load()
+    n_f = n_bc + n_precip + n_other
+    x = np.random.default_rng(100 * rows + n_f).standard_normal((rows, n_f))
+    bc, pc = np.arange(n_bc, dtype=np.int64), np.arange(n_bc, n_bc + n_precip, dtype=np.int64)
+    mean = x.mean(axis=0)
+    h = C.c_void_p()
+    _lib.check(lib.gprx_hms_create(0, ptr(x), rows, n_f, n_f, 0, ptr(bc) if n_bc else None, n_bc, ptr(pc), n_precip, ptr(mean) if with_mean else None,
+                                   C.byref(h)))
+    return lib, h, n_f
+
+
+def test_call_order_of_the_handle_is_enforced():
+    """gprx_hms_cov runs once and only on a handle created without input_mean; gprx_hms_features needs input_mean from either;
+    gprx_hms_components belongs to the Gram route alone."""
+    import ctypes as C
+
+    from gpras_amd import _lib
+    from gpras_amd._lib import ptr
+
+    lib, h, n_f = _raw_hms(8, 1, 4, n_other=1)
+    try:
+        mean, cov, route = np.empty(n_f), np.empty((4, 4)), C.c_int(-1)
+        x_mean, x_std = np.empty(4), np.empty(4)  # n_bc + 0 components + 3
+        assert lib.gprx_hms_features(h, 0, None, None, 0, None, 0, ptr(x_mean), ptr(x_std), 1, None) == _lib.GPRX_ESTATE
+        assert lib.gprx_hms_cov(h, ptr(mean), ptr(cov), C.byref(route)) == _lib.GPRX_OK
+        assert route.value == 0  # HMS_COV: rows >= precip columns
+        assert lib.gprx_hms_cov(h, ptr(mean), ptr(cov), C.byref(route)) == _lib.GPRX_ESTATE
+        u, lam, eofs = np.eye(8)[:, :2].copy(), np.ones(2), np.empty((2, 4))
+        assert lib.gprx_hms_components(h, 2, ptr(u), ptr(lam), ptr(eofs)) == _lib.GPRX_ESTATE
+    finally:
+        lib.gprx_hms_destroy(h)
+    lib, h, n_f = _raw_hms(8, 1, 4, n_other=1, with_mean=True)
+    try:
+        assert lib.gprx_hms_cov(h, ptr(mean), ptr(cov), C.byref(route)) == _lib.GPRX_ESTATE
+    finally:
+        lib.gprx_hms_destroy(h)
+
+
+def test_components_step_checks_k_and_the_retained_eigenvalues():
+    """The same two checks in gprx_hms_components (Gram route) and gprx_pcafit_components: k < rows, eigenvalues positive."""
+    import ctypes as C
+
+    from gpras_amd import _lib
+    from gpras_amd._lib import ptr
+
+    u4, u2, lam4, bad = np.eye(4), np.eye(4)[:, :2].copy(), np.ones(4), np.array([1.0, 0.0])
+    eofs, z = np.empty((4, 40)), np.empty((4, 4))
+    lib, h, n_f = _raw_hms(4, 0, 40)
+    try:
+        mean, cov, route = np.empty(n_f), np.empty((4, 4)), C.c_int(-1)
+        assert lib.gprx_hms_cov(h, ptr(mean), ptr(cov), C.byref(route)) == _lib.GPRX_OK and route.value == 1  # HMS_GRAM
+        assert lib.gprx_hms_components(h, 4, ptr(u4), ptr(lam4), ptr(eofs)) == _lib.GPRX_EINVAL
+        assert lib.gprx_hms_components(h, 2, ptr(u2), ptr(bad), ptr(eofs)) == _lib.GPRX_EINVAL
+        assert b"positive" in lib.gprx_hms_last_error(h)
+    finally:
+        lib.gprx_hms_destroy(h)
+    x = np.random.default_rng(7).standard_normal((4, 40))
+    h = C.c_void_p()
+    _lib.check(lib.gprx_pcafit_create(0, ptr(x), 4, 40, None, None, 2, 0.0, C.byref(h)))  # velocity: every cell is wet
+    try:
+        assert lib.gprx_pcafit_components(h, 4, ptr(u4), ptr(lam4), ptr(eofs), ptr(z)) == _lib.GPRX_EINVAL
+        assert lib.gprx_pcafit_components(h, 2, ptr(u2), ptr(bad), ptr(eofs), ptr(z)) == _lib.GPRX_EINVAL
+        assert b"positive" in lib.gprx_pcafit_last_error(h)
+    finally:
+        lib.gprx_pcafit_destroy(h)
+
+
 def test_pickle_round_trips_both_ways(tmp_path):
     c = CASES["dry_cells"]
     pre = device_fit(c)
