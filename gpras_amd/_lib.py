@@ -187,6 +187,7 @@ PROTOTYPES = {
     "gprx_gemm_splitk": (C.c_int, [C.c_int, C.c_int, C.c_int, _i64, _i64, _i64, C.c_double, _vp, _i64, _vp, _i64, C.c_double, _vp, _i64, _vp, C.c_int,
                                    C.c_int, _i64, _i64, _i64, _i64, _vp, C.c_int]),
     "gprx_trsv_lower": (C.c_int, [C.c_int, _vp, _i64, _vp, _vp, _i64, C.c_int, C.c_int, _i64, _vp]),
+    "gprx_potrf_batched": (C.c_int, [C.c_int, _vp, _i64, _i64, _i64, _vp, _vp, _vp, C.c_int, _i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip]),
     "gprx_trsm_lower_left": (C.c_int, [C.c_int, _vp, _i64, _vp, _vp, _i64, _i64, _i64, C.c_int, _i64, _vp]),
     "gprx_trtri_lower": (C.c_int, [C.c_int, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, C.c_int, _i64, _i64, C.c_int]),
     "gprx_transpose_inplace": (C.c_int, [C.c_int, _vp, _i64, _i64, C.c_int, _i64]),

@@ -645,6 +645,57 @@ int gprx_trtri_lower(int device, const double* l_dev, int64_t lda, const double*
   });
 }
 
+// The batched factorisation, every route of it: potrf_lower with the fused panel (route 0) or the split panel (1), potrf_cells (2).
+// A, inv_diag, the staging area (np * STAGE_LD doubles) and the vector right-hand side of cell c live at the given pointers + c * cs.
+// The schedule comes from a PotrfTuning of the call's own (outer_block: any multiple of 64 -- 64 itself is the only way to the
+// separate K = 64 update; update_tile 64 | 128; 0 = the defaults): the process-wide knobs are neither read nor written.
+// info_host[batch]: 0, or col_base + the 1-based failing pivot of that cell; every cell's word is delivered with GPRX_ENOTPD.
+int gprx_potrf_batched(int device, double* a_dev, int64_t lda, int64_t np, int64_t extra, double* inv_diag_dev, double* stage_dev,
+                       double* yvec_dev, int batch, int64_t cs, int route, int outer_block, int update_tile, int lookahead, int col_base,
+                       int* info_host) {
+  return guarded(nullptr, [&]() -> int {
+    if (!a_dev || !inv_diag_dev || !stage_dev || !info_host) return fail(nullptr, GPRX_EINVAL, "null argument");
+    if (np <= 0 || np % NB) return fail(nullptr, GPRX_EINVAL, "np must be a positive multiple of 64");
+    if (extra < 0 || np > (1 << 30) || extra > (1 << 30)) return fail(nullptr, GPRX_EINVAL, "extra must not be negative, np and extra at most 2^30");
+    if (lda < np || odd(lda) || odd(cs) || cs < 0) return fail(nullptr, GPRX_EINVAL, "lda and cs must be even, lda at least np");
+    if (batch > 1 && cs < lda * (np + extra)) return fail(nullptr, GPRX_EINVAL, "cs shorter than one cell's matrix: the cells would overlap");
+    if (off16(a_dev) || off16(inv_diag_dev) || off16(stage_dev) || (yvec_dev && off16(yvec_dev)))
+      return fail(nullptr, GPRX_EINVAL, "operands must be 16-byte aligned");
+    if (batch < 1 || route < 0 || route > 2 || col_base < 0) return fail(nullptr, GPRX_EINVAL, "batch must be positive, route 0, 1 or 2");
+    if (yvec_dev && (route != 1 || batch == 1 || extra != 0))
+      return fail(nullptr, GPRX_EINVAL, "the vector right-hand side is the split panel's, for batched cells without right-hand-side rows");
+    if (route == 2 && extra % NB) return fail(nullptr, GPRX_EINVAL, "the cell kernel takes right-hand-side rows in tiles of 64");
+    if (lookahead != 0 && (lookahead != 1 || batch > 1 || route == 2)) return fail(nullptr, GPRX_EINVAL, "look-ahead is for one matrix on routes 0 and 1");
+    if (outer_block < 0 || outer_block % NB || (update_tile != 0 && update_tile != 64 && update_tile != 128))
+      return fail(nullptr, GPRX_EINVAL, "outer_block must be a multiple of 64, update_tile 0, 64 or 128");
+    PotrfTuning tune;  // (defaults, not the process-wide knobs)
+    tune.outer_block = outer_block;
+    tune.update_tile = update_tile;
+    tune.split_panel = route == 1 ? 1 : -1;
+    HIPCHK(nullptr, hipSetDevice(device));
+    hipStream_t st = util_stream();
+    int* dinfo = nullptr;
+    HIPCHK(nullptr, hipMalloc((void**)&dinfo, sizeof(int) * batch));
+    hipError_t e = memset_sync(dinfo, 0, sizeof(int) * batch);
+    PotrfStreams ps;
+    if (e == hipSuccess && lookahead) e = ps.init();
+    if (e == hipSuccess)
+      e = route == 2 ? potrf_cells(st, a_dev, lda, (int)np, (int)extra, inv_diag_dev, dinfo, batch, cs, 1, col_base)
+                     : potrf_lower(st, a_dev, lda, (int)np, (int)extra, inv_diag_dev, dinfo, stage_dev, nullptr, lookahead ? &ps : nullptr, batch, cs, 1,
+                                   &tune, col_base, yvec_dev);
+    hipError_t e2 = hipStreamSynchronize(st);
+    if (ps.aux && e2 == hipSuccess) e2 = hipStreamSynchronize(ps.aux);
+    ps.destroy();
+    if (e == hipSuccess && e2 == hipSuccess) e2 = copy_sync(info_host, dinfo, sizeof(int) * batch, hipMemcpyDeviceToHost);
+    hipFree(dinfo);
+    HIPCHK(nullptr, e);
+    HIPCHK(nullptr, e2);
+    for (int c = 0; c < batch; ++c)
+      if (info_host[c]) return fail(nullptr, GPRX_ENOTPD, "matrix not positive definite");
+    return GPRX_OK;
+  });
+}
+
 int gprx_transpose_inplace(int device, double* x_dev, int64_t ld, int64_t n, int cells, int64_t cs) {
   return guarded(nullptr, [&]() -> int {
     if (!x_dev || off16(x_dev)) return fail(nullptr, GPRX_EINVAL, "X must be given, 16-byte aligned");

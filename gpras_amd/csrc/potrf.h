@@ -295,7 +295,8 @@ __global__ __launch_bounds__(256, 2) void potrf_panel_kernel(double* __restrict_
       // row from the diagonal block down, by the 64 columns left of them), applied here to the rows this workgroup holds: one
       // dependent launch less per odd panel (~9 us of a lone matrix's chain).  Operation for operation what gemm_f64 does
       // (accumulators from zero, stages of 16 along k, instruction j of a stage takes k = k0 + 4 g + j; C + (-1) * sum with one
-      // rounding), so the factor is the same bit for bit as with the separate launch (batched cells keep that launch).
+      // rounding), so the factor is the same bit for bit as with the separate launch.  factor_range fuses every pair of panels,
+      // for a lone matrix and for batched cells alike: only a 64-column outer block still makes that launch.
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt)
 #pragma unroll

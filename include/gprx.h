@@ -314,6 +314,20 @@ int gprx_gemm_splitk(int device, int ta, int tb, int64_t m, int64_t n, int64_t k
 int gprx_trsv_lower(int device, const double* l_dev, int64_t lda, const double* inv_diag_dev, double* b_dev, int64_t np, int transpose,
                     int batch, int64_t cs, double* work_dev);
 
+/* gprx_potrf for `batch` matrices by a named route: 0 = the launch sequence with the fused panel, 1 = with the split panel (one
+ * diagonal workgroup per cell, then a rows-only kernel), 2 = one workgroup per cell (extra a multiple of 64).  Cell c has its matrix
+ * at a_dev + c cs, the inverses of its diagonal blocks at inv_diag_dev + c cs, its staging area (np * 129 doubles, scratch of routes 0
+ * and 1) at stage_dev + c cs.  yvec_dev (route 1, batch > 1, extra == 0; else NULL): one right-hand side per cell as a vector of np
+ * entries at yvec_dev + c cs, replaced by L^-1 y.  The schedule is the call's own, the process-wide tuning is neither read nor
+ * changed: outer_block 0 (default) or any multiple of 64, update_tile 0 | 64 | 128, lookahead 1 (batch == 1, routes 0 and 1) = bulk
+ * updates on a second stream.  info_host[batch]: 0 or col_base + the 1-based index of the cell's failing pivot; GPRX_ENOTPD when any
+ * is non-zero.  GPRX_EINVAL before any device work for odd lda or cs, lda < np, batch > 1 with cs < lda (np + extra) (cells that
+ * would overlap), pointers off a 16-byte boundary and every
+ * combination named above that no route takes. */
+int gprx_potrf_batched(int device, double* a_dev, int64_t lda, int64_t np, int64_t extra, double* inv_diag_dev, double* stage_dev,
+                       double* yvec_dev, int batch, int64_t cs, int route, int outer_block, int update_tile, int lookahead, int col_base,
+                       int* info_host);
+
 /* L X = B in place, B (n, ncols); cells systems cs doubles apart.  src (n == 64): the right-hand side is read from there. */
 int gprx_trsm_lower_left(int device, const double* l_dev, int64_t lda, const double* inv_diag_dev, double* b_dev, int64_t ldb, int64_t n,
                          int64_t ncols, int cells, int64_t cs, const double* src_dev);

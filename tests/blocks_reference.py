@@ -5,7 +5,8 @@ Cholesky factor, triangular solves and inverses are spelled out so that no doubl
 reference.  test_blocks_reference.py checks these against mpmath at 50 digits.
 
 The `emu_*` functions are a float64 restatement of the block algorithms of csrc/solve.h (explicit 64 x 64 inverses of the
-diagonal blocks plus products).  tests/golden/make_blocks_bounds.py runs them on the matrices named here and records how far
+diagonal blocks plus products) and of the blocked Cholesky of csrc/potrf.h (emu_potrf: substitution against the diagonal blocks,
+whose inverses it also forms).  tests/golden/make_blocks_bounds.py runs them on the matrices named here and records how far
 they land from the reference; the GPU tests allow 8 x that.
 """
 
@@ -103,9 +104,8 @@ def inv_lower_ld(low: np.ndarray) -> np.ndarray:
 
 
 @functools.lru_cache(maxsize=None)
-def _factor(noise: float, seed: int):
-    """RBF matrix on max(SIZES) random points in 3-D plus noise on the diagonal; its longdouble Cholesky factor rounded to double.
-    The factor of the leading n x n block is the leading block of the factor, so one factorisation serves every size."""
+def _rbf(noise: float, seed: int):
+    """RBF matrix on max(SIZES) random points in 3-D plus noise on the diagonal.  Read-only."""
     n = max(SIZES)
     x = np.random.default_rng([7, seed]).uniform(0.0, 1.0, (n, 3))
     d = x[:, None, :] - x[None, :, :]
@@ -113,9 +113,22 @@ def _factor(noise: float, seed: int):
     # (exp in longdouble, rounded: numpy's double exp differs in the last bit between CPU generations, and the recorded bounds must
     # come out the same everywhere)
     k = np.exp((-0.5 * r2 / 0.3 ** 2).astype(LD)).astype(np.float64) + noise * np.eye(n)
-    low = chol_ld(k).astype(np.float64)
+    k.setflags(write=False)
+    return k
+
+
+@functools.lru_cache(maxsize=None)
+def _factor(noise: float, seed: int):
+    """The longdouble Cholesky factor of _rbf(noise, seed), rounded to double.
+    The factor of the leading n x n block is the leading block of the factor, so one factorisation serves every size."""
+    low = chol_ld(_rbf(noise, seed)).astype(np.float64)
     low.setflags(write=False)
     return low
+
+
+def potrf_input(n: int, noise: float, seed: int = 0) -> np.ndarray:
+    """The matrix whose factor solve_inputs(n, noise, seed) holds: the input of the factorisation tests.  Read-only."""
+    return _rbf(noise, seed)[:n, :n]
 
 
 @functools.lru_cache(maxsize=None)
@@ -163,6 +176,18 @@ def inverse_ratio(low, x) -> float:
     res = np.abs(x @ lo - eye)
     den = low.shape[0] * U * (np.abs(x) @ np.abs(lo) + eye)
     return float(np.max(res / np.where(den > 0, den, LD(1))))  # (den == 0 only above the diagonal, where the residual is exactly 0)
+
+
+def factor_ratio(a, low_hat) -> float:
+    """max over the lower triangle of |A - L L^T| / (u |L| |L|^T) for a computed factor L (its lower triangle is taken).  Higham,
+    Accuracy and Stability, theorem 10.3: at most gamma_{n+1} = (n + 1) u / (1 - (n + 1) u) < (n + 2) u componentwise, whatever
+    the order of the sums."""
+    lo = np.tril(low_hat).astype(LD)
+    res = np.abs(np.asarray(a).astype(LD) - lo @ lo.T)
+    mag = np.abs(np.tril(low_hat))
+    den = U * dot64(mag, mag.T)  # (a sum of positive terms: float64 in a fixed order is exact enough for a ratio, and three times as fast)
+    sel = np.tril(np.ones(lo.shape, bool))
+    return float(np.max(res[sel] / np.where(den[sel] > 0, den[sel], U)))  # (den == 0: every term is zero, so must the entry of A be)
 
 
 def sum_ratio(got, ref, mag) -> float:
@@ -257,6 +282,83 @@ def emu_trtri(low, inv):
     return x
 
 
+def emu_potrf(a, extra_rows=None, by_inverse=False):
+    """float64 restatement of the blocked factorisation of csrc/potrf.h and csrc/potrf_cell.h: right-looking by 64 columns, the
+    diagonal block factored column by column, its inverse formed explicitly by substitution on the identity (what the panel kernel's
+    identity rows do), the rows below it (right-hand-side rows included) by substitution against the diagonal block as in
+    potrf_panel_kernel and potrf_rows_kernel, the trailing update one product per block column.  by_inverse: the rows below a
+    diagonal block (right-hand-side rows included) are products with its explicit inverse instead, as potrf_cell.h forms them.  Only
+    substitution has Higham's componentwise bound, which test_blocks_reference.py holds its recorded factor ratios to; the
+    product's error grows with the condition of the diagonal block (recorded under potrf_cell/: up to 162 where substitution has 13).  Elementwise
+    operations, sqrt, division and dot64 only: the same bits on every machine.
+    Returns (L with zeros above the diagonal, inv_diag (n / 64, 64, 64), the solved rows)."""
+    n = a.shape[0]
+    extra = 0 if extra_rows is None else extra_rows.shape[0]
+    w = np.zeros((n + extra, n))
+    w[:n] = np.tril(a)
+    if extra:
+        w[n:] = extra_rows
+    inv = np.zeros((n // NB, NB, NB))
+    for j0 in range(0, n, NB):
+        j1 = j0 + NB
+        d = w[j0:j1, j0:j1]
+        for k in range(NB):
+            d[k, k] = np.sqrt(d[k, k])
+            d[k + 1:, k] /= d[k, k]
+            d[k + 1:, k + 1:] -= np.tril(np.outer(d[k + 1:, k], d[k + 1:, k]))
+        x = inv[j0 // NB]
+        for i in range(NB):
+            e = np.zeros(NB)
+            e[i] = 1.0
+            x[i] = ((e - dot64(d[i:i + 1, :i], x[:i])[0]) if i else e) / d[i, i]
+        rows = w[j1:, j0:j1]
+        if by_inverse and j1 < n + extra:
+            rows[...] = dot64(rows, x.T)
+        for k in range(NB if j1 < n + extra and not by_inverse else 0):
+            if k:
+                rows[:, k] -= dot64(rows[:, :k], d[k, :k])
+            rows[:, k] /= d[k, k]
+        if j1 < n:
+            low = w[j1:, j0:j1]
+            upd = dot64(low, low[: n - j1].T)
+            w[j1:n, j1:] -= np.tril(upd[: n - j1])
+            w[n:, j1:] -= upd[n - j1:]
+    return w[:n].copy(), inv, w[n:].copy()
+
+
+POTRF_RHS_ROWS = 128  # the right-hand-side rows of a factorisation case; a test takes the first `extra` of them, a vector the first
+
+
+def potrf_rhs(n: int, seed: int) -> np.ndarray:
+    """(POTRF_RHS_ROWS, n): the rows carried below the matrix of potrf_input(n, ., seed)."""
+    return np.ascontiguousarray(rhs(n, POTRF_RHS_ROWS, seed).T)
+
+
+@functools.lru_cache(maxsize=4)  # (35 MB per matrix at n = 2112)
+def exact_factor(n: int, seed: int = 0, nrhs: int = NB):
+    """(A, L0, inv_diag, Y, Z): a positive definite matrix that EVERY blocked schedule factors without a rounding error.
+    L0 = M diag(d), d_j = 2^e with e in -1 .. 2, M unit lower triangular with integers in -2 .. 2: its 64 x 64 blocks below the
+    diagonal sparse (density 0.3), its diagonal blocks I + N with N non-zero only in rows >= 32 and columns < 32 of the block, so
+    N^2 = 0 and the inverse of a diagonal block of L0 is diag(1 / d) (I - N) exactly.  A = L0 L0^T, Y = Z L0^T with integer Z in
+    -3 .. 3 (nrhs right-hand-side rows; row 0 serves as the vector).  Every pivot is a power of four and every intermediate value
+    of any blocked schedule a small multiple of 1/4 (or of 1/16 in an inverse), far below 2^53 of them: L0, the inverses and Z
+    must come back bit for bit, under every summation order.  Read-only."""
+    rng = np.random.default_rng([23, n, seed])
+    m = np.eye(n)
+    for bi in range(n // NB):
+        for bj in range(bi):
+            m[NB * bi:NB * bi + NB, NB * bj:NB * bj + NB] = rng.integers(-2, 3, (NB, NB)) * (rng.random((NB, NB)) < 0.3)
+        m[NB * bi + NB // 2:NB * bi + NB, NB * bi:NB * bi + NB // 2] = rng.integers(-2, 3, (NB // 2, NB // 2)) * (rng.random((NB // 2, NB // 2)) < 0.3)
+    d = 2.0 ** rng.integers(-1, 3, n)
+    low = m * d[None, :]
+    inv = np.stack([(2.0 * np.eye(NB) - m[i:i + NB, i:i + NB]) / d[i:i + NB, None] for i in range(0, n, NB)])
+    z = rng.integers(-3, 4, (nrhs, n)).astype(np.float64)
+    out = (low @ low.T, low, inv, z @ low.T, z)  # (sums of a few thousand multiples of 1/4 below 2^20: exact in any order)
+    for v in out:
+        v.setflags(write=False)
+    return out
+
+
 def emu_colreduce(m, w, rows_per_chunk):
     """colreduce_partial + the chunk sum of colreduce_final: rows of a chunk alternate between two accumulators."""
     nrows = m.shape[0]
@@ -309,6 +411,14 @@ def compute_bounds() -> dict:
                     out[f"trsm/c{ncols}/{key}"] = solve_ratio(low, emu_trsm(low, inv, bm), bm)
                 x = emu_trtri(low, inv)
                 out[f"trtri/{key}"] = inverse_ratio(low, x)
+                # the factorisation itself: beta and the inverse blocks against the emulation's OWN factor, as the tests take the device's
+                bp = potrf_rhs(n, seed)
+                lh, ih, bh = emu_potrf(potrf_input(n, noise, seed), bp)
+                out[f"potrf/{key}"] = factor_ratio(potrf_input(n, noise, seed), lh)
+                out[f"potrf_beta/{key}"] = solve_ratio(lh, bh.T, bp.T)
+                out[f"potrf_inv/{key}"] = max(inverse_ratio(lh[i:i + NB, i:i + NB], ih[i // NB]) for i in range(0, n, NB))
+                # the same with the rows as products with the explicit inverses (potrf_cell.h): not within Higham's constant
+                out[f"potrf_cell/{key}"] = factor_ratio(potrf_input(n, noise, seed), emu_potrf(potrf_input(n, noise, seed), by_inverse=True)[0])
     for seed in SEEDS:
         for n in ALPHA_N:
             xin, beta = alpha_input(n, seed), vec(n, seed)

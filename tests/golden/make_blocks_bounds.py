@@ -4,6 +4,8 @@ For every solve, inverse and reduction case of tests/test_gpu_solve_blocks.py a 
 csrc/solve.h (tests/blocks_reference.py, emu_*: explicit inverses of the 64 x 64 diagonal blocks plus products) runs on exactly the
 matrices the test uses, and its worst componentwise ratio against the longdouble reference is recorded:
 
+  factor      |A - L L^T|   / (u |L| |L|^T)      (tests/test_gpu_potrf_batched.py; emu_potrf restates csrc/potrf.h, and its solved
+                                                   rows and inverse blocks are taken against its own factor)
   solves      |op(L) X - B| / (n u (|op(L)| |X| + |B|))
   inverse     |X L - I|     / (n u (|X| |L| + I))
   reductions  |got - ref|   / (sum of the magnitudes of the terms), not below u = 2^-53

@@ -84,6 +84,63 @@ def test_recorded_bounds_are_what_the_script_writes():
         assert fh.read() == mod.render()
 
 
+def test_recorded_factor_limits_stay_within_highams_constant():
+    """What the GPU tests allow a factor, 8 x the recorded ratio, never exceeds n + 2: |A - L L^T| <= gamma_{n+1} |L| |L|^T holds for
+    the Cholesky factor under ANY order of its sums (Higham, theorem 10.3), so a limit above it would allow more than rounding."""
+    keys = [k for k in br.bounds() if k.startswith("potrf/")]
+    assert len(keys) == len(br.SIZES) * len(br.NOISES) * len(br.SEEDS)
+    for k in keys:
+        n = int(k.split("/")[1][1:])
+        assert 8.0 * br.bounds()[k] <= n + 2, (k, br.bounds()[k])
+    # products with the explicit inverses (potrf_cell/ keys, the cell kernel's form) have no such bound: recorded, and from two block
+    # columns on 8 x the ratio is beyond n + 2 on every noise-1e-6 matrix, which is why the GPU test caps that limit at n + 2
+    cell = {k: v for k, v in br.bounds().items() if k.startswith("potrf_cell/")}
+    assert len(cell) == len(keys) and all(v >= br.bounds()[k.replace("potrf_cell/", "potrf/")] for k, v in cell.items())
+    assert all(8.0 * v > int(k.split("/")[1][1:]) + 2 for k, v in cell.items() if "/n64/" not in k and br.tag(br.NOISES[1]) in k)
+
+
+def test_emulated_factorisation_against_the_longdouble_factor():
+    """emu_potrf (float64, blocked) against chol_ld and the longdouble solves: the well-conditioned matrices to 1e-11, the others by
+    their residuals alone (Higham's constant for the factor; the solves and inverses within the n u of their ratios)."""
+    for noise in br.NOISES:
+        for n in (64, 192, 320):
+            a, rows = br.potrf_input(n, noise, 1), br.potrf_rhs(n, 1)[:3]
+            low, inv, beta = br.emu_potrf(a, rows)
+            assert np.all(np.triu(low, 1) == 0.0)
+            assert br.factor_ratio(a, low) <= n + 2
+            assert br.solve_ratio(low, beta.T, rows.T) <= 1.0
+            assert max(br.inverse_ratio(low[i:i + 64, i:i + 64], inv[i // 64]) for i in range(0, n, 64)) <= 1.0
+            if noise == br.NOISES[0]:
+                ref, ref_inv = br.solve_inputs(n, noise, 1)
+                assert br.rel_err(low, ref) < 1e-11 and br.rel_err(inv, ref_inv) < 1e-11
+                assert br.rel_err(beta.T, br.solve_lower_ld(ref, rows.T)) < 1e-11
+    # a factor with one wrong element is seen: the ratio counts roundings, and 1e-9 relative is millions of them
+    low = br.emu_potrf(br.potrf_input(128, br.NOISES[0], 0))[0]
+    low[100, 37] *= 1.0 + 1e-9
+    assert br.factor_ratio(br.potrf_input(128, br.NOISES[0], 0), low) > 1e4
+
+
+def test_exact_factor_is_reproduced_without_rounding():
+    """exact_factor's matrix under two schedules with different sums -- LAPACK's and the blocked float64 emulation with explicit
+    inverses: L0, the inverses of its diagonal blocks and Z come back bit for bit."""
+    from scipy.linalg import cholesky, solve_triangular
+
+    for n in (64, 192, 320, 1088):
+        a, low0, inv0, y, z = br.exact_factor(n, 2)
+        assert np.array_equal(np.tril(low0), low0) and np.max(np.abs(a)) < 2.0 ** 20 and np.max(np.abs(inv0)) <= 4.0
+        assert set(np.unique(np.log2(np.diag(low0)))) <= {-1.0, 0.0, 1.0, 2.0}
+        assert np.array_equal(a * 4.0, np.rint(a * 4.0)) and np.array_equal(y * 2.0, np.rint(y * 2.0))
+        for i in range(0, n, 64):
+            assert np.array_equal(inv0[i // 64] @ low0[i:i + 64, i:i + 64], np.eye(64))
+        got = cholesky(a, lower=True)
+        assert np.array_equal(got, low0)
+        assert np.array_equal(solve_triangular(got, y.T, lower=True).T, z)
+        low, inv, beta = br.emu_potrf(a, y)
+        assert np.array_equal(low, low0) and np.array_equal(inv, inv0) and np.array_equal(beta, z)
+    a1, a2 = br.exact_factor(128, 0)[0], br.exact_factor(128, 1)[0]
+    assert not np.array_equal(a1, a2)  # (one matrix per cell)
+
+
 def test_canary_is_a_nan_with_its_own_bits():
     c = br.canary((3, 2))
     assert np.all(np.isnan(c)) and np.all(br.is_canary(c))

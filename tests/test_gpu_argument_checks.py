@@ -261,6 +261,36 @@ def test_optimizers_with_nothing_to_do_do_not_look_at_the_cells(case):
                         assert same_bits(bits(now), bits(given))
 
 
+def test_batched_potrf_probe_refuses_what_no_route_takes(lib):
+    """gprx_potrf_batched, by return code only: nothing of this reaches a kernel, and info keeps what the caller put there."""
+    buf = DeviceBuffer(8 * 65536)
+    p, off = buf.ptr, buf.at(1)
+    info = np.full(4, -77, dtype=np.int32)
+    ip = info.ctypes.data_as(C.POINTER(C.c_int))
+
+    def call(a=p, lda=128, n=128, extra=0, inv=p, stage=p, y=None, batch=1, cs=0, route=0, outer=0, tile=0, lookahead=0, col_base=0, out=ip):
+        return lib.gprx_potrf_batched(0, a, lda, n, extra, inv, stage, y, batch, cs, route, outer, tile, lookahead, col_base, out)
+
+    refused = {
+        "a null": call(a=None), "inv_diag null": call(inv=None), "stage null": call(stage=None), "info null": call(out=None),
+        "np 0": call(n=0), "np negative": call(n=-64), "np % 64": call(n=96), "extra negative": call(extra=-1),
+        "odd lda": call(lda=129), "lda < np": call(lda=126), "odd cs": call(batch=2, cs=32769), "negative cs": call(batch=2, cs=-2),
+        "cs 0 with cells": call(batch=2, cs=0), "cs shorter than a cell": call(batch=2, cs=128 * 128 - 2),
+        "cs shorter than a cell with its right-hand-side rows": call(batch=2, cs=128 * 128, extra=64),
+        "a off 16 bytes": call(a=off), "inv_diag off 16 bytes": call(inv=off), "stage off 16 bytes": call(stage=off),
+        "yvec off 16 bytes": call(y=off, batch=2, cs=32768, route=1),
+        "batch 0": call(batch=0), "route 3": call(route=3), "route -1": call(route=-1), "col_base negative": call(col_base=-1),
+        "yvec on the fused panel": call(y=p, batch=2, cs=32768, route=0), "yvec on the cell kernel": call(y=p, batch=2, cs=32768, route=2),
+        "yvec with one matrix": call(y=p, batch=1, route=1), "yvec with right-hand-side rows": call(y=p, batch=2, cs=32768, route=1, extra=64),
+        "cell kernel with ragged rows": call(route=2, extra=40), "look-ahead with cells": call(batch=2, cs=32768, lookahead=1),
+        "look-ahead on the cell kernel": call(route=2, lookahead=1), "lookahead 2": call(lookahead=2),
+        "outer_block 96": call(outer=96), "outer_block negative": call(outer=-64), "update_tile 32": call(tile=32),
+    }
+    assert {k: v for k, v in refused.items() if v != _lib.GPRX_EINVAL} == {}
+    assert np.all(info == -77)
+    buf.free()
+
+
 @pytest.mark.parametrize("which", ["host", "dev", "t"])
 @pytest.mark.parametrize("case", [c for c in CASES if c[2] != 0], indirect=True, ids=case_id)
 def test_batched_sparse_predict_refuses_before_it_factorises(case, which):
