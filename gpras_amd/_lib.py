@@ -97,6 +97,9 @@ PROTOTYPES = {
     "gprx_pca_to_depth_dev": (C.c_int, [_vp, _vp, _i64, C.c_int]),
     "gprx_pca_sqrt_dev": (C.c_int, [_vp, _vp, _i64]),
     "gprx_pca_transpose_dev": (C.c_int, [_vp, _vp, _i64, _i64, _vp]),
+    "gprx_pca_sweep_dev": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, C.c_int, _vp, C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gprx_pca_sweep_ms": (C.c_int, [_vp, _dp]),
+    "gprx_pca_sweep_group": (C.c_int, []),
     "gprx_pcafit_create": (C.c_int, [C.c_int, _vp, _i64, _i64, _vp, _vp, C.c_int, C.c_double, C.POINTER(_vp)]),
     "gprx_pcafit_gram": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_i64)]),
     "gprx_pcafit_components": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),

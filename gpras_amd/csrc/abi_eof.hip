@@ -13,6 +13,7 @@
 #include "hms.h"
 #include "pca.h"
 #include "pca_fit.h"
+#include "sweep.h"
 
 using namespace gprx;
 
@@ -21,8 +22,12 @@ struct gprx_pca_ctx {
   hipStream_t stream = nullptr;
   int64_t cells = 0, cells_p = 0;  // cells_p: leading dimension of the device copies (multiple of 16, zero padded)
   int k = 0, depth = 0;
+  bool has_elev = false;
   Buf mu, wfwd, wrev, elev, E, base, xm, xs;  // per-cell parameters expanded to all cells; E: (k, cells_p)
   Buf dX, dZ, ws, dMean, dVar, dFull, dVfull;
+  Buf sweep_part, sweep_aux;  // gprx_pca_sweep_dev: per-workgroup row sums; event bounds, then the match counts per workgroup
+  hipEvent_t ev[2] = {};
+  double sweep_ms = 0.0;      // device time of the last gprx_pca_sweep_dev
   std::string err;
 };
 
@@ -114,8 +119,9 @@ int gprx_pca_create(int device, int64_t n_cells, int k, const unsigned char* dry
   gprx_pca_handle p = nullptr;
   const int rc = guarded(nullptr, [&]() -> int {
     p = new gprx_pca_ctx();
-    int rc = open_handle(p, device);
+    int rc = open_handle(p, device, p->ev, 2);
     if (rc) return rc;
+    p->has_elev = elevations != nullptr;
     p->cells = n_cells;
     p->cells_p = round_up(n_cells, 16);
     p->k = k;
@@ -151,7 +157,7 @@ int gprx_pca_create(int device, int64_t n_cells, int k, const unsigned char* dry
 int gprx_pca_destroy(gprx_pca_handle p) {
   if (!p) return GPRX_OK;
   release_handle(p->device, p->stream, {p->mu.p, p->wfwd.p, p->wrev.p, p->elev.p, p->E.p, p->base.p, p->xm.p, p->xs.p, p->dX.p, p->dZ.p, p->ws.p, p->dMean.p, p->dVar.p,
-                                           p->dFull.p, p->dVfull.p});
+                                           p->dFull.p, p->dVfull.p, p->sweep_part.p, p->sweep_aux.p}, p->ev, 2);
   delete p;
   return GPRX_OK;
 }
@@ -235,6 +241,96 @@ int gprx_pca_transpose_dev(gprx_pca_handle p, const double* src_dev, int64_t row
     return GPRX_OK;
   });
 }
+
+// The field metrics at every count of `counts` in one pass (sweep.h).  Counts go in groups of SWEEP_SMAX per launch.
+int gprx_pca_sweep_dev(gprx_pca_handle p, const double* mean_dev, const double* var_dev, int64_t rows, const double* truth_dev, int64_t n_events,
+                       const int64_t* event_lo, const int64_t* event_hi, int n_counts, const int* counts, int depth_mode, double v_tol,
+                       double* cell_sums_dev, int* cell_arg_dev, double* truth_peak_dev, int* truth_arg_dev, double* row_sums_dev,
+                       unsigned long long* matches) {
+  return guarded(p, [&]() -> int {
+    if (!p) return fail(p, GPRX_EINVAL, "null handle");
+    if (rows <= 0 || rows >= ((int64_t)1 << 31)) return fail(p, GPRX_EINVAL, "rows must be positive and below 2^31");
+    if (!mean_dev) return fail(p, GPRX_EINVAL, "null argument: mean");
+    if (!truth_dev) return fail(p, GPRX_EINVAL, "the sweep needs the truth field");
+    if (!cell_sums_dev || !cell_arg_dev || !truth_peak_dev || !truth_arg_dev || !row_sums_dev || !matches)
+      return fail(p, GPRX_EINVAL, "null argument: output block");
+    if (n_counts < 1 || n_counts > 64 || !counts) return fail(p, GPRX_EINVAL, "need between 1 and 64 counts");
+    for (int j = 0; j < n_counts; ++j)
+      if (counts[j] < 1 || counts[j] > p->k || (j && counts[j] <= counts[j - 1]))
+        return fail(p, GPRX_EINVAL, "counts must be strictly increasing in [1, " + std::to_string(p->k) + "]");
+    if (depth_mode < 0 || depth_mode > 2) return fail(p, GPRX_EINVAL, "depth mode must be 0 (none), 1 (wse) or 2 (depth)");
+    if (depth_mode && !p->has_elev) return fail(p, GPRX_EINVAL, "the depth conversion needs the cell elevations (the projector was created without them)");
+    if (!(v_tol >= 0.0)) return fail(p, GPRX_EINVAL, "v_tol must be non-negative");
+    if (n_events < 1 || n_events > 65535 || !event_lo || !event_hi) return fail(p, GPRX_EINVAL, "need between 1 and 65535 events");
+    std::vector<std::pair<int64_t, int64_t>> evs((size_t)n_events);
+    int64_t covered = 0;
+    for (int64_t i = 0; i < n_events; ++i) {
+      if (event_lo[i] < 0 || event_hi[i] > rows || event_lo[i] >= event_hi[i])
+        return fail(p, GPRX_EINVAL, "event " + std::to_string((long long)i) + " is empty or outside [0, rows)");
+      evs[(size_t)i] = {event_lo[i], event_hi[i]};
+      covered += event_hi[i] - event_lo[i];
+    }
+    std::sort(evs.begin(), evs.end());
+    for (size_t i = 1; i < evs.size(); ++i)
+      if (evs[i].first < evs[i - 1].second) return fail(p, GPRX_EINVAL, "the events overlap");
+    HIPCHK(p, hipSetDevice(p->device));
+    hipStream_t st = p->stream;
+    const int64_t cells = p->cells;
+    const unsigned nbx = (unsigned)((cells + 255) / 256);
+    const int smax = std::min(n_counts, SWEEP_SMAX);
+    const size_t part_doubles = (size_t)nbx * smax * rows * 3;
+    const size_t match_count = (size_t)n_counts * n_events * nbx;
+    int rc;
+    if ((rc = ensure(p, p->sweep_part, sizeof(double) * part_doubles, "the sweep's row sums")) ||
+        (rc = ensure(p, p->sweep_aux, sizeof(int64_t) * 2 * (size_t)n_events + sizeof(unsigned long long) * match_count)))
+      return rc;
+    int64_t* ev_dev = (int64_t*)p->sweep_aux.p;
+    unsigned long long* match_dev = (unsigned long long*)(ev_dev + 2 * n_events);
+    std::vector<int64_t> ev_h((size_t)2 * n_events);
+    std::copy(event_lo, event_lo + n_events, ev_h.begin());
+    std::copy(event_hi, event_hi + n_events, ev_h.begin() + n_events);
+    HIPCHK(p, hipMemcpyAsync(ev_dev, ev_h.data(), sizeof(int64_t) * ev_h.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(p, hipEventRecord(p->ev[0], st));
+    for (int j0 = 0; j0 < n_counts; j0 += SWEEP_SMAX) {
+      const int nc = std::min(SWEEP_SMAX, n_counts - j0);
+      unsigned packed = 0;
+      for (int j = 0; j < nc; ++j) packed |= (unsigned)counts[j0 + j] << (8 * j);
+      // rows of no event are written by no workgroup: their sums are zero
+      if (covered < rows) HIPCHK(p, hipMemsetAsync(p->sweep_part.p, 0, sizeof(double) * (size_t)nbx * nc * rows * 3, st));
+      SweepArgs a{mean_dev, var_dev, truth_dev, rows, cells, p->k, p->E.p, p->cells_p, p->wrev.p, p->base.p, p->xm.p, p->xs.p, p->elev.p, depth_mode, v_tol,
+                  ev_dev, ev_dev + n_events, n_events, nc, packed, counts[j0 + nc - 1], cell_sums_dev + (size_t)j0 * n_events * 6 * cells,
+                  cell_arg_dev + (size_t)j0 * n_events * cells, j0 == 0 ? truth_peak_dev : nullptr, truth_arg_dev, p->sweep_part.p,
+                  match_dev + (size_t)j0 * n_events * nbx};
+      const dim3 grid(nbx, (unsigned)n_events);
+      if (p->k <= 16) hipLaunchKernelGGL(pca_sweep_kernel<16>, grid, dim3(256), 0, st, a);
+      else hipLaunchKernelGGL(pca_sweep_kernel<64>, grid, dim3(256), 0, st, a);
+      HIPCHK(p, hipGetLastError());
+      const int64_t per_block = (int64_t)nc * rows * 3;
+      hipLaunchKernelGGL(pca_sweep_rows_kernel, dim3((unsigned)((per_block + 255) / 256)), dim3(256), 0, st, (const double*)p->sweep_part.p, (int)nbx,
+                         per_block, row_sums_dev + (size_t)j0 * rows * 3);
+      HIPCHK(p, hipGetLastError());
+    }
+    HIPCHK(p, hipEventRecord(p->ev[1], st));
+    std::vector<unsigned long long> mh(match_count);
+    HIPCHK(p, hipMemcpyAsync(mh.data(), match_dev, sizeof(unsigned long long) * match_count, hipMemcpyDeviceToHost, st));
+    HIPCHK(p, hipStreamSynchronize(st));
+    p->sweep_ms = elapsed_ms(p->ev[0], p->ev[1]);
+    for (size_t i = 0; i < (size_t)n_counts * n_events; ++i) {
+      unsigned long long total = 0;
+      for (unsigned bq = 0; bq < nbx; ++bq) total += mh[i * nbx + bq];
+      matches[i] = total;
+    }
+    return GPRX_OK;
+  });
+}
+
+int gprx_pca_sweep_ms(gprx_pca_handle p, double* ms) {
+  if (!p || !ms) return fail(p, GPRX_EINVAL, "null argument");
+  *ms = p->sweep_ms;
+  return GPRX_OK;
+}
+
+int gprx_pca_sweep_group(void) { return SWEEP_SMAX; }
 
 int gprx_pca_synchronize(gprx_pca_handle p) {
   if (!p) return fail(p, GPRX_EINVAL, "null handle");

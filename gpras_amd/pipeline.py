@@ -204,6 +204,29 @@ class DevicePipeline:
             truth.free()
         return fields
 
+    # ---- cross_validation.py:96-102 (run_spatial_modes) ------------------------------------------------------------------------
+    def mode_count_sweep(self, x_test, hf_test_data_df, counts, t_tol: int = 0, v_tol: float = 0, route: str | None = None):
+        """The metrics of ``export_metric_summary`` at every mode count of ``counts`` from ONE prediction (``gpras_amd.sweep``): predicts
+        once, sends the truth up once, takes the events from the index of ``hf_test_data_df`` and evaluates.  Returns the ``SweepResult``
+        (``scalar_table()``, ``export(base_dir, hf_test_data_df.index, hf_test_data_df.columns, ...)``; the caller closes it).  With the
+        ``hms_upskill`` inputs this is ``run_spatial_modes``; with inputs that are EOF scores themselves it varies the OUTPUT modes only."""
+        from .diagnostics import event_ranges
+        from .sweep import ModeCountSweep
+
+        if len(hf_test_data_df) != np.shape(x_test)[0]:
+            raise ValueError("x_test and hf_test_data_df must have one row per test timestep")
+        sweep = ModeCountSweep(self.projector, counts)
+        names, ranges = event_ranges(hf_test_data_df.index)
+        mean_t, var_t, ns = self.predict_modes_dev(x_test)
+        truth = None
+        try:
+            truth = self.truth_depth_dev(hf_test_data_df.values)
+            return sweep.evaluate(mean_t, var_t, truth, ranges, v_tol=v_tol, t_tol=t_tol, route=route, names=names, rows=ns)
+        finally:
+            for buf in (mean_t, var_t, truth):
+                if buf is not None:
+                    buf.free()
+
     # ---- pipeline.py:90-210 (gen_plots) -----------------------------------------------------------------------------------------
     def diagnostics(self, x_test, hf_test_data_df, lf_test_data=None, n_points: int = 2048, wet_threshold_depth: float = 0.0,
                     include_correct_negative: bool = True) -> dict:

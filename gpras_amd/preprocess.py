@@ -73,6 +73,15 @@ class EOFProjector(DeviceHandle):
         """Take the fitted state of a reference ``PreProcessor`` (attribute names of preprocess.py:868-927)."""
         return cls(pre.dry_indices, pre.elevations, pre.input_mean, pre.weights, pre.eofs, pre.x_mean, pre.x_std, pre.hydraulic_parameter, device=device)
 
+    def truncate(self, k: int) -> "EOFProjector":
+        """A new projector over the first ``k`` modes (``eofs[:k]``, ``x_mean[:k]``, ``x_std[:k]``): the state a fit with
+        ``spatial_mode_count = k`` reaches on the same data (``gpras_amd.sweep``)."""
+        if int(k) != k or not 1 <= k <= self.spatial_mode_count:
+            raise ValueError(f"k must be an integer in [1, {self.spatial_mode_count}]")
+        k = int(k)
+        return type(self)(self.dry_indices, self.elevations, self.input_mean, self.weights, self.eofs[:k], self.x_mean[:k], self.x_std[:k],
+                          self.hydraulic_parameter, device=self.device)
+
     def transform(self, x):
         """(samples, cells) -> EOF space (samples, spatial_mode_count)  (preprocess.py:1009-1038)."""
         x = as_f64(x)

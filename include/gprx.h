@@ -473,6 +473,27 @@ int gprx_pca_synchronize(gprx_pca_handle p);
 int gprx_pca_to_depth_dev(gprx_pca_handle p, double* field_dev, int64_t rows, int add_elevations_first);
 int gprx_pca_sqrt_dev(gprx_pca_handle p, double* field_dev, int64_t count);
 int gprx_pca_transpose_dev(gprx_pca_handle p, const double* src_dev, int64_t rows, int64_t cols, double* dst_dev);
+/* Mode-count sweep (run_spatial_modes, production/analysis/cross_validation.py:96-102): what gprx_metrics_dev returns for the field that
+ * gprx_pca_reverse_dev, gprx_pca_to_depth_dev and gprx_pca_sqrt_dev would give with the projector cut to its first counts[j] modes, for
+ * every j and every event, in one pass that writes no field.  mean_dev, var_dev (may be NULL): (rows, k) of the FULL projector;
+ * truth_dev: (rows, n_cells), already in the metrics' space; events: n_events disjoint, non-empty row ranges [event_lo[i], event_hi[i])
+ * (host arrays, at most 65535); counts: n_counts (1..64) strictly increasing values in [1, k] (host array); depth_mode: 0 none (velocity),
+ * 1 max(y - e, 0) ("wse" models), 2 max((y + e) - e, 0) ("depth" models), both need a projector created with elevations; v_tol >= 0: the
+ * fidelity index at t_tol = 0.  rows < 2^31.  Device outputs:
+ *   cell_sums  (n_counts, n_events, 6, n_cells): per cell over the event's rows: sum (x-y), sum (x-y)^2, sum conf, sum |x-y|, max_t y,
+ *              x at the first timestep of that maximum (what metrics.py:52-53 gathers)
+ *   cell_arg   (n_counts, n_events, n_cells) int32: that timestep, counted from the event's first row
+ *   truth_peak (n_events, n_cells), truth_arg (n_events, n_cells) int32: max_t x and its first timestep
+ *   row_sums   (n_counts, rows, 3): per row over the cells: sum (x-y), sum (x-y)^2, sum conf (0 for rows of no event)
+ * and on the host matches (n_counts, n_events).  Per cell the numbers are those of the per-count chain bit for bit; row_sums is reduced
+ * in another fixed order than gprx_metrics_dev's.  The call synchronises.  GPRX_EINVAL leaves the handle usable. */
+int gprx_pca_sweep_dev(gprx_pca_handle p, const double* mean_dev, const double* var_dev, int64_t rows, const double* truth_dev, int64_t n_events,
+                       const int64_t* event_lo, const int64_t* event_hi, int n_counts, const int* counts, int depth_mode, double v_tol,
+                       double* cell_sums_dev, int* cell_arg_dev, double* truth_peak_dev, int* truth_arg_dev, double* row_sums_dev,
+                       unsigned long long* matches);
+/* device milliseconds of the last gprx_pca_sweep_dev of this handle; the counts one launch of it carries */
+int gprx_pca_sweep_ms(gprx_pca_handle p, double* ms);
+int gprx_pca_sweep_group(void);
 
 /* ---- fitting the EOF preprocessor: PreProcessor.fit (gpras/preprocess.py:947-1007) --------------------------------------- */
 /* The fitted state gprx_pca_create takes, computed on the device.  Single-batch IncrementalPCA (sklearn partial_fit, first
