@@ -32,6 +32,11 @@ UNITS = (
     + [(n, f"{n}.hip", []) for n in ("abi_pseudo", "abi_resample", "abi_align", "abi_diag", "abi_events", "abi_fields", "abi_comm", "abi_eig")]
     + [(f"sf_pass1_k{k}", "sf_pass1.hip", [f"-DSF_KID={k}"]) for k in range(5)]
     + [(f"sf_pass2_k{k}", "sf_pass2.hip", [f"-DSF_KID={k}"]) for k in range(5)]
+    # the same kernels with the held-out row mask (gprx_*_held), in units of their own: a batch without held rows runs code objects
+    # that hold exactly what they held before
+    + [(f"sf_pass1_k{k}_held", "sf_pass1.hip", [f"-DSF_KID={k}", "-DSF_HOLD=1"]) for k in range(5)]
+    + [(f"sf_pass2_k{k}_held", "sf_pass2.hip", [f"-DSF_KID={k}", "-DSF_HOLD=1"]) for k in range(5)]
+    + [("sf_adam_held", "sf_adam_held.hip", []), ("sf_adadelta_held", "sf_adadelta_held.hip", [])]
 )
 SOURCES = sorted({u[1] for u in UNITS})
 

@@ -66,6 +66,10 @@ PROTOTYPES = {
     "gprx_adam_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp]),
     "gprx_adadelta_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "gprx_last_optimizer_route": (C.c_int, [_vp, _ip, _ip]),
+    "gprx_objective_batch_held": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "gprx_adam_batch_held": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "gprx_adadelta_batch_held": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "gprx_predict_batch_held": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _i64, _vp, _vp, C.c_int, _vp, _vp]),
     "gprx_loeo_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "gprx_last_loeo": (C.c_int, [_vp, _ip, _vp]),
     "gprx_comm_runtime_check": (C.c_int, [C.c_int]),

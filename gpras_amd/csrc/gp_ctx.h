@@ -26,6 +26,8 @@ struct gprx_ctx {
   Buf X, Y, invls, alpha, red, Kmat, invD, Xinv, Tmp, partial, xs, Ks, pred;
   Buf dstage;
   std::vector<double> yy;  // y.y per unit
+  std::vector<double> yhost;  // y as uploaded (unit-major, np apart): the held-out forms sum a cell's own y.y over its kept rows from it
+  Buf hold;                   // device table of a batch's held-out row ranges (gp_sparse.h CellHolds): SF_HOLD_W doubles per cell
   int* info = nullptr;
   double* pin = nullptr;  // pinned host staging: [0..63] lengthscales up, [64..71] reductions down, [72] info (as int),
                           // [74] variance, [75] noise (graph replay reads them through the device block `gparams`)
@@ -102,6 +104,15 @@ bool fused_eval() {  // GPRX_FUSED_EVAL=0: an exact evaluation with gradient wai
   return v;
 }
 void fill_nan(double* p, int64_t n) { std::fill(p, p + n, std::numeric_limits<double>::quiet_NaN()); }
+
+// acc + sum of y_i^2 of unit u over the rows [r0, r1) of the handle's data, added in row order: the one loop behind gprx_set_data's y.y of
+// a unit and a held-out cell's own (its kept rows before and behind the range), so that a cell that holds a suffix out gets the bits of
+// a handle that never had those rows
+double yy_rows(gprx_handle h, int u, int64_t r0, int64_t r1, double acc) {
+  const double* yu = h->yhost.data() + (size_t)u * h->np;
+  for (int64_t i = r0; i < r1; ++i) acc += yu[i] * yu[i];
+  return acc;
+}
 
 // kernel-matrix and trace launches evaluate r2 in the handle's distance form (gprx_set_distance_form)
 template <class Args>

@@ -110,11 +110,15 @@ int factorize_batch(gprx_handle h, int count, const int* units, const double* th
   return rc;
 }
 
+// held (gprx_objective_batch_held): hold_lo / hold_hi are checked in front of everything else that looks at the cells, and a batch of
+// ONE cell takes the batched sparse branch as well (objective_impl knows no holds)
 int objective_batch(gprx_handle h, int count, const int* units, const double* theta, const double* z, int mask, double* losses,
-                         double* grads) {
+                         double* grads, bool held = false, const int64_t* hold_lo = nullptr, const int64_t* hold_hi = nullptr) {
   int rc;
   if ((rc = check_handle(h))) return rc;
   if (count < 0 || !units || !theta || !losses) return fail(h, GPRX_EINVAL, "null argument");
+  if (held && (rc = check_holds(h, count, hold_lo, hold_hi))) return rc;
+  const CellHolds holds = held ? CellHolds{hold_lo, hold_hi} : CellHolds{};
   const int64_t gw = h->ntheta + h->m * h->d;
   if (h->m == 0 && count > 1 && h->d <= CELL_PAR - CELL_PAR_LS) {
     // exact models: every stage once for all cells (batched launches), results identical to the loop below
@@ -146,13 +150,14 @@ int objective_batch(gprx_handle h, int count, const int* units, const double* th
     }
     return frc;
   }
-  if (h->m != 0 && count > 1 && h->d <= CELL_PAR - CELL_PAR_LS) {
+  if (h->m != 0 && (count > 1 || (held && count == 1)) && h->d <= CELL_PAR - CELL_PAR_LS) {
     const int64_t nz = h->m * h->d;
     std::vector<Theta> ts;
     if ((rc = decode_cells(h, count, units, theta, z, ts))) return rc;
     std::vector<double> elbo(count), g(grads ? (size_t)count * h->ntheta : 0), gzv(grads ? (size_t)count * nz : 0);
     std::vector<int> st(count);
-    const int frc = sgpr_objective_batch(h, count, units, ts.data(), z, elbo.data(), grads ? g.data() : nullptr, grads ? gzv.data() : nullptr, st.data());
+    const int frc = sgpr_objective_batch(h, count, units, ts.data(), z, elbo.data(), grads ? g.data() : nullptr, grads ? gzv.data() : nullptr, st.data(),
+                                         holds);
     if (frc != GPRX_OK && frc != GPRX_ENOTPD) return frc;
     for (int i = 0; i < count; ++i) {
       losses[i] = -(elbo[i] + log_prior(h, ts[i], mask));  // NaN for a failed cell
@@ -187,13 +192,16 @@ int objective_batch(gprx_handle h, int count, const int* units, const double* th
 
 // gprx_adam_batch and gprx_adadelta_batch: one loop, two updates (kind: SF_OPT_ADAM, SF_OPT_ADADELTA of sgpr_asm.h).  Adadelta has no stop
 // rule, so its batch never shrinks.  last_losses (optional): the loss of each cell's last evaluation.
+// held (gprx_adam_batch_held / gprx_adadelta_batch_held): the ranges are checked first; the resident fused loop carries them in its
+// table, the host-stepped loop hands the running cells' ranges to the held objective.
 int optimizer_batch(gprx_handle h, int kind, int count, const int* units, double* theta, double* z, int mask, int max_iter,
-                           double* last_losses, int* n_evals, int* batches) {
+                           double* last_losses, int* n_evals, int* batches, bool held, const int64_t* hold_lo, const int64_t* hold_hi) {
 #pragma clang fp contract(off)
   int rc;
   if ((rc = check_handle(h))) return rc;
   if (count <= 0 || !units || !theta || !n_evals || max_iter < 0) return fail(h, GPRX_EINVAL, "null argument");
   if (h->m != 0 && !z) return fail(h, GPRX_EINVAL, "z (inducing inputs) is null for a sparse model");
+  if (held && (rc = check_holds(h, count, hold_lo, hold_hi))) return rc;
   const int nt = h->ntheta;
   const int64_t nz = h->m * h->d, gw = nt + nz;
   if (batches) *batches = 0;
@@ -218,23 +226,31 @@ int optimizer_batch(gprx_handle h, int kind, int count, const int* units, double
     std::vector<Theta> checked;
     if ((rc = decode_cells(h, count, units, theta, z, checked))) return rc;
     h->last_route = sgpr_five_launches(h) ? 1 : 2;
-    return (sgpr_five_launches(h) ? sgpr_resident_fused : sgpr_resident_general)(h, kind, count, units, theta, z, mask, max_iter, last_losses, n_evals,
-                                                                                   batches);
+    if (sgpr_five_launches(h))
+      return sgpr_resident_fused(h, kind, count, units, theta, z, mask, max_iter, last_losses, n_evals, batches,
+                                 held ? CellHolds{hold_lo, hold_hi} : CellHolds{});
+    return sgpr_resident_general(h, kind, count, units, theta, z, mask, max_iter, last_losses, n_evals, batches);  // (never held: check_holds)
   }
   std::vector<double> mom((size_t)count * gw, 0.0), vel((size_t)count * gw, 0.0), best(count, std::numeric_limits<double>::infinity());
   std::vector<int> stale(count, 0), active(count);
   for (int i = 0; i < count; ++i) active[i] = i;
   std::vector<int> a_units(count);
+  std::vector<int64_t> a_lo(held ? count : 0), a_hi(held ? count : 0);
   std::vector<double> a_theta((size_t)count * nt), a_z((size_t)count * nz), losses(count), grads((size_t)count * gw);
   for (int t = 1; t <= max_iter && !active.empty(); ++t) {
     const int na = (int)active.size();
     for (int j = 0; j < na; ++j) {
       const int i = active[j];
       a_units[j] = units[i];
+      if (held) {
+        a_lo[j] = hold_lo[i];
+        a_hi[j] = hold_hi[i];
+      }
       std::memcpy(&a_theta[(size_t)j * nt], theta + (size_t)i * nt, sizeof(double) * nt);
       if (nz) std::memcpy(&a_z[(size_t)j * nz], z + (size_t)i * nz, sizeof(double) * nz);
     }
-    rc = objective_batch(h, na, a_units.data(), a_theta.data(), nz ? a_z.data() : nullptr, mask, losses.data(), grads.data());
+    rc = objective_batch(h, na, a_units.data(), a_theta.data(), nz ? a_z.data() : nullptr, mask, losses.data(), grads.data(), held, a_lo.data(),
+                         a_hi.data());
     if (batches) ++*batches;
     for (int j = 0; j < na; ++j) ++n_evals[active[j]];
     if (last_losses)  // (a failed cell holds NaN; after any other error the evaluation wrote no loss)
@@ -265,12 +281,13 @@ int optimizer_batch(gprx_handle h, int kind, int count, const int* units, double
 
 // (gprx_last_optimizer_route: the route and the stream waits of this call)
 int optimizer_routed(gprx_handle h, int kind, int count, const int* units, double* theta, double* z, int mask, int max_iter,
-                            double* last_losses, int* n_evals, int* batches) {
+                            double* last_losses, int* n_evals, int* batches, bool held = false, const int64_t* hold_lo = nullptr,
+                            const int64_t* hold_hi = nullptr) {
   if (h) {
     h->last_route = 0;
     h->host_waits = 0;
   }
-  const int rc = optimizer_batch(h, kind, count, units, theta, z, mask, max_iter, last_losses, n_evals, batches);
+  const int rc = optimizer_batch(h, kind, count, units, theta, z, mask, max_iter, last_losses, n_evals, batches, held, hold_lo, hold_hi);
   if (h) h->last_host_waits = h->host_waits;
   return rc;
 }

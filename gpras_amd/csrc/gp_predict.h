@@ -107,8 +107,10 @@ int predict_dev(gprx_handle h, const double* xs_dev, int64_t ns, double* mean_de
 
 // Core of gprx_predict_batch: the test points are in device memory (xs_dev) and the results go to device memory
 // (means_dev / vars_dev: (count, ns) row-major); asynchronous on the handle's stream after the batched factorisation.
+// holds (gprx_predict_batch_held, checked by the caller): cell i is factorised without its held-out rows; the predict itself reads the
+// cell's factors only and is the one of every other batch (a lone held cell takes the batched branch too).
 int predict_batch_core(gprx_handle h, int count, const int* units, const double* thetas, const double* z, const double* xs_dev, int64_t ns,
-                              double* means_dev, double* vars_dev, int include_noise) {
+                              double* means_dev, double* vars_dev, int include_noise, const CellHolds& holds = CellHolds{}) {
   int rc;
   hipStream_t st = h->stream;
   if (h->m == 0 && h->d <= CELL_PAR - CELL_PAR_LS) {
@@ -143,13 +145,13 @@ int predict_batch_core(gprx_handle h, int count, const int* units, const double*
     h->have_linv = false;  // the single-cell views of the handle may point into the arena: their cached L^-1 is not this batch's
     return GPRX_OK;
   }
-  if (h->m != 0 && count > 1 && h->d <= CELL_PAR - CELL_PAR_LS) {
+  if (h->m != 0 && (count > 1 || holds.lo != nullptr) && h->d <= CELL_PAR - CELL_PAR_LS) {
     // sparse models (what gpras runs): every cell factorised by ONE batched launch sequence, then one batched predict
     std::vector<Theta> ts;
     if ((rc = decode_cells(h, count, units, thetas, z, ts))) return rc;
     std::vector<double> elbo(count);
     std::vector<int> stv(count);
-    if ((rc = sgpr_objective_batch(h, count, units, ts.data(), z, elbo.data(), nullptr, nullptr, stv.data()))) return rc;  // ENOTPD included
+    if ((rc = sgpr_objective_batch(h, count, units, ts.data(), z, elbo.data(), nullptr, nullptr, stv.data(), holds))) return rc;  // ENOTPD included
     if (ns == 0) return GPRX_OK;
     return sgpr_predict_batch(h, count, xs_dev, ns, means_dev, vars_dev, include_noise);
   }
@@ -168,10 +170,13 @@ int predict_batch_core(gprx_handle h, int count, const int* units, const double*
 // its final layout -- whole when all cells fit one slab, by 2-D copies into the slab's columns otherwise.
 constexpr int NO_FORCED_SLAB = std::numeric_limits<int>::min();
 int predict_batch_slabs(gprx_handle h, int count, const int* units, const double* thetas, const double* z, const double* xs, int64_t ns, double* means,
-                        double* vars, int include_noise, bool transposed, int64_t budget, int forced_slab) {
+                        double* vars, int include_noise, bool transposed, int64_t budget, int forced_slab, bool held = false,
+                        const int64_t* hold_lo = nullptr, const int64_t* hold_hi = nullptr) {
   int rc;
   if ((rc = check_handle(h))) return rc;
   if (count <= 0 || !units || !thetas || ns < 0 || (ns > 0 && (!xs || !means || !vars))) return fail(h, GPRX_EINVAL, "null argument");
+  if (held && (rc = check_holds(h, count, hold_lo, hold_hi))) return rc;
+  const CellHolds holds = held ? CellHolds{hold_lo, hold_hi} : CellHolds{};
   int slab = (int)std::max<int64_t>(1, std::min<int64_t>(count, budget / std::max<int64_t>(2 * ns, 1)));
   if (forced_slab != NO_FORCED_SLAB) slab = std::max(1, std::min(count, forced_slab));
   if ((rc = ensure(h, h->xs, sizeof(double) * (ns * h->d + (transposed ? 4 : 2) * ns * slab + 16)))) return rc;
@@ -184,7 +189,7 @@ int predict_batch_slabs(gprx_handle h, int count, const int* units, const double
   for (int c0 = 0; c0 < count; c0 += slab) {
     const int cnt = std::min(slab, count - c0);
     if ((rc = predict_batch_core(h, cnt, units + c0, thetas + (int64_t)c0 * h->ntheta, z ? z + (int64_t)c0 * h->m * h->d : nullptr, dxs, ns, dmean, dvar,
-                                 include_noise)))
+                                 include_noise, holds.from(c0))))
       return rc;
     if (ns > 0 && !transposed) {
       HIPCHK(h, hipMemcpyAsync(means + (int64_t)c0 * ns, dmean, sizeof(double) * ns * cnt, hipMemcpyDeviceToHost, h->stream));

@@ -171,12 +171,20 @@ struct SfJoin {
 // table, every cell runs max_iter steps; `losses` (optional) receives the loss of each cell's last evaluation.
 // The other groups' streams are joined into the handle's stream before EVERY return (SfJoin): after a failed HIP call inside the step
 // loop nothing may stay in flight on buffers the handle reuses.
+// holds (checked by the caller): cells that hold rows out carry their table row through every launch of every step -- each group of cells
+// its own part of the table (sf_params_from) -- and the closing launch takes the cell's own row count and y.y from it.
 int sgpr_resident_fused(gprx_handle h, int kind, int count, const int* units, double* theta, double* z, int mask, int max_iter, double* losses,
-                        int* n_evals, int* batches) {
+                        int* n_evals, int* batches, const CellHolds& holds = CellHolds{}) {
   const SgprLayout L = sgpr_batch_layout(h);
   int rc;
   if ((rc = ensure_sarena(h, count, L))) return rc;
   hipStream_t st = h->stream;
+  std::vector<double> htab;  // (lives until the synchronisation behind the initial state)
+  const bool held = holds.any(count);
+  if (held) {
+    hold_table(h, count, units, holds, htab);
+    if ((rc = hold_upload(h, htab))) return rc;
+  }
   const int nt = h->ntheta;
   const int64_t nz = h->m * h->d, gw = nt + nz;
   const int check_every = resident_check_every();
@@ -205,6 +213,7 @@ int sgpr_resident_fused(gprx_handle h, int kind, int count, const int* units, do
   HIPCHK(h, hipStreamSynchronize(st));
   SfParams p = sgpr_fused_params(h, L, true);
   p.active = ad.active;
+  p.hold = held ? h->hold.p : nullptr;
   p.store_factors = 0;  // (nobody predicts from the cell blocks of a running optimisation)
   const int iso = (h->ard || h->dist_form) ? 0 : 1;
   const int* flags = rs.hflags;

@@ -186,6 +186,70 @@ SfParams sgpr_fused_params(gprx_handle h, const SgprLayout& L, bool want_grad) {
   return p;
 }
 
+// ---- held-out rows (gprx_*_held: the folds of a cross-validation as cells of one batch) ----
+// lo / hi: `count` values each; cell i's model does not see the training rows [lo[i], hi[i]) (lo == hi: it sees all).  A default-
+// constructed value -- what every entry point without "_held" passes -- holds nothing.
+struct CellHolds {
+  const int64_t* lo = nullptr;
+  const int64_t* hi = nullptr;
+  bool any(int count) const {  // some cell holds at least one row
+    if (!lo || !hi) return false;
+    for (int i = 0; i < count; ++i)
+      if (hi[i] != lo[i]) return true;
+    return false;
+  }
+  CellHolds from(int cell0) const { return lo && hi ? CellHolds{lo + cell0, hi + cell0} : CellHolds{}; }
+};
+
+// The argument check of the held forms, before any device work: the handle is one the five fused launches serve, every range lies in
+// [0, n] with lo <= hi, and every cell keeps a row.
+int check_holds(gprx_handle h, int count, const int64_t* lo, const int64_t* hi) {
+  if (!lo || !hi) return fail(h, GPRX_EINVAL, "hold_lo / hold_hi is null");
+  if (h->m == 0) return fail(h, GPRX_EINVAL, "held-out rows: exact model (the held forms serve sparse models on the five fused launches)");
+  if (h->m > NB) return fail(h, GPRX_EINVAL, "held-out rows: more than 64 inducing points (the held forms serve M <= 64)");
+  if (h->d > CELL_PAR - CELL_PAR_LS) return fail(h, GPRX_EINVAL, "held-out rows: more than 64 features (the held forms serve d <= 64)");
+  if (!sgpr_five_launches(h)) return fail(h, GPRX_EINVAL, "held-out rows: \"sgpr_fused\" = 0 (the general launch sequence holds no rows out)");
+  char msg[200];
+  for (int i = 0; i < count; ++i) {
+    if (lo[i] > hi[i]) {
+      snprintf(msg, sizeof msg, "cell %d: hold_lo %lld > hold_hi %lld", i, (long long)lo[i], (long long)hi[i]);
+      return fail(h, GPRX_EINVAL, msg);
+    }
+    if (lo[i] < 0 || hi[i] > h->n) {
+      snprintf(msg, sizeof msg, "cell %d: held range [%lld, %lld) outside [0, %lld]", i, (long long)lo[i], (long long)hi[i], (long long)h->n);
+      return fail(h, GPRX_EINVAL, msg);
+    }
+    if (hi[i] - lo[i] >= h->n) {
+      snprintf(msg, sizeof msg, "cell %d: held range [%lld, %lld) keeps no row", i, (long long)lo[i], (long long)hi[i]);
+      return fail(h, GPRX_EINVAL, msg);
+    }
+  }
+  return GPRX_OK;
+}
+
+// The table the kernels read (SfParams::hold), SF_HOLD_W doubles per cell: [lo, hi, rows kept, y.y of the kept rows].  y.y is summed over
+// the kept rows in row order with gprx_set_data's loop (yy_rows) -- not y.y of the unit minus the held part, which rounds differently:
+// a cell that holds a suffix out gets the bits of a handle created on the rows in front of it.
+void hold_table(gprx_handle h, int count, const int* units, const CellHolds& holds, std::vector<double>& tab) {
+  tab.resize((size_t)count * SF_HOLD_W);
+  for (int i = 0; i < count; ++i) {
+    const int64_t lo = holds.lo[i], hi = holds.hi[i];
+    double* row = &tab[(size_t)i * SF_HOLD_W];
+    row[0] = (double)lo;
+    row[1] = (double)hi;
+    row[2] = (double)(h->n - (hi - lo));
+    row[3] = yy_rows(h, units[i], hi, h->n, yy_rows(h, units[i], 0, lo, 0.0));
+  }
+}
+
+// the table onto the device, in stream order; `tab` must live until the stream has passed the copy
+int hold_upload(gprx_handle h, const std::vector<double>& tab) {
+  int rc;
+  if ((rc = ensure(h, h->hold, sizeof(double) * tab.size()))) return rc;
+  HIPCHK(h, hipMemcpyAsync(h->hold.p, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, h->stream));
+  return GPRX_OK;
+}
+
 // The resident Adam loop on large batches: TWO groups of cells on two streams.  Two of the four launches of a step (mid, Adam + prep) are
 // one workgroup per cell around a 64 x 64 chain: with all cells in lock step the chip idles through them (16 of 256 CUs busy for half of a
 // 16-cell step), and a pass over more than 16 cells takes a second round of 256 workgroups.  Two groups that start one launch apart keep
@@ -219,14 +283,16 @@ SfParams sf_params_from(SfParams p, int cell0) {
   p.cpar += (int64_t)cell0 * CELL_PAR;
   p.cellres += (int64_t)cell0 * p.cellres_stride;
   if (p.active) p.active += cell0;
+  if (p.hold) p.hold += (int64_t)cell0 * SF_HOLD_W;
   if (cell0 != 0) p.stamps = nullptr;
   return p;
 }
 
-int sgpr_fused_enqueue(gprx_handle h, int count, const SgprLayout& L, bool want_grad) {
+int sgpr_fused_enqueue(gprx_handle h, int count, const SgprLayout& L, bool want_grad, const double* hold_dev = nullptr) {
   hipStream_t st = h->stream;
   const SgprStage sg = sgpr_stage(h, count, L);
-  const SfParams p = sgpr_fused_params(h, L, want_grad);
+  SfParams p = sgpr_fused_params(h, L, want_grad);
+  p.hold = hold_dev;
   const int iso = (h->ard || h->dist_form) ? 0 : 1;
   HIPCHK(h, sf_launch_prep(st, h->kid, h->dist_form, p, count, h->spin + sg.par, h->spin + sg.z, h->cellpar.p));
   HIPCHK(h, sf_launch_pass1(st, h->kid, h->dist_form, p, count));
@@ -402,8 +468,8 @@ int sgpr_stage_out_enqueue(gprx_handle h, int count, const SgprLayout& L, bool w
   return GPRX_OK;
 }
 
-int sgpr_batch_enqueue(gprx_handle h, int count, const SgprLayout& L, bool want_grad, const SgprParSrc& ps) {
-  if (sgpr_five_launches(h)) return sgpr_fused_enqueue(h, count, L, want_grad);
+int sgpr_batch_enqueue(gprx_handle h, int count, const SgprLayout& L, bool want_grad, const SgprParSrc& ps, const double* hold_dev = nullptr) {
+  if (sgpr_five_launches(h)) return sgpr_fused_enqueue(h, count, L, want_grad, hold_dev);
   int rc;
   if ((rc = sgpr_stage_in_enqueue(h, count, L))) return rc;
   if ((rc = sgpr_body_enqueue(h, count, L, want_grad, ps))) return rc;
@@ -454,11 +520,19 @@ int sgpr_replay(gprx_handle h, std::map<std::pair<int, int>, hipGraphExec_t>& gr
 }
 
 // elbo_out[c] (NaN if a Cholesky failed), g: count x ntheta constrained-parameter derivatives, gz: count x m x d (host);
-// g / gz may be null (loss only).  status[c]: GPRX_OK / GPRX_ENOTPD.
+// g / gz may be null (loss only).  status[c]: GPRX_OK / GPRX_ENOTPD.  holds: checked by the caller (check_holds); a batch in which no
+// cell holds a row takes the launches without the table.
 int sgpr_objective_batch(gprx_handle h, int count, const int* units, const Theta* ts, const double* zs, double* elbo_out, double* g, double* gz,
-                         int* status) {
+                         int* status, const CellHolds& holds = CellHolds{}) {
   const SgprLayout L = sgpr_batch_layout(h);
   int rc;
+  std::vector<double> htab;  // (lives until the wait below)
+  const bool held = holds.any(count);
+  if (held) {
+    hold_table(h, count, units, holds, htab);
+    if ((rc = hold_upload(h, htab))) return rc;
+  }
+  const double* hold_dev = held ? h->hold.p : nullptr;
   const bool direct = h->d > CELL_PAR - CELL_PAR_LS;  // (SgprParSrc)
   if (direct && count != 1) return fail(h, GPRX_EINVAL, "d > 64: sparse models are evaluated one cell at a time");
   if ((rc = ensure_sarena(h, count, L))) return rc;
@@ -479,7 +553,7 @@ int sgpr_objective_batch(gprx_handle h, int count, const int* units, const Theta
   if (!sgpr_five_launches(h) && !direct &&
       (rc = sgpr_replay(h, h->sgraphs, {count, want_grad ? 1 : 0}, [&] { return sgpr_batch_enqueue(h, count, L, want_grad, ps); }, &replayed)))
     return rc;
-  if (!replayed && (rc = sgpr_batch_enqueue(h, count, L, want_grad, ps))) return rc;
+  if (!replayed && (rc = sgpr_batch_enqueue(h, count, L, want_grad, ps, hold_dev))) return rc;
   const double* hres = h->spin + sg.res;
   const double* hred = h->spin + sg.red;
   const double* hsum = h->spin + sg.sum;
@@ -487,8 +561,10 @@ int sgpr_objective_batch(gprx_handle h, int count, const int* units, const Theta
   HIPCHK(h, wait_stream(h, st));
   h->factorized = false;  // (objective_impl sets it for a lone model: cell block 0 is then what gprx_predict reads)
   int first_error = GPRX_OK;
-  const double nn = (double)h->n;
   for (int c = 0; c < count; ++c) {
+    // (a cell that holds rows out: its own row count and y.y, the values its row of the table carries to the resident loop)
+    const double nn = held ? htab[(size_t)c * SF_HOLD_W + 2] : (double)h->n;
+    const double yy = held ? htab[(size_t)c * SF_HOLD_W + 3] : h->yy[units[c]];
     int info = 0;
     std::memcpy(&info, hres + (size_t)c * CELL_RES + 2, sizeof(int));
     if (status) status[c] = info == 0 ? GPRX_OK : GPRX_ENOTPD;
@@ -503,7 +579,7 @@ int sgpr_objective_batch(gprx_handle h, int count, const int* units, const Theta
     }
     const double* red = hred + (size_t)c * 8;
     const double s = ts[c].noise, v = ts[c].variance;
-    elbo_out[c] = sgpr_asm_elbo(nn, h->yy[units[c]], v, s, red);  // (sgpr_asm.h: the resident Adam loop forms the same sums on the device)
+    elbo_out[c] = sgpr_asm_elbo(nn, yy, v, s, red);  // (sgpr_asm.h: the resident Adam loop forms the same sums on the device)
     if (!g) continue;
     const double* hs = hsum + (size_t)c * 2 * width;
     double* gc = g + (size_t)c * h->ntheta;

@@ -140,7 +140,7 @@ int gprx_destroy(gprx_handle h) {
   hipSetDevice(h->device);
   if (h->stream) hipStreamSynchronize(h->stream);
   for (Buf* b : {&h->X, &h->Y, &h->invls, &h->alpha, &h->red, &h->Kmat, &h->invD, &h->Xinv, &h->Tmp, &h->partial, &h->xs, &h->Ks, &h->pred,
-                 &h->dstage, &h->arena, &h->cellpar, &h->cellres, &h->garena, &h->gpartial, &h->apart, &h->twork, &h->sarena})
+                 &h->dstage, &h->arena, &h->cellpar, &h->cellres, &h->garena, &h->gpartial, &h->apart, &h->twork, &h->sarena, &h->hold})
     if (b->p && !b->borrowed) hipFree(b->p);
   if (h->bpin) hipHostFree(h->bpin);
   if (h->spin) hipHostFree(h->spin);
@@ -223,12 +223,9 @@ int gprx_set_data(gprx_handle h, const double* x, const double* y, int n_units) 
     HIPCHK(h, copy_sync(h->Y.p, yt.data(), sizeof(double) * yt.size(), hipMemcpyHostToDevice));
     h->n_units = n_units;
     forget_factorizations(h, true);  // resident batch slots were factorised from the old data
+    h->yhost.swap(yt);
     h->yy.assign(n_units, 0.0);
-    for (int u = 0; u < n_units; ++u) {
-      double acc = 0.0;
-      for (int64_t i = 0; i < h->n; ++i) acc += y[i * n_units + u] * y[i * n_units + u];
-      h->yy[u] = acc;
-    }
+    for (int u = 0; u < n_units; ++u) h->yy[u] = yy_rows(h, u, 0, h->n, 0.0);
     return GPRX_OK;
   });
 }
@@ -358,6 +355,34 @@ int gprx_predict_batch_t(gprx_handle h, int count, const int* units, const doubl
   return guarded(h, [&]() -> int {
     return predict_batch_slabs(h, count, units, thetas, z, xs, ns, means_t, vars_t, include_noise, true, (int64_t)1 << 26,
                                env_int("GPRX_PREDICT_SLAB", NO_FORCED_SLAB));
+  });
+}
+
+// ---- the held-out forms (include/gprx.h "Held-out rows"): their parents with one row range per cell that the cell's model does not see ----
+int gprx_objective_batch_held(gprx_handle h, int count, const int* units, const double* theta, const double* z, int mask, double* losses,
+                              double* grads, const int64_t* hold_lo, const int64_t* hold_hi) {
+  return guarded(h, [&]() -> int { return objective_batch(h, count, units, theta, z, mask, losses, grads, true, hold_lo, hold_hi); });
+}
+
+int gprx_adam_batch_held(gprx_handle h, int count, const int* units, double* theta, double* z, int mask, int max_iter, int* n_evals, int* batches,
+                         const int64_t* hold_lo, const int64_t* hold_hi) {
+  return guarded(h, [&]() -> int {
+    return optimizer_routed(h, SF_OPT_ADAM, count, units, theta, z, mask, max_iter, nullptr, n_evals, batches, true, hold_lo, hold_hi);
+  });
+}
+
+int gprx_adadelta_batch_held(gprx_handle h, int count, const int* units, double* theta, double* z, int mask, int max_iter, double* losses,
+                             int* n_evals, int* batches, const int64_t* hold_lo, const int64_t* hold_hi) {
+  return guarded(h, [&]() -> int {
+    return optimizer_routed(h, SF_OPT_ADADELTA, count, units, theta, z, mask, max_iter, losses, n_evals, batches, true, hold_lo, hold_hi);
+  });
+}
+
+int gprx_predict_batch_held(gprx_handle h, int count, const int* units, const double* thetas, const double* z, const double* xs, int64_t ns,
+                            double* means, double* vars, int include_noise, const int64_t* hold_lo, const int64_t* hold_hi) {
+  return guarded(h, [&]() -> int {
+    return predict_batch_slabs(h, count, units, thetas, z, xs, ns, means, vars, include_noise, false, (int64_t)1 << 27, NO_FORCED_SLAB, true, hold_lo,
+                               hold_hi);
   });
 }
 

@@ -6,7 +6,8 @@ namespace gprx {
 
 hipError_t sf_launch_adadelta_prep(hipStream_t st, int kid, int form, int iso, const SfParams& p, int cells, const SfAdam& adam,
                                    double* cpar_dst) {
-  return sf_launch_step_prep<SF_OPT_ADADELTA>(st, kid, form, iso, p, cells, adam, cpar_dst);
+  if (p.hold != nullptr) return sf_launch_adadelta_prep_held(st, kid, form, iso, p, cells, adam, cpar_dst);  // (sf_adadelta_held.hip)
+  return sf_launch_step_prep<SF_OPT_ADADELTA, 0>(st, kid, form, iso, p, cells, adam, cpar_dst);
 }
 
 }  // namespace gprx

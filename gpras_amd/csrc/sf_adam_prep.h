@@ -3,13 +3,15 @@
 // keeps running, Kuu of the NEW variables, its factor and the factor's inverse (sf_prep_compute): the updated Z and hyperparameters pass
 // through LDS, one dependent launch and one trip through memory fewer per step than an update launch + sf_prep.
 // The kernel and its launcher as templates over the optimiser (OPT: SF_OPT_ADAM, SF_OPT_ADADELTA of sgpr_asm.h); each optimiser's
-// fifteen instantiations are compiled in a translation unit of their own (sf_adam.hip, sf_adadelta.hip), which build in parallel.
+// fifteen instantiations are compiled in a translation unit of their own (sf_adam.hip, sf_adadelta.hip), which build in parallel --
+// twice: HOLD = 1 (sf_adam_held.hip, sf_adadelta_held.hip: units of their own, sf_pass1.hip says why) serves batches whose cells hold
+// rows out (SfParams::hold given), HOLD = 0 is the launch without that table.
 #pragma once
 #include "sf_cell_dev.h"
 
 namespace gprx {
 
-template <int KID, int FORM, int ISO, int OPT>
+template <int KID, int FORM, int ISO, int OPT, int HOLD>
 __global__ __launch_bounds__(256) void sf_adam_prep_kernel(SfParams p, SfAdam ad, double* __restrict__ cpar_dst) {
   SF_PREP_LDS_DECL
   const int cell = blockIdx.x, tid = threadIdx.x;
@@ -27,7 +29,7 @@ __global__ __launch_bounds__(256) void sf_adam_prep_kernel(SfParams p, SfAdam ad
   double* sTh = sred + 8;
   int* keep = reinterpret_cast<int*>(sTh + (2 + CELL_PAR - CELL_PAR_LS));
   static_assert(2 * (2 + CELL_PAR - CELL_PAR_LS) + 8 + (2 + CELL_PAR - CELL_PAR_LS) + 2 <= 2 * NB * PSUB, "the update's scratch fits into the sub-panel buffer");
-  sf_adam_body<ISO, OPT>(p, ad, cell, tid, shs, sred, sTh, sQ, keep);
+  sf_adam_body<ISO, OPT, HOLD>(p, ad, cell, tid, shs, sred, sTh, sQ, keep);
   __syncthreads();
   if (*keep == 0) return;
   const double parv = sf_par_from_theta(sTh, ad, cell, p.d, tid);
@@ -40,9 +42,9 @@ __global__ __launch_bounds__(256) void sf_adam_prep_kernel(SfParams p, SfAdam ad
   sf_prep_compute<KID, FORM>(p, cell, A, sQ, sZ, sIn, sXb, sTab, sPar, tid);
 }
 
-template <int OPT>
+template <int OPT, int HOLD>
 hipError_t sf_launch_step_prep(hipStream_t st, int kid, int form, int iso, const SfParams& p, int cells, const SfAdam& adam, double* cpar_dst) {
-#define SF_AP(K_, F_, I_) hipLaunchKernelGGL((sf_adam_prep_kernel<K_, F_, I_, OPT>), dim3(cells), dim3(256), 0, st, p, adam, cpar_dst);
+#define SF_AP(K_, F_, I_) hipLaunchKernelGGL((sf_adam_prep_kernel<K_, F_, I_, OPT, HOLD>), dim3(cells), dim3(256), 0, st, p, adam, cpar_dst);
 #define SF_CASE(K_)                  \
   case K_:                           \
     if (form) {                      \

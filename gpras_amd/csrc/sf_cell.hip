@@ -385,14 +385,16 @@ hipError_t sf_launch_final(hipStream_t st, int iso, const SfParams& p, int cells
   return hipGetLastError();
 }
 
+// (a batch that holds rows out -- p.hold given -- takes the HOLD = 1 kernels of the -DSF_HOLD=1 units)
 hipError_t sf_launch_pass1(hipStream_t st, int kid, int form, const SfParams& p, int cells) {
-#define SF_CASE(K_) return sf_launch_pass1_kid##K_(st, form, p, cells);
+#define SF_CASE(K_) return p.hold != nullptr ? sf_launch_pass1_held_kid##K_(st, form, p, cells) : sf_launch_pass1_kid##K_(st, form, p, cells);
   SF_KID_SWITCH(kid, SF_CASE)
 #undef SF_CASE
 }
 
 hipError_t sf_launch_pass2(hipStream_t st, int kid, int form, int iso, const SfParams& p, int cells) {
-#define SF_CASE(K_) return sf_launch_pass2_kid##K_(st, form, iso, p, cells);
+#define SF_CASE(K_) \
+  return p.hold != nullptr ? sf_launch_pass2_held_kid##K_(st, form, iso, p, cells) : sf_launch_pass2_kid##K_(st, form, iso, p, cells);
   SF_KID_SWITCH(kid, SF_CASE)
 #undef SF_CASE
 }

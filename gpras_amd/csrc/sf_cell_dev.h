@@ -166,11 +166,12 @@ __device__ __forceinline__ double opt_step_hyper(const SfAdam& ad, int k, int ma
 }
 
 // thread 255: ELBO, the priors in log_prior's order, the loss, the stop rule (Adam; an Adadelta cell runs exactly max_iter steps: best /
-// stale stay untouched) and the counters of step t.  Returns whether the cell keeps running.
+// stale stay untouched) and the counters of step t.  Returns whether the cell keeps running.  yy_cell: the cell's own y.y (a cell that
+// holds rows out, sgpr_fused.h), null: that of its unit.
 template <int OPT>
 __device__ __forceinline__ bool opt_step_close(const SfAdam& ad, int cell, int t, int mask, int max_iter, double nn, double variance, double noise,
-                                               const double* ls, const double* sred) {
-  const double elbo = sgpr_asm_elbo(nn, ad.yy[ad.units[cell]], variance, noise, sred);
+                                               const double* ls, const double* sred, const double* yy_cell = nullptr) {
+  const double elbo = sgpr_asm_elbo(nn, yy_cell != nullptr ? *yy_cell : ad.yy[ad.units[cell]], variance, noise, sred);
   double lp = 0.0;
   {
 #pragma clang fp contract(off)
@@ -202,7 +203,8 @@ __device__ __forceinline__ bool opt_step_close(const SfAdam& ad, int cell, int t
 // Kuu from them).  Returns through *keep (LDS int, written by thread 255) whether the cell keeps running.  Every thread must call it;
 // it contains one __syncthreads().
 // OPT: SF_OPT_ADAM as above; SF_OPT_ADADELTA reads no alpha table and keeps its two accumulators in mom / vel (opt_element, opt_step_close).
-template <int ISO, int OPT = SF_OPT_ADAM>
+// HOLD = 1 (SfParams::hold given): the row count and y.y of the tail are the cell's own, from its row of the table.
+template <int ISO, int OPT = SF_OPT_ADAM, int HOLD = 0>
 __device__ __forceinline__ void sf_adam_body(const SfParams& p, const SfAdam& ad, int cell, int tid, double* __restrict__ shs, double* __restrict__ sred,
                                              double* __restrict__ sTh, double* __restrict__ sZnew, int* __restrict__ keep) {
   const double* par = p.cpar + (int64_t)cell * CELL_PAR;
@@ -219,7 +221,12 @@ __device__ __forceinline__ void sf_adam_body(const SfParams& p, const SfAdam& ad
   sf_reduce_sums<ISO>(p, P2, ls, tid, &sred[4], shs);
   __syncthreads();
   const double variance = par[0], noise = par[1];
-  const double nn = (double)p.n;
+  double nn = (double)p.n;
+  const double* yy_cell = nullptr;
+  if constexpr (HOLD != 0) {
+    nn = p.hold[(int64_t)cell * SF_HOLD_W + 2];
+    yy_cell = p.hold + (int64_t)cell * SF_HOLD_W + 3;
+  }
   double* th = ad.theta + (int64_t)cell * nt;
   double* mom = ad.mom + (int64_t)cell * gw;
   double* vel = ad.vel + (int64_t)cell * gw;
@@ -258,7 +265,7 @@ __device__ __forceinline__ void sf_adam_body(const SfParams& p, const SfAdam& ad
     }
   }
   if (tid == 255) {  // (a thread with no hyperparameter of its own)
-    const bool go = opt_step_close<OPT>(ad, cell, t, ad.mask, ad.max_iter, nn, variance, noise, ls, sred);
+    const bool go = opt_step_close<OPT>(ad, cell, t, ad.mask, ad.max_iter, nn, variance, noise, ls, sred, yy_cell);
     if (keep) *keep = go ? 1 : 0;
   }
 }

@@ -1,11 +1,22 @@
-// Fused sparse evaluation (sgpr_fused.h), launch 2, for ONE kernel id: compiled with -DSF_KID=k (gpras_amd/_build.py).
+// Fused sparse evaluation (sgpr_fused.h), launch 2, for ONE kernel id: compiled with -DSF_KID=k (gpras_amd/_build.py), and a second time
+// with -DSF_HOLD=1 for the kernels that mask held-out rows.  A unit of their own, not further instantiations beside the others: what else
+// a code object holds moves the registers of its kernels (sf_pass1_kernel<0, 0, 6> went from 190 to 226 VGPRs with its HOLD = 1 twin in
+// the same unit, ten pass-2 kernels gained 4 to 8 bytes of scratch), and a batch without held rows runs the code it always ran.
 #include "sgpr_fused_dev.h"
 
 #ifndef SF_KID
 #error "compile with -DSF_KID=0..4"
 #endif
+#ifndef SF_HOLD
+#define SF_HOLD 0
+#endif
 #define SF_CAT2(a, b) a##b
 #define SF_CAT(a, b) SF_CAT2(a, b)
+#if SF_HOLD
+#define SF_LAUNCHER(stem_) SF_CAT(stem_##_held_kid, SF_KID)
+#else
+#define SF_LAUNCHER(stem_) SF_CAT(stem_##_kid, SF_KID)
+#endif
 
 namespace gprx {
 
@@ -18,6 +29,8 @@ namespace gprx {
 // ten 16 x 16 tiles on or below the diagonal: waves 0 .. 7 take tiles 0 .. 7, waves 0 and 1 also 8 and 9).
 // NP = 6 / 8: d <= 12 / 16, Z is staged once per workgroup and the distance loops run over NP pairs of dimensions unconditionally;
 // NP == 0: any d <= 64, restaged per tile and chunk of 16 dimensions.
+// HOLD = 1 (SfParams::hold given): a column inside the cell's held-out range is masked like the padding behind n -- P and the staged y
+// are zero there; HOLD = 0 is the kernel without the test.
 constexpr int SF_NT = 512;
 constexpr int SF_NC = 8;  // columns per lane in the row-lane layout
 __device__ __forceinline__ int sf_row_block(int wave) { return (wave < 4) ? (wave & 1) : 3 - (wave & 1); }  // 0 1 0 1 3 2 3 2
@@ -27,7 +40,7 @@ __device__ __forceinline__ void sf_lower_tile(int t, int& rb, int& cb) {
   cb = t - rb * (rb + 1) / 2;
 }
 
-template <int KID, int FORM, int NP>
+template <int KID, int FORM, int NP, int HOLD>
 __global__ __launch_bounds__(SF_NT) void sf_pass1_kernel(SfParams p) {
   __shared__ __attribute__((aligned(16))) double sPA[NB * SF_LD];  // the tile of Kuf, then A' in its place
   __shared__ __attribute__((aligned(16))) double sZ[NB * SF_DKP];
@@ -45,6 +58,11 @@ __global__ __launch_bounds__(SF_NT) void sf_pass1_kernel(SfParams p) {
   double* A = p.arena + (int64_t)cell * p.ss;
   const double* zp = A + p.oZ;
   const double* yp = p.Y + (int64_t)unit * p.np;
+  int hlo = 0, hhi = 0;  // (wave-uniform: scalar registers)
+  if constexpr (HOLD != 0) {
+    hlo = (int)p.hold[(int64_t)cell * SF_HOLD_W];
+    hhi = (int)p.hold[(int64_t)cell * SF_HOLD_W + 1];
+  }
   SF_STAMP(p, 32, 0)
   exp_tab_fill(sTab);
   const int ntiles = min(SF_TILES, (p.np - chunk * SF_CHUNK) / NB);
@@ -80,7 +98,13 @@ __global__ __launch_bounds__(SF_NT) void sf_pass1_kernel(SfParams p) {
       if constexpr (NP == 0) sf_stage<FORM, SF_NT>(zp, 0, p.m, p.d, k0, ls, sZ, tid);
       if (k0 == 0) {
         sf_stage_put<FORM, SF_NT>(raw, j0, p.n, p.d, 0, ls, sXc, tid);
-        if (tid < NB) sY[tid] = yp[j0 + tid];  // (zero beyond n: Y is padded)
+        if (tid < NB) {
+          if constexpr (HOLD != 0) {
+            const double yv = yp[j0 + tid];  // (read unconditionally, as below: Y is padded to np; a held y is selected away)
+            sY[tid] = sf_kept<HOLD>(j0 + tid, p.n, hlo, hhi) ? yv : 0.0;
+          }
+          else sY[tid] = yp[j0 + tid];  // (zero beyond n: Y is padded)
+        }
       } else {
         sf_stage<FORM, SF_NT>(p.X, j0, p.n, p.d, k0, ls, sXc, tid);
       }
@@ -96,7 +120,7 @@ __global__ __launch_bounds__(SF_NT) void sf_pass1_kernel(SfParams p) {
       double rr = r2[jj];
       if constexpr (FORM != 0) rr = expanded_r2(na, nb[jj], rr);
       const double pv = variance * corr_g<KID>(rr, sTab);  // (evaluated for every lane, selected afterwards: no branch around the table read)
-      sPA[lane * SF_LD + col] = (lane < p.m && j0 + col < p.n) ? pv : 0.0;
+      sPA[lane * SF_LD + col] = sf_live<HOLD>(lane < p.m, j0 + col, p.n, hlo, hhi) ? pv : 0.0;
     }
     __syncthreads();
     if (t == 0) { SF_STAMP(p, 32, 4) }
@@ -170,13 +194,13 @@ __global__ __launch_bounds__(SF_NT) void sf_pass1_kernel(SfParams p) {
   SF_STAMP(p, 32, 9)
 }
 
-hipError_t SF_CAT(sf_launch_pass1_kid, SF_KID)(hipStream_t st, int form, const SfParams& p, int cells) {
+hipError_t SF_LAUNCHER(sf_launch_pass1)(hipStream_t st, int form, const SfParams& p, int cells) {
   const dim3 grid(p.nchunks, cells), block(SF_NT);
   const int np = p.d <= 12 ? 6 : (p.d <= SF_DK ? 8 : 0);
-#define SF_P1(F_)                                                                              \
-  if (np == 6) hipLaunchKernelGGL((sf_pass1_kernel<SF_KID, F_, 6>), grid, block, 0, st, p);    \
-  else if (np == 8) hipLaunchKernelGGL((sf_pass1_kernel<SF_KID, F_, 8>), grid, block, 0, st, p); \
-  else hipLaunchKernelGGL((sf_pass1_kernel<SF_KID, F_, 0>), grid, block, 0, st, p);
+#define SF_P1(F_)                                                                                       \
+  if (np == 6) hipLaunchKernelGGL((sf_pass1_kernel<SF_KID, F_, 6, SF_HOLD>), grid, block, 0, st, p);    \
+  else if (np == 8) hipLaunchKernelGGL((sf_pass1_kernel<SF_KID, F_, 8, SF_HOLD>), grid, block, 0, st, p); \
+  else hipLaunchKernelGGL((sf_pass1_kernel<SF_KID, F_, 0, SF_HOLD>), grid, block, 0, st, p);
   if (form) {
     SF_P1(1)
   } else {

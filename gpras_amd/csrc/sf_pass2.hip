@@ -1,11 +1,20 @@
-// Fused sparse evaluation (sgpr_fused.h), launch 4, for ONE kernel id: compiled with -DSF_KID=k (gpras_amd/_build.py).
+// Fused sparse evaluation (sgpr_fused.h), launch 4, for ONE kernel id: compiled with -DSF_KID=k (gpras_amd/_build.py), and a second time
+// with -DSF_HOLD=1 for the kernels that mask held-out rows (a unit of their own: sf_pass1.hip says why).
 #include "sgpr_fused_dev.h"
 
 #ifndef SF_KID
 #error "compile with -DSF_KID=0..4"
 #endif
+#ifndef SF_HOLD
+#define SF_HOLD 0
+#endif
 #define SF_CAT2(a, b) a##b
 #define SF_CAT(a, b) SF_CAT2(a, b)
+#if SF_HOLD
+#define SF_LAUNCHER(stem_) SF_CAT(stem_##_held_kid, SF_KID)
+#else
+#define SF_LAUNCHER(stem_) SF_CAT(stem_##_kid, SF_KID)
+#endif
 
 namespace gprx {
 
@@ -22,6 +31,8 @@ namespace gprx {
 // MFMA layout: wave w owns row block w >> 1 (16 rows) and the column blocks 2 (w & 1), 2 (w & 1) + 1 of W P.
 // Registers: what crosses the MFMA product per element is ONE value (v h; isotropic: also r2) -- sum w g is formed in the MFMA layout
 // as sum (W P) o P + sum_j y_j (P^T m)_j, so g dies with the store of P.
+// HOLD = 1 (SfParams::hold given): a column inside the cell's held-out range is masked like the padding behind n in the P tile, the
+// residual / rank-one term and the weights, and its staged y is zero; HOLD = 0 is the kernel without the test.
 constexpr int SF_NT = 512;
 constexpr int SF_NC = 8;  // columns per lane in the row-lane layout
 
@@ -183,7 +194,7 @@ __device__ __forceinline__ void sf_pass2_tail(const SfParams& p, double* __restr
 }
 
 
-template <int KID, int FORM, int ISO, int NP>
+template <int KID, int FORM, int ISO, int NP, int HOLD>
 __global__ __launch_bounds__(SF_NT) void sf_pass2_kernel(SfParams p) {
   constexpr int NKC = NP > 0 ? 1 : 0;
   constexpr int DZN = NP > 0 ? 2 * NP : 4 * SF_DK;  // dimensions this lane accumulates dK/dZ for
@@ -204,6 +215,11 @@ __global__ __launch_bounds__(SF_NT) void sf_pass2_kernel(SfParams p) {
   double* A = p.arena + (int64_t)cell * p.ss;
   const double* zp = A + p.oZ;
   const double* yp = p.Y + (int64_t)unit * p.np;
+  int hlo = 0, hhi = 0;  // (wave-uniform: scalar registers)
+  if constexpr (HOLD != 0) {
+    hlo = (int)p.hold[(int64_t)cell * SF_HOLD_W];
+    hhi = (int)p.hold[(int64_t)cell * SF_HOLD_W + 1];
+  }
   SF_STAMP(p, 96, 0)
   constexpr bool isq = false;  // (the tile loop below only sees columns of Kuf; its Kuu branches are compiled out)
   const double* colpts = p.X;
@@ -240,7 +256,13 @@ __global__ __launch_bounds__(SF_NT) void sf_pass2_kernel(SfParams p) {
       if constexpr (NKC != 1) sf_stage<FORM, SF_NT>(zp, 0, p.m, p.d, k0, ls, sZ, tid);
       if (k0 == 0) {
         sf_stage_put<FORM, SF_NT>(raw, j0, ncolpts, p.d, 0, ls, sXc, tid);
-        if (tid < NB) sY[tid] = isq ? 0.0 : yp[j0 + tid];
+        if (tid < NB) {
+          if constexpr (HOLD != 0) {
+            const double yv = yp[j0 + tid];  // (read unconditionally, as below: Y is padded to np; a held y is selected away)
+            sY[tid] = sf_kept<HOLD>(j0 + tid, p.n, hlo, hhi) ? yv : 0.0;
+          }
+          else sY[tid] = isq ? 0.0 : yp[j0 + tid];
+        }
       } else {
         sf_stage<FORM, SF_NT>(colpts, j0, ncolpts, p.d, k0, ls, sXc, tid);
       }
@@ -262,7 +284,7 @@ __global__ __launch_bounds__(SF_NT) void sf_pass2_kernel(SfParams p) {
       corr_gh<KID>(rr, gv, hv);
       wh[jj] = variance * hv;
       if (!isq) {
-        sPA[lane * SF_LD + col] = (lane < p.m && j0 + col < p.n) ? variance * gv : 0.0;
+        sPA[lane * SF_LD + col] = sf_live<HOLD>(lane < p.m, j0 + col, p.n, hlo, hhi) ? variance * gv : 0.0;
       } else {
         // sum G_Q g directly (no product in front of it)
         const double wq = (lane < p.m && col < p.m) ? A[p.oGQ + lane * NB + col] : 0.0;
@@ -309,7 +331,7 @@ __global__ __launch_bounds__(SF_NT) void sf_pass2_kernel(SfParams p) {
       __syncthreads();
       if (tid < NB) {
         const double qv = ((sQp[0][tid] + sQp[1][tid]) + (sQp[2][tid] + sQp[3][tid])) + ((sQp[4][tid] + sQp[5][tid]) + (sQp[6][tid] + sQp[7][tid]));
-        const bool live = j0 + tid < p.n;
+        const bool live = sf_kept<HOLD>(j0 + tid, p.n, hlo, hhi);
         const double rv = live ? sY[tid] - qv : 0.0;
         resid = __builtin_fma(rv, rv, resid);
         if (live) sg = __builtin_fma(sY[tid], qv, sg);  // the rank-one part of sum G_P o P: sum_j y_j (P^T m)_j
@@ -320,7 +342,7 @@ __global__ __launch_bounds__(SF_NT) void sf_pass2_kernel(SfParams p) {
         const int col = wave * SF_NC + jj;
         double wv = inv_s * sPA[lane * SF_LD + col];
         wv = __builtin_fma(inv_s * mrow, sY[col], wv);
-        wh[jj] = (lane < p.m && j0 + col < p.n) ? wv * wh[jj] : 0.0;
+        wh[jj] = sf_live<HOLD>(lane < p.m, j0 + col, p.n, hlo, hhi) ? wv * wh[jj] : 0.0;
       }
     }
     if constexpr (ISO != 0) {
@@ -408,13 +430,13 @@ __global__ __launch_bounds__(SF_NT) void sf_pass2_kernel(SfParams p) {
   SF_STAMP(p, 96, 9)
 }
 
-hipError_t SF_CAT(sf_launch_pass2_kid, SF_KID)(hipStream_t st, int form, int iso, const SfParams& p, int cells) {
+hipError_t SF_LAUNCHER(sf_launch_pass2)(hipStream_t st, int form, int iso, const SfParams& p, int cells) {
   const dim3 grid(p.nchunks, cells), block(SF_NT);
   const int np = p.d <= 12 ? 6 : (p.d <= SF_DK ? 8 : 0);
-#define SF_P2(F_, I_)                                                                                \
-  if (np == 6) hipLaunchKernelGGL((sf_pass2_kernel<SF_KID, F_, I_, 6>), grid, block, 0, st, p);      \
-  else if (np == 8) hipLaunchKernelGGL((sf_pass2_kernel<SF_KID, F_, I_, 8>), grid, block, 0, st, p); \
-  else hipLaunchKernelGGL((sf_pass2_kernel<SF_KID, F_, I_, 0>), grid, block, 0, st, p);
+#define SF_P2(F_, I_)                                                                                         \
+  if (np == 6) hipLaunchKernelGGL((sf_pass2_kernel<SF_KID, F_, I_, 6, SF_HOLD>), grid, block, 0, st, p);      \
+  else if (np == 8) hipLaunchKernelGGL((sf_pass2_kernel<SF_KID, F_, I_, 8, SF_HOLD>), grid, block, 0, st, p); \
+  else hipLaunchKernelGGL((sf_pass2_kernel<SF_KID, F_, I_, 0, SF_HOLD>), grid, block, 0, st, p);
   if (form) {
     SF_P2(1, 0)
   } else if (iso) {

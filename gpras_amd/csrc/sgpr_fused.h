@@ -35,6 +35,14 @@ constexpr int SF_DK = 16;      // dimensions per staging pass
 constexpr int SF_DKP = 18;     // LDS row stride of the staged coordinates (144 bytes: 16-byte aligned rows, lanes 36 dwords apart)
 constexpr int SF_LD = 68;      // LDS row stride of the 64 x 64 operand images (16-byte aligned rows; 4 rows = 32 banks apart)
 constexpr int SF_P2_HEAD = 4 + 64;  // pass-2 partial block: [0] sum w g, [1] sum w v h r2 (isotropic), [2] residual, [3] -, [4 ..) sum w v h ds_k^2, then dZ
+// Held-out rows (event-fold cross-validation: the folds of one training set as cells of one batch).  A cell may carry ONE range [lo, hi)
+// of training rows that its model does not see.  The two streamed passes mask a held column exactly as they mask the padding behind n:
+// its entry of the P tile and its staged y are 0.0, so everything the column would add -- to S, u, W P, the residual, the rank-one term
+// and every dK sum -- is an exact zero; chunks and tiles stay where they are.  The scalar tail takes the cell's own row count and y.y
+// from the table.  The pass kernels and the resident loop's closing launch are compiled twice (HOLD = 0 / 1, the HOLD = 1 kernels in
+// translation units of their own: -DSF_HOLD=1, sf_adam_held.hip, sf_adadelta_held.hip): without a table the code that runs is the code
+// without this feature, register for register (profiles/crossval_resources.txt).
+constexpr int SF_HOLD_W = 4;  // doubles per cell of SfParams::hold
 
 struct SfParams {
   const double* X;     // (n, d) training inputs
@@ -52,6 +60,9 @@ struct SfParams {
   int store_factors;   // 1: L, LB, LB^-1 and c go to the cell block as well (the predict path reads them); the resident optimiser needs none of them
   const int* active;   // device-resident optimiser: per cell 0 = this cell has stopped (every launch returns at once for it); null: all run
   unsigned long long* stamps;  // development aid: null, or SF_STAMP_WORDS words that workgroup (0, 0) fills with s_memtime at its phase boundaries
+  const double* hold;  // held-out rows: per cell SF_HOLD_W doubles [lo, hi, rows kept = n - (hi - lo), y.y of the kept rows] -- the cell's model
+                       // does not see the training rows [lo, hi); null: no cell holds anything (the launchers then pick the HOLD = 0 kernels).
+                       // (last: the members in front of it stay where the HOLD = 0 kernels have always read them)
 };
 // Device-resident Adam (gpr.py:147-173 for every cell of a batch): the optimiser's state lives in device memory, a step is the five
 // launches with sf_adam_kernel as the fifth, the host looks at the stop flags every few steps only.
@@ -95,14 +106,22 @@ hipError_t sf_launch_adam_prep(hipStream_t st, int kid, int form, int iso, const
 // no early stop -- a cell runs until adam.max_iter.
 hipError_t sf_launch_adadelta_prep(hipStream_t st, int kid, int form, int iso, const SfParams& p, int cells, const SfAdam& adam,
                                    double* cpar_dst);
+// (the two launches above hand a batch that holds rows out -- p.hold given -- to these: the HOLD = 1 kernels, sf_adam_held.hip /
+// sf_adadelta_held.hip)
+hipError_t sf_launch_adam_prep_held(hipStream_t st, int kid, int form, int iso, const SfParams& p, int cells, const SfAdam& adam,
+                                    double* cpar_dst);
+hipError_t sf_launch_adadelta_prep_held(hipStream_t st, int kid, int form, int iso, const SfParams& p, int cells, const SfAdam& adam,
+                                        double* cpar_dst);
 hipError_t sf_launch_pass1(hipStream_t st, int kid, int form, const SfParams& p, int cells);
 hipError_t sf_launch_mid(hipStream_t st, const SfParams& p, int cells);
 hipError_t sf_launch_pass2(hipStream_t st, int kid, int form, int iso, const SfParams& p, int cells);
 hipError_t sf_launch_final(hipStream_t st, int iso, const SfParams& p, int cells, double* res_host, double* red_host, double* sums_host,
                            double* dz_host);
-#define SF_DECLARE_PASS(K_)                                                                       \
-  hipError_t sf_launch_pass1_kid##K_(hipStream_t st, int form, const SfParams& p, int cells);     \
-  hipError_t sf_launch_pass2_kid##K_(hipStream_t st, int form, int iso, const SfParams& p, int cells);
+#define SF_DECLARE_PASS(K_)                                                                                \
+  hipError_t sf_launch_pass1_kid##K_(hipStream_t st, int form, const SfParams& p, int cells);              \
+  hipError_t sf_launch_pass2_kid##K_(hipStream_t st, int form, int iso, const SfParams& p, int cells);     \
+  hipError_t sf_launch_pass1_held_kid##K_(hipStream_t st, int form, const SfParams& p, int cells);         \
+  hipError_t sf_launch_pass2_held_kid##K_(hipStream_t st, int form, int iso, const SfParams& p, int cells);
 SF_DECLARE_PASS(0)
 SF_DECLARE_PASS(1)
 SF_DECLARE_PASS(2)

@@ -11,6 +11,26 @@
 
 namespace gprx {
 
+// column j of Kuf is a training row that the cell's model sees: in front of n and, HOLD = 1, outside the cell's held-out range [hlo, hhi)
+// (sgpr_fused.h "Held-out rows"); HOLD = 0 is the test `j < n` that the passes have always made.  HOLD = 1 is ONE more comparison and no
+// short-circuit (0 <= j - hlo < hhi - hlo as unsigned numbers; an empty range has width 0 and holds nothing): the mask stays a select
+// around arithmetic that is evaluated unconditionally, as in the HOLD = 0 kernels -- a branch would move parts of the kernel function
+// into another basic block, and products and sums that the compiler contracts into fma in one block stay apart across two.
+template <int HOLD>
+__device__ __forceinline__ bool sf_kept(int j, int n, int hlo, int hhi) {
+  if constexpr (HOLD != 0) return (j < n) & ((unsigned)(j - hlo) >= (unsigned)(hhi - hlo));
+  else return j < n;
+}
+// element (row, column j) of a Kuf tile is live: the row is an inducing point (row_ok) and the column is kept.  HOLD = 0 is the
+// expression the passes have always written, `row_ok && j < n`.  HOLD = 1 joins the two with `&`: behind `&&` the longer column test
+// became a branch on row_ok, the compiler sank a part of the kernel function (1 + sqrt(3) r of Matern32) into the taken side, and the
+// product and the sum that make ONE fma in the HOLD = 0 kernel were rounded apart -- every entry of that cell's gradient moved by 1e-12.
+template <int HOLD>
+__device__ __forceinline__ bool sf_live(bool row_ok, int j, int n, int hlo, int hhi) {
+  if constexpr (HOLD != 0) return row_ok & sf_kept<HOLD>(j, n, hlo, hhi);
+  else return row_ok && j < n;
+}
+
 // ---- staging --------------------------------------------------------------------------------------------------------
 // 64 points x 16 dimensions [k0, k0 + 16) of `pts` (row-major, d per point), scaled by the lengthscales, into dst[64][SF_DKP].
 // Points >= nvalid and dimensions >= d are staged as zeros (they add exact zeros to every sum).  FORM as kmat.h: 0 = x * (1 / l), the

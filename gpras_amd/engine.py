@@ -81,6 +81,22 @@ class Engine(DeviceHandle):
             raise ValueError(f"Z must have shape {(self.m, self.d)}, got {z.shape}")
         return z, ptr(z)
 
+    def _hold_arrays(self, holds, count: int):
+        """``holds`` -- ``None``, or per cell ``None`` / ``(lo, hi)``: the training rows ``[lo, hi)`` that cell's model does not see -- as
+        the two int64 arrays of the ``gprx_*_held`` calls; ``(None, None)`` when no cell names a range (the call without holds)."""
+        if holds is None:
+            return None, None
+        holds = list(holds)
+        if len(holds) != count:
+            raise ValueError(f"holds must have one entry per cell ({count}), got {len(holds)}")
+        if all(hd is None for hd in holds):
+            return None, None
+        pairs = [(0, 0) if hd is None else tuple(hd) for hd in holds]
+        if any(len(pr) != 2 for pr in pairs):
+            raise ValueError("every hold must be None or a (lo, hi) pair")
+        arr = np.array(pairs, dtype=np.int64).reshape(count, 2)
+        return np.ascontiguousarray(arr[:, 0]), np.ascontiguousarray(arr[:, 1])
+
     @_locked
     def objective(self, unit: int, theta, z, mask: int, want_grad: bool = True):
         """``training_loss`` and (optionally) its gradient ``[d theta | d Z]`` for one output unit."""
@@ -114,10 +130,11 @@ class Engine(DeviceHandle):
         return losses, status == 0
 
     @_locked
-    def objective_batch(self, units, thetas, mask: int, want_grad: bool = True, zs=None):
+    def objective_batch(self, units, thetas, mask: int, want_grad: bool = True, zs=None, holds=None):
         """``training_loss`` (and gradient ``[d theta | d Z]``) of ``len(units)`` cells by batched launches
         (``gprx_objective_batch``): exact models, or sparse models with one ``Z`` per cell in ``zs (cells, M, d)``.
-        Returns ``(losses, grads or None, ok)``; failed cells hold NaN."""
+        Returns ``(losses, grads or None, ok)``; failed cells hold NaN.  ``holds``: per cell ``None`` or the training rows
+        ``(lo, hi)`` its model does not see (``gprx_objective_batch_held``: sparse models with M <= 64, d <= 64)."""
         units = np.ascontiguousarray(units, dtype=np.int32)
         thetas = as_f64(thetas)
         if thetas.shape != (units.size, self.n_theta):
@@ -132,12 +149,18 @@ class Engine(DeviceHandle):
         # pre-filled; the gradient block, 64 KB at 16 cells of M = 50, is filled below for the cells without a finite loss only)
         losses = np.full(units.size, np.nan)
         grads = np.empty((units.size, self.n_theta + self.m * self.d)) if want_grad else None
-        rc = self._lib.gprx_objective_batch(self._h, units.size, ptr(units), ptr(thetas), zp, mask, ptr(losses), ptr(grads) if want_grad else None)
+        hlo, hhi = self._hold_arrays(holds, units.size)
+        if hlo is None:
+            rc = self._lib.gprx_objective_batch(self._h, units.size, ptr(units), ptr(thetas), zp, mask, ptr(losses), ptr(grads) if want_grad else None)
+        else:
+            rc = self._lib.gprx_objective_batch_held(self._h, units.size, ptr(units), ptr(thetas), zp, mask, ptr(losses),
+                                                     ptr(grads) if want_grad else None, ptr(hlo), ptr(hhi))
         if rc == _lib.GPRX_ENOMEM and units.size > 1:
             # the batch does not fit in device memory: two half batches (values do not depend on the batch composition)
             half = units.size // 2
-            lo = self.objective_batch(units[:half], thetas[:half], mask, want_grad, None if zs is None else zs[:half])
-            hi = self.objective_batch(units[half:], thetas[half:], mask, want_grad, None if zs is None else zs[half:])
+            hs = list(holds) if hlo is not None else [None] * units.size
+            lo = self.objective_batch(units[:half], thetas[:half], mask, want_grad, None if zs is None else zs[:half], hs[:half])
+            hi = self.objective_batch(units[half:], thetas[half:], mask, want_grad, None if zs is None else zs[half:], hs[half:])
             return (np.concatenate([lo[0], hi[0]]), None if not want_grad else np.concatenate([lo[1], hi[1]]), np.concatenate([lo[2], hi[2]]))
         if rc not in (_lib.GPRX_OK, _lib.GPRX_ENOTPD):
             check(rc, self._h)
@@ -147,14 +170,14 @@ class Engine(DeviceHandle):
         return losses, grads, ok
 
     @_locked
-    def adam_batch(self, units, thetas, mask: int, max_iter: int, zs=None):
+    def adam_batch(self, units, thetas, mask: int, max_iter: int, zs=None, holds=None):
         """``_optimize_adam`` (gpr.py:147-173) for ``len(units)`` cells in lock step inside the library (``gprx_adam_batch``).  Sparse
         models with d <= 64 run the loop resident on the device -- around the five fused launches for M <= 64, around the general
         launch sequence with its step kernel otherwise (tuning key ``"sgpr_resident"`` = 0: never; ``last_optimizer_route()`` tells
         which loop ran); other models take one batched evaluation per step, the update on the C side.  Returns ``(thetas, zs,
         n_evals, batches)`` -- the optimiser's variables after the run (copies), evaluations per cell, batched evaluations made.
         Raises as ``objective_batch`` does when a cell stops being positive definite (the arrays of that step are attached to the
-        exception as ``.state``)."""
+        exception as ``.state``).  ``holds``: as ``objective_batch`` (``gprx_adam_batch_held``)."""
         units = np.ascontiguousarray(units, dtype=np.int32)
         thetas = np.array(thetas, dtype=np.float64, order="C")
         if thetas.shape != (units.size, self.n_theta):
@@ -167,7 +190,12 @@ class Engine(DeviceHandle):
             zp = ptr(zs)
         n_evals = np.zeros(units.size, dtype=np.int32)
         batches = C.c_int()
-        rc = self._lib.gprx_adam_batch(self._h, units.size, ptr(units), ptr(thetas), zp, int(mask), int(max_iter), ptr(n_evals), C.byref(batches))
+        hlo, hhi = self._hold_arrays(holds, units.size)
+        if hlo is None:
+            rc = self._lib.gprx_adam_batch(self._h, units.size, ptr(units), ptr(thetas), zp, int(mask), int(max_iter), ptr(n_evals), C.byref(batches))
+        else:
+            rc = self._lib.gprx_adam_batch_held(self._h, units.size, ptr(units), ptr(thetas), zp, int(mask), int(max_iter), ptr(n_evals),
+                                                C.byref(batches), ptr(hlo), ptr(hhi))
         if rc != _lib.GPRX_OK:
             try:
                 check(rc, self._h)
@@ -186,11 +214,12 @@ class Engine(DeviceHandle):
         return route.value, waits.value
 
     @_locked
-    def adadelta_batch(self, units, thetas, mask: int, max_iter: int, zs=None):
+    def adadelta_batch(self, units, thetas, mask: int, max_iter: int, zs=None, holds=None):
         """``_optimize_adadelta`` (gpr.py:176-192) for ``len(units)`` cells in lock step inside the library (``gprx_adadelta_batch``),
         the twin of ``adam_batch`` (same routes, ``last_optimizer_route()``): exactly ``max_iter`` steps per cell.  Returns
         ``(thetas, zs, n_evals, batches, losses)`` -- ``losses`` holds each cell's last loss (NaN where no evaluation was made).
-        Raises as ``adam_batch`` does, with ``.state`` ``(thetas, zs, n_evals, batches)``."""
+        Raises as ``adam_batch`` does, with ``.state`` ``(thetas, zs, n_evals, batches)``.  ``holds``: as ``objective_batch``
+        (``gprx_adadelta_batch_held``)."""
         units = np.ascontiguousarray(units, dtype=np.int32)
         thetas = np.array(thetas, dtype=np.float64, order="C")
         if thetas.shape != (units.size, self.n_theta):
@@ -204,9 +233,16 @@ class Engine(DeviceHandle):
         n_evals = np.zeros(units.size, dtype=np.int32)
         losses = np.full(units.size, np.nan)
         batches = C.c_int()
-        rc = self._lib.gprx_adadelta_batch(
-            self._h, units.size, ptr(units), ptr(thetas), zp, int(mask), int(max_iter), ptr(losses), ptr(n_evals), C.byref(batches)
-        )
+        hlo, hhi = self._hold_arrays(holds, units.size)
+        if hlo is None:
+            rc = self._lib.gprx_adadelta_batch(
+                self._h, units.size, ptr(units), ptr(thetas), zp, int(mask), int(max_iter), ptr(losses), ptr(n_evals), C.byref(batches)
+            )
+        else:
+            rc = self._lib.gprx_adadelta_batch_held(
+                self._h, units.size, ptr(units), ptr(thetas), zp, int(mask), int(max_iter), ptr(losses), ptr(n_evals), C.byref(batches),
+                ptr(hlo), ptr(hhi)
+            )
         if rc != _lib.GPRX_OK:
             try:
                 check(rc, self._h)
@@ -245,10 +281,11 @@ class Engine(DeviceHandle):
         return mean, var
 
     @_locked
-    def predict_batch(self, units, thetas, xs, zs=None, include_noise: bool = True):
+    def predict_batch(self, units, thetas, xs, zs=None, include_noise: bool = True, holds=None):
         """The whole predict loop of gpr.py:336-339 in one call (``gprx_predict_batch``): cell ``i`` = (``units[i]``,
         ``thetas[i]``, ``zs[i]`` for sparse models) is factorised -- all cells by one batched launch sequence -- and predicts at
-        the shared ``xs``.  Returns ``(means, variances)``, each ``(cells, N*)``."""
+        the shared ``xs``.  Returns ``(means, variances)``, each ``(cells, N*)``.  ``holds``: as ``objective_batch`` -- every cell is
+        factorised without its held-out rows (``gprx_predict_batch_held``)."""
         units = np.ascontiguousarray(units, dtype=np.int32)
         thetas = as_f64(thetas)
         xs = as_f64(xs)
@@ -264,8 +301,13 @@ class Engine(DeviceHandle):
             zp = ptr(zs)
         means = np.empty((units.size, xs.shape[0]))
         variances = np.empty((units.size, xs.shape[0]))
-        check(self._lib.gprx_predict_batch(self._h, units.size, ptr(units), ptr(thetas), zp, ptr(xs), xs.shape[0], ptr(means), ptr(variances),
-                                           int(include_noise)), self._h)
+        hlo, hhi = self._hold_arrays(holds, units.size)
+        if hlo is None:
+            check(self._lib.gprx_predict_batch(self._h, units.size, ptr(units), ptr(thetas), zp, ptr(xs), xs.shape[0], ptr(means), ptr(variances),
+                                               int(include_noise)), self._h)
+        else:
+            check(self._lib.gprx_predict_batch_held(self._h, units.size, ptr(units), ptr(thetas), zp, ptr(xs), xs.shape[0], ptr(means),
+                                                    ptr(variances), int(include_noise), ptr(hlo), ptr(hhi)), self._h)
         return means, variances
 
     @_locked

@@ -91,6 +91,9 @@ class GPRAS:
         self.x = x.astype(np.float64)
         self.y = y.astype(np.float64)
         opt = OPTIMIZERS[optimization_method]  # KeyError before any device work, as the reference (gpr.py:272)
+        # (what cross_validate refits every fold with)
+        self.fit_args = dict(n_inducing=n_inducing, inducing_initializer=inducing_initializer, optimization_method=optimization_method, ard=ard,
+                             **opt_kwargs)
         self._init_models(self.x, self.y, n_inducing, inducing_initializer, ard, workers=workers)
         self._run_optimizers(self.models, optimization_method, lockstep, opt_kwargs)
 
@@ -299,6 +302,18 @@ class GPRAS:
         from .loeo import leave_event_out
 
         return leave_event_out(self, events, route=route, include_noise=include_noise)
+
+    def cross_validate(self, events: Any, **overrides: Any):
+        """Extension: event-fold cross-validation with the arguments of the last ``fit`` -- for every event the model is REFITTED on all
+        other rows (inducing points, hyperparameters and all) and predicts at the event's rows (``gpras_amd.crossval.cross_validate``;
+        ``overrides`` replace recorded arguments or add ``route=`` / ``include_noise=``).  Returns a ``CrossValidationResult``."""
+        from .crossval import cross_validate
+
+        if self.x is None or not hasattr(self, "fit_args"):
+            raise ValueError("cross_validate needs the data and arguments of a fit(): call fit first")
+        kwargs = dict(self.fit_args, device=self.device, distance_form=self.distance_form)
+        kwargs.update(overrides)
+        return cross_validate(self.kernel_str, self.x, self.y, events, **kwargs)
 
     def to_file(self, json_path: str | Path, model_dir: str | Path | None = None) -> None:
         """Serialize the trained model (gpr.py:344-366).

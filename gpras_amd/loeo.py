@@ -4,7 +4,8 @@ scores one fixed split per pipeline run.
 
 The hyperparameters and the inducing points stay the fitted ones: nothing is re-optimised per fold.  The numbers answer "how well does
 this configuration predict a storm it has not seen, given these hyperparameters"; a full cross-validation, which also refits the
-hyperparameters without the storm, is a different (and 35 times more expensive) quantity.
+hyperparameters without the storm, is a different (and 35 times more expensive) quantity: ``gpras_amd.crossval.cross_validate``
+(``GPRAS.cross_validate``) computes that one, with the folds as cells of one batched fit.
 
 Two routes give the same quantity:
 

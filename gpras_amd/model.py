@@ -43,6 +43,9 @@ class GPModel:
         self.w_noise = float(softplus_inv(noise - NOISE_LOWER))
         self.mask = TRAIN_VARIANCE | TRAIN_LENGTHSCALE | TRAIN_NOISE | (TRAIN_Z if Z is not None else 0)
         self.n_evals = 0
+        # (lo, hi): training rows of the backend that this model does not see -- a fold of gpras_amd.crossval; None: all rows.  The
+        # batched drivers pass it along (optimizers._evaluate_many, _PackedBatch)
+        self.hold = None
 
     def backend_x(self):
         """Training inputs (``model.data[0]`` in the reference, gpr.py:80)."""
@@ -173,15 +176,26 @@ class GPModel:
         return np.concatenate(parts) if parts else np.zeros(0)
 
     # -- loss ------------------------------------------------------------------------------------------
+    def _objective(self, want_grad: bool):
+        """One evaluation of this model: ``backend.objective``, or -- a model that holds rows out -- a one-cell held batch."""
+        if self.hold is None:
+            return self.backend.objective(self.unit, self.theta(), self.Z, self.mask, want_grad=want_grad)
+        losses, grads, ok = self.backend.objective_batch(
+            [self.unit], self.theta()[None, :], self.mask, want_grad=want_grad, zs=None if self.Z is None else self.Z[None], holds=[self.hold]
+        )
+        if not ok.all():
+            raise np.linalg.LinAlgError(f"kernel matrix not positive definite for unit {self.unit}")
+        return float(losses[0]), (None if grads is None else grads[0])
+
     def loss_and_grad(self):
         """``training_loss`` and its gradient w.r.t. ``get_vector()``."""
         self.n_evals += 1
-        loss, grad = self.backend.objective(self.unit, self.theta(), self.Z, self.mask, want_grad=True)
+        loss, grad = self._objective(True)
         return loss, self._pack_grad(grad)
 
     def training_loss(self) -> float:
         self.n_evals += 1
-        loss, _ = self.backend.objective(self.unit, self.theta(), self.Z, self.mask, want_grad=False)
+        loss, _ = self._objective(False)
         return loss
 
     def training_loss_many(self, variances, lengthscales, noises, chunk: int = 64):
@@ -209,6 +223,11 @@ class GPModel:
 
     def predict_y(self, xs):
         """Mean and observation variance (``SGPR.predict_y``, gpr.py:337), each of shape (N*, 1)."""
+        if self.hold is not None:
+            mean, var = self.backend.predict_batch(
+                [self.unit], self.theta()[None, :], xs, zs=None if self.Z is None else self.Z[None], include_noise=True, holds=[self.hold]
+            )
+            return mean[0][:, None], var[0][:, None]
         self.backend.objective(self.unit, self.theta(), self.Z, self.mask, want_grad=False)
         mean, var = self.backend.predict(xs, include_noise=True)
         return mean[:, None], var[:, None]

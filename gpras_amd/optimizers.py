@@ -183,6 +183,13 @@ def _differential_evolution_leg(model, popsize: int, max_iter: int, seed, verbos
 # mode's trajectory -- including its own early stop -- is bit-identical), and every step is one batched evaluation
 # (Engine.objective_batch).  GPRAS.fit uses them in lock-step mode.  The drivers that mix Adam stages with L-BFGS-B or differential
 # evolution batch their Adam stages the same way and run the rest under gpras_amd.lockstep (_run_leg); L-BFGS-B alone runs there whole.
+def _holds_of(models):
+    """The models' held-out row ranges (``GPModel.hold``) as the ``holds`` argument of the engine's batched calls; None when no model
+    holds anything, so that such batches make the calls they always made."""
+    holds = [getattr(m, "hold", None) for m in models]
+    return None if all(h is None for h in holds) else holds
+
+
 def _evaluate_many(models, want_grad: bool = True, stats: dict | None = None):
     if stats is not None:
         stats["batches"] = stats.get("batches", 0) + 1
@@ -190,16 +197,18 @@ def _evaluate_many(models, want_grad: bool = True, stats: dict | None = None):
     mask = models[0].mask
     if any(m.mask != mask for m in models):
         raise ValueError("all models of a batched step must share the trainable mask")
-    if len(models) == 1:
+    holds = _holds_of(models)
+    if len(models) == 1 and holds is None:
         loss, grad = eng.objective(models[0].unit, models[0].theta(), models[0].Z, mask, want_grad=want_grad)
         losses, grads = np.array([loss]), (None if grad is None else grad[None, :])
     else:
         units = [m.unit for m in models]
         thetas = np.stack([m.theta() for m in models])
+        extra = {} if holds is None else {"holds": holds}  # (models that hold rows out: the folds of gpras_amd.crossval)
         if models[0].Z is None:
-            losses, grads, ok = eng.objective_batch(units, thetas, mask, want_grad=want_grad)
+            losses, grads, ok = eng.objective_batch(units, thetas, mask, want_grad=want_grad, **extra)
         else:
-            losses, grads, ok = eng.objective_batch(units, thetas, mask, want_grad=want_grad, zs=np.stack([m.Z for m in models]))
+            losses, grads, ok = eng.objective_batch(units, thetas, mask, want_grad=want_grad, zs=np.stack([m.Z for m in models]), **extra)
         if not ok.all():
             raise np.linalg.LinAlgError(f"kernel matrix not positive definite for unit(s) {[units[i] for i in np.flatnonzero(~ok)]}")
     for m in models:
@@ -224,6 +233,7 @@ class _PackedBatch:
         self.units = np.array([m.unit for m in models], dtype=np.int32)
         self.thetas = np.stack([m.theta() for m in models])
         self.zs = None if models[0].Z is None else np.stack([m.Z for m in models]).astype(np.float64)
+        self.holds = _holds_of(models)
         zsize = 0 if self.zs is None else self.zs[0].size
         theta_cols, x_cols, grad_cols, pos = [], [], [], 0
         self.z_cols = None
@@ -257,7 +267,9 @@ class _PackedBatch:
         if stats is not None:
             stats["batches"] = stats.get("batches", 0) + 1
         units = self.units[rows]
-        losses, grads, ok = self.eng.objective_batch(units, self.thetas[rows], self.mask, want_grad=True, zs=None if self.zs is None else self.zs[rows])
+        extra = {} if self.holds is None else {"holds": [self.holds[i] for i in rows]}
+        losses, grads, ok = self.eng.objective_batch(units, self.thetas[rows], self.mask, want_grad=True, zs=None if self.zs is None else self.zs[rows],
+                                                     **extra)
         if not ok.all():
             raise np.linalg.LinAlgError(f"kernel matrix not positive definite for unit(s) {[int(units[i]) for i in np.flatnonzero(~ok)]}")
         for i in rows:
@@ -332,7 +344,8 @@ def _loop_in_library(batch: "_PackedBatch", x, max_iter: int, stats, library_loo
         batch.write_back(x)
 
     try:
-        out = library_loop(batch.units, batch.thetas, batch.mask, max_iter, zs=batch.zs)
+        extra = {} if batch.holds is None else {"holds": batch.holds}
+        out = library_loop(batch.units, batch.thetas, batch.mask, max_iter, zs=batch.zs, **extra)
     except MemoryError:
         # the batch does not fit in device memory: the Python loop splits its evaluations (Engine.objective_batch); the library
         # ran out on the first evaluation, before any update

@@ -423,6 +423,34 @@ int gprx_adadelta_batch(gprx_handle h, int count, const int* units, double* thet
  * allocation of a handle's buffers on its first call is not counted. */
 int gprx_last_optimizer_route(gprx_handle h, int* route, int* host_waits);
 
+/* ---- Held-out rows: the folds of a cross-validation as cells of ONE batch ---------------------------------------------------------
+ * The four calls below are gprx_objective_batch, gprx_adam_batch, gprx_adadelta_batch and gprx_predict_batch with one more property
+ * per cell: cell i's model does not see the training rows [hold_lo[i], hold_hi[i]) of the handle's data (`count` values each, behind
+ * the arguments of the parent call).  Everything the parent's contract says holds, with "the data" read as "the kept rows": the loss
+ * and the gradient are those of the model on x[keep], y[keep] (the reference's SGPR built on the fold's rows, as
+ * production/analysis/cross_validation.py refits it), the optimiser loops run on that loss, and gprx_predict_batch_held factorises
+ * every cell without its held rows before it predicts at xs (host arrays, results (count, ns)).
+ *   hold_lo[i] == hold_hi[i]: the cell holds nothing; its results have the bits of the parent call.  A call in which no cell holds a
+ *     row runs the parent's launches.
+ *   A cell's values do not depend on what the other cells hold, on its position in the batch or on the batch's size, bit for bit; a
+ *     cell that holds the suffix [k, n) out has the bits of the same cell on a handle created with the first k rows: a held column
+ *     contributes exact zeros to every sum, chunks of 256 columns are added in chunk order, and the row count and y.y of the scalar
+ *     tail are formed over the kept rows in row order, as gprx_set_data forms them.
+ *   They serve sparse handles on the five fused launches: m <= 64, d <= 64, "sgpr_fused" = 1.  The resident loop carries the ranges
+ *     through every step (each group of cells of a large batch its own part); with "sgpr_resident" = 0 or GPRX_ADAM_HOST=1 the
+ *     host-stepped loop hands them to the held objective; both give the same variables bit for bit.  gprx_last_optimizer_route
+ *     reports as for the parents.
+ *   GPRX_EINVAL, before any device work and with the reason in gprx_last_error: an exact handle, m > 64, d > 64, "sgpr_fused" = 0,
+ *     a null range array, hold_lo[i] > hold_hi[i], a range outside [0, n], a range that keeps no row. */
+int gprx_objective_batch_held(gprx_handle h, int count, const int* units, const double* theta, const double* z, int mask, double* losses,
+                              double* grads, const int64_t* hold_lo, const int64_t* hold_hi);
+int gprx_adam_batch_held(gprx_handle h, int count, const int* units, double* theta, double* z, int mask, int max_iter, int* n_evals, int* batches,
+                         const int64_t* hold_lo, const int64_t* hold_hi);
+int gprx_adadelta_batch_held(gprx_handle h, int count, const int* units, double* theta, double* z, int mask, int max_iter, double* losses,
+                             int* n_evals, int* batches, const int64_t* hold_lo, const int64_t* hold_hi);
+int gprx_predict_batch_held(gprx_handle h, int count, const int* units, const double* thetas, const double* z, const double* xs, int64_t ns,
+                            double* means, double* vars, int include_noise, const int64_t* hold_lo, const int64_t* hold_hi);
+
 /* Leave-one-event-out predictions of fitted sparse models on their own training rows (model selection: the held-out score of every
  * training event of production/analysis/cross_validation.py without one refit per event).  Cell i = (units[i], thetas[i], z block i)
  * is factorised once; for every event e = rows [ev_lo[e], ev_hi[e]) of the handle's x the call returns, at those rows, SGPR predict_y
