@@ -5,7 +5,7 @@ The library is several translation units (one object each, compiled in parallel,
 `gp_resident.h`, `gp_objective.h`, `gp_predict.h`, `gp_loeo.h`, included into that one unit so that its kernels are instantiated once), `abi_eof.hip` (EOF projection, its fit, HmsPreProcessor), `abi_pseudo.hip`, `abi_resample.hip` (LF-to-HF mesh resampling), `abi_align.hip` (per-event temporal clipping), `abi_diag.hip` (sort, scatter summary and detection codes of the diagnostic plots), `abi_events.hip` (storm-event selection),
 `abi_fields.hip` (metrics, k-means, row gather), `abi_comm.hip` (RCCL), `abi_eig.hip` (symmetric eigensolver), all over the host toolkit of `abi_common.h` -- and the fused
 sparse evaluation, whose pass kernels are compiled once per kernel id (`-DSF_KID=k`) and whose resident-loop launch once per optimiser
-(`sf_adam.hip`, `sf_adadelta.hip` over `sf_adam_prep.h`), the leave-one-event-out downdate (`sf_loeo.hip`), beside the step kernel of the resident loop of the general sparse launch
+(`sf_adam.hip`, `sf_adadelta.hip` over `sf_adam_prep.h`), the leave-one-event-out downdate (`sf_loeo.hip`; `sf_loeo_blocked.hip` for 64 < M <= 320, driven by `gp_loeo_blocked.h`), beside the step kernel of the resident loop of the general sparse launch
 sequence (`sgpr_step.hip`).  A unit includes only the kernel headers it
 launches: a kernel with external linkage may live in one unit only.  An object is rebuilt when its source, any header its last
 compile read (hipcc `-MD` dependency file) or the flags changed.
@@ -28,7 +28,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-val
 FLAGS += os.environ.get("GPRX_EXTRA_FLAGS", "").split()
 # (object name, source, extra defines)
 UNITS = (
-    [("gprx", "gprx.hip", []), ("abi_eof", "abi_eof.hip", []), ("sf_cell", "sf_cell.hip", []), ("sf_loeo", "sf_loeo.hip", []), ("sf_adam", "sf_adam.hip", []), ("sf_adadelta", "sf_adadelta.hip", []), ("sgpr_step", "sgpr_step.hip", [])]
+    [("gprx", "gprx.hip", []), ("abi_eof", "abi_eof.hip", []), ("sf_cell", "sf_cell.hip", []), ("sf_loeo", "sf_loeo.hip", []), ("sf_loeo_blocked", "sf_loeo_blocked.hip", []), ("sf_adam", "sf_adam.hip", []), ("sf_adadelta", "sf_adadelta.hip", []), ("sgpr_step", "sgpr_step.hip", [])]
     + [(n, f"{n}.hip", []) for n in ("abi_pseudo", "abi_resample", "abi_align", "abi_diag", "abi_events", "abi_fields", "abi_comm", "abi_eig")]
     + [(f"sf_pass1_k{k}", "sf_pass1.hip", [f"-DSF_KID={k}"]) for k in range(5)]
     + [(f"sf_pass2_k{k}", "sf_pass2.hip", [f"-DSF_KID={k}"]) for k in range(5)]

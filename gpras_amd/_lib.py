@@ -72,6 +72,8 @@ PROTOTYPES = {
     "gprx_predict_batch_held": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _i64, _vp, _vp, C.c_int, _vp, _vp]),
     "gprx_loeo_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "gprx_last_loeo": (C.c_int, [_vp, _ip, _vp]),
+    "gprx_loeo_batch_blocked": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp]),
+    "gprx_last_loeo_blocked": (C.c_int, [_vp, _ip, _ip, _vp]),
     "gprx_comm_runtime_check": (C.c_int, [C.c_int]),
     "gprx_comm_unique_id": (C.c_int, [_vp]),
     "gprx_comm_init": (C.c_int, [C.c_int, C.c_int, C.c_int, _vp, C.POINTER(_vp)]),
@@ -210,7 +212,7 @@ PROTOTYPES = {
 # keys of gprx_set_tuning / gprx_set_handle_tuning (include/gprx.h)
 TUNING_KEYS = (
     "outer_block", "update_tile", "no_lookahead", "split_panel", "dag", "rhs_vector", "cell_kernel", "poison_workspace", "predict_path",
-    "sgpr_fused", "sgpr_resident", "wait_handover_us", "sgpr_groups_from",
+    "sgpr_fused", "sgpr_resident", "wait_handover_us", "sgpr_groups_from", "loeo_blocked_potrf",
 )
 
 _lib = None

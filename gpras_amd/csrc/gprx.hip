@@ -64,6 +64,7 @@ hipStream_t util_stream() {
 #include "gp_objective.h"
 #include "gp_predict.h"
 #include "gp_loeo.h"
+#include "gp_loeo_blocked.h"
 
 namespace {
 
@@ -140,8 +141,10 @@ int gprx_destroy(gprx_handle h) {
   hipSetDevice(h->device);
   if (h->stream) hipStreamSynchronize(h->stream);
   for (Buf* b : {&h->X, &h->Y, &h->invls, &h->alpha, &h->red, &h->Kmat, &h->invD, &h->Xinv, &h->Tmp, &h->partial, &h->xs, &h->Ks, &h->pred,
-                 &h->dstage, &h->arena, &h->cellpar, &h->cellres, &h->garena, &h->gpartial, &h->apart, &h->twork, &h->sarena, &h->hold})
+                 &h->dstage, &h->arena, &h->cellpar, &h->cellres, &h->garena, &h->gpartial, &h->apart, &h->twork, &h->sarena, &h->hold, &h->loeo_ws})
     if (b->p && !b->borrowed) hipFree(b->p);
+  for (auto& ev : h->loeo_ev)
+    if (ev) hipEventDestroy(ev);
   if (h->bpin) hipHostFree(h->bpin);
   if (h->spin) hipHostFree(h->spin);
   if (h->sf_stamps) hipFree(h->sf_stamps);
@@ -396,6 +399,23 @@ int gprx_last_loeo(gprx_handle h, int* ran, double* stage_ms) {
   *ran = h->last_loeo;
   if (stage_ms) std::copy(h->loeo_ms, h->loeo_ms + 4, stage_ms);
   return GPRX_OK;
+}
+
+int gprx_loeo_batch_blocked(gprx_handle h, int count, const int* units, const double* thetas, const double* z, int n_events, const int64_t* ev_lo,
+                            const int64_t* ev_hi, double* means, double* vars, int include_noise, int max_slots, int* status) {
+  return guarded(h, [&]() -> int {
+    return loeo_blocked_batch(h, count, units, thetas, z, n_events, ev_lo, ev_hi, means, vars, include_noise, max_slots, status);
+  });
+}
+
+int gprx_last_loeo_blocked(gprx_handle h, int* ran, int* groups, double* stage_ms) {
+  return guarded(h, [&]() -> int {
+    if (!h || !ran || !groups) return fail(h, GPRX_EINVAL, "null argument");
+    *ran = h->last_loeo_blocked;
+    *groups = h->loeo_blocked_groups;
+    if (stage_ms) std::copy(h->loeo_blocked_ms, h->loeo_blocked_ms + 6, stage_ms);
+    return GPRX_OK;
+  });
 }
 
 int gprx_mem_info(int device, int64_t* free_bytes, int64_t* total_bytes) {
@@ -876,6 +896,8 @@ bool apply_tuning(PotrfTuning& t, int& predict_path, int& fused, int& resident, 
   else if (k == "sgpr_resident" && value >= 0 && value <= 1) resident = value;  // 0: sparse optimiser loops are stepped by the host
   else if (k == "wait_handover_us" && value >= 0) wait_handover_us() = value;  // (process-wide whichever entry point sets it)
   else if (k == "sgpr_groups_from" && value >= 0) sf_groups_from() = value;    // (process-wide; 0: the resident Adam loop never splits a batch into groups)
+  // measurement aid of the blocked leave-one-event-out route (process-wide; -1: the schedule gp_loeo_blocked.h fixes per mp)
+  else if (k == "loeo_blocked_potrf" && value >= -1 && value <= 2) loeo_blocked_potrf_force() = value;
   else return false;
   return true;
 }

@@ -34,4 +34,29 @@ struct LoeoParams {
 // grid (events, cells), 256 threads
 hipError_t sf_launch_loeo(hipStream_t st, const LoeoParams& p, int events, int cells);
 
+// ---- the same downdate for 64 < M <= 320 (sf_loeo_blocked.hip; mp = 64 works too): H is mp x mp and lives in a workspace slot per
+// (cell, event) in device memory; the batched Cholesky and triangular inverse of the library run between the first and the other two of the kernels below.
+// Slot of (cell, event e of the group) = ws + (cell * group_events + e) * slot_stride; inside it, in doubles:
+//   oH   H, then Lh (mp x mp, ld mp; the gram kernel writes the tiles on and below the diagonal, diagonal tiles in full)
+//   oP   P = Lh^-1 (mp x mp, ld mp; only the tiles on and below the diagonal are read, the diagonal tiles through a mask)
+//   oU   u = t2 y[lo:hi] (mp), oCp: c' = P (c - u / s) (mp), oInfo: the info word of the slot's Cholesky (an int)
+// Workgroups share nothing and every sum has one order: the result of a (cell, event) has the same bits whatever else the launch holds.
+struct LoeoBlockedParams {
+  LoeoParams base;      // arena, cell table, outputs and the event table of THIS GROUP (status from the group's first event on)
+  int mp;               // 64 * ceil(M / 64), at most LOEO_BLOCKED_MAX_MP
+  int group_events;
+  double* ws;
+  int64_t slot_stride;
+  int64_t oH, oP, oU, oCp, oInfo;
+};
+constexpr int LOEO_BLOCKED_MAX_MP = 320;
+
+// grid (lower tiles of H, events of the group, cells): H = I - t2 t2^T / s, u = t2 y, info word zeroed
+hipError_t sf_launch_loeo_gram(hipStream_t st, const LoeoBlockedParams& p, int cells);
+// grid (row bands, events of the group, cells): c' = P (c - u / s)
+hipError_t sf_launch_loeo_cprime(hipStream_t st, const LoeoBlockedParams& p, int cells);
+// grid (chunks, events of the group, cells), chunks = ceil(longest event of the group / 64): mean, var += colsum(W^2) (+ s); a slot whose
+// info word is set writes it into status and NaN into its rows.
+hipError_t sf_launch_loeo_apply(hipStream_t st, const LoeoBlockedParams& p, int chunks, int cells);
+
 }  // namespace gprx

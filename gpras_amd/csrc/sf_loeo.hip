@@ -4,23 +4,9 @@
 #include <limits>
 
 #include "sf_loeo.h"
+#include "sf_loeo_dev.h"
 
 namespace gprx {
-
-// the 64 columns [c0, c0 + 64) of the event's t2 (rows = inducing points) into sT; columns beyond the event are staged as zeros
-__device__ __forceinline__ void loeo_stage(const double* __restrict__ T, int64_t ldk, int c0, int nc, double* __restrict__ sT, int tid) {
-  double v[16];
-#pragma unroll
-  for (int e = 0; e < 16; ++e) {
-    const int q = tid + 256 * e, i = q >> 6, j = q & 63;
-    v[e] = T[(int64_t)i * ldk + c0 + min(j, nc - 1)];  // (unconditional loads from clamped columns, masks afterwards)
-  }
-#pragma unroll
-  for (int e = 0; e < 16; ++e) {
-    const int q = tid + 256 * e, i = q >> 6, j = q & 63;
-    sT[i * SM_LD + j] = j < nc ? v[e] : 0.0;
-  }
-}
 
 // MFMA layout as chain_step's: wave w owns row band w (rows 16 w .. 16 w + 15), lane (g = lane >> 4, r = lane & 15) holds C[16 w + g + 4 q][16 kt + r];
 // instruction j of k stage ks takes k = 16 ks + 4 g + j.

@@ -367,6 +367,43 @@ class Engine(DeviceHandle):
         return bool(ran.value), {"factorize_ms": ms[0], "head_ms": ms[1], "downdate_ms": ms[2], "tiles_ms": ms[3]}
 
     @_locked
+    def loeo_batch_blocked(self, units, thetas, zs, ranges, include_noise: bool = True, max_slots: int = 0):
+        """``loeo_batch`` for sparse models with up to 320 inducing points (``gprx_loeo_batch_blocked``): the same quantity, outputs and
+        status, with the downdated factor of every (cell, event) in a slot of a device workspace and the batched Cholesky and
+        triangular inverse of the library over the slots of a group of events.  ``max_slots`` > 0 caps the slots of a group (a group
+        always holds one event at least); 0 takes the default cap of the workspace.  A (cell, event) result has the same bits whatever
+        else the call holds.  Raises ``ValueError`` for models and ranges the route does not take; ``last_loeo`` is not touched."""
+        from .loeo import check_event_ranges
+
+        units = np.ascontiguousarray(units, dtype=np.int32)
+        thetas = as_f64(thetas)
+        if thetas.shape != (units.size, self.n_theta):
+            raise ValueError(f"thetas must be ({units.size}, {self.n_theta})")
+        lo, hi = check_event_ranges(ranges, self.n)
+        if int(max_slots) < 0:
+            raise ValueError("max_slots must be >= 0")
+        zs = as_f64(zs) if self.m != 0 else None
+        if zs is not None and zs.shape != (units.size, self.m, self.d):
+            raise ValueError(f"zs must be ({units.size}, {self.m}, {self.d})")
+        means = np.full((units.size, self.n), np.nan)
+        variances = np.full((units.size, self.n), np.nan)
+        status = np.zeros((units.size, lo.size), dtype=np.int32)
+        check(self._lib.gprx_loeo_batch_blocked(self._h, units.size, ptr(units), ptr(thetas), None if zs is None else ptr(zs), lo.size, ptr(lo),
+                                                ptr(hi), ptr(means), ptr(variances), int(include_noise), int(max_slots), ptr(status)), self._h)
+        return means, variances, status
+
+    @_locked
+    def last_loeo_blocked(self):
+        """``(ran, groups, stage_ms)`` of the last ``loeo_batch_blocked`` call (``gprx_last_loeo_blocked``): whether it ran to the end, in
+        how many groups of events, and the times of the batched factorisation (host clock), of the first tile's predict head, of the
+        first group's gram kernel, Cholesky plus inverse and apply kernels, and of everything up to the copies out (device)."""
+        ran, groups = C.c_int(), C.c_int()
+        ms = (C.c_double * 6)()
+        check(self._lib.gprx_last_loeo_blocked(self._h, C.byref(ran), C.byref(groups), ms), self._h)
+        return bool(ran.value), int(groups.value), {"factorize_ms": ms[0], "head_ms": ms[1], "gram_ms": ms[2], "chol_inverse_ms": ms[3],
+                                                    "apply_ms": ms[4], "total_ms": ms[5]}
+
+    @_locked
     def predict_batch_dev(self, units, thetas, xs_dev, ns: int, means_dev, vars_dev, zs=None, include_noise: bool = True, wait: bool = True):
         """``predict_batch`` with the test points and the ``(cells, N*)`` results in device memory (``gprx_predict_batch_dev``)."""
         units = np.ascontiguousarray(units, dtype=np.int32)

@@ -298,7 +298,8 @@ class GPRAS:
     def leave_event_out(self, events: Any, route: str = "auto", include_noise: bool = True) -> tuple[NDArray[Any], NDArray[Any]]:
         """Extension: leave-one-event-out mean and variance on the training rows, each ``(N, K)`` as ``predict(self.x)`` -- at every
         event's rows the prediction of the model on all other rows, at the fitted hyperparameters and inducing points (not re-optimised
-        per fold).  ``events``: ``(lo, hi)`` row ranges, one label per row, or a pandas index (``gpras_amd.loeo.leave_event_out``)."""
+        per fold).  ``events``: ``(lo, hi)`` row ranges, one label per row, or a pandas index (``gpras_amd.loeo.leave_event_out``).
+        ``route``: ``"auto"``, ``"downdate"`` (M <= 64), ``"refactor"`` or ``"blocked"`` (the downdate for M <= 320, opt-in)."""
         from .loeo import leave_event_out
 
         return leave_event_out(self, events, route=route, include_noise=include_noise)

@@ -7,14 +7,17 @@ this configuration predict a storm it has not seen, given these hyperparameters"
 hyperparameters without the storm, is a different (and 35 times more expensive) quantity: ``gpras_amd.crossval.cross_validate``
 (``GPRAS.cross_validate``) computes that one, with the folds as cells of one batched fit.
 
-Two routes give the same quantity:
+Three routes give the same quantity:
 
 ``"downdate"``  sparse models with M <= 64, d <= 64 and events of at most 4096 rows: one factorisation per mode, then one 64 x 64 Cholesky
                 per (mode, event) on the device (``Engine.loeo_batch``, ``gprx_loeo_batch``).
 ``"refactor"``  the definition on existing calls: per event an ``Engine`` on the remaining rows and ``predict_batch`` at the event's rows.
                 Serves every model (M > 64, d > 64, exact models, longer events).
+``"blocked"``   sparse models with M <= 320, d <= 64 and events of at most 4096 rows: the same downdate with the M x M factor of every
+                (mode, event) in a workspace in device memory -- kernels of its own around the library's batched Cholesky and
+                triangular inverse (``Engine.loeo_batch_blocked``, ``gprx_loeo_batch_blocked``).  Opt-in.
 
-``"auto"`` takes the downdate where it applies.
+``"auto"`` takes the downdate where it applies and the refactor route elsewhere; it never chooses ``"blocked"``.
 """
 
 from __future__ import annotations
@@ -26,7 +29,8 @@ from .diagnostics import check_ranges
 DOWNDATE_MAX_M = 64
 DOWNDATE_MAX_D = 64
 DOWNDATE_MAX_ROWS = 4096  # rows of one event: a tile of the sparse predict
-ROUTES = ("auto", "downdate", "refactor")
+BLOCKED_MAX_M = 320
+ROUTES = ("auto", "downdate", "refactor", "blocked")
 
 
 def check_event_ranges(ranges, rows: int):
@@ -95,6 +99,23 @@ def downdate_applies(gpr, lo, hi) -> str | None:
     return None
 
 
+def blocked_applies(gpr, lo, hi) -> str | None:
+    """None when the blocked downdate takes this model and these events, else the reason it does not."""
+    if not gpr.models:
+        return "the model is not fitted"
+    if any(m.Z is None for m in gpr.models):
+        return "exact model (n_inducing=None)"
+    if max(np.shape(m.Z)[0] for m in gpr.models) > BLOCKED_MAX_M:
+        return f"more than {BLOCKED_MAX_M} inducing points"
+    if gpr.x.shape[1] > DOWNDATE_MAX_D:
+        return f"more than {DOWNDATE_MAX_D} features"
+    if int((hi - lo).max()) > DOWNDATE_MAX_ROWS:
+        return f"an event of more than {DOWNDATE_MAX_ROWS} rows"
+    if not all(hasattr(m.backend, "loeo_batch_blocked") for m in gpr.models):
+        return "the backend has no loeo_batch_blocked"
+    return None
+
+
 def _by_engine(gpr):
     groups: dict[int, list[int]] = {}
     for i, m in enumerate(gpr.models):
@@ -102,7 +123,7 @@ def _by_engine(gpr):
     return groups.values()
 
 
-def _downdate(gpr, lo, hi, include_noise):
+def _downdate(gpr, lo, hi, include_noise, call="loeo_batch"):
     n, k = gpr.x.shape[0], len(gpr.models)
     mean, var = np.full((n, k), np.nan), np.full((n, k), np.nan)
     ranges = list(zip(lo.tolist(), hi.tolist()))
@@ -114,12 +135,17 @@ def _downdate(gpr, lo, hi, include_noise):
             units = [gpr.models[i].unit for i in part]
             thetas = np.stack([gpr.models[i].theta() for i in part])
             zs = np.stack([gpr.models[i].Z for i in part])
-            mu, vv, status = eng.loeo_batch(units, thetas, zs, ranges, include_noise=include_noise)
+            mu, vv, status = getattr(eng, call)(units, thetas, zs, ranges, include_noise=include_noise)
             if status.any():
                 cell, ev = np.argwhere(status)[0]
                 raise np.linalg.LinAlgError(f"mode {part[cell]}, event {ev}: the downdated factor is not positive definite")
             mean[:, part], var[:, part] = mu.T, vv.T
     return mean, var
+
+
+def _blocked(gpr, lo, hi, include_noise):
+    """``_downdate`` through ``Engine.loeo_batch_blocked``: the same chunks of modes, the same error."""
+    return _downdate(gpr, lo, hi, include_noise, call="loeo_batch_blocked")
 
 
 def _refactor(gpr, lo, hi, include_noise):
@@ -153,17 +179,25 @@ def leave_event_out(gpr, events, route: str = "auto", include_noise: bool = True
     """``(mean, var)``, each ``(N, K)`` as ``gpr.predict(gpr.x)`` returns them: at the rows of every event the prediction of the model on
     all other rows, at the fitted hyperparameters and inducing points (NOT re-optimised per fold); NaN at rows of no event.  ``events``:
     a list of ``(lo, hi)`` row ranges, one label per row, or a pandas index whose first level is the event.  Every argument is checked
-    before the first library call; ``gpr.last_loeo_route`` names the route that ran."""
+    before the first library call; ``gpr.last_loeo_route`` names the route that ran.  ``route``: ``"auto"`` (the downdate where it
+    applies, else the refactor route), ``"downdate"``, ``"refactor"`` or ``"blocked"`` (M <= 320, opt-in); a named route that does not
+    apply is a ``ValueError``."""
     if route not in ROUTES:
         raise ValueError(f"route must be one of {ROUTES}, got {route!r}")
     if gpr.x is None or not gpr.models:
         raise ValueError("leave_event_out needs a fitted model")
     lo, hi = resolve_events(events, gpr.x.shape[0])
-    why_not = downdate_applies(gpr, lo, hi)
-    if route == "downdate" and why_not is not None:
-        raise ValueError(f"route='downdate' does not apply: {why_not}")
-    use = "downdate" if (route != "refactor" and why_not is None) else "refactor"
-    out = (_downdate if use == "downdate" else _refactor)(gpr, lo, hi, include_noise)
+    if route == "blocked":
+        why_not = blocked_applies(gpr, lo, hi)
+        if why_not is not None:
+            raise ValueError(f"route='blocked' does not apply: {why_not}")
+        use = "blocked"
+    else:
+        why_not = downdate_applies(gpr, lo, hi)
+        if route == "downdate" and why_not is not None:
+            raise ValueError(f"route='downdate' does not apply: {why_not}")
+        use = "downdate" if (route != "refactor" and why_not is None) else "refactor"
+    out = {"downdate": _downdate, "blocked": _blocked, "refactor": _refactor}[use](gpr, lo, hi, include_noise)
     gpr.last_loeo_route = use
     return out
 

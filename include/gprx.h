@@ -472,6 +472,25 @@ int gprx_loeo_batch(gprx_handle h, int count, const int* units, const double* th
  * the first tile, [2] the downdate kernel of the first tile, [3] everything between the first tile's start and the copies out (device). */
 int gprx_last_loeo(gprx_handle h, int* ran, double* stage_ms);
 
+/* The same leave-one-event-out predictions for sparse models with up to 320 inducing points (mp = 64 ceil(M / 64) <= 320; mp = 64 is
+ * taken too).  H is mp x mp and no longer fits one workgroup: every (cell, event) gets a SLOT of a device workspace, and the downdate
+ * runs per GROUP of consecutive events of a tile whose count x events slots fit the workspace -- a kernel that writes H = I - t2 t2^T / s
+ * tile by tile and u = t2 y, the batched Cholesky and the batched triangular inverse (P = Lh^-1) over all slots of the group under a
+ * schedule fixed by mp alone, c' = P (c - u / s), and a kernel that forms W = P t2 per 64-column chunk of the event with
+ * mean = W^T c' and var += colsum(W^2) (+ s last).  Every sum has one order and workgroups share nothing: a (cell, event) result has
+ * the same bits whatever else is in the batch, the event list, the tile or the group.  Outputs, status and return values as
+ * gprx_loeo_batch.  max_slots > 0: at most so many slots per group (a group always holds at least one event); 0: as many as the
+ * default workspace cap (2 GiB) holds.  GPRX_EINVAL, before any device work: an exact handle, mp > 320, d > 64, the range rules of
+ * gprx_loeo_batch, max_slots < 0.  GPRX_ENOMEM: the workspace does not fit the free device memory.  gprx_last_loeo is not touched. */
+int gprx_loeo_batch_blocked(gprx_handle h, int count, const int* units, const double* thetas, const double* z, int n_events, const int64_t* ev_lo,
+                            const int64_t* ev_hi, double* means, double* vars, int include_noise, int max_slots, int* status);
+
+/* ran: 1 when the handle's last gprx_loeo_batch_blocked ran to the end, 0 when it returned an error (or none was made); groups: how many
+ * groups it ran.  stage_ms (optional, 6 doubles): [0] the batched factorisation (host clock, its wait included), [1] the predict head of
+ * the first tile, then of the first group [2] the kernel that writes H, [3] the Cholesky and the inverse, [4] c' and the apply kernel,
+ * [5] everything between the first tile's start and the copies out (device). */
+int gprx_last_loeo_blocked(gprx_handle h, int* ran, int* groups, double* stage_ms);
+
 /* ---- EOF (PCA) projection either side of the GP path: SURVEY.md section 8(f) row N1 ------------------- */
 /* One projector = the fitted state of a reference PreProcessor (gpras/preprocess.py:868-927): `dry` (n_cells bytes, 1 =
  * always-dry cell, may be NULL = none), `elevations` (n_cells, needed for depth mode and for filling dry cells in wse mode),
@@ -889,7 +908,10 @@ int gprx_gather_rows(int device, const double* field_dev, int64_t rows, int64_t 
  * CUs) as two groups of cells on two streams, one launch apart, so that one group's one-workgroup-per-cell launches overlap the
  * other's streamed passes (default 17; 1: always; 0: never; every cell's values are the same bits either way).
  * "wait_handover_us" (process-wide): microseconds of polling after which a wait hands over to hipStreamSynchronize (default
- * 200 000; tests set 0 to force the hand-over). */
+ * 200 000; tests set 0 to force the hand-over).
+ * "loeo_blocked_potrf" (process-wide, a measurement aid of gprx_loeo_batch_blocked; -1, the default, keeps the schedule fixed per
+ * mp): the schedule of chol(H) over the slots -- 0 launch sequence with the fused panel, 1 with the split panel, 2 one workgroup per
+ * slot (not at mp = 64). */
 int gprx_set_tuning(const char* key, int value);
 int gprx_set_handle_tuning(gprx_handle h, const char* key, int value);
 
