@@ -6,7 +6,7 @@ The library is several translation units (one object each, compiled in parallel,
 `abi_fields.hip` (metrics, k-means, row gather), `abi_comm.hip` (RCCL), `abi_eig.hip` (symmetric eigensolver), all over the host toolkit of `abi_common.h` -- and the fused
 sparse evaluation, whose pass kernels are compiled once per kernel id (`-DSF_KID=k`) and whose resident-loop launch once per optimiser
 (`sf_adam.hip`, `sf_adadelta.hip` over `sf_adam_prep.h`), the leave-one-event-out downdate (`sf_loeo.hip`; `sf_loeo_blocked.hip` for 64 < M <= 320, driven by `gp_loeo_blocked.h`), beside the step kernel of the resident loop of the general sparse launch
-sequence (`sgpr_step.hip`).  A unit includes only the kernel headers it
+sequence (`sgpr_step.hip`; `sgpr_held.hip` holds that sequence's twins for held-out rows).  A unit includes only the kernel headers it
 launches: a kernel with external linkage may live in one unit only.  An object is rebuilt when its source, any header its last
 compile read (hipcc `-MD` dependency file) or the flags changed.
 """
@@ -37,6 +37,8 @@ UNITS = (
     + [(f"sf_pass1_k{k}_held", "sf_pass1.hip", [f"-DSF_KID={k}", "-DSF_HOLD=1"]) for k in range(5)]
     + [(f"sf_pass2_k{k}_held", "sf_pass2.hip", [f"-DSF_KID={k}", "-DSF_HOLD=1"]) for k in range(5)]
     + [("sf_adam_held", "sf_adam_held.hip", []), ("sf_adadelta_held", "sf_adadelta_held.hip", [])]
+    # the twins of the general launch sequence (64 < M, or "sgpr_fused" = 0) that read the hold table: Kuf build, stage-in, step kernel
+    + [("sgpr_held", "sgpr_held.hip", [])]
 )
 SOURCES = sorted({u[1] for u in UNITS})
 

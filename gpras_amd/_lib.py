@@ -213,6 +213,7 @@ PROTOTYPES = {
 TUNING_KEYS = (
     "outer_block", "update_tile", "no_lookahead", "split_panel", "dag", "rhs_vector", "cell_kernel", "poison_workspace", "predict_path",
     "sgpr_fused", "sgpr_resident", "wait_handover_us", "sgpr_groups_from", "loeo_blocked_potrf",
+    "held_general",  # (gprx_set_handle_tuning only)
 )
 
 _lib = None

@@ -11,6 +11,9 @@ Two routes:
                (event, mode); cell (e, k) holds the rows of event e out (``Engine.*_batch(holds=...)``, ``gprx_*_held``).  The resident
                optimiser loops are at their best with many cells, and E K of them share one training set.  Serves sparse models with
                M <= 64 and d <= 64 and the drivers that are batched loops from end to end (``adam``, ``two-stage``, ``adadelta``).
+``"held_general"`` the held route for 64 < M <= 320: the same cells, drivers and predict calls on an engine whose handle has
+               ``"held_general"`` = 1, so that the general launch sequence masks the held rows.  Only on request:
+               ``"auto"`` does not take it.
 ``"engines"``  the definition: per fold ``GPRAS(kernel).fit(x[keep], y[keep], ...)`` then ``.predict(x[a:b])``.  Serves everything.
 
 ``"auto"`` takes ``"held"`` where it applies.  The routes agree at a fold's initial state to rounding (1e-8); after optimiser steps
@@ -27,8 +30,9 @@ import numpy as np
 
 from .loeo import event_scores, resolve_events
 
-ROUTES = ("auto", "held", "engines")
+ROUTES = ("auto", "held", "held_general", "engines")
 HELD_MAX_M = 64
+HELD_GENERAL_MAX_M = 320  # the bound of the blocked leave-one-event-out route
 HELD_MAX_D = 64
 HELD_METHODS = ("adam", "two-stage", "adadelta")  # drivers whose every evaluation goes through the batched loops
 HELD_MAX_CELLS = 128  # cells per batched driver call, as GPRAS._run_optimizers
@@ -77,6 +81,22 @@ def held_applies(n_inducing, d: int, optimization_method: str) -> str | None:
     return None
 
 
+def held_general_applies(n_inducing, d: int, optimization_method: str) -> str | None:
+    """None when ``route="held_general"`` takes this configuration (sparse, 64 < M <= 320, d <= 64, one batched loop), else the reason it
+    does not."""
+    if n_inducing is None:
+        return "exact model (n_inducing=None)"
+    if int(n_inducing) <= HELD_MAX_M:
+        return f"no more than {HELD_MAX_M} inducing points (route='held' serves them)"
+    if int(n_inducing) > HELD_GENERAL_MAX_M:
+        return f"more than {HELD_GENERAL_MAX_M} inducing points"
+    if d > HELD_MAX_D:
+        return f"more than {HELD_MAX_D} features"
+    if optimization_method not in HELD_METHODS:
+        return f"optimization_method {optimization_method!r} is not one batched loop (held routes: {', '.join(HELD_METHODS)})"
+    return None
+
+
 def _checked(kernel, x, y, events, n_inducing, inducing_initializer, optimization_method, route, start):
     """Every argument error, before any library call.  Returns ``(x, y, lo, hi, route that will run)``."""
     from .gpr import _REFERENCE_ONLY, KERNEL_FACTORY
@@ -108,6 +128,11 @@ def _checked(kernel, x, y, events, n_inducing, inducing_initializer, optimizatio
     why_not = held_applies(n_inducing, x.shape[1], optimization_method)
     if route == "held" and why_not is not None:
         raise ValueError(f"route='held' does not apply: {why_not}")
+    if route == "held_general":
+        why_not_general = held_general_applies(n_inducing, x.shape[1], optimization_method)
+        if why_not_general is not None:
+            raise ValueError(f"route='held_general' does not apply: {why_not_general}")
+        return x, y, lo, hi, "held_general"
     return x, y, lo, hi, ("engines" if (route == "engines" or why_not is not None) else "held")
 
 
@@ -131,7 +156,7 @@ def _losses(models):
     return out
 
 
-def _held(helper, x, y, lo, hi, n_inducing, inducing_initializer, optimization_method, ard, include_noise, start, opt_kwargs):
+def _held(helper, x, y, lo, hi, n_inducing, inducing_initializer, optimization_method, ard, include_noise, start, opt_kwargs, general=False):
     from .engine import Engine
     from .model import GPModel
     from .optimizers import BATCHED_OPTIMIZERS
@@ -145,6 +170,8 @@ def _held(helper, x, y, lo, hi, n_inducing, inducing_initializer, optimization_m
         inits.append((helper._create_inducing(x[keep], int(n_inducing), inducing_initializer), np.mean(abs(x[keep]))))
     eng = Engine(helper.kernel_str, x, y, int(n_inducing), ard=bool(ard), device=helper.device, distance_form=helper.distance_form)
     try:
+        if general:
+            eng.set_handle_tuning("held_general", 1)
         models = []
         for e, mode in fold_cells(len(ranges), k):
             mod = GPModel(eng, mode, inits[e][0], 1.0, inits[e][1], 1.0)
@@ -175,7 +202,8 @@ def _held(helper, x, y, lo, hi, n_inducing, inducing_initializer, optimization_m
         eng.close()
     shape = (len(ranges), k)
     timings = {"init_ms": 1e3 * (t1 - t0), "fit_ms": 1e3 * (t2 - t1), "predict_ms": 1e3 * (t3 - t2), "total_ms": 1e3 * (t3 - t0)}
-    return CrossValidationResult(mean, var, ranges, thetas, zs, n_evals.reshape(shape), first.reshape(shape), last.reshape(shape), "held", timings)
+    return CrossValidationResult(mean, var, ranges, thetas, zs, n_evals.reshape(shape), first.reshape(shape), last.reshape(shape),
+                                 "held_general" if general else "held", timings)
 
 
 def _engines(helper, x, y, lo, hi, n_inducing, inducing_initializer, optimization_method, ard, include_noise, start, opt_kwargs):
@@ -231,5 +259,7 @@ def cross_validate(kernel, x, y, events, n_inducing, inducing_initializer="kmean
 
     x, y, lo, hi, use = _checked(kernel, x, y, events, n_inducing, inducing_initializer, optimization_method, route, start)
     helper = GPRAS(kernel, device=device, distance_form=distance_form)
+    if use == "held_general":
+        return _held(helper, x, y, lo, hi, n_inducing, inducing_initializer, optimization_method, ard, include_noise, start, opt_kwargs, general=True)
     run = _held if use == "held" else _engines
     return run(helper, x, y, lo, hi, n_inducing, inducing_initializer, optimization_method, ard, include_noise, start, opt_kwargs)

@@ -33,9 +33,9 @@ struct gprx_ctx {
                           // [74] variance, [75] noise (graph replay reads them through the device block `gparams`)
   double* gparams = nullptr;            // device {variance, noise} for captured kernel-matrix builds
   std::map<int, hipGraphExec_t> graphs;  // unit -> captured single-stream exact factorisation
-  std::map<std::pair<int, int>, hipGraphExec_t> sgraphs;  // (cells, with gradient) -> captured sparse batch evaluation
+  std::map<std::pair<int, int>, hipGraphExec_t> sgraphs;  // (cells, with gradient [+ GRAPH_HELD: with the hold table]) -> captured sparse batch evaluation
   bool sgraph_off = false;                                // a capture failed once: this handle stays on eager launches
-  std::map<std::pair<int, int>, hipGraphExec_t> rgraphs;  // (cells, optimiser) -> captured step of the resident loop of the launch sequence
+  std::map<std::pair<int, int>, hipGraphExec_t> rgraphs;  // (cells, optimiser [+ GRAPH_HELD]) -> captured step of the resident loop of the launch sequence
   int sgpr_resident = 1;                                  // sparse models: the optimiser loops stay on the device ("sgpr_resident" tuning key)
   int last_route = 0, last_host_waits = 0;                // gprx_last_optimizer_route
   int last_loeo = 0;                                      // gprx_last_loeo: the last gprx_loeo_batch ran its downdate kernel
@@ -46,6 +46,7 @@ struct gprx_ctx {
   hipEvent_t loeo_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // created by its first call
   int host_waits = 0;                                     // stream waits of the running optimiser call (wait_stream and the loops' own)
   int sgpr_fused = 1;                                     // M <= 64: the five-launch evaluation of sgpr_fused.h ("sgpr_fused" tuning key)
+  int held_general = 0;                                   // the held forms also serve the general launch sequence ("held_general" handle tuning key)
   Buf adam_dev;                                           // device state of the resident optimiser loops (resident_state)
   double* adam_pin = nullptr;                             // pinned: stop flags of the cells + the error word, read every few steps
   size_t adam_pin_bytes = 0;
@@ -259,6 +260,20 @@ void drop_graph_map(Map& graphs) {
   for (auto& kv : graphs)
     if (kv.second) hipGraphExecDestroy(kv.second);
   graphs.clear();
+}
+// Graphs of the general sparse sequence that read the hold table (h->hold) have keys of their own: the second word of the key carries
+// GRAPH_HELD.  They hold the table's ADDRESS (its contents are read at replay): whoever moves the buffer drops them.
+constexpr int GRAPH_HELD = 2;
+void drop_held_graphs(gprx_handle h) {
+  for (auto* graphs : {&h->sgraphs, &h->rgraphs})
+    for (auto it = graphs->begin(); it != graphs->end();) {
+      if ((it->first.second & GRAPH_HELD) != 0) {
+        if (it->second) hipGraphExecDestroy(it->second);
+        it = graphs->erase(it);
+      } else {
+        ++it;
+      }
+    }
 }
 void drop_graphs(gprx_handle h) {
   drop_graph_map(h->graphs);

@@ -192,8 +192,9 @@ int objective_batch(gprx_handle h, int count, const int* units, const double* th
 
 // gprx_adam_batch and gprx_adadelta_batch: one loop, two updates (kind: SF_OPT_ADAM, SF_OPT_ADADELTA of sgpr_asm.h).  Adadelta has no stop
 // rule, so its batch never shrinks.  last_losses (optional): the loss of each cell's last evaluation.
-// held (gprx_adam_batch_held / gprx_adadelta_batch_held): the ranges are checked first; the resident fused loop carries them in its
-// table, the host-stepped loop hands the running cells' ranges to the held objective.
+// held (gprx_adam_batch_held / gprx_adadelta_batch_held): the ranges are checked first; the resident loops carry them in their table (the
+// one around the general launch sequence re-uploads it whenever it reopens for the cells that still run), the host-stepped loop hands the
+// running cells' ranges to the held objective.
 int optimizer_batch(gprx_handle h, int kind, int count, const int* units, double* theta, double* z, int mask, int max_iter,
                            double* last_losses, int* n_evals, int* batches, bool held, const int64_t* hold_lo, const int64_t* hold_hi) {
 #pragma clang fp contract(off)
@@ -229,7 +230,8 @@ int optimizer_batch(gprx_handle h, int kind, int count, const int* units, double
     if (sgpr_five_launches(h))
       return sgpr_resident_fused(h, kind, count, units, theta, z, mask, max_iter, last_losses, n_evals, batches,
                                  held ? CellHolds{hold_lo, hold_hi} : CellHolds{});
-    return sgpr_resident_general(h, kind, count, units, theta, z, mask, max_iter, last_losses, n_evals, batches);  // (never held: check_holds)
+    return sgpr_resident_general(h, kind, count, units, theta, z, mask, max_iter, last_losses, n_evals, batches,
+                                 held ? CellHolds{hold_lo, hold_hi} : CellHolds{});  // (held here: "held_general" = 1, check_holds)
   }
   std::vector<double> mom((size_t)count * gw, 0.0), vel((size_t)count * gw, 0.0), best(count, std::numeric_limits<double>::infinity());
   std::vector<int> stale(count, 0), active(count);

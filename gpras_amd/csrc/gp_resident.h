@@ -316,8 +316,12 @@ int sgpr_resident_fused(gprx_handle h, int kind, int count, const int* units, do
 // the host reads the stop flags and the error word.  Between two reads a stopped cell is still evaluated but the step kernel leaves it
 // alone; at a read where cells have stopped the residency is closed (state down) and reopened for the cells that still run (state up,
 // stage-in): a cell's bits depend neither on its slot nor on the batch size.  Failure: as sgpr_resident_fused.
+// holds (checked by the caller; "held_general" = 1): every opening of a residency uploads the table rows of the cells that still run, in
+// their new slots; the stage-in, the Kuf build and the step kernel are then their twins of sgpr_held.hip, and the step is captured under a
+// key of its own (GRAPH_HELD).  A residency in which no running cell holds a row takes the launches and graphs without the table -- as
+// the host-stepped loop does, which hands the running cells' ranges to the held objective.
 int sgpr_resident_general(gprx_handle h, int kind, int count, const int* units, double* theta, double* z, int mask, int max_iter, double* losses,
-                          int* n_evals, int* batches) {
+                          int* n_evals, int* batches, const CellHolds& holds = CellHolds{}) {
   const SgprLayout L = sgpr_batch_layout(h);
   int rc;
   if ((rc = ensure_sarena(h, count, L))) return rc;
@@ -348,6 +352,24 @@ int sgpr_resident_general(gprx_handle h, int kind, int count, const int* units, 
     std::vector<double> hd(rs.n_dbl, 0.0), zc((size_t)na * nz);
     std::vector<int> hi(rs.n_int, 0);
     const SgprStage sg = sgpr_stage(h, na, L);
+    // the running cells' ranges and units, in their slots of this residency
+    std::vector<int64_t> a_lo(na, 0), a_hi(na, 0);
+    std::vector<int> a_units(na);
+    std::vector<double> htab;  // (lives until the synchronisation behind the stage-in)
+    for (int j = 0; j < na; ++j) {
+      a_units[j] = units[active[j]];
+      if (holds.lo && holds.hi) {
+        a_lo[j] = holds.lo[active[j]];
+        a_hi[j] = holds.hi[active[j]];
+      }
+    }
+    const CellHolds a_holds{a_lo.data(), a_hi.data()};
+    const bool held = a_holds.any(na);
+    if (held) {
+      hold_table(h, na, a_units.data(), a_holds, htab);
+      if ((rc = hold_upload(h, htab))) return rc;
+    }
+    const double* hold_dev = held ? h->hold.p : nullptr;
     Theta row_theta;
     for (int j = 0; j < na; ++j) {
       const int i = active[j];
@@ -368,15 +390,15 @@ int sgpr_resident_general(gprx_handle h, int kind, int count, const int* units, 
     std::memcpy(&hd[rs.o_yy], h->yy.data(), sizeof(double) * h->n_units);
     HIPCHK(h, hipMemcpyAsync(h->adam_dev.p, hd.data(), sizeof(double) * rs.n_dbl, hipMemcpyHostToDevice, st));
     HIPCHK(h, hipMemcpyAsync(ad.stale, hi.data(), sizeof(int) * rs.n_int, hipMemcpyHostToDevice, st));
-    if ((rc = sgpr_stage_in_enqueue(h, na, L))) return rc;
+    if ((rc = sgpr_stage_in_enqueue(h, na, L, hold_dev))) return rc;
     HIPCHK(h, hipGetLastError());
     ++h->host_waits;
     HIPCHK(h, hipStreamSynchronize(st));  // (the host vectors and the pinned rows are free again)
     const SgprStep sa = sgpr_step_params(h, L, reinterpret_cast<const int*>(rs.win + check_every));
     auto step_enqueue = [&]() -> int {
       int erc;
-      if ((erc = sgpr_body_enqueue(h, na, L, true, ps))) return erc;
-      HIPCHK(h, sgpr_launch_step(st, kind, sa, ad, na));
+      if ((erc = sgpr_body_enqueue(h, na, L, true, ps, hold_dev))) return erc;
+      HIPCHK(h, sgpr_launch_step(st, kind, sa, ad, na, hold_dev));
       return GPRX_OK;
     };
     // ---- windows of check_every steps until a cell stops ----
@@ -393,7 +415,7 @@ int sgpr_resident_general(gprx_handle h, int kind, int count, const int* units, 
       HIPCHK(h, hipMemcpyAsync(rs.win, rs.hwin, sizeof(double) * ((size_t)check_every + 2), hipMemcpyHostToDevice, st));
       for (int i = 0; i < k; ++i) {
         bool replayed = false;
-        if ((rc = sgpr_replay(h, h->rgraphs, {na, kind}, step_enqueue, &replayed))) return rc;
+        if ((rc = sgpr_replay(h, h->rgraphs, {na, kind + (held ? GRAPH_HELD : 0)}, step_enqueue, &replayed))) return rc;
         if (!replayed && (rc = step_enqueue())) return rc;
       }
       done += k;

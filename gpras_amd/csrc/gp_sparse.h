@@ -201,14 +201,17 @@ struct CellHolds {
   CellHolds from(int cell0) const { return lo && hi ? CellHolds{lo + cell0, hi + cell0} : CellHolds{}; }
 };
 
-// The argument check of the held forms, before any device work: the handle is one the five fused launches serve, every range lies in
-// [0, n] with lo <= hi, and every cell keeps a row.
+// The argument check of the held forms, before any device work: the handle is one the five fused launches serve -- or, with the handle
+// tuning key "held_general" = 1, any sparse handle with d <= 64: the general launch sequence then masks the rows as well (sgpr_held.hip) --
+// every range lies in [0, n] with lo <= hi, and every cell keeps a row.
 int check_holds(gprx_handle h, int count, const int64_t* lo, const int64_t* hi) {
+  const bool general = h->held_general != 0;
   if (!lo || !hi) return fail(h, GPRX_EINVAL, "hold_lo / hold_hi is null");
   if (h->m == 0) return fail(h, GPRX_EINVAL, "held-out rows: exact model (the held forms serve sparse models on the five fused launches)");
-  if (h->m > NB) return fail(h, GPRX_EINVAL, "held-out rows: more than 64 inducing points (the held forms serve M <= 64)");
+  if (!general && h->m > NB) return fail(h, GPRX_EINVAL, "held-out rows: more than 64 inducing points (the held forms serve M <= 64)");
   if (h->d > CELL_PAR - CELL_PAR_LS) return fail(h, GPRX_EINVAL, "held-out rows: more than 64 features (the held forms serve d <= 64)");
-  if (!sgpr_five_launches(h)) return fail(h, GPRX_EINVAL, "held-out rows: \"sgpr_fused\" = 0 (the general launch sequence holds no rows out)");
+  if (!general && !sgpr_five_launches(h))
+    return fail(h, GPRX_EINVAL, "held-out rows: \"sgpr_fused\" = 0 (the general launch sequence holds no rows out)");
   char msg[200];
   for (int i = 0; i < count; ++i) {
     if (lo[i] > hi[i]) {
@@ -242,9 +245,14 @@ void hold_table(gprx_handle h, int count, const int* units, const CellHolds& hol
   }
 }
 
-// the table onto the device, in stream order; `tab` must live until the stream has passed the copy
+// the table onto the device, in stream order; `tab` must live until the stream has passed the copy.  A table that outgrows its buffer
+// moves: the captured sequences that read it are dropped first (the stream is idle between calls: every evaluation ends with a wait).
 int hold_upload(gprx_handle h, const std::vector<double>& tab) {
   int rc;
+  if (h->hold.bytes < sizeof(double) * tab.size()) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    drop_held_graphs(h);
+  }
   if ((rc = ensure(h, h->hold, sizeof(double) * tab.size()))) return rc;
   HIPCHK(h, hipMemcpyAsync(h->hold.p, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, h->stream));
   return GPRX_OK;
@@ -308,18 +316,27 @@ int sgpr_fused_enqueue(gprx_handle h, int count, const SgprLayout& L, bool want_
 // hipGraph and replayed (sgpr_objective_batch): ~45 launches whose enqueue cost, not their device time, bounded a step.
 // The sequence in three parts -- stage-in, body, stage-out -- so that the resident optimiser loop (sgpr_resident_general) can run the body
 // alone between two launches of its step kernel; a host-driven evaluation (sgpr_batch_enqueue) is the three in a row.
-int sgpr_stage_in_enqueue(gprx_handle h, int count, const SgprLayout& L) {
+// hold_dev (here and in the body): the batch's hold table on the device when a cell holds rows out -- the stage-in and the Kuf build are
+// then their twins of sgpr_held.hip, which write the held entries of y and the held columns of P as exact zeros; every other launch is
+// the one it always was.  Null: today's launches.
+int sgpr_stage_in_enqueue(gprx_handle h, int count, const SgprLayout& L, const double* hold_dev = nullptr) {
   const int np = (int)h->np, m = (int)h->m, d = h->d;
   const SgprStage sg = sgpr_stage(h, count, L);
   double* A0 = h->sarena.p;
   static_assert(CELL_RES <= 256 && CELL_PAR <= 256, "sgpr_stage_in_kernel moves them with its first workgroup");
+  if (hold_dev != nullptr) {
+    HIPCHK(h, sgpr_launch_stage_in_held(h->stream, (std::max(np, m * d) + 255) / 256, count, (const double*)h->Y.p, np,
+                                        (const double*)(h->spin + sg.par), CELL_PAR, h->cellpar.p, (const double*)(h->spin + sg.z), m * d, A0 + L.oZ,
+                                        A0 + L.oY, L.ss, h->cellres.p, CELL_RES, hold_dev));
+    return GPRX_OK;
+  }
   hipLaunchKernelGGL(sgpr_stage_in_kernel, dim3((std::max(np, m * d) + 255) / 256, count), dim3(256), 0, h->stream, (const double*)h->Y.p, np,
                      (const double*)(h->spin + sg.par), CELL_PAR, h->cellpar.p, (const double*)(h->spin + sg.z), m * d, A0 + L.oZ, A0 + L.oY, L.ss,
                      h->cellres.p, CELL_RES);
   return GPRX_OK;
 }
 
-int sgpr_body_enqueue(gprx_handle h, int count, const SgprLayout& L, bool want_grad, const SgprParSrc& ps) {
+int sgpr_body_enqueue(gprx_handle h, int count, const SgprLayout& L, bool want_grad, const SgprParSrc& ps, const double* hold_dev = nullptr) {
   const int mp = (int)h->mp, np = (int)h->np, m = (int)h->m, n = (int)h->n, d = h->d;
   const int64_t ss = L.ss, mm = (int64_t)mp * mp;
   const size_t pitch = sizeof(double) * (size_t)ss;
@@ -342,7 +359,10 @@ int sgpr_body_enqueue(gprx_handle h, int count, const SgprLayout& L, bool want_g
   kq.a_stride = ss;
   kq.b_stride = ss;
   kq.diag_const = 1;
-  HIPCHK(h, launch_kmat_pair(st, h->kid, with_form(kp, h), with_form(kq, h), count));  // Kuf and Kuu in one launch
+  if (hold_dev != nullptr)
+    HIPCHK(h, launch_kmat_pair_held(st, h->kid, with_form(kp, h), with_form(kq, h), count, hold_dev));
+  else
+    HIPCHK(h, launch_kmat_pair(st, h->kid, with_form(kp, h), with_form(kq, h), count));  // Kuf and Kuu in one launch
   int* info0 = reinterpret_cast<int*>(h->cellres.p + 2);
   HIPCHK(h, potrf_lower(st, A0 + L.oQm, mp, mp, 0, A0 + L.oInvDL, info0, A0 + L.oStage, nullptr, nullptr, count, ss, 2 * CELL_RES, &h->tune));
   const bool one_block = mp == NB;  // M <= 64 (the reference's default is 50): every M x M matrix is one 64 x 64 tile
@@ -471,8 +491,9 @@ int sgpr_stage_out_enqueue(gprx_handle h, int count, const SgprLayout& L, bool w
 int sgpr_batch_enqueue(gprx_handle h, int count, const SgprLayout& L, bool want_grad, const SgprParSrc& ps, const double* hold_dev = nullptr) {
   if (sgpr_five_launches(h)) return sgpr_fused_enqueue(h, count, L, want_grad, hold_dev);
   int rc;
-  if ((rc = sgpr_stage_in_enqueue(h, count, L))) return rc;
-  if ((rc = sgpr_body_enqueue(h, count, L, want_grad, ps))) return rc;
+  if (hold_dev != nullptr && ps.table == nullptr) return fail(h, GPRX_EINVAL, "held-out rows: d > 64");  // (check_holds refuses it first)
+  if ((rc = sgpr_stage_in_enqueue(h, count, L, hold_dev))) return rc;
+  if ((rc = sgpr_body_enqueue(h, count, L, want_grad, ps, hold_dev))) return rc;
   if ((rc = sgpr_stage_out_enqueue(h, count, L, want_grad))) return rc;
   HIPCHK(h, hipGetLastError());
   return GPRX_OK;
@@ -521,7 +542,8 @@ int sgpr_replay(gprx_handle h, std::map<std::pair<int, int>, hipGraphExec_t>& gr
 
 // elbo_out[c] (NaN if a Cholesky failed), g: count x ntheta constrained-parameter derivatives, gz: count x m x d (host);
 // g / gz may be null (loss only).  status[c]: GPRX_OK / GPRX_ENOTPD.  holds: checked by the caller (check_holds); a batch in which no
-// cell holds a row takes the launches without the table.
+// cell holds a row takes the launches without the table -- and, on the general sequence, the graphs without it: a held sequence is
+// captured under a key of its own (GRAPH_HELD), and reads the table's contents, uploaded in front of every call, at replay.
 int sgpr_objective_batch(gprx_handle h, int count, const int* units, const Theta* ts, const double* zs, double* elbo_out, double* g, double* gz,
                          int* status, const CellHolds& holds = CellHolds{}) {
   const SgprLayout L = sgpr_batch_layout(h);
@@ -551,7 +573,8 @@ int sgpr_objective_batch(gprx_handle h, int count, const int* units, const Theta
   // (the five launches of the fused evaluation go out eagerly: replaying them from a graph starts the first kernel later than a direct
   // launch does -- 178.8 against 172.5 us per 16-cell evaluation, MI355X_MICROARCH.md "graph-replay-floor")
   if (!sgpr_five_launches(h) && !direct &&
-      (rc = sgpr_replay(h, h->sgraphs, {count, want_grad ? 1 : 0}, [&] { return sgpr_batch_enqueue(h, count, L, want_grad, ps); }, &replayed)))
+      (rc = sgpr_replay(h, h->sgraphs, {count, (want_grad ? 1 : 0) + (held ? GRAPH_HELD : 0)},
+                        [&] { return sgpr_batch_enqueue(h, count, L, want_grad, ps, hold_dev); }, &replayed)))
     return rc;
   if (!replayed && (rc = sgpr_batch_enqueue(h, count, L, want_grad, ps, hold_dev))) return rc;
   const double* hres = h->spin + sg.res;

@@ -915,7 +915,12 @@ int gprx_set_handle_tuning(gprx_handle h, const char* key, int value) {
   return guarded(h, [&]() -> int {
     if (!h || !key) return fail(h, GPRX_EINVAL, "null argument");
     const int fused_before = h->sgpr_fused;
-    if (!apply_tuning(h->tune, h->predict_path, h->sgpr_fused, h->sgpr_resident, key, value)) return fail(h, GPRX_EINVAL, "unknown tuning key or bad value");
+    if (std::string(key) == "held_general") {  // (a handle key only: gprx.h)
+      if (value < 0 || value > 1) return fail(h, GPRX_EINVAL, "unknown tuning key or bad value");
+      h->held_general = value;
+    } else if (!apply_tuning(h->tune, h->predict_path, h->sgpr_fused, h->sgpr_resident, key, value)) {
+      return fail(h, GPRX_EINVAL, "unknown tuning key or bad value");
+    }
     if (hipSetDevice(h->device) == hipSuccess && hipStreamSynchronize(h->stream) == hipSuccess) drop_graphs(h);  // captured with the old schedule
     if (h->sgpr_fused != fused_before) {  // the cell blocks of the two sparse schedules differ (sgpr_batch_layout): the arena is rebuilt on the next call
       h->sarena_slots = 0;

@@ -50,12 +50,25 @@ struct KmatArgs {
   int tri = 0;                         // mode 1 launched on the T (T + 1) / 2 lower tiles only (launch_kmat sets it): blockIdx.x counts them row by row
 };
 
+// Held-out rows (kmat_pair_held_kernel: the Kuf build of a batch whose cells hold training rows out, gp_sparse.h CellHolds).  `hold` is the
+// batch's table, KM_HOLD_W doubles per cell, [0] = lo, [1] = hi: the columns [lo, hi) of the cell's rectangle are written as 0.0, exactly
+// as the padding columns j >= n2 are.  The element test of the HOLD = 1 build is ONE more comparison than `vi && j < n2`, unsigned
+// (0 <= j - lo < hi - lo; an empty range has width 0 and holds nothing) and joined with `&`: behind `&&` the longer test becomes a branch
+// that moves the block structure, and with it the fma contraction, of the arithmetic around it (sgpr_fused_dev.h found that).  The
+// HOLD = 0 build keeps the text it always had: routed through a shared helper its instructions came out in another operand order.
+constexpr int KM_HOLD_W = 4;
+__device__ __forceinline__ bool km_live_held(bool vi, int j, int n2, int hlo, int hhi) {
+  return vi & (j < n2) & ((unsigned)(j - hlo) >= (unsigned)(hhi - hlo));
+}
+
 // Stage KM_DC scaled coordinates of 64 points: sA[point][KM_DC] (row broadcast reads),
 // sBt[KM_DC][64] (lane-contiguous reads).
 // FORM (compile time: the default difference form keeps the registers and code of the kernel it always was -- as a run-time
 // branch the expanded form's extra accumulators cost the default path 50 %: 2.8 -> 4.2 ms for 128 cells of N = 4096)
-template <int KID, int FORM = 0>
-__device__ __forceinline__ void kmat_body(KmatArgs p, int bx, double (*sA)[KM_DC], double (*sBt)[KM_BT_LD], double* __restrict__ sTab) {
+// HOLD = 1 (mode 0 only, batched: blockIdx.y = cell): the held-out columns of the cell are zeros (above)
+template <int KID, int FORM = 0, int HOLD = 0>
+__device__ __forceinline__ void kmat_body(KmatArgs p, int bx, double (*sA)[KM_DC], double (*sBt)[KM_BT_LD], double* __restrict__ sTab,
+                                          const double* __restrict__ hold = nullptr) {
   int ti, tj;
   if (p.tri) {
     // bx = ti (ti + 1) / 2 + tj, tj <= ti: only the tiles the Cholesky reads are launched (the full T x T grid returned at once in 49 %
@@ -73,6 +86,24 @@ __device__ __forceinline__ void kmat_body(KmatArgs p, int bx, double (*sA)[KM_DC
   const int i0 = ti * KM_T, j0 = tj * KM_T;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int cp = lane & 31, rsub = lane >> 5;
+  int hlo = 0, hhi = 0;
+  if constexpr (HOLD != 0) {
+    hlo = (int)hold[(int64_t)blockIdx.y * KM_HOLD_W];
+    hhi = (int)hold[(int64_t)blockIdx.y * KM_HOLD_W + 1];
+    // all 64 columns held (a fold is one to several whole tiles): the zeros, and nothing is staged
+    if (j0 >= hlo && j0 + KM_T <= hhi) {
+      double* out = p.out + (p.cell_par ? (int64_t)blockIdx.y * p.out_stride : 0);
+      d2 zero;
+      zero.x = zero.y = 0.0;
+#pragma unroll
+      for (int it = 0; it < 8; ++it) {
+        const int i = i0 + wave * 16 + 2 * it + rsub;
+        const int j = j0 + 2 * cp;
+        if (i < p.n1p && j < p.n2p) *reinterpret_cast<d2*>(out + (int64_t)i * p.ld + j) = zero;
+      }
+      return;
+    }
+  }
   double diag_keep = p.diag_add;
   if (p.cell_par) {
     const double* par = p.cell_par + (int64_t)blockIdx.y * CELL_PAR;
@@ -176,7 +207,9 @@ __device__ __forceinline__ void kmat_body(KmatArgs p, int bx, double (*sA)[KM_DC
   }
   // interior tiles (every row and column a real point, no diagonal element): no bounds or diagonal selects -- they were ~10 of the
   // ~61 fp64-rate instructions per element, and all but 2 T - 1 of the T (T + 1) / 2 lower tiles of a T x T matrix are interior
-  if (i0 + KM_T <= p.n1 && j0 + KM_T <= p.n2 && ti != tj) {  // (i == j only happens inside tiles with ti == tj)
+  bool cut = false;  // HOLD = 1: a tile that a (non-empty) hold cuts takes the selects below
+  if constexpr (HOLD != 0) cut = (hhi > hlo) & (j0 < hhi) & (j0 + KM_T > hlo);
+  if (i0 + KM_T <= p.n1 && j0 + KM_T <= p.n2 && ti != tj && !cut) {  // (i == j only happens inside tiles with ti == tj)
 #pragma unroll
     for (int it = 0; it < 8; ++it) {
       const int i = i0 + wave * 16 + 2 * it + rsub;
@@ -205,8 +238,13 @@ __device__ __forceinline__ void kmat_body(KmatArgs p, int bx, double (*sA)[KM_DC
     if (i >= p.n1p || j >= p.n2p) continue;
     d2 v;
     const bool vi = i < p.n1;
-    v.x = (vi && j < p.n2) ? p.variance * corr_g<KID>(acc[it][0], sTab) : 0.0;
-    v.y = (vi && j + 1 < p.n2) ? p.variance * corr_g<KID>(acc[it][1], sTab) : 0.0;
+    if constexpr (HOLD != 0) {
+      v.x = km_live_held(vi, j, p.n2, hlo, hhi) ? p.variance * corr_g<KID>(acc[it][0], sTab) : 0.0;
+      v.y = km_live_held(vi, j + 1, p.n2, hlo, hhi) ? p.variance * corr_g<KID>(acc[it][1], sTab) : 0.0;
+    } else {
+      v.x = (vi && j < p.n2) ? p.variance * corr_g<KID>(acc[it][0], sTab) : 0.0;
+      v.y = (vi && j + 1 < p.n2) ? p.variance * corr_g<KID>(acc[it][1], sTab) : 0.0;
+    }
     if (i == j) v.x += (vi && j < p.n2) ? p.diag_add : p.pad_diag;
     if (i == j + 1) v.y += (vi && j + 1 < p.n2) ? p.diag_add : p.pad_diag;
     *reinterpret_cast<d2*>(p.out + (int64_t)i * p.ld + j) = v;
@@ -233,6 +271,25 @@ __global__ __launch_bounds__(256) void kmat_pair_kernel(KmatArgs p, KmatArgs q, 
     kmat_body<KID, FORM>(q, (int)blockIdx.x - first, sA, sBt, sTab);
 }
 
+// The same launch for a batch whose cells hold rows out: the p rectangle (Kuf) masks each cell's columns [lo, hi) of `hold`, the q
+// matrix (Kuu) never sees the table.  A kernel of its own, in a unit of its own (sgpr_held.hip, which also defines the launcher below):
+// the code objects that calls without holds run hold what they held before.
+template <int KID, int FORM = 0>
+__global__ __launch_bounds__(256) void kmat_pair_held_kernel(KmatArgs p, KmatArgs q, int first, const double* __restrict__ hold) {
+  __shared__ __attribute__((aligned(16))) double sA[KM_T][KM_DC];
+  __shared__ __attribute__((aligned(16))) double sBt[KM_DC][KM_BT_LD];
+  __shared__ __attribute__((aligned(16))) double sTab[64];
+  if ((int)blockIdx.x < first)
+    kmat_body<KID, FORM, 1>(p, (int)blockIdx.x, sA, sBt, sTab, hold);
+  else
+    kmat_body<KID, FORM>(q, (int)blockIdx.x - first, sA, sBt, sTab);
+}
+// p: mode 0, batched through the cell-parameter table; hold: `batch` rows of KM_HOLD_W doubles on the device
+hipError_t launch_kmat_pair_held(hipStream_t st, int kid, KmatArgs p, KmatArgs q, int batch, const double* hold);
+
+// (GPRX_KMAT_NO_LAUNCHERS: a unit that wants the kernel bodies alone -- sgpr_held.hip -- leaves the two inline launchers out, and with them
+// the instantiations of kmat_kernel / kmat_pair_kernel that the device pass would otherwise emit into its code object as well)
+#ifndef GPRX_KMAT_NO_LAUNCHERS
 inline hipError_t launch_kmat(hipStream_t st, int kid, KmatArgs p, int batch = 1) {
   const int tiles_m = (p.n1p + KM_T - 1) / KM_T;
   p.tiles_n = (p.n2p + KM_T - 1) / KM_T;
@@ -285,5 +342,6 @@ inline hipError_t launch_kmat_pair(hipStream_t st, int kid, KmatArgs p, KmatArgs
 #undef GPRX_KMAT_CASE
   return hipGetLastError();
 }
+#endif  // GPRX_KMAT_NO_LAUNCHERS
 
 }  // namespace gprx

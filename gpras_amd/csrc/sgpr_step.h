@@ -25,6 +25,15 @@ struct SgprStep {
 
 // ad.mask, ad.max_iter and ad.alpha_t1 are NOT read (ctl carries them); ad.alpha is the window's table.  opt: SF_OPT_ADAM / SF_OPT_ADADELTA.
 // grid = (cells), 256 threads
-hipError_t sgpr_launch_step(hipStream_t st, int opt, const SgprStep& a, const SfAdam& ad, int cells);
+// hold (held-out rows, sgpr_fused.h: SF_HOLD_W doubles per cell on the device): given, the launch is the twin kernel of sgpr_held.hip, which
+// takes every cell's row count and y.y from its row of the table; null: a.n and the y.y of the cell's unit, the kernel of sgpr_step.hip.
+hipError_t sgpr_launch_step(hipStream_t st, int opt, const SgprStep& a, const SfAdam& ad, int cells, const double* hold = nullptr);
+hipError_t sgpr_launch_step_held(hipStream_t st, int opt, const SgprStep& a, const SfAdam& ad, int cells, const double* hold);
+
+// The stage-in of a batch whose cells hold rows out (sgpr_held.hip): sgpr_stage_in_kernel (sgpr.h) with the staged y of a held row 0.0.
+// Same arguments and grid, and the batch's table.
+hipError_t sgpr_launch_stage_in_held(hipStream_t st, int blocks_x, int cells, const double* Y, int np, const double* par_host, int par_doubles,
+                                     double* cell_par, const double* z_host, int zn, double* z_dst, double* y_dst, int64_t cs, double* cell_res,
+                                     int res_doubles, const double* hold);
 
 }  // namespace gprx

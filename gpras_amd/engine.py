@@ -69,6 +69,14 @@ class Engine(DeviceHandle):
         check(self._lib.gprx_set_distance_form(self._h, _lib.DISTANCE_FORMS[form]), self._h)
         self.distance_form = form
 
+    @_locked
+    def set_handle_tuning(self, key: str, value: int) -> None:
+        """One of ``_lib.TUNING_KEYS`` for this engine's handle alone (``gprx_set_handle_tuning``): ``"held_general"`` = 1 lets the
+        ``holds`` of the batched calls reach sparse models on the general launch sequence (M > 64, or ``"sgpr_fused"`` = 0)."""
+        if key not in _lib.TUNING_KEYS:
+            raise ValueError(f"unknown tuning key {key!r}")
+        check(self._lib.gprx_set_handle_tuning(self._h, key.encode(), int(value)), self._h)
+
     def _create(self):
         check(self._lib.gprx_create(self.device, self.n, self.d, self.m, self._kernel_id, int(self.ard), C.byref(self._h)))
 
@@ -134,7 +142,8 @@ class Engine(DeviceHandle):
         """``training_loss`` (and gradient ``[d theta | d Z]``) of ``len(units)`` cells by batched launches
         (``gprx_objective_batch``): exact models, or sparse models with one ``Z`` per cell in ``zs (cells, M, d)``.
         Returns ``(losses, grads or None, ok)``; failed cells hold NaN.  ``holds``: per cell ``None`` or the training rows
-        ``(lo, hi)`` its model does not see (``gprx_objective_batch_held``: sparse models with M <= 64, d <= 64)."""
+        ``(lo, hi)`` its model does not see (``gprx_objective_batch_held``: sparse models with M <= 64, d <= 64; with
+        ``set_handle_tuning("held_general", 1)`` every sparse model with d <= 64)."""
         units = np.ascontiguousarray(units, dtype=np.int32)
         thetas = as_f64(thetas)
         if thetas.shape != (units.size, self.n_theta):

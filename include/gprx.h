@@ -440,8 +440,14 @@ int gprx_last_optimizer_route(gprx_handle h, int* route, int* host_waits);
  *     through every step (each group of cells of a large batch its own part); with "sgpr_resident" = 0 or GPRX_ADAM_HOST=1 the
  *     host-stepped loop hands them to the held objective; both give the same variables bit for bit.  gprx_last_optimizer_route
  *     reports as for the parents.
- *   GPRX_EINVAL, before any device work and with the reason in gprx_last_error: an exact handle, m > 64, d > 64, "sgpr_fused" = 0,
- *     a null range array, hold_lo[i] > hold_hi[i], a range outside [0, n], a range that keeps no row. */
+ *   With the handle tuning key "held_general" = 1 they also serve sparse handles with d <= 64 on the general launch sequence (m > 64,
+ *     or "sgpr_fused" = 0): the held columns of Kuf and the held entries of the staged y are exact zeros, so every later launch adds
+ *     exact zeros for them.  Everything above holds there EXCEPT the suffix property: the trace partials are summed over
+ *     tiles_m x tiles_n partials and the GEMM route changes at np = 1024, so the bits depend on the handle's n.  Calls in which no
+ *     cell holds a row, and every call without "_held", run the launches and graphs they always ran.
+ *   GPRX_EINVAL, before any device work and with the reason in gprx_last_error: an exact handle, m > 64, d > 64, "sgpr_fused" = 0
+ *     (the last two: unless "held_general" = 1), a null range array, hold_lo[i] > hold_hi[i], a range outside [0, n], a range that
+ *     keeps no row. */
 int gprx_objective_batch_held(gprx_handle h, int count, const int* units, const double* theta, const double* z, int mask, double* losses,
                               double* grads, const int64_t* hold_lo, const int64_t* hold_hi);
 int gprx_adam_batch_held(gprx_handle h, int count, const int* units, double* theta, double* z, int mask, int max_iter, int* n_evals, int* batches,
@@ -903,6 +909,9 @@ int gprx_gather_rows(int device, const double* field_dev, int64_t rows, int64_t 
  * general launch sequence (gprx_objective_batch); a handle's cell blocks are rebuilt when its value changes.
  * "sgpr_resident": 1 (default) the optimiser loops of sparse models with d <= 64 (gprx_adam_batch, gprx_adadelta_batch) stay on the
  * device, 0: the host-stepped loop for every sparse model -- one process can run both routes (gprx_last_optimizer_route).
+ * "held_general" (gprx_set_handle_tuning only; default 0): 1: the four gprx_*_held calls also serve sparse handles with d <= 64 on the
+ * GENERAL launch sequence -- m > 64, and m <= 64 with "sgpr_fused" = 0 -- whose Kuf build, stage-in and step kernel then read the hold
+ * table (csrc/sgpr_held.hip); 0: they refuse such handles, as described at gprx_objective_batch_held.
  * "sgpr_groups_from" (process-wide): the device-resident Adam loop runs a batch of at least this many cells (stated at N = 4096, i.e.
  * 16 chunks of 256 training points per cell: the criterion is cells x chunks > 16 (value - 1), a pass that needs a second round of the
  * CUs) as two groups of cells on two streams, one launch apart, so that one group's one-workgroup-per-cell launches overlap the
