@@ -113,6 +113,9 @@ PROTOTYPES = {
     "gprx_pcafit_eig": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_i64), _ip]),
     "gprx_pcafit_components_dev": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "gprx_pcafit_eig_ms": (C.c_int, [_vp, _dp]),
+    "gprx_pcafit_create_auto": (C.c_int, [C.c_int, _vp, _i64, _i64, _vp, _vp, C.c_int, C.c_double, _ip, C.POINTER(_vp)]),
+    "gprx_pcafit_cov": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_i64)]),
+    "gprx_pcafit_components_cov": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "gprx_pcafit_destroy": (C.c_int, [_vp]),
     "gprx_eigh_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(_vp)]),
     "gprx_eigh": (C.c_int, [_vp, C.c_int, _vp, _i64, _vp, _vp]),
@@ -214,7 +217,9 @@ TUNING_KEYS = (
     "outer_block", "update_tile", "no_lookahead", "split_panel", "dag", "rhs_vector", "cell_kernel", "poison_workspace", "predict_path",
     "sgpr_fused", "sgpr_resident", "wait_handover_us", "sgpr_groups_from", "loeo_blocked_potrf",
     "held_general",  # (gprx_set_handle_tuning only)
+    "pcafit_rowsplit",  # (gprx_set_tuning only: read when gprx_pcafit_create_auto runs)
 )
+PCAFIT_ROUTES = ("gram", "covariance")  # GPRX_PCAFIT_GRAM, GPRX_PCAFIT_COV
 
 _lib = None
 

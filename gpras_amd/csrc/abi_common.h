@@ -121,6 +121,10 @@ inline int64_t pca_chunk_doubles() {
   return v;
 }
 
+// "pcafit_rowsplit" (gprx_set_tuning; process-wide, read by gprx_pcafit_create_auto): 1 = the covariance route of the EOF fit runs its
+// row-split kernels, 0 = the one-thread-per-cell kernels on the same operation list.  Defined in gprx.hip, beside the other keys.
+int& pcafit_rowsplit_tuning();
+
 // dst (cols, rows) <- src (rows, cols)^T on `st` (pca.h transpose_small_kernel; defined in abi_eof.hip, the unit that holds pca.h)
 void launch_transpose_small(hipStream_t st, const double* src, int64_t rows, int64_t cols, double* dst);
 

@@ -13,6 +13,7 @@
 #include "hms.h"
 #include "pca.h"
 #include "pca_fit.h"
+#include "pca_fit_tall.h"
 #include "sweep.h"
 
 using namespace gprx;
@@ -395,11 +396,14 @@ const char* gprx_pca_last_error(gprx_pca_handle p) { return p ? p->err.c_str() :
 // ---- fitting the EOF preprocessor (PreProcessor.fit, gpras/preprocess.py:947-1007) ---------------------------------------
 struct gprx_pcafit_ctx {
   int device = 0, mode = 0;
+  int route = GPRX_PCAFIT_GRAM;  // GPRX_PCAFIT_COV: the covariance route of gprx_pcafit_create_auto (pca_fit_tall.h)
+  int rowsplit = 1;              // covariance route: the row-split kernels ("pcafit_rowsplit" at the time of the create)
   hipStream_t stream = nullptr;
   int64_t rows = 0, rows_p = 0, cells = 0, n_wet = 0, ldc = 0;  // ldc: leading dimension of the compacted matrices (multiple of 16)
   double *xc1 = nullptr, *xc2 = nullptr, *A = nullptr, *E = nullptr, *Z = nullptr;
-  double *G = nullptr;                                    // the Gram matrix, inside ws
-  double *U = nullptr, *lam = nullptr, *eig_ws = nullptr;  // device eigensolver: eigenvectors (rows, rows), ascending eigenvalues, workspace
+  double *G = nullptr;                                    // the Gram matrix (covariance route: the covariance), inside ws
+  double *U = nullptr, *lam = nullptr, *eig_ws = nullptr;  // device eigensolver: eigenvectors (gdim, gdim), ascending eigenvalues, workspace
+  int64_t gdim() const { return route == GPRX_PCAFIT_COV ? n_wet : rows; }  // order of G
   std::vector<double> lam_h;                               // the eigenvalues, descending (empty before gprx_pcafit_eig)
   double eig_ms = 0.0;
   Buf ws;  // split-K slabs, then their sum
@@ -411,80 +415,99 @@ struct gprx_pcafit_ctx {
 };
 
 namespace {
-// steps 1-3: upload, column statistics + classes, compaction + both centrings, Gram matrix
-int pcafit_run(gprx_pcafit_handle f, const double* x, const double* elevations, const double* weights, double thr) {
+// Device temporaries of a create: x, the per-cell vectors and the operation list; on the covariance route also the leaves, the
+// leaf scratch and ("pcafit_rowsplit" = 0) the row-major Xc2.  When the create ends the stream is waited for and they are freed; the
+// host copies of what an asynchronous upload reads live as long.
+struct PcafitTemps {
+  double *X = nullptr, *elev = nullptr, *w = nullptr, *mu = nullptr, *m2 = nullptr, *lsum = nullptr, *lmax = nullptr, *lmin = nullptr, *xc2 = nullptr;
+  unsigned char *cls = nullptr, *lnan = nullptr;
+  int64_t* idx = nullptr;
+  int2 *ops = nullptr, *leaves = nullptr;
+  int nops = 0;
+  std::vector<int2> ops_h, leaves_h;
+  std::vector<int64_t> idx_h;
+  DevTemps owner;
+  explicit PcafitTemps(hipStream_t st)
+      : owner(st, {(void**)&X, (void**)&elev, (void**)&w, (void**)&mu, (void**)&m2, (void**)&lsum, (void**)&lmax, (void**)&lmin, (void**)&xc2, (void**)&cls,
+                   (void**)&lnan, (void**)&idx, (void**)&ops, (void**)&leaves}) {}
+};
+
+// the operation list T.ops_h goes to the device (a second list replaces the first once the stream has run what read it)
+int pcafit_set_ops(gprx_pcafit_handle f, PcafitTemps& T) {
+  hipStream_t st = f->stream;
+  if (T.ops) {
+    HIPCHK(f, hipStreamSynchronize(st));
+    HIPCHK(f, hipFree(T.ops));
+    T.ops = nullptr;
+  }
+  T.nops = (int)T.ops_h.size();
+  HIPCHK(f, hipMalloc((void**)&T.ops, sizeof(int2) * T.ops_h.size()));
+  HIPCHK(f, hipMemcpyAsync(T.ops, T.ops_h.data(), sizeof(int2) * T.ops_h.size(), hipMemcpyHostToDevice, st));
+  return GPRX_OK;
+}
+
+// x goes up once, with the elevations and the weights
+int pcafit_upload(gprx_pcafit_handle f, PcafitTemps& T, const double* x, const double* elevations, const double* weights) {
   const int64_t rows = f->rows, cells = f->cells;
   const size_t xb = sizeof(double) * (size_t)rows * cells;
   hipStream_t st = f->stream;
-  // device memory of the whole fit, before anything is allocated: x, per-cell vectors, both compacted matrices, Gram slabs
-  {
-    const int64_t ldc_max = round_up(cells, 16);
-    const int64_t nsplit = gram_plan(rows, ldc_max).nsplit;
-    const double need = (double)xb + 8.0 * (4.0 * cells + (double)(rows + f->rows_p) * ldc_max + (double)(nsplit + 1) * rows * rows) + cells;
-    int rc0;
-    if ((rc0 = need_device_bytes(f, need, "the fit"))) return rc0;
-  }
-  double *X = nullptr, *elev = nullptr, *w = nullptr, *mu = nullptr, *m2 = nullptr;
-  unsigned char* cls = nullptr;
-  int64_t* idx = nullptr;
-  int2* ops = nullptr;
-  DevTemps tmp(st, {(void**)&X, (void**)&elev, (void**)&w, (void**)&mu, (void**)&m2, (void**)&cls, (void**)&idx, (void**)&ops});
-  std::vector<int2> ops_h;
-  int depth = 0;
-  pcafit_pairwise_ops(0, (int)rows, 0, ops_h, depth);
-  if (depth > PCAFIT_STACK) return fail(f, GPRX_EINVAL, "too many samples for the pairwise column sums");
-  const int nops = (int)ops_h.size();
-  HIPCHK(f, hipMalloc((void**)&ops, sizeof(int2) * ops_h.size()));
-  HIPCHK(f, hipMemcpyAsync(ops, ops_h.data(), sizeof(int2) * ops_h.size(), hipMemcpyHostToDevice, st));
-  HIPCHK(f, hipMalloc((void**)&X, xb));
-  HIPCHK(f, hipMalloc((void**)&mu, sizeof(double) * cells));
-  HIPCHK(f, hipMalloc((void**)&cls, (size_t)cells));
+  HIPCHK(f, hipMalloc((void**)&T.X, xb));
+  HIPCHK(f, hipMalloc((void**)&T.mu, sizeof(double) * cells));
+  HIPCHK(f, hipMalloc((void**)&T.cls, (size_t)cells));
   if (f->mode != PCAFIT_VELOCITY) {
-    HIPCHK(f, hipMalloc((void**)&elev, sizeof(double) * cells));
-    HIPCHK(f, hipMemcpyAsync(elev, elevations, sizeof(double) * cells, hipMemcpyHostToDevice, st));
+    HIPCHK(f, hipMalloc((void**)&T.elev, sizeof(double) * cells));
+    HIPCHK(f, hipMemcpyAsync(T.elev, elevations, sizeof(double) * cells, hipMemcpyHostToDevice, st));
   }
   if (weights) {
-    HIPCHK(f, hipMalloc((void**)&w, sizeof(double) * cells));
-    HIPCHK(f, hipMemcpyAsync(w, weights, sizeof(double) * cells, hipMemcpyHostToDevice, st));
+    HIPCHK(f, hipMalloc((void**)&T.w, sizeof(double) * cells));
+    HIPCHK(f, hipMemcpyAsync(T.w, weights, sizeof(double) * cells, hipMemcpyHostToDevice, st));
   }
-  // 1. x goes up once; one pass gives the classes and the column means
   HIPCHK(f, hipEventRecord(f->ev[0], st));
-  HIPCHK(f, hipMemcpyAsync(X, x, xb, hipMemcpyHostToDevice, st));
+  HIPCHK(f, hipMemcpyAsync(T.X, x, xb, hipMemcpyHostToDevice, st));
   HIPCHK(f, hipEventRecord(f->ev[1], st));
-  hipLaunchKernelGGL(pcafit_colstats_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, (const double*)X, rows, cells,
-                     (const double*)elev, f->mode, thr, (const int2*)ops, nops, cls, mu);
-  HIPCHK(f, hipGetLastError());
-  HIPCHK(f, hipEventRecord(f->ev[2], st));
-  std::vector<double> mu_h((size_t)cells);
+  return GPRX_OK;
+}
+
+// the classes and the column means come down; the wet cells (class != AD) in ascending order: x[:, ~dry_indices]
+int pcafit_wet_cells(gprx_pcafit_handle f, PcafitTemps& T, std::vector<double>& mu_h) {
+  const int64_t cells = f->cells;
+  hipStream_t st = f->stream;
+  mu_h.resize((size_t)cells);
   f->cls.resize((size_t)cells);
-  HIPCHK(f, hipMemcpyAsync(f->cls.data(), cls, (size_t)cells, hipMemcpyDeviceToHost, st));
-  HIPCHK(f, hipMemcpyAsync(mu_h.data(), mu, sizeof(double) * cells, hipMemcpyDeviceToHost, st));
+  HIPCHK(f, hipMemcpyAsync(f->cls.data(), T.cls, (size_t)cells, hipMemcpyDeviceToHost, st));
+  HIPCHK(f, hipMemcpyAsync(mu_h.data(), T.mu, sizeof(double) * cells, hipMemcpyDeviceToHost, st));
   HIPCHK(f, hipStreamSynchronize(st));
-  // wet cells (class != AD) in ascending order: x[:, ~dry_indices]
-  std::vector<int64_t> idx_h;
-  idx_h.reserve((size_t)cells);
+  T.idx_h.clear();
+  T.idx_h.reserve((size_t)cells);
   for (int64_t c = 0; c < cells; ++c)
-    if (f->cls[c] != 1) idx_h.push_back(c);
-  f->n_wet = (int64_t)idx_h.size();
-  if (f->n_wet < rows)
-    return fail(f, GPRX_EINVAL, "the fit needs at least as many wet cells as samples: " + std::to_string((long long)f->n_wet) + " wet cells, " +
-                                     std::to_string((long long)rows) + " samples");
+    if (f->cls[c] != 1) T.idx_h.push_back(c);
+  f->n_wet = (int64_t)T.idx_h.size();
+  return GPRX_OK;
+}
+
+// input_mean over the wet cells and the leading dimension of the compacted matrices, once the route is known
+void pcafit_keep_mean(gprx_pcafit_handle f, const PcafitTemps& T, const std::vector<double>& mu_h) {
   f->mean.resize((size_t)f->n_wet);
-  for (int64_t j = 0; j < f->n_wet; ++j) f->mean[j] = mu_h[idx_h[j]];
+  for (int64_t j = 0; j < f->n_wet; ++j) f->mean[j] = mu_h[T.idx_h[j]];
   f->ldc = round_up(f->n_wet, 16);
-  const int64_t ldc = f->ldc;
+}
+
+// Gram route, steps 2 and 3: compaction + both centrings, Gram matrix
+int pcafit_gram_stage(gprx_pcafit_handle f, PcafitTemps& T) {
+  const int64_t rows = f->rows, cells = f->cells, ldc = f->ldc;
+  hipStream_t st = f->stream;
   // 2. compaction, centring, weighting, then IncrementalPCA's centring; xc2 has rows_p rows (zero beyond `rows`: the K padding
   //    of the components GEMM)
-  HIPCHK(f, hipMalloc((void**)&idx, sizeof(int64_t) * f->n_wet));
-  HIPCHK(f, hipMalloc((void**)&m2, sizeof(double) * ldc));
+  HIPCHK(f, hipMalloc((void**)&T.idx, sizeof(int64_t) * f->n_wet));
+  HIPCHK(f, hipMalloc((void**)&T.m2, sizeof(double) * ldc));
   HIPCHK(f, hipMalloc((void**)&f->xc1, sizeof(double) * rows * ldc));
   HIPCHK(f, hipMalloc((void**)&f->xc2, sizeof(double) * f->rows_p * ldc));
-  HIPCHK(f, hipMemcpyAsync(idx, idx_h.data(), sizeof(int64_t) * f->n_wet, hipMemcpyHostToDevice, st));
+  HIPCHK(f, hipMemcpyAsync(T.idx, T.idx_h.data(), sizeof(int64_t) * f->n_wet, hipMemcpyHostToDevice, st));
   if (f->rows_p > rows) HIPCHK(f, hipMemsetAsync(f->xc2 + rows * ldc, 0, sizeof(double) * (f->rows_p - rows) * ldc, st));
   HIPCHK(f, hipEventRecord(f->ev[3], st));
-  hipLaunchKernelGGL(pcafit_compact_kernel, dim3((unsigned)((ldc + 255) / 256)), dim3(256), 0, st, (const double*)X, rows, cells,
-                     (const int64_t*)idx, f->n_wet, ldc, (const double*)elev, f->mode, (const double*)mu, (const double*)w,
-                     (const int2*)ops, nops, f->xc1, f->xc2, m2);
+  hipLaunchKernelGGL(pcafit_compact_kernel, dim3((unsigned)((ldc + 255) / 256)), dim3(256), 0, st, (const double*)T.X, rows, cells,
+                     (const int64_t*)T.idx, f->n_wet, ldc, (const double*)T.elev, f->mode, (const double*)T.mu, (const double*)T.w,
+                     (const int2*)T.ops, T.nops, f->xc1, f->xc2, T.m2);
   HIPCHK(f, hipGetLastError());
   HIPCHK(f, hipEventRecord(f->ev[4], st));
   // 3. G = Xc2 Xc2^T: lower-triangle tiles, split-K slabs summed in a fixed order
@@ -499,6 +522,148 @@ int pcafit_run(gprx_pcafit_handle f, const double* x, const double* elevations, 
   return GPRX_OK;
 }
 
+// leaf + combine pair over `cols` columns of src (rows, ld): the column sums in the order of T.ops (pca_fit_tall.h)
+int pcafit_rowsplit_sums(gprx_pcafit_handle f, PcafitTemps& T, bool stats, const double* src, int64_t ld, int64_t cols, double thr, unsigned char* cls, double* mean) {
+  const int64_t nleaves = (int64_t)T.leaves_h.size(), ncb = (cols + PCAFIT_LEAF_COLS - 1) / PCAFIT_LEAF_COLS;
+  const int64_t nwg = ncb * ((nleaves + PCAFIT_LEAF_GROUP - 1) / PCAFIT_LEAF_GROUP);
+  if (nwg >= ((int64_t)1 << 31)) return fail(f, GPRX_EINVAL, "x is too large for the grid of the leaf pass");
+  hipLaunchKernelGGL(stats ? pcafit_leaf_kernel<true> : pcafit_leaf_kernel<false>, dim3((unsigned)nwg), dim3(256), 0, f->stream, src, ld, cols,
+                     (const double*)T.elev, f->mode, (const int2*)T.leaves, nleaves, ncb, T.lsum, T.lmax, T.lmin, T.lnan);
+  HIPCHK(f, hipGetLastError());
+  hipLaunchKernelGGL(stats ? pcafit_combine_kernel<true> : pcafit_combine_kernel<false>, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, f->stream,
+                     (const double*)T.lsum, (const double*)T.lmax, (const double*)T.lmin, (const unsigned char*)T.lnan, cols, f->rows, (const int2*)T.ops,
+                     T.nops, f->mode, thr, cls, mean);
+  HIPCHK(f, hipGetLastError());
+  return GPRX_OK;
+}
+
+// Covariance route (pca_fit_tall.h), x on the device already: statistics in numpy's chunked order, compaction, second centring
+// written cell-major, C = Xc2^T Xc2.
+int pcafit_cov_stage(gprx_pcafit_handle f, PcafitTemps& T, double thr) {
+  const int64_t rows = f->rows, rp = f->rows_p, cells = f->cells, cells_p = round_up(cells, 16);
+  hipStream_t st = f->stream;
+  int rc, depth = 0;
+  T.ops_h.clear();
+  pcafit_chunked_ops(rows, T.ops_h, depth);
+  if (depth > PCAFIT_STACK) return fail(f, GPRX_EINVAL, "too many samples for the pairwise column sums");
+  if (T.ops_h.size() >= ((size_t)1 << 31)) return fail(f, GPRX_EINVAL, "too many samples for the operation list");
+  T.leaves_h.clear();
+  for (const int2& op : T.ops_h)
+    if (op.x >= 0) T.leaves_h.push_back(op);
+  const int64_t nleaves = (int64_t)T.leaves_h.size();
+  if (f->rowsplit) {
+    // the leaf scratch serves the statistics (cells columns) and the second centring (ldc <= cells_p columns)
+    if ((rc = need_device_bytes(f, 8.0 * (double)nleaves * (cells_p + 2.0 * cells + 1.0) + (double)nleaves * cells + 8.0 * T.ops_h.size(),
+                                "the leaf sums of the fit")))
+      return rc;
+    HIPCHK(f, hipMalloc((void**)&T.leaves, sizeof(int2) * nleaves));
+    HIPCHK(f, hipMalloc((void**)&T.lsum, sizeof(double) * nleaves * cells_p));
+    HIPCHK(f, hipMalloc((void**)&T.lmax, sizeof(double) * nleaves * cells));
+    HIPCHK(f, hipMalloc((void**)&T.lmin, sizeof(double) * nleaves * cells));
+    HIPCHK(f, hipMalloc((void**)&T.lnan, (size_t)nleaves * cells));
+    HIPCHK(f, hipMemcpyAsync(T.leaves, T.leaves_h.data(), sizeof(int2) * nleaves, hipMemcpyHostToDevice, st));
+  }
+  if ((rc = pcafit_set_ops(f, T))) return rc;
+  // 1. classes and column means
+  HIPCHK(f, hipEventRecord(f->ev[6], st));
+  if (f->rowsplit) {
+    if ((rc = pcafit_rowsplit_sums(f, T, true, T.X, cells, cells, thr, T.cls, T.mu))) return rc;
+  } else {
+    hipLaunchKernelGGL(pcafit_colstats_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, (const double*)T.X, rows, cells,
+                       (const double*)T.elev, f->mode, thr, (const int2*)T.ops, T.nops, T.cls, T.mu);
+    HIPCHK(f, hipGetLastError());
+  }
+  HIPCHK(f, hipEventRecord(f->ev[7], st));
+  std::vector<double> mu_h;
+  if ((rc = pcafit_wet_cells(f, T, mu_h))) return rc;
+  const int64_t n = f->n_wet;
+  if (n < 1) return fail(f, GPRX_EINVAL, "the fit needs at least one wet cell");
+  if (n > 16384)
+    return fail(f, GPRX_EINVAL, "the covariance route needs n_wet <= 16384 (eigendecomposition of n_wet x n_wet): " + std::to_string((long long)n) + " wet cells, " +
+                                    std::to_string((long long)rows) + " samples");
+  f->route = GPRX_PCAFIT_COV;
+  pcafit_keep_mean(f, T, mu_h);
+  const int64_t ldc = f->ldc, r2 = ldc;  // rows of Xc2^T: n_wet padded to 16
+  const SplitK sk = gram_plan(n, rp);
+  if (rp + sk.kchunk >= ((int64_t)1 << 31)) return fail(f, GPRX_EINVAL, "too many samples for the covariance product");
+  if ((rc = need_device_bytes(f, 8.0 * ((double)rows * ldc * (f->rowsplit ? 1.0 : 2.0) + (double)r2 * rp + (double)(sk.nsplit + 1) * n * n + 3.0 * ldc),
+                              "the covariance route of the fit")))
+    return rc;
+  // 2. compaction, centring, weighting; IncrementalPCA's centring written as Xc2^T (r2, rows_p), zero padded
+  HIPCHK(f, hipMalloc((void**)&T.idx, sizeof(int64_t) * n));
+  HIPCHK(f, hipMalloc((void**)&T.m2, sizeof(double) * ldc));
+  HIPCHK(f, hipMalloc((void**)&f->xc1, sizeof(double) * rows * ldc));
+  HIPCHK(f, hipMalloc((void**)&f->xc2, sizeof(double) * r2 * rp));
+  HIPCHK(f, hipMemcpyAsync(T.idx, T.idx_h.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice, st));
+  const dim3 tgrid((unsigned)((rp + 31) / 32), (unsigned)((r2 + 31) / 32));
+  HIPCHK(f, hipEventRecord(f->ev[3], st));
+  if (f->rowsplit) {
+    hipLaunchKernelGGL(pcafit_compact_rows_kernel, dim3((unsigned)((ldc + 255) / 256), (unsigned)std::min<int64_t>(rows, 8192)), dim3(256), 0, st,
+                       (const double*)T.X, rows, cells, (const int64_t*)T.idx, n, ldc, (const double*)T.elev, f->mode, (const double*)T.mu,
+                       (const double*)T.w, f->xc1);
+    HIPCHK(f, hipGetLastError());
+    if ((rc = pcafit_rowsplit_sums(f, T, false, f->xc1, ldc, ldc, thr, nullptr, T.m2))) return rc;
+    hipLaunchKernelGGL(pcafit_centre_t_kernel, tgrid, dim3(256), 0, st, (const double*)f->xc1, rows, ldc, n, (const double*)T.m2, f->xc2, r2, rp);
+  } else {
+    HIPCHK(f, hipMalloc((void**)&T.xc2, sizeof(double) * rows * ldc));
+    hipLaunchKernelGGL(pcafit_compact_kernel, dim3((unsigned)((ldc + 255) / 256)), dim3(256), 0, st, (const double*)T.X, rows, cells,
+                       (const int64_t*)T.idx, n, ldc, (const double*)T.elev, f->mode, (const double*)T.mu, (const double*)T.w, (const int2*)T.ops,
+                       T.nops, f->xc1, T.xc2, T.m2);
+    HIPCHK(f, hipGetLastError());
+    hipLaunchKernelGGL(pcafit_centre_t_kernel, tgrid, dim3(256), 0, st, (const double*)T.xc2, rows, ldc, n, (const double*)nullptr, f->xc2, r2, rp);
+  }
+  HIPCHK(f, hipGetLastError());
+  HIPCHK(f, hipEventRecord(f->ev[4], st));
+  // 3. C = Xc2^T Xc2 (n_wet, n_wet): the Gram stage on the cell-major matrix, K = rows_p
+  if ((rc = gram_lower(f, st, f->xc2, rp, n, rp, f->ws, &f->G))) return rc;
+  HIPCHK(f, hipEventRecord(f->ev[5], st));
+  HIPCHK(f, hipStreamSynchronize(st));
+  HIPCHK(f, hipFree(f->xc2));  // the components of this route are the eigenvectors themselves: Xc2^T is not read again
+  f->xc2 = nullptr;
+  f->ms[0] = elapsed_ms(f->ev[0], f->ev[1]);
+  f->ms[1] = elapsed_ms(f->ev[6], f->ev[7]);
+  f->ms[2] = elapsed_ms(f->ev[3], f->ev[4]);
+  f->ms[3] = elapsed_ms(f->ev[4], f->ev[5]);
+  return GPRX_OK;
+}
+
+// steps 1-3.  auto_route: fewer wet cells than samples, or a shape the Gram route does not take, goes to the covariance route
+int pcafit_run(gprx_pcafit_handle f, const double* x, const double* elevations, const double* weights, double thr, bool auto_route) {
+  const int64_t rows = f->rows, cells = f->cells;
+  const double xb = 8.0 * (double)rows * cells;
+  hipStream_t st = f->stream;
+  PcafitTemps T(st);
+  int rc;
+  if (!auto_route || (rows <= cells && rows <= 16384)) {
+    // device memory of the whole fit, before anything is allocated: x, per-cell vectors, both compacted matrices, Gram slabs
+    const int64_t ldc_max = round_up(cells, 16);
+    const int64_t nsplit = gram_plan(rows, ldc_max).nsplit;
+    const double need = xb + 8.0 * (4.0 * cells + (double)(rows + f->rows_p) * ldc_max + (double)(nsplit + 1) * rows * rows) + cells;
+    if ((rc = need_device_bytes(f, need, "the fit"))) return rc;
+    int depth = 0;
+    pcafit_pairwise_ops(0, (int)rows, 0, T.ops_h, depth);
+    if (depth > PCAFIT_STACK) return fail(f, GPRX_EINVAL, "too many samples for the pairwise column sums");
+    if ((rc = pcafit_set_ops(f, T)) || (rc = pcafit_upload(f, T, x, elevations, weights))) return rc;
+    // 1. x goes up once; one pass gives the classes and the column means
+    hipLaunchKernelGGL(pcafit_colstats_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, (const double*)T.X, rows, cells,
+                       (const double*)T.elev, f->mode, thr, (const int2*)T.ops, T.nops, T.cls, T.mu);
+    HIPCHK(f, hipGetLastError());
+    HIPCHK(f, hipEventRecord(f->ev[2], st));
+    std::vector<double> mu_h;
+    if ((rc = pcafit_wet_cells(f, T, mu_h))) return rc;
+    if (f->n_wet >= rows) {
+      pcafit_keep_mean(f, T, mu_h);
+      return pcafit_gram_stage(f, T);
+    }
+    if (!auto_route)
+      return fail(f, GPRX_EINVAL, "the fit needs at least as many wet cells as samples: " + std::to_string((long long)f->n_wet) + " wet cells, " +
+                                       std::to_string((long long)rows) + " samples");
+  } else {
+    if ((rc = need_device_bytes(f, xb + 8.0 * 4.0 * cells + cells, "the fit")) || (rc = pcafit_upload(f, T, x, elevations, weights))) return rc;
+  }
+  return pcafit_cov_stage(f, T, thr);
+}
+
 // the blocks of the components step: A (k, rows_p), E (k, ldc), Z (rows, k)
 int pcafit_components_alloc(gprx_pcafit_handle f, int k) {
   if (f->A) HIPCHK(f, hipFree(f->A));
@@ -511,16 +676,22 @@ int pcafit_components_alloc(gprx_pcafit_handle f, int k) {
   return GPRX_OK;
 }
 
-// steps 5 and 6 from A = diag(lambda^-1/2) U_k^T on the device (K padded to rows_p with zeros)
+// steps 5 and 6 from A = diag(lambda^-1/2) U_k^T on the device (K padded to rows_p with zeros); covariance route: from the
+// eigenvectors in the rows of E
 int pcafit_project(gprx_pcafit_handle f, int k, double* eofs, double* z) {
   const int64_t rows = f->rows, rp = f->rows_p, ldc = f->ldc;
   hipStream_t st = f->stream;
   const SplitK sk = splitk_plan((rows + 63) / 64 * ((k + 63) / 64), ldc, rows * k);
   int rc;
   if ((rc = ensure(f, f->ws, sizeof(double) * (size_t)sk.nsplit * rows * k))) return rc;
-  // 5. E = A Xc2, then svd_flip on its rows
+  // 5. E = A Xc2, then svd_flip on its rows (covariance route: E holds the eigenvectors already, only the flip is left)
   HIPCHK(f, hipEventRecord(f->ev[5], st));
-  if ((rc = components_gemm(f, st, k, f->A, rp, f->xc2, ldc, f->n_wet, f->E))) return rc;
+  if (f->route == GPRX_PCAFIT_COV) {
+    hipLaunchKernelGGL(pcafit_sign_flip_kernel, dim3((unsigned)k), dim3(256), 0, st, f->E, ldc, f->n_wet);
+    HIPCHK(f, hipGetLastError());
+  } else if ((rc = components_gemm(f, st, k, f->A, rp, f->xc2, ldc, f->n_wet, f->E))) {
+    return rc;
+  }
   HIPCHK(f, hipEventRecord(f->ev[6], st));
   // 6. Z = Xc1 E^T (split-K NT; the padding columns of both operands are zero)
   HIPCHK(f, launch_gemm_splitk(st, 0, 1, (int)rows, k, (int)ldc, 1.0, f->xc1, ldc, f->E, ldc, 0.0, f->Z, k, f->ws.p, sk.kchunk));
@@ -536,7 +707,7 @@ int pcafit_project(gprx_pcafit_handle f, int k, double* eofs, double* z) {
 
 // step 4 on the device: G = U diag(lambda) U^T by the block Jacobi solver (eig_jacobi.h); G is overwritten
 int pcafit_eig(gprx_pcafit_handle f, int* sweeps) {
-  const int64_t rows = f->rows;
+  const int64_t rows = f->gdim();  // the order of G: n_samples, or n_wet on the covariance route
   hipStream_t st = f->stream;
   const size_t wsb = eig_jacobi_workspace_bytes((int)rows);
   int rc;
@@ -582,27 +753,62 @@ int gprx_pcafit_create(int device, const double* x, int64_t n_samples, int64_t n
     f->rows_p = round_up(n_samples, 16);
     f->cells = n_cells;
     const int rc = open_handle(f, device, f->ev, 8);
-    return rc ? rc : pcafit_run(f, x, elevations, weights, wet_threshold);
+    return rc ? rc : pcafit_run(f, x, elevations, weights, wet_threshold, false);
   });
   if (rc) gprx_pcafit_destroy(f);
   else *out = f;
   return rc;
 }
 
-int gprx_pcafit_gram(gprx_pcafit_handle f, unsigned char* classes, double* input_mean, double* gram, int64_t* n_wet) {
-  if (!f) return fail(f, GPRX_EINVAL, "null handle");
-  if (!classes || !input_mean || !gram || !n_wet) return fail(f, GPRX_EINVAL, "null argument");
+int gprx_pcafit_create_auto(int device, const double* x, int64_t n_samples, int64_t n_cells, const double* elevations, const double* weights,
+                            int mode, double wet_threshold, int* route, gprx_pcafit_handle* out) {
+  if (!out) return fail(nullptr, GPRX_EINVAL, "out is null");
+  *out = nullptr;
+  if (!x || !route) return fail(nullptr, GPRX_EINVAL, "x or route is null");
+  if (mode < PCAFIT_WSE || mode > PCAFIT_VELOCITY) return fail(nullptr, GPRX_EINVAL, "mode must be 0 (wse), 1 (depth) or 2 (velocity)");
+  if (mode != PCAFIT_VELOCITY && !elevations) return fail(nullptr, GPRX_EINVAL, "wse and depth need the cell elevations");
+  if (n_samples < 2 || n_cells < 1 || n_samples >= ((int64_t)1 << 31) - 16) return fail(nullptr, GPRX_EINVAL, "need 2 <= n_samples < 2^31 - 16 and n_cells >= 1");
+  gprx_pcafit_handle f = nullptr;
+  const int rc = guarded(nullptr, [&]() -> int {
+    f = new gprx_pcafit_ctx();
+    f->mode = mode;
+    f->rows = n_samples;
+    f->rows_p = round_up(n_samples, 16);
+    f->cells = n_cells;
+    f->rowsplit = pcafit_rowsplit_tuning();
+    const int rc = open_handle(f, device, f->ev, 8);
+    return rc ? rc : pcafit_run(f, x, elevations, weights, wet_threshold, true);
+  });
+  if (rc) {
+    gprx_pcafit_destroy(f);
+  } else {
+    *route = f->route;
+    *out = f;
+  }
+  return rc;
+}
+
+namespace {
+const char* pcafit_route_name(gprx_pcafit_handle f) { return f->route == GPRX_PCAFIT_COV ? "covariance" : "Gram"; }
+
+int pcafit_wrong_route(gprx_pcafit_handle f, const char* call, const char* instead) {
+  return fail(f, GPRX_ESTATE, std::string(call) + ": this handle took the " + pcafit_route_name(f) + " route; call " + instead);
+}
+
+// classes, input_mean, G (gdim, gdim) and n_wet to the host; G comes down from the device on the first call
+int pcafit_fetch(gprx_pcafit_handle f, unsigned char* classes, double* input_mean, double* g, int64_t* n_wet, const char* what) {
   if (f->gram.empty()) {
-    if (f->U) return fail(f, GPRX_ESTATE, "the device eigensolver has overwritten the Gram matrix of this handle");
-    if (f->A) return fail(f, GPRX_ESTATE, "the components step has reused the block that held the Gram matrix");
+    if (f->U) return fail(f, GPRX_ESTATE, std::string("the device eigensolver has overwritten the ") + what + " matrix of this handle");
+    if (f->A) return fail(f, GPRX_ESTATE, std::string("the components step has reused the block that held the ") + what + " matrix");
     const int rc = guarded(f, [&]() -> int {
       HIPCHK(f, hipSetDevice(f->device));
-      f->gram.resize((size_t)f->rows * f->rows);
-      const hipError_t e = hipMemcpyAsync(f->gram.data(), f->G, sizeof(double) * f->rows * f->rows, hipMemcpyDeviceToHost, f->stream);
+      const size_t n = (size_t)f->gdim();
+      f->gram.resize(n * n);
+      const hipError_t e = hipMemcpyAsync(f->gram.data(), f->G, sizeof(double) * n * n, hipMemcpyDeviceToHost, f->stream);
       const hipError_t e2 = e == hipSuccess ? hipStreamSynchronize(f->stream) : e;
       if (e2 != hipSuccess) {
         f->gram.clear();
-        return fail(f, GPRX_EHIP, std::string("download of the Gram matrix: ") + hipGetErrorString(e2));
+        return fail(f, GPRX_EHIP, std::string("download of the ") + what + " matrix: " + hipGetErrorString(e2));
       }
       return GPRX_OK;
     });
@@ -610,19 +816,53 @@ int gprx_pcafit_gram(gprx_pcafit_handle f, unsigned char* classes, double* input
   }
   std::memcpy(classes, f->cls.data(), f->cls.size());
   std::memcpy(input_mean, f->mean.data(), sizeof(double) * f->mean.size());
-  std::memcpy(gram, f->gram.data(), sizeof(double) * f->gram.size());
+  std::memcpy(g, f->gram.data(), sizeof(double) * f->gram.size());
   *n_wet = f->n_wet;
   return GPRX_OK;
+}
+}  // namespace
+
+int gprx_pcafit_gram(gprx_pcafit_handle f, unsigned char* classes, double* input_mean, double* gram, int64_t* n_wet) {
+  if (!f) return fail(f, GPRX_EINVAL, "null handle");
+  if (!classes || !input_mean || !gram || !n_wet) return fail(f, GPRX_EINVAL, "null argument");
+  if (f->route != GPRX_PCAFIT_GRAM) return pcafit_wrong_route(f, "gprx_pcafit_gram", "gprx_pcafit_cov");
+  return pcafit_fetch(f, classes, input_mean, gram, n_wet, "Gram");
+}
+
+int gprx_pcafit_cov(gprx_pcafit_handle f, unsigned char* classes, double* input_mean, double* cov, int64_t* n_wet) {
+  if (!f) return fail(f, GPRX_EINVAL, "null handle");
+  if (!classes || !input_mean || !cov || !n_wet) return fail(f, GPRX_EINVAL, "null argument");
+  if (f->route != GPRX_PCAFIT_COV) return pcafit_wrong_route(f, "gprx_pcafit_cov", "gprx_pcafit_gram");
+  return pcafit_fetch(f, classes, input_mean, cov, n_wet, "covariance");
 }
 
 int gprx_pcafit_components(gprx_pcafit_handle f, int k, const double* u, const double* lam, double* eofs, double* z) {
   if (!f) return fail(f, GPRX_EINVAL, "null handle");
+  if (f->route != GPRX_PCAFIT_GRAM) return pcafit_wrong_route(f, "gprx_pcafit_components", "gprx_pcafit_components_cov");
   return guarded(f, [&]() -> int {
     int rc;
     if ((rc = check_components(f, k, f->rows, "n_samples", !u || !lam || !eofs || !z, lam)) || k == 0) return rc;
     HIPCHK(f, hipSetDevice(f->device));
     std::vector<double> a;  // read by the upload until pcafit_project has waited for the stream
     if ((rc = pcafit_components_alloc(f, k)) || (rc = upload_scaled_ut(f, f->stream, u, lam, k, f->rows, f->rows_p, a, f->A))) return rc;
+    return pcafit_project(f, k, eofs, z);
+  });
+}
+
+int gprx_pcafit_components_cov(gprx_pcafit_handle f, int k, const double* v, double* eofs, double* z) {
+  if (!f) return fail(f, GPRX_EINVAL, "null handle");
+  if (f->route != GPRX_PCAFIT_COV) return pcafit_wrong_route(f, "gprx_pcafit_components_cov", "gprx_pcafit_components");
+  return guarded(f, [&]() -> int {
+    if (k < 0 || k >= f->rows || k > f->n_wet) return fail(f, GPRX_EINVAL, "need 0 <= k <= min(n_samples - 1, n_wet) (centring removes one direction)");
+    if (k == 0) return GPRX_OK;
+    if (!v || !eofs || !z) return fail(f, GPRX_EINVAL, "null argument");
+    HIPCHK(f, hipSetDevice(f->device));
+    int rc;
+    if ((rc = pcafit_components_alloc(f, k))) return rc;
+    // the eigenvectors are the components: rows of E, padding columns zero (pcafit_project waits for the stream before v may go)
+    HIPCHK(f, hipMemsetAsync(f->E, 0, sizeof(double) * (size_t)k * f->ldc, f->stream));
+    HIPCHK(f, hipMemcpy2DAsync(f->E, sizeof(double) * f->ldc, v, sizeof(double) * f->n_wet, sizeof(double) * f->n_wet, (size_t)k, hipMemcpyHostToDevice,
+                               f->stream));
     return pcafit_project(f, k, eofs, z);
   });
 }
@@ -646,12 +886,20 @@ int gprx_pcafit_components_dev(gprx_pcafit_handle f, int k, double* eofs, double
   if (f->lam_h.empty()) return fail(f, GPRX_ESTATE, "gprx_pcafit_eig has not run on this handle");
   return guarded(f, [&]() -> int {
     int rc;
+    if (f->route == GPRX_PCAFIT_COV && k > f->n_wet) return fail(f, GPRX_EINVAL, "need 0 <= k <= min(n_samples - 1, n_wet) (the covariance has n_wet eigenpairs)");
     if ((rc = check_components(f, k, f->rows, "n_samples", !eofs || !z, f->lam_h.data())) || k == 0) return rc;
     HIPCHK(f, hipSetDevice(f->device));
     if ((rc = pcafit_components_alloc(f, k))) return rc;
-    const int64_t total = (int64_t)k * f->rows_p;
-    hipLaunchKernelGGL(pcafit_scale_u_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, f->stream, (const double*)f->U, (const double*)f->lam,
-                       f->rows, f->rows_p, k, f->A);
+    if (f->route == GPRX_PCAFIT_COV) {
+      // the leading eigenvector columns of U, gathered as the rows of E
+      const int64_t total = (int64_t)k * f->ldc;
+      hipLaunchKernelGGL(pcafit_gather_v_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, f->stream, (const double*)f->U, f->n_wet, k, f->E,
+                         f->ldc);
+    } else {
+      const int64_t total = (int64_t)k * f->rows_p;
+      hipLaunchKernelGGL(pcafit_scale_u_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, f->stream, (const double*)f->U, (const double*)f->lam,
+                         f->rows, f->rows_p, k, f->A);
+    }
     HIPCHK(f, hipGetLastError());
     return pcafit_project(f, k, eofs, z);
   });

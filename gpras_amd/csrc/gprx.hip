@@ -40,6 +40,11 @@ std::string& last_error() {
   return msg;
 }
 
+int& pcafit_rowsplit_tuning() {
+  static int v = 1;  // gprx_set_tuning("pcafit_rowsplit", ...): see abi_common.h
+  return v;
+}
+
 // (see abi_common.h: the one utility stream per device of the whole library)
 hipStream_t util_stream() {
   static std::mutex m;
@@ -898,6 +903,8 @@ bool apply_tuning(PotrfTuning& t, int& predict_path, int& fused, int& resident, 
   else if (k == "sgpr_groups_from" && value >= 0) sf_groups_from() = value;    // (process-wide; 0: the resident Adam loop never splits a batch into groups)
   // measurement aid of the blocked leave-one-event-out route (process-wide; -1: the schedule gp_loeo_blocked.h fixes per mp)
   else if (k == "loeo_blocked_potrf" && value >= -1 && value <= 2) loeo_blocked_potrf_force() = value;
+  // yardstick of the covariance route of the EOF fit (process-wide; read when gprx_pcafit_create_auto runs): 0 = one thread per cell
+  else if (k == "pcafit_rowsplit" && value >= 0 && value <= 1) pcafit_rowsplit_tuning() = value;
   else return false;
   return true;
 }

@@ -6,7 +6,8 @@ format, and ``compute_norths_rule`` (:1323-1353).
 and the Gram matrix of the single-batch ``IncrementalPCA``, then the EOFs and the training projection); the
 eigendecomposition of the small (n_samples x n_samples) Gram matrix runs on the host (``PreProcessor.eigensolver = "host"``, the
 default) or on the device (``"device"``: the Gram matrix is not downloaded, only its eigenvalues are), North's rule on the host
-(DESIGN.md section 3.12).
+(DESIGN.md section 3.12).  ``PreProcessor.sample_route = "auto"`` also fits more samples than wet cells, by the n_wet x n_wet
+covariance (``gprx_pcafit_create_auto`` / ``_cov`` / ``_components_cov``).
 ``EOFProjector`` holds a fitted state and runs the two projections through ``libgprx.so``; ``PreProcessor`` keeps one for
 ``transform`` / ``reverse_transform``.
 Difference from the reference: a ``PreProcessor`` fitted WITHOUT weights keeps ``weights = np.empty(0)``
@@ -146,9 +147,11 @@ def compute_norths_rule(pca: Any) -> int:
     return int(ind)
 
 
-def check_fit_args(x, elevations, weights, spatial_mode_count, hydraulic_parameter):
+def check_fit_args(x, elevations, weights, spatial_mode_count, hydraulic_parameter, allow_tall=False):
     """The domain of the device fit, checked before any device work: float64 (cast here), 2 <= n_samples <= n_cells (the
     fit itself also needs n_samples <= n_wet: one IncrementalPCA batch), k <= n_samples - 1 (the rank left after centring).
+    ``allow_tall`` (``sample_route = "auto"``) lifts only the n_samples <= n_cells check; the mode count is then bounded by
+    min(n_samples - 1, n_cells), and by min(n_samples - 1, n_wet) once the fit knows n_wet.
     Returns the cast (x, elevations, weights)."""
     if hydraulic_parameter not in MODES:
         raise ValueError(f"unknown hydraulic_parameter {hydraulic_parameter!r}")
@@ -156,7 +159,10 @@ def check_fit_args(x, elevations, weights, spatial_mode_count, hydraulic_paramet
     if x.ndim != 2:
         raise ValueError("x must be (samples, cells)")
     n_s, n_cells = x.shape
-    if n_s < 2 or n_s > n_cells:
+    if allow_tall:
+        if n_s < 2 or n_cells < 1 or n_s >= 2**31 - 16:
+            raise ValueError(f"the fit needs 2 <= samples < 2^31 - 16 and at least one cell; x is {x.shape}")
+    elif n_s < 2 or n_s > n_cells:
         raise ValueError(f"the fit needs 2 <= samples <= cells (one IncrementalPCA batch); x is {x.shape}")
     if elevations is None or np.size(elevations) == 0:
         if hydraulic_parameter != "velocity":
@@ -171,8 +177,9 @@ def check_fit_args(x, elevations, weights, spatial_mode_count, hydraulic_paramet
         if weights.shape != (n_cells,):
             raise ValueError(f"weights must be ({n_cells},)")
     if spatial_mode_count is not None:
-        if int(spatial_mode_count) != spatial_mode_count or not 0 <= spatial_mode_count <= n_s - 1:
-            raise ValueError(f"spatial_mode_count must be an integer in [0, {n_s - 1}] (centring leaves rank samples - 1)")
+        k_max = min(n_s - 1, n_cells) if allow_tall else n_s - 1
+        if int(spatial_mode_count) != spatial_mode_count or not 0 <= spatial_mode_count <= k_max:
+            raise ValueError(f"spatial_mode_count must be an integer in [0, {k_max}] (centring leaves rank samples - 1)")
     return x, elevations, weights
 
 
@@ -182,6 +189,11 @@ class PreProcessor:
 
     device = 0
     eigensolver = "host"  # "host": numpy.linalg.eigh of the downloaded Gram matrix; "device": gprx_pcafit_eig (block Jacobi)
+    # "gram": n_samples <= n_wet only (one IncrementalPCA batch of at most as many rows as columns), anything else is a ValueError.
+    # "auto": that route, same bits, when n_samples <= n_wet; otherwise the covariance route (n_wet x n_wet, n_wet <= 16384), the
+    # reference's fit on more rows than columns or on several batches.  ``last_route`` tells which ran.
+    sample_route = "gram"
+    last_route = None
 
     def __init__(self, spatial_mode_count: int = 0, input_mean=None, wet_threshold: float = 0.03, elevations=None,
                  hydraulic_parameter: str = "wse", wetness_classes=None, weights=None, eofs=None, eigenvalues=None,
@@ -218,47 +230,65 @@ class PreProcessor:
         """PreProcessor.fit (preprocess.py:947-1007) on the device; North's rule picks the mode count when it is None."""
         if self.eigensolver not in ("host", "device"):
             raise ValueError(f"eigensolver must be 'host' or 'device', not {self.eigensolver!r}")
-        x, elev, w = check_fit_args(x, elevations, weights, spatial_mode_count, self.hydraulic_parameter)
+        if self.sample_route not in ("gram", "auto"):
+            raise ValueError(f"sample_route must be 'gram' or 'auto', not {self.sample_route!r}")
+        auto = self.sample_route == "auto"
+        x, elev, w = check_fit_args(x, elevations, weights, spatial_mode_count, self.hydraulic_parameter, allow_tall=auto)
         n_s, n_cells = x.shape
         on_device = self.eigensolver == "device"
         self.last_eig_sweeps = None
         lib = _lib.load()
         mode = MODES.index(self.hydraulic_parameter)
-        with scoped_handle(lib.gprx_pcafit_create, "gprx_pcafit_destroy", self.device, ptr(x), n_s, n_cells, None if elev is None else ptr(elev),
-                           None if w is None else ptr(w), mode, float(self.wet_threshold)) as h:
+        route = C.c_int(0)
+        args = (self.device, ptr(x), n_s, n_cells, None if elev is None else ptr(elev), None if w is None else ptr(w), mode, float(self.wet_threshold))
+        handle = (scoped_handle(lib.gprx_pcafit_create_auto, "gprx_pcafit_destroy", *args, C.byref(route)) if auto
+                  else scoped_handle(lib.gprx_pcafit_create, "gprx_pcafit_destroy", *args))
+        with handle as h:
+            cov = _lib.PCAFIT_ROUTES[route.value] == "covariance"
+            g_side = min(n_cells, 16384) if cov else n_s  # the covariance is (n_wet, n_wet), n_wet <= min(n_cells, 16384)
             codes = np.empty(n_cells, dtype=np.uint8)
             mean = np.empty(n_cells)
             n_wet = C.c_int64()
-            # the SVD of the twice-centred matrix from the eigendecomposition of its Gram matrix, largest first
+            # the SVD of the twice-centred matrix from the eigendecomposition of its Gram matrix (n_samples x n_samples), or on the
+            # covariance route of its covariance (n_wet x n_wet, at most n_cells), largest first
             if on_device:
-                lam = np.empty(n_s)
+                lam = np.empty(g_side)
                 sweeps = C.c_int()
                 check(lib.gprx_pcafit_eig(h, ptr(codes), ptr(mean), ptr(lam), C.byref(n_wet), C.byref(sweeps)))
-                lam = np.maximum(lam, 0.0)
+                lam = np.maximum(lam[: n_wet.value] if cov else lam, 0.0)
             else:
-                gram = np.empty((n_s, n_s))
-                check(lib.gprx_pcafit_gram(h, ptr(codes), ptr(mean), ptr(gram), C.byref(n_wet)))
+                gram = np.empty((g_side, g_side))
+                check((lib.gprx_pcafit_cov if cov else lib.gprx_pcafit_gram)(h, ptr(codes), ptr(mean), ptr(gram), C.byref(n_wet)))
+                if cov:  # the library wrote (n_wet, n_wet) contiguously at the start of the block
+                    gram = gram.reshape(-1)[: n_wet.value**2].reshape(n_wet.value, n_wet.value)
                 lam, u = np.linalg.eigh(gram)
                 lam, u = np.maximum(lam[::-1], 0.0), u[:, ::-1]
             n_wet = n_wet.value
             pca = PCAFit(explained_variance_=lam / (n_s - 1), n_samples_seen_=n_s)
             k = compute_norths_rule(pca) if spatial_mode_count is None else int(spatial_mode_count)
-            if k > n_s - 1 or (k > 0 and not lam[k - 1] > 0.0):
-                raise ValueError(f"{k} modes exceed the numerical rank of the centred data ({n_s} samples)")
+            if k > min(n_s - 1, len(lam)) or (k > 0 and not lam[k - 1] > 0.0):
+                raise ValueError(f"{k} modes exceed the numerical rank of the centred data ({n_s} samples, {n_wet} wet cells)" if cov else
+                                 f"{k} modes exceed the numerical rank of the centred data ({n_s} samples)")
             eofs = np.empty((k, n_wet))
             z = np.empty((n_s, k))
             if on_device:
                 check(lib.gprx_pcafit_components_dev(h, k, ptr(eofs), ptr(z)))
+            elif cov:
+                v_k = np.ascontiguousarray(u[:, :k].T)  # the eigenvectors are the components, up to svd_flip
+                check(lib.gprx_pcafit_components_cov(h, k, ptr(v_k), ptr(eofs), ptr(z)))
             else:
                 u_k = np.ascontiguousarray(u[:, :k])
                 lam_k = np.ascontiguousarray(lam[:k])
                 check(lib.gprx_pcafit_components(h, k, ptr(u_k), ptr(lam_k), ptr(eofs), ptr(z)))
             self.last_timings_ms = self._timings(lib, h)
+            if cov:  # the fourth stage of this route is the covariance product
+                self.last_timings_ms["covariance"], self.last_timings_ms["gram"] = self.last_timings_ms["gram"], 0.0
             if on_device:
                 ms = C.c_double()
                 check(lib.gprx_pcafit_eig_ms(h, C.byref(ms)))
                 self.last_timings_ms["eigensolver"] = ms.value
                 self.last_eig_sweeps = sweeps.value
+        self.last_route = "covariance" if cov else "gram"
         self.elevations = elevations if elev is None else elev
         self.wetness_classes = CLASS_NAMES[codes]
         self.input_mean = mean[:n_wet].copy()

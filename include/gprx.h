@@ -586,6 +586,25 @@ int gprx_pcafit_timings(gprx_pcafit_handle f, double* ms);
 int gprx_pcafit_eig(gprx_pcafit_handle f, unsigned char* classes, double* input_mean, double* lam, int64_t* n_wet, int* sweeps);
 int gprx_pcafit_components_dev(gprx_pcafit_handle f, int k, double* eofs, double* z);
 int gprx_pcafit_eig_ms(gprx_pcafit_handle f, double* ms);
+/* The fit for any number of samples.  create_auto uploads x and takes the Gram route when n_samples <=
+ * n_wet (and n_samples <= min(n_cells, 16384)): the handle then behaves as one from gprx_pcafit_create, bit for bit.  Otherwise it
+ * takes the COVARIANCE route, the reference's IncrementalPCA on one batch of more rows than columns or on several batches: the
+ * statistics with the column means in numpy's order for long columns (pieces of 8192 rows, each in its pairwise tree, added left to
+ * right: input_mean stays bit-identical to the reference), compaction, the second centring and C = Xc2^T Xc2 (n_wet, n_wet), unscaled.
+ * Domain of that route: 2 <= n_samples < 2^31 - 16, 1 <= n_wet <= 16384.  *route: GPRX_PCAFIT_GRAM or GPRX_PCAFIT_COV.
+ *   cov: the counterpart of gprx_pcafit_gram: classes, input_mean, C and n_wet (same call-order rules).
+ *   components_cov: v (k, n_wet) row-major, the eigenvectors of the k largest eigenvalues of C as rows, unflipped, 0 <= k <=
+ *     min(n_samples - 1, n_wet); eofs (k, n_wet) = v with svd_flip(u_based_decision=False) applied, z (n_samples, k) = Xc_once eofs^T.
+ *   gprx_pcafit_eig / components_dev serve a covariance-route handle as well: lam then has n_wet entries and the components are the
+ *     leading eigenvector columns of U, gathered on the device as rows.
+ * A call that does not fit the handle's route (gram / components on a covariance handle, cov / components_cov on a Gram handle)
+ * returns GPRX_ESTATE with a message that names the route.  Timings: the fourth value is the covariance product on that route. */
+#define GPRX_PCAFIT_GRAM 0
+#define GPRX_PCAFIT_COV 1
+int gprx_pcafit_create_auto(int device, const double* x, int64_t n_samples, int64_t n_cells, const double* elevations, const double* weights,
+                            int mode, double wet_threshold, int* route, gprx_pcafit_handle* out);
+int gprx_pcafit_cov(gprx_pcafit_handle f, unsigned char* classes, double* input_mean, double* cov, int64_t* n_wet);
+int gprx_pcafit_components_cov(gprx_pcafit_handle f, int k, const double* v, double* eofs, double* z);
 int gprx_pcafit_destroy(gprx_pcafit_handle f);
 const char* gprx_pcafit_last_error(gprx_pcafit_handle f);
 
@@ -920,7 +939,11 @@ int gprx_gather_rows(int device, const double* field_dev, int64_t rows, int64_t 
  * 200 000; tests set 0 to force the hand-over).
  * "loeo_blocked_potrf" (process-wide, a measurement aid of gprx_loeo_batch_blocked; -1, the default, keeps the schedule fixed per
  * mp): the schedule of chol(H) over the slots -- 0 launch sequence with the fused panel, 1 with the split panel, 2 one workgroup per
- * slot (not at mp = 64). */
+ * slot (not at mp = 64).
+ * "pcafit_rowsplit" (process-wide, the yardstick of the covariance route of the EOF fit; a fit handle does all of its device work
+ * inside gprx_pcafit_create_auto, which reads the value when it runs): 1 (default) the statistics, the compaction and the second
+ * centring of that route run the row-split kernels of csrc/pca_fit_tall.h, 0: the one-thread-per-cell kernels of the Gram route on
+ * the same chunked operation list.  Same bits either way. */
 int gprx_set_tuning(const char* key, int value);
 int gprx_set_handle_tuning(gprx_handle h, const char* key, int value);
 
