@@ -54,6 +54,7 @@ PROTOTYPES = {
     "gprx_last_batch_ms": (C.c_int, [_vp, _dp]),
     "gprx_predict_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _i64, _vp, _vp, C.c_int]),
     "gprx_predict_batch_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _i64, _vp, _vp, C.c_int]),
+    "gprx_predict_joint_batch_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _i64, _vp, _vp, C.c_int]),
     "gprx_predict": (C.c_int, [_vp, _vp, _i64, _vp, _vp, C.c_int]),
     "gprx_predict_dev": (C.c_int, [_vp, _vp, _i64, _vp, _vp, C.c_int]),
     "gprx_last_timings": (C.c_int, [_vp, _dp]),
@@ -106,6 +107,12 @@ PROTOTYPES = {
     "gprx_pca_sweep_dev": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, C.c_int, _vp, C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gprx_pca_sweep_ms": (C.c_int, [_vp, _dp]),
     "gprx_pca_sweep_group": (C.c_int, []),
+    "gprx_pca_ensemble_peaks_dev": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, C.c_int, _vp]),
+    "gprx_pca_ensemble_ms": (C.c_int, [_vp, _dp]),
+    "gprx_pca_pack_scores_dev": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp]),
+    "gprx_pca_ensemble_group": (C.c_int, [_vp, _i64, _ip]),
+    "gprx_pca_member_peaks_dev": (C.c_int, [_vp, _vp, _i64, _i64, _vp]),
+    "gprx_pca_member_stats_dev": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gprx_pcafit_create": (C.c_int, [C.c_int, _vp, _i64, _i64, _vp, _vp, C.c_int, C.c_double, C.POINTER(_vp)]),
     "gprx_pcafit_gram": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_i64)]),
     "gprx_pcafit_components": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),

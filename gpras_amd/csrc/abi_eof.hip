@@ -15,6 +15,7 @@
 #include "pca_fit.h"
 #include "pca_fit_tall.h"
 #include "sweep.h"
+#include "ensemble.h"
 
 using namespace gprx;
 
@@ -29,6 +30,8 @@ struct gprx_pca_ctx {
   Buf sweep_part, sweep_aux;  // gprx_pca_sweep_dev: per-workgroup row sums; event bounds, then the match counts per workgroup
   hipEvent_t ev[2] = {};
   double sweep_ms = 0.0;      // device time of the last gprx_pca_sweep_dev
+  Buf ens_part;               // gprx_pca_member_stats_dev: per-workgroup wet areas
+  double ens_ms = 0.0;        // device time of the last gprx_pca_ensemble_peaks_dev
   std::string err;
 };
 
@@ -158,7 +161,7 @@ int gprx_pca_create(int device, int64_t n_cells, int k, const unsigned char* dry
 int gprx_pca_destroy(gprx_pca_handle p) {
   if (!p) return GPRX_OK;
   release_handle(p->device, p->stream, {p->mu.p, p->wfwd.p, p->wrev.p, p->elev.p, p->E.p, p->base.p, p->xm.p, p->xs.p, p->dX.p, p->dZ.p, p->ws.p, p->dMean.p, p->dVar.p,
-                                           p->dFull.p, p->dVfull.p, p->sweep_part.p, p->sweep_aux.p}, p->ev, 2);
+                                           p->dFull.p, p->dVfull.p, p->sweep_part.p, p->sweep_aux.p, p->ens_part.p}, p->ev, 2);
   delete p;
   return GPRX_OK;
 }
@@ -332,6 +335,140 @@ int gprx_pca_sweep_ms(gprx_pca_handle p, double* ms) {
 }
 
 int gprx_pca_sweep_group(void) { return SWEEP_SMAX; }
+
+// ---- peak ensembles (ensemble.h) ---------------------------------------------------------------------------------------------------
+namespace {
+// members per workgroup of the fused kernel: about four workgroups per compute unit before a workgroup takes a second member
+int ensemble_group(int64_t cells, int64_t members) {
+  const int64_t nbx = (cells + 255) / 256;
+  const int64_t groups_wanted = (1024 + nbx - 1) / nbx;
+  int64_t group = std::max<int64_t>(1, std::min<int64_t>(16, members / groups_wanted));
+  while ((members + group - 1) / group > 65535) ++group;
+  return (int)group;
+}
+
+int check_members(gprx_pca_handle p, int64_t members, int64_t rows_e) {
+  if (members < 1 || rows_e < 1) return fail(p, GPRX_EINVAL, "members and the event's rows must be positive");
+  if (rows_e >= ((int64_t)1 << 31) || members >= ((int64_t)1 << 31) / rows_e) return fail(p, GPRX_EINVAL, "members x rows must stay below 2^31");
+  return GPRX_OK;
+}
+}  // namespace
+
+int gprx_pca_ensemble_peaks_dev(gprx_pca_handle p, const double* scores_dev, int64_t members, int64_t rows_e, int depth_mode, int member_group,
+                                double* peak_dev) {
+  return guarded(p, [&]() -> int {
+    if (!p) return fail(p, GPRX_EINVAL, "null handle");
+    if (!scores_dev || !peak_dev) return fail(p, GPRX_EINVAL, "null argument");
+    int rc;
+    if ((rc = check_members(p, members, rows_e))) return rc;
+    if (depth_mode < 0 || depth_mode > 2) return fail(p, GPRX_EINVAL, "depth mode must be 0 (none), 1 (wse) or 2 (depth)");
+    if (depth_mode && !p->has_elev) return fail(p, GPRX_EINVAL, "the depth conversion needs the cell elevations (the projector was created without them)");
+    if (member_group < 0 || member_group > 64) return fail(p, GPRX_EINVAL, "member_group must be 0 (the launcher's choice) or between 1 and 64");
+    const int group = member_group ? member_group : ensemble_group(p->cells, members);
+    const int64_t ngroups = (members + group - 1) / group;
+    if (ngroups > 65535) return fail(p, GPRX_EINVAL, "too many member groups: raise member_group");
+    HIPCHK(p, hipSetDevice(p->device));
+    hipStream_t st = p->stream;
+    EnsembleArgs a{scores_dev, members, rows_e, p->cells, p->k, p->E.p, p->cells_p, p->wrev.p, p->base.p, p->xm.p, p->xs.p, p->elev.p, depth_mode, group, peak_dev};
+    const dim3 grid((unsigned)((p->cells + 255) / 256), (unsigned)ngroups);
+    HIPCHK(p, hipEventRecord(p->ev[0], st));
+    if (p->k <= 16) hipLaunchKernelGGL(pca_ensemble_peaks_kernel<16>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(pca_ensemble_peaks_kernel<64>, grid, dim3(256), 0, st, a);
+    HIPCHK(p, hipGetLastError());
+    HIPCHK(p, hipEventRecord(p->ev[1], st));
+    HIPCHK(p, hipStreamSynchronize(st));
+    p->ens_ms = elapsed_ms(p->ev[0], p->ev[1]);
+    return GPRX_OK;
+  });
+}
+
+int gprx_pca_pack_scores_dev(gprx_pca_handle p, const double* mean_dev, const double* w_dev, int64_t members, int64_t rows_e, int64_t tp,
+                             double* scores_dev) {
+  return guarded(p, [&]() -> int {
+    if (!p) return fail(p, GPRX_EINVAL, "null handle");
+    if (!mean_dev || !w_dev || !scores_dev) return fail(p, GPRX_EINVAL, "null argument");
+    int rc;
+    if ((rc = check_members(p, members, rows_e))) return rc;
+    if (tp < rows_e) return fail(p, GPRX_EINVAL, "the padded row count is smaller than the event's rows");
+    HIPCHK(p, hipSetDevice(p->device));
+    const int64_t total = members * rows_e * p->k;
+    hipLaunchKernelGGL(ensemble_pack_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 8192)), dim3(256), 0, p->stream, mean_dev, w_dev, members,
+                       rows_e, tp, p->k, scores_dev);
+    HIPCHK(p, hipGetLastError());
+    return GPRX_OK;
+  });
+}
+
+int gprx_pca_ensemble_ms(gprx_pca_handle p, double* ms) {
+  if (!p || !ms) return fail(p, GPRX_EINVAL, "null argument");
+  *ms = p->ens_ms;
+  return GPRX_OK;
+}
+
+int gprx_pca_ensemble_group(gprx_pca_handle p, int64_t members, int* group) {
+  if (!p || !group) return fail(p, GPRX_EINVAL, "null argument");
+  if (members < 1) return fail(p, GPRX_EINVAL, "members must be positive");
+  *group = ensemble_group(p->cells, members);
+  return GPRX_OK;
+}
+
+int gprx_pca_member_peaks_dev(gprx_pca_handle p, const double* field_dev, int64_t members, int64_t rows_e, double* peak_dev) {
+  return guarded(p, [&]() -> int {
+    if (!p) return fail(p, GPRX_EINVAL, "null handle");
+    if (!field_dev || !peak_dev) return fail(p, GPRX_EINVAL, "null argument");
+    int rc;
+    if ((rc = check_members(p, members, rows_e))) return rc;
+    if (members > 65535) return fail(p, GPRX_EINVAL, "at most 65535 members per call");
+    HIPCHK(p, hipSetDevice(p->device));
+    hipLaunchKernelGGL(field_member_peaks_kernel, dim3((unsigned)((p->cells + 255) / 256), (unsigned)members), dim3(256), 0, p->stream, field_dev, rows_e,
+                       p->cells, peak_dev);
+    HIPCHK(p, hipGetLastError());
+    return GPRX_OK;
+  });
+}
+
+int gprx_pca_member_stats_dev(gprx_pca_handle p, const double* peak_dev, int64_t members, int n_thr, const double* thresholds, int n_rank, const int* ranks,
+                              const double* area_dev, int* exceed_dev, double* mean_dev, double* std_dev, double* order_dev, double* wet_area_dev) {
+  return guarded(p, [&]() -> int {
+    if (!p) return fail(p, GPRX_EINVAL, "null handle");
+    if (!peak_dev || !mean_dev || !std_dev) return fail(p, GPRX_EINVAL, "null argument");
+    if (members < 1 || members > ENS_SMAX) return fail(p, GPRX_EINVAL, "members must be between 1 and " + std::to_string(ENS_SMAX));
+    if (n_thr < 0 || n_thr > ENS_TMAX || (n_thr && (!thresholds || !exceed_dev || !wet_area_dev)))
+      return fail(p, GPRX_EINVAL, "at most " + std::to_string(ENS_TMAX) + " thresholds, with their output blocks");
+    if (n_rank < 0 || n_rank > ENS_RMAX || (n_rank && (!ranks || !order_dev)))
+      return fail(p, GPRX_EINVAL, "at most " + std::to_string(ENS_RMAX) + " ranks, with their output block");
+    for (int j = 0; j < n_thr; ++j)
+      if (thresholds[j] != thresholds[j]) return fail(p, GPRX_EINVAL, "a threshold is NaN");
+    for (int j = 0; j < n_rank; ++j)
+      if (ranks[j] < 0 || ranks[j] >= members) return fail(p, GPRX_EINVAL, "ranks must lie in [0, members)");
+    HIPCHK(p, hipSetDevice(p->device));
+    hipStream_t st = p->stream;
+    const int64_t cells = p->cells;
+    const unsigned nbx = (unsigned)((cells + 255) / 256);
+    MemberStatsArgs a{};
+    a.peak = peak_dev, a.members = members, a.cells = cells, a.n_thr = n_thr, a.n_rank = n_rank;
+    for (int j = 0; j < n_thr; ++j) a.thr[j] = thresholds[j];
+    for (int j = 0; j < n_rank; ++j) a.rank[j] = ranks[j];
+    a.exceed = exceed_dev, a.mean = mean_dev, a.std = std_dev, a.order = order_dev;
+    hipLaunchKernelGGL(member_cell_stats_kernel, dim3(nbx), dim3(256), 0, st, a);
+    HIPCHK(p, hipGetLastError());
+    if (n_thr) {
+      int rc;
+      if ((rc = ensure(p, p->ens_part, sizeof(double) * (size_t)members * n_thr * nbx))) return rc;
+      MemberAreaArgs b{};
+      b.peak = peak_dev, b.area = area_dev, b.members = members, b.cells = cells, b.n_thr = n_thr, b.part = p->ens_part.p;
+      for (int j = 0; j < n_thr; ++j) b.thr[j] = thresholds[j];
+      hipLaunchKernelGGL(member_area_kernel, dim3(nbx, (unsigned)members), dim3(256), 0, st, b);
+      HIPCHK(p, hipGetLastError());
+      const int64_t total = members * n_thr;
+      hipLaunchKernelGGL(member_area_sum_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const double*)p->ens_part.p, (int)nbx, total,
+                         wet_area_dev);
+      HIPCHK(p, hipGetLastError());
+    }
+    HIPCHK(p, hipStreamSynchronize(st));
+    return GPRX_OK;
+  });
+}
 
 int gprx_pca_synchronize(gprx_pca_handle p) {
   if (!p) return fail(p, GPRX_EINVAL, "null handle");

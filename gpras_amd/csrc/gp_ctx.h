@@ -42,6 +42,7 @@ struct gprx_ctx {
   double loeo_ms[4] = {0, 0, 0, 0};                       // ... and its stage times (gprx.h)
   int last_loeo_blocked = 0, loeo_blocked_groups = 0;     // gprx_last_loeo_blocked: the last gprx_loeo_batch_blocked ran to the end, in so many groups
   double loeo_blocked_ms[6] = {0, 0, 0, 0, 0, 0};         // ... and its stage times (gprx.h)
+  Buf joint_ws;                                           // gprx_predict_joint_batch_dev: covariance, factorisation scratch and info per cell (gp_joint.h)
   Buf loeo_ws;                                            // its workspace: one slot per (cell, event) of a group (gp_loeo_blocked.h)
   hipEvent_t loeo_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // created by its first call
   int host_waits = 0;                                     // stream waits of the running optimiser call (wait_stream and the loops' own)

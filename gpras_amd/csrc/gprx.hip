@@ -70,6 +70,7 @@ hipStream_t util_stream() {
 #include "gp_predict.h"
 #include "gp_loeo.h"
 #include "gp_loeo_blocked.h"
+#include "gp_joint.h"
 
 namespace {
 
@@ -146,7 +147,7 @@ int gprx_destroy(gprx_handle h) {
   hipSetDevice(h->device);
   if (h->stream) hipStreamSynchronize(h->stream);
   for (Buf* b : {&h->X, &h->Y, &h->invls, &h->alpha, &h->red, &h->Kmat, &h->invD, &h->Xinv, &h->Tmp, &h->partial, &h->xs, &h->Ks, &h->pred,
-                 &h->dstage, &h->arena, &h->cellpar, &h->cellres, &h->garena, &h->gpartial, &h->apart, &h->twork, &h->sarena, &h->hold, &h->loeo_ws})
+                 &h->dstage, &h->arena, &h->cellpar, &h->cellres, &h->garena, &h->gpartial, &h->apart, &h->twork, &h->sarena, &h->hold, &h->loeo_ws, &h->joint_ws})
     if (b->p && !b->borrowed) hipFree(b->p);
   for (auto& ev : h->loeo_ev)
     if (ev) hipEventDestroy(ev);
@@ -349,6 +350,11 @@ int gprx_predict_batch_dev(gprx_handle h, int count, const int* units, const dou
     if (count <= 0 || !units || !thetas || ns < 0 || (ns > 0 && (!xs_dev || !means_dev || !vars_dev))) return fail(h, GPRX_EINVAL, "null argument");
     return predict_batch_core(h, count, units, thetas, z, xs_dev, ns, means_dev, vars_dev, include_noise);
   });
+}
+
+int gprx_predict_joint_batch_dev(gprx_handle h, int count, const int* units, const double* thetas, const double* z, const double* xs_dev, int64_t ns,
+                                 double* means_dev, double* lc_dev, int include_noise) {
+  return guarded(h, [&]() -> int { return predict_joint_batch(h, count, units, thetas, z, xs_dev, ns, means_dev, lc_dev, include_noise); });
 }
 
 int gprx_predict_batch(gprx_handle h, int count, const int* units, const double* thetas, const double* z, const double* xs, int64_t ns,

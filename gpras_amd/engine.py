@@ -432,6 +432,26 @@ class Engine(DeviceHandle):
             check(self._lib.gprx_synchronize(self._h), self._h)
 
     @_locked
+    def predict_joint_batch_dev(self, units, thetas, xs_dev, ns: int, means_dev, lc_dev, zs=None, include_noise: bool = True):
+        """The joint prediction of sparse cells over ONE event's ``ns <= 1024`` test points (``gprx_predict_joint_batch_dev``): ``means_dev
+        (cells, ns)`` and ``lc_dev (cells, Tp, Tp)``, the lower Cholesky factors of the predictive covariances padded with the identity to
+        ``Tp`` = ``ns`` rounded up to 64; both in device memory.  Synchronises.  ``gpras_amd.ensemble.joint_applies`` names what is served."""
+        units = np.ascontiguousarray(units, dtype=np.int32)
+        thetas = as_f64(thetas)
+        if thetas.shape != (units.size, self.n_theta):
+            raise ValueError(f"thetas must be ({units.size}, {self.n_theta})")
+        if self.m == 0:
+            raise ValueError("the joint prediction does not serve this model: exact model (n_inducing=None)")
+        if zs is None:
+            raise ValueError(f"zs (the cells' inducing inputs, ({units.size}, {self.m}, {self.d})) is required")
+        zs = as_f64(zs)
+        if zs.shape != (units.size, self.m, self.d):
+            raise ValueError(f"zs must be ({units.size}, {self.m}, {self.d})")
+        p = lambda b: b.ptr if hasattr(b, "ptr") else b  # noqa: E731
+        check(self._lib.gprx_predict_joint_batch_dev(self._h, units.size, ptr(units), ptr(thetas), ptr(zs), p(xs_dev), int(ns), p(means_dev), p(lc_dev),
+                                                     int(include_noise)), self._h)
+
+    @_locked
     def predict_dev(self, xs_dev, ns: int, mean_dev, var_dev, include_noise: bool = True, wait: bool = True):
         """The same with device pointers (``gprx_predict_dev``): inputs and outputs stay resident in HBM."""
         p = lambda b: b.ptr if hasattr(b, "ptr") else b  # noqa: E731

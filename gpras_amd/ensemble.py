@@ -1,0 +1,345 @@
+"""Peak ensembles: joint posterior draws of a fitted ``GPRAS`` pushed through the field chain to maps of an EVENT's peak.
+
+Every uncertainty ``GPRAS.predict`` returns is a marginal per (time step, cell); the reference forms the 2.5 % / 97.5 % bands from it
+(production/analysis/pipeline.py:262-263).  What a flood-risk user asks for is a functional of a whole event -- the probability that the
+event's maximum depth exceeds a threshold, the quantile maps of the peak depth, the distribution of the inundated area -- and the
+maximum over an event's rows does not follow from marginals: the GP's predictions at those rows are strongly correlated.
+
+``PeakEnsemble(gpr, projector).evaluate(x_test, ranges, members, ...)`` works event by event:
+
+* ``Engine.predict_joint_batch_dev`` (``gprx_predict_joint_batch_dev``): per mode the mean over the event's rows and the lower Cholesky
+  factor ``Lc`` of the joint predictive covariance ``Kss - tmp1^T tmp1 + tmp2^T tmp2`` (the quantities of gpflow's ``SGPR.predict_f`` with
+  the diagonal kept joint), padded with the identity to ``Tp`` = rows rounded up to 64;
+* standard normals ``Zn (K, S, Tp)`` from the caller or from ``np.random.default_rng(seed)``, drawn event by event in the order of
+  ``ranges`` as ``rng.standard_normal((K, S, rows))``; ``W_k = Zn_k Lc_k^T`` by the batched fp64 GEMM and one packing kernel give the
+  members' scores ``(S rows, K)``.  Modes are independent of each other, as the reference's variance propagation assumes, and so are events;
+* ``route="fused"``: ``gprx_pca_ensemble_peaks_dev`` (csrc/ensemble.h) walks every member's rows per cell and writes only
+  ``peak (S, cells)``;  ``route="refield"``: the same numbers, bit for bit, from ``gprx_pca_reverse_dev`` -> ``gprx_pca_to_depth_dev`` on
+  slabs of whole members and a per-member row maximum;
+* ``gprx_pca_member_stats_dev``: exceedance counts, mean, standard deviation, order statistics and wet areas over the members.
+
+DESIGN.md section 3.23 has the mapping, the determinism argument and the measurement behind ``DEFAULT_ROUTE``.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass, field
+
+import numpy as np
+
+from . import _lib
+from ._device import StageTimer, slab_rows
+from ._lib import DeviceBuffer, as_f64, check, ptr
+from .diagnostics import check_ranges
+
+ROUTES = ("fused", "refield")
+DEFAULT_ROUTE = "fused"  # the route measured faster at the production shape (profiles/ensemble_peaks.json)
+DEPTH_MODES = {"velocity": 0, "wse": 1, "depth": 2}
+JOINT_MAX_M, JOINT_MAX_ROWS, JOINT_MAX_D = 320, 1024, 64
+MAX_MEMBERS, MAX_THRESHOLDS, MAX_RANKS = 4096, 8, 8
+STAGES = ("joint", "draw_upload", "draws", "peaks", "stats")  # (the statistics' stage includes their download)
+
+
+def joint_applies(n_inducing, d: int, rows: int) -> str | None:
+    """None when ``gprx_predict_joint_batch_dev`` takes this configuration, else the reason it does not."""
+    if n_inducing is None:
+        return "exact model (n_inducing=None)"
+    if int(n_inducing) > JOINT_MAX_M:
+        return f"more than {JOINT_MAX_M} inducing points"
+    if d > JOINT_MAX_D:
+        return f"more than {JOINT_MAX_D} features"
+    if rows > JOINT_MAX_ROWS:
+        return f"an event of more than {JOINT_MAX_ROWS} rows"
+    if rows < 1:
+        return "an event without rows"
+    return None
+
+
+def padded_rows(rows: int) -> int:
+    """``Tp``: an event's rows rounded up to 64, the order of its padded Cholesky factor."""
+    return (int(rows) + 63) // 64 * 64
+
+
+def quantile_ranks(quantiles, members: int) -> np.ndarray:
+    """``floor(q (S - 1))`` per quantile: the rank ``np.quantile(..., method="lower")`` reads."""
+    q = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
+    if q.ndim != 1 or np.any(~(q >= 0.0)) or np.any(~(q <= 1.0)):
+        raise ValueError("quantiles must lie in [0, 1]")
+    return np.floor(q * (int(members) - 1)).astype(np.int32)
+
+
+def check_stats_args(members: int, thresholds, ranks):
+    """``(thresholds float64, ranks int32)`` as ``gprx_pca_member_stats_dev`` takes them."""
+    members = int(members)
+    if not 1 <= members <= MAX_MEMBERS:
+        raise ValueError(f"members must be between 1 and {MAX_MEMBERS}")
+    thr = np.ascontiguousarray(np.atleast_1d(np.asarray(thresholds, dtype=np.float64)))
+    if thr.ndim != 1 or thr.size > MAX_THRESHOLDS:
+        raise ValueError(f"at most {MAX_THRESHOLDS} thresholds")
+    if np.any(np.isnan(thr)):
+        raise ValueError("a threshold is NaN")
+    rk = np.atleast_1d(np.asarray(ranks))
+    if rk.size and rk.dtype.kind not in "iu":
+        raise ValueError("ranks must be integers")
+    rk = np.ascontiguousarray(rk, dtype=np.int32)
+    if rk.ndim != 1 or rk.size > MAX_RANKS:
+        raise ValueError(f"at most {MAX_RANKS} ranks")
+    if np.any(rk < 0) or np.any(rk >= members):
+        raise ValueError("ranks must lie in [0, members)")
+    return thr, rk
+
+
+def check_event_ranges(ranges, rows: int):
+    """The events' ``(lo, hi)`` as int64 arrays: non-empty, inside ``[0, rows]``, in ascending order and disjoint."""
+    lo, hi = check_ranges(ranges, rows)
+    if np.any(lo[1:] < lo[:-1]):
+        raise ValueError("the events must be in ascending order")
+    if np.any(lo[1:] < hi[:-1]):
+        raise ValueError("the events overlap")
+    return lo, hi
+
+
+@dataclass
+class EnsembleResult:
+    """Per event ``e``: ``p_exceed (E, n_thr, cells)`` = exceedance counts / S; ``peak_mean``, ``peak_std`` ``(E, cells)`` (ddof = 0);
+    ``peak_quantiles (E, n_q, cells)`` = the order statistic of rank ``floor(q (S - 1))``; ``wet_area (E, S, n_thr)``; ``exceed_counts`` the
+    integer counts themselves."""
+
+    p_exceed: np.ndarray
+    peak_mean: np.ndarray
+    peak_std: np.ndarray
+    peak_quantiles: np.ndarray
+    wet_area: np.ndarray
+    exceed_counts: np.ndarray
+    thresholds: np.ndarray
+    quantiles: np.ndarray
+    ranges: list
+    members: int
+    route: str
+    last_timings_ms: dict = field(default_factory=dict)
+    names: list = field(default_factory=list)  # the events' labels (``DevicePipeline.peak_ensemble``)
+
+
+class PeakEnsemble:
+    def __init__(self, gpr, projector):
+        """``gpr``: a fitted (or loaded) ``gpras_amd.GPRAS`` of sparse models; ``projector``: the ``EOFProjector`` of its outputs."""
+        if not getattr(gpr, "models", None):
+            raise ValueError("the GPRAS model has not been fitted or loaded")
+        if len(gpr.models) != projector.spatial_mode_count:
+            raise ValueError(f"the model has {len(gpr.models)} outputs, the projector {projector.spatial_mode_count} spatial modes")
+        self.gpr, self.projector = gpr, projector
+        self.device = projector.device
+        self._lib = _lib.load()
+        self.last_device_peaks_ms = 0.0  # device time of the last fused peak kernel (``gprx_pca_ensemble_ms``)
+
+    # ---- 1. joint prediction over one event -------------------------------------------------------------------------------------------
+    def joint_dev(self, x_event, include_noise: bool = True):
+        """``(mean, Lc, rows)``: device buffers ``(K, rows)`` and ``(K, Tp, Tp)`` of one event's joint prediction.  The caller frees them."""
+        x = as_f64(np.asarray(x_event).astype(np.float64))
+        models = self.gpr.models
+        if x.ndim != 2 or x.shape[1] != self.gpr.x.shape[1]:
+            raise ValueError(f"x must be (rows, {self.gpr.x.shape[1]})")
+        rows, k = int(x.shape[0]), len(models)
+        for mod in models:
+            why_not = joint_applies(None if mod.Z is None else mod.Z.shape[0], x.shape[1], rows)
+            if why_not:
+                raise ValueError(f"the joint prediction does not serve this model: {why_not}")
+        tp = padded_rows(rows)
+        dev = self.device
+        xs_dev = DeviceBuffer.from_array(x, dev)
+        mean = DeviceBuffer(8 * k * rows, dev)
+        lc = DeviceBuffer(8 * k * tp * tp, dev)
+        try:
+            by_engine: dict[int, list[int]] = {}
+            for i, mod in enumerate(models):
+                by_engine.setdefault(id(mod.backend), []).append(i)
+            for idx in by_engine.values():
+                eng = models[idx[0]].backend
+                chunk = max(1, min(64, eng.max_cells(want_grad=False)))
+                runs: list[list[int]] = []
+                for i in idx:
+                    if runs and runs[-1][-1] + 1 == i and len(runs[-1]) < chunk:
+                        runs[-1].append(i)
+                    else:
+                        runs.append([i])
+                for part in runs:
+                    units = [models[i].unit for i in part]
+                    thetas = np.stack([models[i].theta() for i in part])
+                    zs = np.stack([models[i].Z for i in part])
+                    eng.predict_joint_batch_dev(units, thetas, xs_dev, rows, mean.at(part[0] * rows), lc.at(part[0] * tp * tp), zs=zs,
+                                                include_noise=include_noise)
+        except Exception:
+            mean.free()
+            lc.free()
+            raise
+        finally:
+            xs_dev.free()
+        return mean, lc, rows
+
+    # ---- 2. draws -----------------------------------------------------------------------------------------------------------------------
+    def scores_dev(self, mean_dev, lc_dev, normals, members: int, rows: int, timer: StageTimer | None = None) -> DeviceBuffer:
+        """The members' scores ``(S rows, K)`` on the device: ``scores[s, t, k] = mean[k, t] + (Zn_k Lc_k^T)[s, t]``.  ``normals``: ``(K, S, rows)``
+        or ``(K, S, Tp)`` standard normals on the host (the columns beyond ``rows`` meet the identity padding and are not read back)."""
+        k, tp, dev = self.projector.spatial_mode_count, padded_rows(rows), self.device
+        zn = np.asarray(normals, dtype=np.float64)
+        if zn.ndim != 3 or zn.shape[:2] != (k, members) or zn.shape[2] not in (rows, tp):
+            raise ValueError(f"normals must be ({k}, {members}, {rows}) or ({k}, {members}, {tp})")
+        zp = np.zeros((k, members, tp))
+        zp[:, :, : zn.shape[2]] = zn
+        zbuf = wbuf = scores = None
+        try:
+            zbuf = DeviceBuffer.from_array(zp, dev)
+            wbuf = DeviceBuffer(8 * k * members * tp, dev)
+            scores = DeviceBuffer(8 * members * rows * k, dev)
+            if timer is not None:
+                timer.link_bytes += zbuf.nbytes
+                timer.lap("draw_upload")
+            # W_k (S, Tp) = Zn_k (S, Tp) . Lc_k^T: the (0, 1) form, op(B) = Lc^T upper triangular (Lc's strict upper triangle is zero)
+            check(self._lib.gprx_gemm_batched(dev, 0, 1, members, tp, tp, 1.0, zbuf.ptr, tp, lc_dev.ptr if hasattr(lc_dev, "ptr") else lc_dev, tp, 0.0,
+                                              wbuf.ptr, tp, _lib.GEMM_B_UPPER, 64, k, members * tp, tp * tp, members * tp, 1, 0, 0, 0, None, 0, None, 0))
+            check(self._lib.gprx_pca_pack_scores_dev(self.projector.handle, mean_dev.ptr if hasattr(mean_dev, "ptr") else mean_dev, wbuf.ptr, members,
+                                                     rows, tp, scores.ptr))
+            check(self._lib.gprx_pca_synchronize(self.projector.handle))
+        except Exception:
+            if scores is not None:
+                scores.free()
+            raise
+        finally:
+            for buf in (zbuf, wbuf):
+                if buf is not None:
+                    buf.free()
+        if timer is not None:
+            timer.lap("draws")
+        return scores
+
+    # ---- 3. peaks -----------------------------------------------------------------------------------------------------------------------
+    def member_peaks_dev(self, scores, members: int, rows: int, route: str | None = None, member_group: int = 0) -> DeviceBuffer:
+        """``peak (S, cells)`` on the device from the members' scores: a host array ``(S, rows, K)`` or a device buffer of that block."""
+        route = DEFAULT_ROUTE if route is None else route
+        if route not in ROUTES:
+            raise ValueError(f"route must be one of {ROUTES}")
+        pr, lib, dev = self.projector, self._lib, self.device
+        members, rows = int(members), int(rows)
+        if members < 1 or rows < 1:
+            raise ValueError("members and rows must be positive")
+        if pr.hydraulic_parameter != "velocity" and pr.elevations is None:
+            raise ValueError("wse_2_depth needs the cell elevations (the projector was built without them)")
+        k, cells = pr.spatial_mode_count, pr.n_cells
+        owned = None
+        if not hasattr(scores, "ptr"):
+            arr = as_f64(scores)
+            if arr.shape != (members, rows, k):
+                raise ValueError(f"scores must be ({members}, {rows}, {k})")
+            scores = owned = DeviceBuffer.from_array(arr, dev)
+        elif getattr(scores, "nbytes", 8 * members * rows * k) < 8 * members * rows * k:
+            raise ValueError("the scores buffer is too small")
+        peak = DeviceBuffer(8 * members * cells, dev)
+        try:
+            ph = pr.handle
+            if route == "fused":
+                check(lib.gprx_pca_ensemble_peaks_dev(ph, scores.ptr, members, rows, DEPTH_MODES[pr.hydraulic_parameter], int(member_group), peak.ptr))
+                ms = C.c_double()
+                check(lib.gprx_pca_ensemble_ms(ph, C.byref(ms)))
+                self.last_device_peaks_ms = ms.value
+            else:
+                per_slab = max(1, min(members, 65535, slab_rows(pr) // rows))
+                fieldbuf = DeviceBuffer(8 * per_slab * rows * cells, dev)
+                try:
+                    for s0 in range(0, members, per_slab):
+                        ns = min(per_slab, members - s0)
+                        check(lib.gprx_pca_reverse_dev(ph, scores.at(s0 * rows * k), None, ns * rows, fieldbuf.ptr, None))
+                        if pr.hydraulic_parameter != "velocity":
+                            check(lib.gprx_pca_to_depth_dev(ph, fieldbuf.ptr, ns * rows, int(pr.hydraulic_parameter == "depth")))
+                        check(lib.gprx_pca_member_peaks_dev(ph, fieldbuf.ptr, ns, rows, peak.at(s0 * cells)))
+                    check(lib.gprx_pca_synchronize(ph))
+                finally:
+                    fieldbuf.free()
+        except Exception:
+            peak.free()
+            raise
+        finally:
+            if owned is not None:
+                owned.free()
+        return peak
+
+    # ---- 4. statistics ------------------------------------------------------------------------------------------------------------------
+    def member_stats(self, peak_dev, members: int, thresholds=(), ranks=(), cell_areas=None) -> dict:
+        """The statistics over the members of a ``(S, cells)`` peak block on the device, as host arrays: ``exceed (n_thr, cells)`` int32,
+        ``mean``, ``std`` ``(cells,)``, ``order (n_rank, cells)``, ``wet_area (S, n_thr)``."""
+        thr, rk = check_stats_args(members, thresholds, ranks)
+        pr, dev = self.projector, self.device
+        cells, members = pr.n_cells, int(members)
+        area = None
+        if cell_areas is not None:
+            a = as_f64(cell_areas)
+            if a.shape != (cells,):
+                raise ValueError(f"cell_areas must be ({cells},)")
+            area = DeviceBuffer.from_array(a, dev)
+        n_thr, n_rk = int(thr.size), int(rk.size)
+        # one block: exceed (int32) | mean | std | order | wet_area
+        o_mean = (4 * n_thr * cells + 7) // 8
+        o_std, o_order = o_mean + cells, o_mean + 2 * cells
+        o_wet = o_order + n_rk * cells
+        out = DeviceBuffer(8 * (o_wet + members * n_thr + 1), dev)
+        try:
+            check(self._lib.gprx_pca_member_stats_dev(pr.handle, peak_dev.ptr if hasattr(peak_dev, "ptr") else peak_dev, members, n_thr, ptr(thr), n_rk,
+                                                      ptr(rk), None if area is None else area.ptr, out.ptr, out.at(o_mean), out.at(o_std), out.at(o_order),
+                                                      out.at(o_wet)))
+            host = out.to_array((o_wet + members * n_thr,))
+        finally:
+            out.free()
+            if area is not None:
+                area.free()
+        exceed = host[:o_mean].view(np.int32)[: n_thr * cells].reshape(n_thr, cells).copy()
+        return {"exceed": exceed, "mean": host[o_mean:o_std].copy(), "std": host[o_std:o_order].copy(),
+                "order": host[o_order:o_wet].reshape(n_rk, cells).copy(), "wet_area": host[o_wet:].reshape(members, n_thr).copy()}
+
+    # ---- the whole chain ------------------------------------------------------------------------------------------------------------------
+    def evaluate(self, x_test, ranges, members: int, thresholds=(0.5,), quantiles=(0.05, 0.5, 0.95), seed=0, normals=None, cell_areas=None,
+                 include_noise: bool = True, route: str | None = None) -> EnsembleResult:
+        """``x_test (rows, d)``; ``ranges``: the events' ``(lo, hi)`` row ranges, ascending and disjoint; ``members``: S.  ``normals``: one
+        ``(K, S, rows_e)`` array per event instead of the generator seeded with ``seed``."""
+        route = DEFAULT_ROUTE if route is None else route
+        if route not in ROUTES:
+            raise ValueError(f"route must be one of {ROUTES}")
+        x = np.asarray(x_test)
+        if x.ndim != 2:
+            raise ValueError("x_test must be (rows, d)")
+        lo, hi = check_event_ranges(ranges, x.shape[0])
+        members = int(members)
+        thr, _ = check_stats_args(members, thresholds, ())
+        q = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
+        _, rk = check_stats_args(members, (), quantile_ranks(q, members))
+        if normals is not None and len(normals) != lo.size:
+            raise ValueError("one array of normals per event")
+        k, cells, ne = self.projector.spatial_mode_count, self.projector.n_cells, int(lo.size)
+        rng = None if normals is not None else np.random.default_rng(seed)
+        timer = StageTimer(STAGES)
+        counts = np.zeros((ne, thr.size, cells), dtype=np.int32)
+        mean, std = np.zeros((ne, cells)), np.zeros((ne, cells))
+        order = np.zeros((ne, rk.size, cells))
+        wet = np.zeros((ne, members, thr.size))
+        device_peaks = 0.0
+        for e, (a, b) in enumerate(zip(lo.tolist(), hi.tolist())):
+            rows = b - a
+            mean_dev = lc_dev = scores = peak = None
+            try:
+                mean_dev, lc_dev, _ = self.joint_dev(x[a:b], include_noise=include_noise)
+                timer.lap("joint")
+                zn = rng.standard_normal((k, members, rows)) if rng is not None else normals[e]  # (timed with its upload: "draw_upload")
+                scores = self.scores_dev(mean_dev, lc_dev, zn, members, rows, timer=timer)
+                peak = self.member_peaks_dev(scores, members, rows, route=route)
+                timer.lap("peaks")
+                device_peaks += self.last_device_peaks_ms if route == "fused" else 0.0
+                st = self.member_stats(peak, members, thr, rk, cell_areas)
+                timer.lap("stats")
+            finally:
+                for buf in (mean_dev, lc_dev, scores, peak):
+                    if buf is not None:
+                        buf.free()
+            counts[e], mean[e], std[e], order[e], wet[e] = st["exceed"], st["mean"], st["std"], st["order"], st["wet_area"]
+        timings = timer.finish()
+        if route == "fused":
+            timings["device_peaks"] = device_peaks
+        return EnsembleResult(counts / members, mean, std, order, wet, counts, thr, q, list(zip(lo.tolist(), hi.tolist())), members, route, timings)

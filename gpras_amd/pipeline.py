@@ -227,6 +227,22 @@ class DevicePipeline:
                 if buf is not None:
                     buf.free()
 
+    def peak_ensemble(self, x_test, hf_test_data_df_or_index, members: int, **kwargs):
+        """Maps of every event's PEAK from ``members`` joint posterior draws (``gpras_amd.ensemble``): exceedance probabilities, mean, standard
+        deviation and quantiles of the peak per cell and the wet area per member.  The events come from the two-level ``(event, timestep)``
+        index of ``hf_test_data_df_or_index`` (a data frame or the index itself, one entry per row of ``x_test``); ``kwargs`` are those of
+        ``PeakEnsemble.evaluate``.  Returns its ``EnsembleResult`` with the events' labels in ``names``."""
+        from .diagnostics import event_ranges
+        from .ensemble import PeakEnsemble
+
+        index = getattr(hf_test_data_df_or_index, "index", hf_test_data_df_or_index)
+        if callable(index) or len(index) != np.shape(x_test)[0]:
+            raise ValueError("x_test and the index must have one row per test timestep")
+        names, ranges = event_ranges(index)
+        result = PeakEnsemble(self.gpr, self.projector).evaluate(x_test, ranges, members, **kwargs)
+        result.names = list(names)
+        return result
+
     # ---- pipeline.py:90-210 (gen_plots) -----------------------------------------------------------------------------------------
     def diagnostics(self, x_test, hf_test_data_df, lf_test_data=None, n_points: int = 2048, wet_threshold_depth: float = 0.0,
                     include_correct_negative: bool = True) -> dict:

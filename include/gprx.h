@@ -371,6 +371,17 @@ int gprx_predict_batch_t(gprx_handle h, int count, const int* units, const doubl
 int gprx_predict_batch_dev(gprx_handle h, int count, const int* units, const double* thetas, const double* z, const double* xs_dev, int64_t ns,
                            double* means_dev, double* vars_dev, int include_noise);
 
+/* The JOINT predictive distribution of the same cells over the test points of ONE event: means_dev (count, ns) as above (equal to
+ * gprx_predict_batch_dev's bit for bit: tested, for lone cells too, which that call evaluates through the single-model entry) and lc_dev (count, Tp, Tp), Tp = ns rounded up to 64: per cell the lower Cholesky factor of
+ *   C = Kss - tmp1^T tmp1 + tmp2^T tmp2 + noise I,   tmp1 = L^-1 Kus,  tmp2 = LB^-1 tmp1
+ * (gpflow SGPR.predict_f with full_cov), zeros above the diagonal, the identity on the padding.  include_noise == 0: the noise is left
+ * out and jitter * variance (jitter = 1e-6, the library's Kuu jitter) goes on the diagonal instead before the factorisation: the
+ * noise-free covariance of correlated rows is singular to working precision.  Sparse models with M <= 320, 1 <= ns <= 1024, d <= 64;
+ * anything else is GPRX_EINVAL before any device work.  A non-positive pivot is GPRX_ENOTPD, the message names the cell.  The call
+ * synchronises. */
+int gprx_predict_joint_batch_dev(gprx_handle h, int count, const int* units, const double* thetas, const double* z, const double* xs_dev, int64_t ns,
+                                 double* means_dev, double* lc_dev, int include_noise);
+
 /* The reference's Adam driver (gpr.py:147-173: tf.keras.optimizers.Adam() defaults, at most max_iter steps, early stop once the
  * relative improvement of the loss stayed <= 1e-5 for more than 50 consecutive steps) for `count` cells in lock step.
  * Sparse models with M <= 64 (round 5): the loop is RESIDENT ON THE DEVICE -- variables, moments, best loss and patience counters
@@ -547,6 +558,34 @@ int gprx_pca_sweep_dev(gprx_pca_handle p, const double* mean_dev, const double* 
 /* device milliseconds of the last gprx_pca_sweep_dev of this handle; the counts one launch of it carries */
 int gprx_pca_sweep_ms(gprx_pca_handle p, double* ms);
 int gprx_pca_sweep_group(void);
+/* Peak ensembles: members of a predictive distribution in EOF-score space pushed through the field chain of ONE event and reduced to the
+ * event's peak per (member, cell), without writing a field.  scores_dev: (members * rows_e, k), member s in rows [s rows_e, (s + 1) rows_e)
+ * -- the (rows, k) layout gprx_pca_reverse_dev reads; depth_mode as for gprx_pca_sweep_dev; member_group: members a workgroup carries, 0 for
+ * the launcher's choice (gprx_pca_ensemble_group), else 1..64; peak_dev: (members, n_cells).  peak[s, c] is, bit for bit and whatever the
+ * grouping, the first maximum over the rows of member s of gprx_pca_reverse_dev -> gprx_pca_to_depth_dev on that member's rows.
+ * members * rows_e < 2^31.  The call synchronises; gprx_pca_ensemble_ms: device milliseconds of the last one. */
+int gprx_pca_ensemble_peaks_dev(gprx_pca_handle p, const double* scores_dev, int64_t members, int64_t rows_e, int depth_mode, int member_group,
+                                double* peak_dev);
+int gprx_pca_ensemble_ms(gprx_pca_handle p, double* ms);
+/* Draws into that layout: scores[(s rows_e + t) k + kk] = mean[kk, t] + w[kk, s, t] for t < rows_e; mean_dev (k, rows_e) and the factor of
+ * gprx_predict_joint_batch_dev give w_dev (k, members, tp) = Zn Lc^T through gprx_gemm_batched.  Asynchronous on the projector's stream. */
+int gprx_pca_pack_scores_dev(gprx_pca_handle p, const double* mean_dev, const double* w_dev, int64_t members, int64_t rows_e, int64_t tp,
+                             double* scores_dev);
+int gprx_pca_ensemble_group(gprx_pca_handle p, int64_t members, int* group);
+/* The last step of the same result on the existing kernels: field_dev (members * rows_e, n_cells) as gprx_pca_reverse_dev and
+ * gprx_pca_to_depth_dev leave it; peak_dev (members, n_cells): per member the first maximum over its rows (a NaN is the maximum, as
+ * gprx_metrics_dev has it).  At most 65535 members per call.  Asynchronous on the projector's stream. */
+int gprx_pca_member_peaks_dev(gprx_pca_handle p, const double* field_dev, int64_t members, int64_t rows_e, double* peak_dev);
+/* Statistics over the members of peak_dev (members, n_cells), 1 <= members <= 4096, every sum in member order:
+ *   exceed (n_thr, n_cells) int32: the count of peak > thresholds[j] (strict), n_thr <= 8 (host array, no NaN)
+ *   mean (n_cells): the plain sum over s = 0, 1, ... divided by members;  std (n_cells): sqrt of the sum of the squared deviations from
+ *     that mean (second pass, each a rounded product then a rounded addition) divided by members (ddof = 0)
+ *   order (n_rank, n_cells): the order statistics np.sort(peak, axis=0)[ranks[j]], exactly; n_rank <= 8 ranks in [0, members) (host array)
+ *   wet_area (members, n_thr): sum over the cells of area[c] [peak[s, c] > thresholds[j]]; area_dev (n_cells) NULL: every area 1.0, the
+ *     sum is an exact count.  Fixed order (lanes of a wave, waves of a workgroup, workgroups ascending): repeated calls give the same bits.
+ * exceed / wet_area may be NULL when n_thr = 0, order when n_rank = 0.  The call synchronises.  GPRX_EINVAL leaves the handle usable. */
+int gprx_pca_member_stats_dev(gprx_pca_handle p, const double* peak_dev, int64_t members, int n_thr, const double* thresholds, int n_rank, const int* ranks,
+                              const double* area_dev, int* exceed_dev, double* mean_dev, double* std_dev, double* order_dev, double* wet_area_dev);
 
 /* ---- fitting the EOF preprocessor: PreProcessor.fit (gpras/preprocess.py:947-1007) --------------------------------------- */
 /* The fitted state gprx_pca_create takes, computed on the device.  Single-batch IncrementalPCA (sklearn partial_fit, first

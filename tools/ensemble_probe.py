@@ -1,0 +1,117 @@
+"""Peak ensemble at a production shape: the fused peak kernel against ``route="refield"`` (reverse -> depth -> per-member row maximum on
+the existing kernels), alternating, by the stage timer of ``PeakEnsemble.evaluate`` (host milliseconds around work that ends in a
+synchronisation) and the device time of the fused launches.
+
+    python tools/ensemble_probe.py [--events 35] [--event-rows 86] [--cells 100000] [--modes 50] [--members 256] [--repeats 3]
+                                   [--out profiles/ensemble_peaks.json]
+
+A ``GPRAS`` of ``--modes`` sparse models (M = 50, a few Adam steps: the probe times the prediction side) feeds ``PeakEnsemble.evaluate``.
+The first round warms both routes up and compares them (every output bit for bit), so that a faster number is a number for the same
+answer.  The FMA rate counts the fused multiply-adds the result needs -- members x rows x cells x modes -- over the device time of the
+fused kernel, against the 78.6 TFLOP/s (39.3 T fma/s) AMD quotes for fp64 vector work on this part; the draw + upload share is the host
+time of generating the normals and sending them up over the whole call."""
+
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+FP64_VECTOR_PEAK_FMA = 39.3e12
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--events", type=int, default=35)
+    ap.add_argument("--event-rows", type=int, default=86)
+    ap.add_argument("--cells", type=int, default=100_000)
+    ap.add_argument("--modes", type=int, default=50)
+    ap.add_argument("--members", type=int, default=256)
+    ap.add_argument("--train-rows", type=int, default=1000)
+    ap.add_argument("--features", type=int, default=8)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--hydraulic-parameter", default="wse")
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+
+    from gpras_amd.ensemble import PeakEnsemble
+    from gpras_amd.gpr import GPRAS
+    from gpras_amd.preprocess import EOFProjector
+    from gpras_amd.synth import make_regression
+
+    rng = np.random.default_rng(0)
+    cells, k, rows, members = args.cells, args.modes, args.events * args.event_rows, args.members
+    dry = np.zeros(cells, dtype=bool)
+    dry[rng.choice(cells, size=cells // 50, replace=False)] = True
+    n_wet = int(cells - dry.sum())
+    elev = rng.uniform(0.0, 2.0, size=cells)
+    proj = EOFProjector(dry, elev, rng.uniform(0.2, 1.0, size=n_wet) + elev[~dry], rng.uniform(0.5, 1.5, size=n_wet),
+                        rng.standard_normal((k, n_wet)) / np.sqrt(n_wet), rng.standard_normal(k) * 0.1, rng.uniform(0.5, 2.0, size=k) * np.sqrt(n_wet) * 0.05,
+                        hydraulic_parameter=args.hydraulic_parameter)
+    x, y, xs = make_regression(args.train_rows, args.features, n_outputs=k, n_test=rows, config=7)
+    gpr = GPRAS("Matern32")
+    gpr.fit(x, y, 50, "kmeans", "adam", max_iter=3)
+    ranges = [(i * args.event_rows, (i + 1) * args.event_rows) for i in range(args.events)]
+    ens = PeakEnsemble(gpr, proj)
+    # the generator's share alone: the normals of one call, drawn as evaluate draws them
+    t0 = time.perf_counter()
+    g = np.random.default_rng(1)
+    for _ in ranges:
+        g.standard_normal((k, members, args.event_rows))
+    draw_ms = (time.perf_counter() - t0) * 1e3
+
+    def run(route):
+        return ens.evaluate(xs, ranges, members, thresholds=(0.5, 1.0), quantiles=(0.05, 0.5, 0.95), seed=1, route=route)
+
+    stages = {"fused": [], "refield": []}
+    same = None
+    for rep in range(args.repeats + 1):
+        for route in ("fused", "refield") if rep % 2 == 0 else ("refield", "fused"):
+            res = run(route)
+            if rep == 0:
+                if route == "fused":
+                    keep = res
+                else:
+                    same = all(np.array_equal(getattr(keep, n), getattr(res, n)) for n in ("exceed_counts", "peak_mean", "peak_std", "peak_quantiles", "wet_area"))
+            else:
+                stages[route].append(res.last_timings_ms)
+
+    def med(route, key):
+        return statistics.median(t[key] for t in stages[route])
+
+    fmas = float(members) * rows * cells * k
+    keys = ("joint", "draw_upload", "draws", "peaks", "stats", "total")
+    out = {
+        "shape": {"events": args.events, "event_rows": args.event_rows, "rows": rows, "cells": cells, "modes": k, "members": members,
+                  "train_rows": args.train_rows, "inducing": 50, "hydraulic_parameter": args.hydraulic_parameter},
+        "repeats": args.repeats, "routes_agree_bit_for_bit": bool(same),
+        "stage_ms_median": {route: {key: med(route, key) for key in keys} for route in stages},
+        "peaks_ms": {route: {"median": med(route, "peaks"), "min": min(t["peaks"] for t in stages[route]), "max": max(t["peaks"] for t in stages[route])}
+                     for route in stages},
+        "fused_device_peaks_ms_median": med("fused", "device_peaks"),
+        "fma_count": fmas,
+        "fp64_vector_peak_fma_per_s": FP64_VECTOR_PEAK_FMA,
+        "host_normals_ms": draw_ms,
+    }
+    out["fused_fma_per_s"] = fmas / (out["fused_device_peaks_ms_median"] * 1e-3)
+    out["fused_share_of_fp64_vector_peak"] = out["fused_fma_per_s"] / FP64_VECTOR_PEAK_FMA
+    out["speedup_refield_over_fused_peaks_stage"] = out["peaks_ms"]["refield"]["median"] / out["peaks_ms"]["fused"]["median"]
+    out["speedup_refield_over_fused_total"] = med("refield", "total") / med("fused", "total")
+    out["draw_upload_share_of_total"] = {route: med(route, "draw_upload") / med(route, "total") for route in stages}
+    text = json.dumps(out, indent=1, sort_keys=True)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+    proj.close()
+
+
+if __name__ == "__main__":
+    main()
