@@ -111,6 +111,8 @@ PROTOTYPES = {
     "gprx_pca_ensemble_ms": (C.c_int, [_vp, _dp]),
     "gprx_pca_pack_scores_dev": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp]),
     "gprx_pca_ensemble_group": (C.c_int, [_vp, _i64, _ip]),
+    "gprx_pca_normals_dev": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _i64, _i64, _i64, _i64, _i64, _i64, C.c_int, _vp]),
+    "gprx_pca_normal_transform_dev": (C.c_int, [_vp, _vp, _i64, _vp]),
     "gprx_pca_member_peaks_dev": (C.c_int, [_vp, _vp, _i64, _i64, _vp]),
     "gprx_pca_member_stats_dev": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gprx_pcafit_create": (C.c_int, [C.c_int, _vp, _i64, _i64, _vp, _vp, C.c_int, C.c_double, C.POINTER(_vp)]),

@@ -399,6 +399,42 @@ int gprx_pca_pack_scores_dev(gprx_pca_handle p, const double* mean_dev, const do
   });
 }
 
+int gprx_pca_normals_dev(gprx_pca_handle p, uint64_t seed, uint64_t stream, int64_t event, int64_t member0, int64_t members, int64_t pair_offset,
+                         int64_t rows_e, int64_t tp, int raw, double* zn_dev) {
+  return guarded(p, [&]() -> int {
+    if (!p) return fail(p, GPRX_EINVAL, "null handle");
+    if (!zn_dev) return fail(p, GPRX_EINVAL, "null argument");
+    if ((uintptr_t)zn_dev % 16) return fail(p, GPRX_EINVAL, "the block of normals must be 16-byte aligned");
+    int rc;
+    if ((rc = check_members(p, members, rows_e))) return rc;
+    if (tp < rows_e) return fail(p, GPRX_EINVAL, "the padded row count is smaller than the event's rows");
+    if (tp % 64) return fail(p, GPRX_EINVAL, "the padded row count must be a multiple of 64");
+    if (member0 < 0 || member0 > ENS_SMAX - members) return fail(p, GPRX_EINVAL, "the members must lie in [0, " + std::to_string(ENS_SMAX) + ")");
+    if (event < 0) return fail(p, GPRX_EINVAL, "the event index must not be negative");
+    if (pair_offset < 0) return fail(p, GPRX_EINVAL, "pair_offset must be 0 (off) or positive");
+    if (pair_offset && member0 + members > 2 * pair_offset) return fail(p, GPRX_EINVAL, "with pair_offset set the members must lie below 2 pair_offset");
+    HIPCHK(p, hipSetDevice(p->device));
+    NormalsArgs a{seed, stream, event, member0, members, pair_offset, rows_e, tp, p->k, raw ? 1 : 0, reinterpret_cast<unsigned long long*>(zn_dev)};
+    const int64_t total = (int64_t)p->k * members * (tp / 4);
+    hipLaunchKernelGGL(ensemble_normals_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 8192)), dim3(256), 0, p->stream, a);
+    HIPCHK(p, hipGetLastError());
+    return GPRX_OK;
+  });
+}
+
+int gprx_pca_normal_transform_dev(gprx_pca_handle p, const uint64_t* words_dev, int64_t n, double* z_dev) {
+  return guarded(p, [&]() -> int {
+    if (!p) return fail(p, GPRX_EINVAL, "null handle");
+    if (!words_dev || !z_dev) return fail(p, GPRX_EINVAL, "null argument");
+    if (n < 1 || n >= ((int64_t)1 << 31)) return fail(p, GPRX_EINVAL, "the word count must be positive and below 2^31");
+    HIPCHK(p, hipSetDevice(p->device));
+    hipLaunchKernelGGL(ensemble_normal_transform_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 8192)), dim3(256), 0, p->stream,
+                       reinterpret_cast<const unsigned long long*>(words_dev), n, z_dev);
+    HIPCHK(p, hipGetLastError());
+    return GPRX_OK;
+  });
+}
+
 int gprx_pca_ensemble_ms(gprx_pca_handle p, double* ms) {
   if (!p || !ms) return fail(p, GPRX_EINVAL, "null argument");
   *ms = p->ens_ms;

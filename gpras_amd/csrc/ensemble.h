@@ -17,8 +17,12 @@
 // waves per SIMD; <16> 80 VGPRs, six waves; no scratch.
 //
 // member_cell_stats_kernel, member_area_kernel, member_area_sum_kernel: the statistics over the members, all in fixed orders.
+//
+// ensemble_normals_kernel: the standard normals of an event drawn by address (normals.h: Philox4x64-10, AS 241), in place of the host
+// generator and its upload.  gfx950: 122 VGPRs, four waves per SIMD, no scratch, no LDS.
 #pragma once
 #include "gprx_common.h"
+#include "normals.h"
 #include "pca.h"
 
 namespace gprx {
@@ -120,6 +124,52 @@ __global__ __launch_bounds__(256) void ensemble_pack_kernel(const double* __rest
     const int64_t st = i / k, s = st / rows_e, t = st - s * rows_e;
     scores[i] = mean[(int64_t)kk * rows_e + t] + W[((int64_t)kk * members + s) * tp + t];
   }
+}
+
+// The standard normals of one event, made where they are used: zn (k, members, tp), zn[kk, sl, t] = the draw of address (seed, stream, event,
+// mode kk, member member0 + sl, row t) of normals.h for t < rows_e, an exact zero beyond (those columns meet the identity padding of Lc).
+// A thread owns one Philox block, four consecutive t of one (kk, sl) -- tp is a multiple of 64, so no block straddles a row -- and writes
+// its 32 bytes with two 16-byte stores: consecutive lanes, consecutive 32 bytes.  Blocks wholly in the padding skip the generator.
+// pair_offset = h > 0: the absolute member s >= h reads the counter of member s - h and flips the sign bit (-z bit for bit).  raw: the
+// 64-bit words of the counter read instead of the normals, the sign flip left out.
+struct NormalsArgs {
+  uint64_t seed, stream;
+  int64_t event, member0, members, pair_offset, rows_e, tp;
+  int k, raw;
+  unsigned long long* zn;  // (k, members, tp): doubles, or the words when raw
+};
+__global__ __launch_bounds__(256) void ensemble_normals_kernel(NormalsArgs p) {
+  const int64_t bpr = p.tp >> 2;  // blocks per (mode, member) row
+  const int64_t total = (int64_t)p.k * p.members * bpr;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int64_t b = i % bpr, ks = i / bpr, sl = ks % p.members, kk = ks / p.members;
+    int64_t s = p.member0 + sl;
+    const bool negate = p.pair_offset > 0 && s >= p.pair_offset;
+    if (negate) s -= p.pair_offset;
+    const int64_t t0 = b << 2;
+    unsigned long long out[4] = {0ull, 0ull, 0ull, 0ull};
+    if (t0 < p.rows_e) {
+      uint64_t w[4];
+      nrm_block(p.seed, p.stream, (uint64_t)p.event, (uint64_t)kk, (uint64_t)s, (uint64_t)t0, w);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (t0 + j >= p.rows_e) continue;
+        if (p.raw) {
+          out[j] = w[j];
+        } else {
+          const unsigned long long zb = (unsigned long long)__double_as_longlong(nrm_normal(w[j]));
+          out[j] = negate ? zb ^ 0x8000000000000000ull : zb;
+        }
+      }
+    }
+    ulonglong2* dst = reinterpret_cast<ulonglong2*>(p.zn + (i << 2));  // (the block (kk, sl, b) starts at element 4 i; 16-byte aligned with zn)
+    dst[0] = make_ulonglong2(out[0], out[1]);
+    dst[1] = make_ulonglong2(out[2], out[3]);
+  }
+}
+// z[i] = the normal of word w[i] by the same inline transform: the way in for words no draw reaches (the far tail r > 5 needs u < 1.4e-11)
+__global__ __launch_bounds__(256) void ensemble_normal_transform_kernel(const unsigned long long* __restrict__ w, int64_t n, double* __restrict__ z) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) z[i] = nrm_normal((uint64_t)w[i]);
 }
 
 // The last step of the refield route: peak[s, c] = the first maximum over the rows_e rows of member s of a resident field

@@ -11,7 +11,9 @@ maximum over an event's rows does not follow from marginals: the GP's prediction
   factor ``Lc`` of the joint predictive covariance ``Kss - tmp1^T tmp1 + tmp2^T tmp2`` (the quantities of gpflow's ``SGPR.predict_f`` with
   the diagonal kept joint), padded with the identity to ``Tp`` = rows rounded up to 64;
 * standard normals ``Zn (K, S, Tp)`` from the caller or from ``np.random.default_rng(seed)``, drawn event by event in the order of
-  ``ranges`` as ``rng.standard_normal((K, S, rows))``; ``W_k = Zn_k Lc_k^T`` by the batched fp64 GEMM and one packing kernel give the
+  ``ranges`` as ``rng.standard_normal((K, S, rows))`` -- or, with ``rng="device"``, drawn on the device by address
+  (``gprx_pca_normals_dev``, csrc/normals.h: Philox4x64-10 and Wichura's AS 241; a draw is a function of seed, stream, event, mode, member
+  and row alone); ``W_k = Zn_k Lc_k^T`` by the batched fp64 GEMM and one packing kernel give the
   members' scores ``(S rows, K)``.  Modes are independent of each other, as the reference's variance propagation assumes, and so are events;
 * ``route="fused"``: ``gprx_pca_ensemble_peaks_dev`` (csrc/ensemble.h) walks every member's rows per cell and writes only
   ``peak (S, cells)``;  ``route="refield"``: the same numbers, bit for bit, from ``gprx_pca_reverse_dev`` -> ``gprx_pca_to_depth_dev`` on
@@ -35,6 +37,12 @@ from .diagnostics import check_ranges
 
 ROUTES = ("fused", "refield")
 DEFAULT_ROUTE = "fused"  # the route measured faster at the production shape (profiles/ensemble_peaks.json)
+RNGS = ("host", "device")
+# "host" keeps the bits every earlier release drew (np.random.default_rng(seed), one sequential stream); "device" draws by address on the
+# GPU (csrc/normals.h) and removes the host generator and the upload from the call -- measured in one run at the production shape
+# (profiles/ensemble_rng.json): the draw_upload stage 300 ms against 3.1 ms, the whole call 1.05 s against 0.73 s.
+# The default stays "host" so that a seed keeps its draws.
+DEFAULT_RNG = "host"
 DEPTH_MODES = {"velocity": 0, "wse": 1, "depth": 2}
 JOINT_MAX_M, JOINT_MAX_ROWS, JOINT_MAX_D = 320, 1024, 64
 MAX_MEMBERS, MAX_THRESHOLDS, MAX_RANKS = 4096, 8, 8
@@ -90,6 +98,18 @@ def check_stats_args(members: int, thresholds, ranks):
     return thr, rk
 
 
+def check_seed(value, name: str) -> int:
+    """``value`` as the unsigned 64-bit integer a key word of the device generator is."""
+    try:
+        v = int(value)
+        ok = v == value and 0 <= v < 2**64
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{name} must be an integer in [0, 2**64)")
+    return v
+
+
 def check_event_ranges(ranges, rows: int):
     """The events' ``(lo, hi)`` as int64 arrays: non-empty, inside ``[0, rows]``, in ascending order and disjoint."""
     lo, hi = check_ranges(ranges, rows)
@@ -119,6 +139,7 @@ class EnsembleResult:
     route: str
     last_timings_ms: dict = field(default_factory=dict)
     names: list = field(default_factory=list)  # the events' labels (``DevicePipeline.peak_ensemble``)
+    rng: str = DEFAULT_RNG  # where the normals were drawn ("host" also when the caller passed ``normals``)
 
 
 class PeakEnsemble:
@@ -178,22 +199,61 @@ class PeakEnsemble:
         return mean, lc, rows
 
     # ---- 2. draws -----------------------------------------------------------------------------------------------------------------------
+    def normals_dev(self, event: int, members: int, rows: int, seed: int = 0, stream: int = 0, antithetic: bool = False, member0: int = 0,
+                    raw: bool = False) -> DeviceBuffer:
+        """The standard normals ``(K, members, Tp)`` of event ``event`` on the device, as ``scores_dev`` takes them: the draw of
+        ``(seed, stream, event, mode, member0 + slot, row)`` by ``gprx_pca_normals_dev`` (include/gprx.h has the addressing), exact zeros in the
+        columns ``rows <= t < Tp``.  ``antithetic``: the second half of the ``members`` (counted from member 0; ``members`` even) is the exact
+        negation of the first; a slice ``member0, members`` of a larger antithetic ensemble passes ``antithetic=`` that ensemble's half size.
+        ``raw``: the generator's 64-bit words instead (``to_array(...).view(np.uint64)``).  The caller frees the buffer."""
+        event, members, rows, member0 = int(event), int(members), int(rows), int(member0)
+        seed, stream = check_seed(seed, "seed"), check_seed(stream, "stream")
+        if members < 1 or rows < 1:
+            raise ValueError("members and rows must be positive")
+        if isinstance(antithetic, (bool, np.bool_)):
+            if antithetic and (member0 != 0 or members % 2):
+                raise ValueError("antithetic=True pairs the halves of an even number of members counted from member 0; pass the half size for a slice")
+            pair = members // 2 if antithetic else 0
+        else:
+            pair = int(antithetic)
+        k, tp = self.projector.spatial_mode_count, padded_rows(rows)
+        zbuf = DeviceBuffer(8 * k * members * tp, self.device)
+        try:
+            rc = self._lib.gprx_pca_normals_dev(self.projector.handle, seed, stream, event, member0, members, pair, rows, tp, int(bool(raw)), zbuf.ptr)
+            if rc == _lib.GPRX_EINVAL:
+                raise ValueError((self._lib.gprx_pca_last_error(self.projector.handle) or b"").decode())
+            check(rc)
+            # the batched GEMM that reads the block runs on the library's utility stream, not the projector's: hand over a finished block
+            check(self._lib.gprx_pca_synchronize(self.projector.handle))
+        except Exception:
+            zbuf.free()
+            raise
+        return zbuf
+
     def scores_dev(self, mean_dev, lc_dev, normals, members: int, rows: int, timer: StageTimer | None = None) -> DeviceBuffer:
         """The members' scores ``(S rows, K)`` on the device: ``scores[s, t, k] = mean[k, t] + (Zn_k Lc_k^T)[s, t]``.  ``normals``: ``(K, S, rows)``
-        or ``(K, S, Tp)`` standard normals on the host (the columns beyond ``rows`` meet the identity padding and are not read back)."""
+        or ``(K, S, Tp)`` standard normals on the host (the columns beyond ``rows`` meet the identity padding and are not read back), or a
+        ``DeviceBuffer`` of the ``(K, S, Tp)`` block with zeros in those columns (``normals_dev``): nothing is staged or uploaded then, and
+        the buffer stays the caller's."""
         k, tp, dev = self.projector.spatial_mode_count, padded_rows(rows), self.device
-        zn = np.asarray(normals, dtype=np.float64)
-        if zn.ndim != 3 or zn.shape[:2] != (k, members) or zn.shape[2] not in (rows, tp):
-            raise ValueError(f"normals must be ({k}, {members}, {rows}) or ({k}, {members}, {tp})")
-        zp = np.zeros((k, members, tp))
-        zp[:, :, : zn.shape[2]] = zn
+        resident = isinstance(normals, DeviceBuffer)
+        if resident:
+            if normals.nbytes < 8 * k * members * tp:
+                raise ValueError(f"the normals buffer must hold ({k}, {members}, {tp}) doubles")
+        else:
+            zn = np.asarray(normals, dtype=np.float64)
+            if zn.ndim != 3 or zn.shape[:2] != (k, members) or zn.shape[2] not in (rows, tp):
+                raise ValueError(f"normals must be ({k}, {members}, {rows}) or ({k}, {members}, {tp})")
+            zp = np.zeros((k, members, tp))
+            zp[:, :, : zn.shape[2]] = zn
         zbuf = wbuf = scores = None
         try:
-            zbuf = DeviceBuffer.from_array(zp, dev)
+            zbuf = normals if resident else DeviceBuffer.from_array(zp, dev)
             wbuf = DeviceBuffer(8 * k * members * tp, dev)
             scores = DeviceBuffer(8 * members * rows * k, dev)
             if timer is not None:
-                timer.link_bytes += zbuf.nbytes
+                if not resident:
+                    timer.link_bytes += zbuf.nbytes
                 timer.lap("draw_upload")
             # W_k (S, Tp) = Zn_k (S, Tp) . Lc_k^T: the (0, 1) form, op(B) = Lc^T upper triangular (Lc's strict upper triangle is zero)
             check(self._lib.gprx_gemm_batched(dev, 0, 1, members, tp, tp, 1.0, zbuf.ptr, tp, lc_dev.ptr if hasattr(lc_dev, "ptr") else lc_dev, tp, 0.0,
@@ -206,7 +266,7 @@ class PeakEnsemble:
                 scores.free()
             raise
         finally:
-            for buf in (zbuf, wbuf):
+            for buf in (wbuf,) if resident else (zbuf, wbuf):
                 if buf is not None:
                     buf.free()
         if timer is not None:
@@ -297,12 +357,27 @@ class PeakEnsemble:
 
     # ---- the whole chain ------------------------------------------------------------------------------------------------------------------
     def evaluate(self, x_test, ranges, members: int, thresholds=(0.5,), quantiles=(0.05, 0.5, 0.95), seed=0, normals=None, cell_areas=None,
-                 include_noise: bool = True, route: str | None = None) -> EnsembleResult:
+                 include_noise: bool = True, route: str | None = None, rng: str = DEFAULT_RNG, stream=0, antithetic: bool = False) -> EnsembleResult:
         """``x_test (rows, d)``; ``ranges``: the events' ``(lo, hi)`` row ranges, ascending and disjoint; ``members``: S.  ``normals``: one
-        ``(K, S, rows_e)`` array per event instead of the generator seeded with ``seed``."""
+        ``(K, S, rows_e)`` array per event instead of the generator seeded with ``seed``.  ``rng="host"``: ``np.random.default_rng(seed)``, one
+        sequential stream over the events; ``rng="device"``: event ``e`` takes ``normals_dev(e, members, rows_e, seed, stream, antithetic)`` --
+        every draw a function of ``(seed, stream, e, mode, member, row)`` alone, so the members of a smaller ensemble are the first members
+        of a larger one; ``antithetic`` (device only, ``members`` even): member ``s + S / 2`` draws the negation of member ``s``."""
         route = DEFAULT_ROUTE if route is None else route
         if route not in ROUTES:
             raise ValueError(f"route must be one of {ROUTES}")
+        if rng not in RNGS:
+            raise ValueError(f"rng must be one of {RNGS}")
+        if rng == "device" and normals is not None:
+            raise ValueError('normals were given: rng="device" would draw its own')
+        # (the host generator keeps taking whatever np.random.default_rng takes -- None, a sequence --; an integer is held to the key's range)
+        if rng == "device" or isinstance(seed, (int, np.integer)):
+            seed = check_seed(seed, "seed")
+        stream = check_seed(stream, "stream")
+        if antithetic and rng != "device":
+            raise ValueError('antithetic=True needs rng="device": the host stream has no member addressing to pair')
+        if antithetic and int(members) % 2:
+            raise ValueError("antithetic=True needs an even number of members")
         x = np.asarray(x_test)
         if x.ndim != 2:
             raise ValueError("x_test must be (rows, d)")
@@ -314,7 +389,7 @@ class PeakEnsemble:
         if normals is not None and len(normals) != lo.size:
             raise ValueError("one array of normals per event")
         k, cells, ne = self.projector.spatial_mode_count, self.projector.n_cells, int(lo.size)
-        rng = None if normals is not None else np.random.default_rng(seed)
+        host_rng = np.random.default_rng(seed) if rng == "host" and normals is None else None
         timer = StageTimer(STAGES)
         counts = np.zeros((ne, thr.size, cells), dtype=np.int32)
         mean, std = np.zeros((ne, cells)), np.zeros((ne, cells))
@@ -323,11 +398,15 @@ class PeakEnsemble:
         device_peaks = 0.0
         for e, (a, b) in enumerate(zip(lo.tolist(), hi.tolist())):
             rows = b - a
-            mean_dev = lc_dev = scores = peak = None
+            mean_dev = lc_dev = scores = peak = zn = None
             try:
                 mean_dev, lc_dev, _ = self.joint_dev(x[a:b], include_noise=include_noise)
                 timer.lap("joint")
-                zn = rng.standard_normal((k, members, rows)) if rng is not None else normals[e]  # (timed with its upload: "draw_upload")
+                # (timed with its upload, where there is one: "draw_upload")
+                if rng == "device":
+                    zn = self.normals_dev(e, members, rows, seed, stream, bool(antithetic))
+                else:
+                    zn = host_rng.standard_normal((k, members, rows)) if host_rng is not None else normals[e]
                 scores = self.scores_dev(mean_dev, lc_dev, zn, members, rows, timer=timer)
                 peak = self.member_peaks_dev(scores, members, rows, route=route)
                 timer.lap("peaks")
@@ -335,11 +414,12 @@ class PeakEnsemble:
                 st = self.member_stats(peak, members, thr, rk, cell_areas)
                 timer.lap("stats")
             finally:
-                for buf in (mean_dev, lc_dev, scores, peak):
+                for buf in (mean_dev, lc_dev, scores, peak, zn if rng == "device" else None):
                     if buf is not None:
                         buf.free()
             counts[e], mean[e], std[e], order[e], wet[e] = st["exceed"], st["mean"], st["std"], st["order"], st["wet_area"]
         timings = timer.finish()
         if route == "fused":
             timings["device_peaks"] = device_peaks
-        return EnsembleResult(counts / members, mean, std, order, wet, counts, thr, q, list(zip(lo.tolist(), hi.tolist())), members, route, timings)
+        return EnsembleResult(counts / members, mean, std, order, wet, counts, thr, q, list(zip(lo.tolist(), hi.tolist())), members, route, timings,
+                              rng=rng)

@@ -572,6 +572,24 @@ int gprx_pca_ensemble_ms(gprx_pca_handle p, double* ms);
 int gprx_pca_pack_scores_dev(gprx_pca_handle p, const double* mean_dev, const double* w_dev, int64_t members, int64_t rows_e, int64_t tp,
                              double* scores_dev);
 int gprx_pca_ensemble_group(gprx_pca_handle p, int64_t members, int* group);
+/* The standard normals of one event, generated on the device: zn_dev (k, members, tp) as gprx_gemm_batched reads it ahead of
+ * gprx_pca_pack_scores_dev, k the handle's mode count.  THE ADDRESSING IS THE CONTRACT: a draw is a pure function of
+ * (seed, stream, event, mode, member, row) and of nothing else -- not of k, members, rows_e, member0 or the order of the calls:
+ *   Philox4x64-10 (Random123's definition, the generator of numpy.random.Philox) with counter = (t >> 2, s, kk, e) and key = (seed, stream);
+ *   the draw of row t is word w = t & 3 of that block;  e = event: the event's index in the caller's list of events, kk the mode, s the
+ *   ABSOLUTE member member0 + sl of slot sl;  seed and stream are unsigned 64-bit.
+ *   u = ((w >> 12) + 0.5) 2^-52, never 0 or 1;  z = PPND16(u), Wichura's algorithm AS 241 with every operation rounded once (csrc/normals.h).
+ * zn[kk, sl, t] is that z for t < rows_e and an exact zero for rows_e <= t < tp.  raw = 1: the 64-bit words themselves are written
+ * instead (read the block as uint64_t; the padding columns are zero words).  pair_offset = h > 0 (antithetic ensembles): the absolute
+ * member s >= h is the exact negation of member s - h -- the same counter, the sign bit flipped (raw: the same words); 0 switches it off.
+ * members >= 1, rows_e >= 1, members * rows_e < 2^31; tp >= rows_e, tp % 64 == 0; member0 >= 0, member0 + members <= 4096; event >= 0;
+ * pair_offset >= 0 and, when set, member0 + members <= 2 pair_offset; zn_dev 16-byte aligned.  GPRX_EINVAL leaves the handle usable.
+ * Asynchronous on the projector's stream. */
+int gprx_pca_normals_dev(gprx_pca_handle p, uint64_t seed, uint64_t stream, int64_t event, int64_t member0, int64_t members, int64_t pair_offset,
+                         int64_t rows_e, int64_t tp, int raw, double* zn_dev);
+/* z_dev[i] = the normal of the word words_dev[i], 0 <= i < n < 2^31, by the same transform (u, then PPND16): the way in for words that no
+ * draw reaches, the far tail and the two extreme words among them.  Asynchronous on the projector's stream. */
+int gprx_pca_normal_transform_dev(gprx_pca_handle p, const uint64_t* words_dev, int64_t n, double* z_dev);
 /* The last step of the same result on the existing kernels: field_dev (members * rows_e, n_cells) as gprx_pca_reverse_dev and
  * gprx_pca_to_depth_dev leave it; peak_dev (members, n_cells): per member the first maximum over its rows (a NaN is the maximum, as
  * gprx_metrics_dev has it).  At most 65535 members per call.  Asynchronous on the projector's stream. */

@@ -3,13 +3,18 @@ the existing kernels), alternating, by the stage timer of ``PeakEnsemble.evaluat
 synchronisation) and the device time of the fused launches.
 
     python tools/ensemble_probe.py [--events 35] [--event-rows 86] [--cells 100000] [--modes 50] [--members 256] [--repeats 3]
-                                   [--out profiles/ensemble_peaks.json]
+                                   [--rng host|device|both] [--out profiles/ensemble_peaks.json]
 
 A ``GPRAS`` of ``--modes`` sparse models (M = 50, a few Adam steps: the probe times the prediction side) feeds ``PeakEnsemble.evaluate``.
 The first round warms both routes up and compares them (every output bit for bit), so that a faster number is a number for the same
 answer.  The FMA rate counts the fused multiply-adds the result needs -- members x rows x cells x modes -- over the device time of the
 fused kernel, against the 78.6 TFLOP/s (39.3 T fma/s) AMD quotes for fp64 vector work on this part; the draw + upload share is the host
-time of generating the normals and sending them up over the whole call."""
+time of generating the normals and sending them up over the whole call.
+
+``--rng host`` (the default) and ``--rng device`` run that comparison of the routes with the one generator.  ``--rng both`` compares the
+generators instead (profiles/ensemble_rng.json): ``rng="host"`` -- ``np.random.default_rng`` and the upload, the route every earlier release
+took and the yardstick -- against ``rng="device"`` (``gprx_pca_normals_dev``), alternating in one run on the default route, by the same stage
+timer; ``draw_upload`` is the stage the generator is timed in."""
 
 from __future__ import annotations
 
@@ -27,6 +32,44 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 FP64_VECTOR_PEAK_FMA = 39.3e12
 
 
+def compare_generators(args, run, shape, draw_ms) -> None:
+    """``rng="host"`` against ``rng="device"`` on the default route, alternating; the first round warms both up."""
+    from gpras_amd.ensemble import DEFAULT_RNG, DEFAULT_ROUTE
+
+    stages = {"host": [], "device": []}
+    finite = True
+    for rep in range(args.repeats + 1):
+        for rng in ("host", "device") if rep % 2 == 0 else ("device", "host"):
+            res = run(DEFAULT_ROUTE, rng)
+            if rep == 0:
+                finite = finite and bool(np.all(np.isfinite(res.peak_mean)) and np.all(np.isfinite(res.peak_std)))
+            else:
+                stages[rng].append(res.last_timings_ms)
+
+    def med(rng, key):
+        return statistics.median(t[key] for t in stages[rng])
+
+    keys = ("joint", "draw_upload", "draws", "peaks", "stats", "total")
+    out = {
+        "shape": shape, "route": DEFAULT_ROUTE, "repeats": args.repeats, "outputs_finite": finite, "default_rng": DEFAULT_RNG,
+        "stage_ms_median": {rng: {key: med(rng, key) for key in keys} for rng in stages},
+        "total_ms": {rng: {"median": med(rng, "total"), "min": min(t["total"] for t in stages[rng]), "max": max(t["total"] for t in stages[rng])}
+                     for rng in stages},
+        "draw_upload_ms": {rng: {"median": med(rng, "draw_upload"), "min": min(t["draw_upload"] for t in stages[rng]),
+                                 "max": max(t["draw_upload"] for t in stages[rng])} for rng in stages},
+        "host_link_bytes": {rng: stages[rng][0]["host_link_bytes"] for rng in stages},
+        "host_normals_ms": draw_ms,
+        "normals_per_call": float(shape["modes"]) * shape["members"] * shape["rows"],
+    }
+    out["speedup_host_over_device_draw_upload"] = med("host", "draw_upload") / med("device", "draw_upload")
+    out["speedup_host_over_device_total"] = med("host", "total") / med("device", "total")
+    text = json.dumps(out, indent=1, sort_keys=True)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--events", type=int, default=35)
@@ -38,6 +81,7 @@ def main() -> None:
     ap.add_argument("--features", type=int, default=8)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--hydraulic-parameter", default="wse")
+    ap.add_argument("--rng", choices=("host", "device", "both"), default="host")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
 
@@ -67,8 +111,15 @@ def main() -> None:
         g.standard_normal((k, members, args.event_rows))
     draw_ms = (time.perf_counter() - t0) * 1e3
 
-    def run(route):
-        return ens.evaluate(xs, ranges, members, thresholds=(0.5, 1.0), quantiles=(0.05, 0.5, 0.95), seed=1, route=route)
+    def run(route, rng=args.rng):
+        return ens.evaluate(xs, ranges, members, thresholds=(0.5, 1.0), quantiles=(0.05, 0.5, 0.95), seed=1, route=route, rng=rng)
+
+    shape = {"events": args.events, "event_rows": args.event_rows, "rows": rows, "cells": cells, "modes": k, "members": members,
+             "train_rows": args.train_rows, "inducing": 50, "hydraulic_parameter": args.hydraulic_parameter}
+    if args.rng == "both":
+        compare_generators(args, run, shape, draw_ms)
+        proj.close()
+        return
 
     stages = {"fused": [], "refield": []}
     same = None
@@ -89,8 +140,7 @@ def main() -> None:
     fmas = float(members) * rows * cells * k
     keys = ("joint", "draw_upload", "draws", "peaks", "stats", "total")
     out = {
-        "shape": {"events": args.events, "event_rows": args.event_rows, "rows": rows, "cells": cells, "modes": k, "members": members,
-                  "train_rows": args.train_rows, "inducing": 50, "hydraulic_parameter": args.hydraulic_parameter},
+        "shape": shape, "rng": args.rng,
         "repeats": args.repeats, "routes_agree_bit_for_bit": bool(same),
         "stage_ms_median": {route: {key: med(route, key) for key in keys} for route in stages},
         "peaks_ms": {route: {"median": med(route, "peaks"), "min": min(t["peaks"] for t in stages[route]), "max": max(t["peaks"] for t in stages[route])}
