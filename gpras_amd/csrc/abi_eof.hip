@@ -16,6 +16,7 @@
 #include "pca_fit_tall.h"
 #include "sweep.h"
 #include "ensemble.h"
+#include "verify.h"
 
 using namespace gprx;
 
@@ -32,6 +33,7 @@ struct gprx_pca_ctx {
   double sweep_ms = 0.0;      // device time of the last gprx_pca_sweep_dev
   Buf ens_part;               // gprx_pca_member_stats_dev: per-workgroup wet areas
   double ens_ms = 0.0;        // device time of the last gprx_pca_ensemble_peaks_dev
+  double ver_ms = 0.0;        // device time of the last gprx_pca_member_verify_dev
   std::string err;
 };
 
@@ -504,6 +506,48 @@ int gprx_pca_member_stats_dev(gprx_pca_handle p, const double* peak_dev, int64_t
     HIPCHK(p, hipStreamSynchronize(st));
     return GPRX_OK;
   });
+}
+
+int gprx_pca_member_verify_dev(gprx_pca_handle p, const double* peak_dev, const double* obs_dev, int64_t members, int n_rank, const int* ranks,
+                               double* crps_dev, int* below_dev, int* equal_dev, double* order_dev) {
+  return guarded(p, [&]() -> int {
+    if (!p) return fail(p, GPRX_EINVAL, "null handle");
+    if (!peak_dev || !obs_dev || !crps_dev || !below_dev || !equal_dev) return fail(p, GPRX_EINVAL, "null argument");
+    if (members < 1 || members > ENS_SMAX) return fail(p, GPRX_EINVAL, "members must be between 1 and " + std::to_string(ENS_SMAX));
+    if (n_rank < 0 || n_rank > ENS_RMAX || (n_rank && (!ranks || !order_dev)))
+      return fail(p, GPRX_EINVAL, "at most " + std::to_string(ENS_RMAX) + " ranks, with their output block");
+    for (int j = 0; j < n_rank; ++j)
+      if (ranks[j] < 0 || ranks[j] >= members) return fail(p, GPRX_EINVAL, "ranks must lie in [0, members)");
+    HIPCHK(p, hipSetDevice(p->device));
+    hipStream_t st = p->stream;
+    MemberVerifyArgs a{};
+    a.peak = peak_dev, a.obs = obs_dev, a.members = members, a.cells = p->cells, a.n_rank = n_rank;
+    a.log_sp = verify_log_sp(members);
+    for (int j = 0; j < n_rank; ++j) a.rank[j] = ranks[j];
+    a.crps = crps_dev, a.below = below_dev, a.equal = equal_dev, a.order = order_dev;
+    const int64_t tile_cells = verify_tile_keys(a.log_sp) >> a.log_sp;
+    const dim3 grid((unsigned)((p->cells + tile_cells - 1) / tile_cells));
+    HIPCHK(p, hipEventRecord(p->ev[0], st));
+    if (verify_tile_keys(a.log_sp) == 8192) hipLaunchKernelGGL(member_verify_kernel<8192>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(member_verify_kernel<4096>, grid, dim3(256), 0, st, a);
+    HIPCHK(p, hipGetLastError());
+    HIPCHK(p, hipEventRecord(p->ev[1], st));
+    HIPCHK(p, hipStreamSynchronize(st));
+    p->ver_ms = elapsed_ms(p->ev[0], p->ev[1]);
+    return GPRX_OK;
+  });
+}
+
+int gprx_pca_member_verify_ms(gprx_pca_handle p, double* ms) {
+  if (!p || !ms) return fail(p, GPRX_EINVAL, "null argument");
+  *ms = p->ver_ms;
+  return GPRX_OK;
+}
+
+int gprx_pca_member_verify_tile(int64_t members, int* tile_cells) {
+  if (!tile_cells || members < 1 || members > ENS_SMAX) return fail(nullptr, GPRX_EINVAL, "members must be between 1 and " + std::to_string(ENS_SMAX));
+  *tile_cells = verify_tile_keys(verify_log_sp(members)) >> verify_log_sp(members);
+  return GPRX_OK;
 }
 
 int gprx_pca_synchronize(gprx_pca_handle p) {

@@ -18,9 +18,12 @@ maximum over an event's rows does not follow from marginals: the GP's prediction
 * ``route="fused"``: ``gprx_pca_ensemble_peaks_dev`` (csrc/ensemble.h) walks every member's rows per cell and writes only
   ``peak (S, cells)``;  ``route="refield"``: the same numbers, bit for bit, from ``gprx_pca_reverse_dev`` -> ``gprx_pca_to_depth_dev`` on
   slabs of whole members and a per-member row maximum;
-* ``gprx_pca_member_stats_dev``: exceedance counts, mean, standard deviation, order statistics and wet areas over the members.
+* ``gprx_pca_member_stats_dev``: exceedance counts, mean, standard deviation, order statistics and wet areas over the members;
+* with ``observed=`` the truth: ``gprx_pca_member_verify_dev`` (csrc/verify.h) sorts every cell's members on chip and scores them against the
+  event's observed peak -- the CRPS and the rank counts per cell --, and ``PeakVerification`` aggregates those maps on the host: rank
+  histogram, mean CRPS, Brier score, reliability table, coverage of a quantile band.
 
-DESIGN.md section 3.23 has the mapping, the determinism argument and the measurement behind ``DEFAULT_ROUTE``.
+DESIGN.md section 3.23 has the mapping, the determinism argument and the measurement behind ``DEFAULT_ROUTE``; section 3.24 the verification.
 """
 
 from __future__ import annotations
@@ -46,7 +49,7 @@ DEFAULT_RNG = "host"
 DEPTH_MODES = {"velocity": 0, "wse": 1, "depth": 2}
 JOINT_MAX_M, JOINT_MAX_ROWS, JOINT_MAX_D = 320, 1024, 64
 MAX_MEMBERS, MAX_THRESHOLDS, MAX_RANKS = 4096, 8, 8
-STAGES = ("joint", "draw_upload", "draws", "peaks", "stats")  # (the statistics' stage includes their download)
+STAGES = ("joint", "draw_upload", "draws", "peaks", "stats")  # (the statistics' stage includes their download; ``observed=`` adds "verify")
 
 
 def joint_applies(n_inducing, d: int, rows: int) -> str | None:
@@ -98,6 +101,24 @@ def check_stats_args(members: int, thresholds, ranks):
     return thr, rk
 
 
+def check_verify_args(members: int, ranks) -> np.ndarray:
+    """``ranks`` int32 as ``gprx_pca_member_verify_dev`` takes them: at most ``MAX_RANKS`` integers in ``[0, members)``, ``members`` in range."""
+    return check_stats_args(members, (), ranks)[1]
+
+
+def check_observed(observed, rows: int, cells: int):
+    """``observed`` of ``evaluate``: a ``DeviceBuffer`` of at least ``(rows, cells)`` doubles as it is, anything else as a float64 array of
+    exactly that shape."""
+    if isinstance(observed, DeviceBuffer):
+        if observed.nbytes < 8 * rows * cells:
+            raise ValueError(f"the observed buffer must hold ({rows}, {cells}) doubles")
+        return observed
+    arr = as_f64(observed)
+    if arr.shape != (rows, cells):
+        raise ValueError(f"observed must be ({rows}, {cells}): one row per row of x_test, one column per cell")
+    return arr
+
+
 def check_seed(value, name: str) -> int:
     """``value`` as the unsigned 64-bit integer a key word of the device generator is."""
     try:
@@ -140,6 +161,100 @@ class EnsembleResult:
     last_timings_ms: dict = field(default_factory=dict)
     names: list = field(default_factory=list)  # the events' labels (``DevicePipeline.peak_ensemble``)
     rng: str = DEFAULT_RNG  # where the normals were drawn ("host" also when the caller passed ``normals``)
+    verification: "PeakVerification | None" = None  # the ensemble against the observed peaks (``evaluate(observed=...)``)
+
+
+@dataclass
+class PeakVerification:
+    """The ensemble of every event against the peak that happened, per cell as ``gprx_pca_member_verify_dev`` leaves it: ``crps (E, cells)``,
+    ``below`` and ``equal`` ``(E, cells)`` int32 -- the members below the observed peak and equal to it, -1 where the observation or a member
+    is NaN --, ``observed_peak (E, cells)``, and the result's ``exceed_counts (E, n_thr, cells)`` at ``thresholds``.  The aggregations are
+    host numpy over these ``(E, cells)`` maps: O(cells), and exact integers where they count.  A cell with an infinite member or
+    observation is valid (its counts are counts) while its CRPS may be NaN: pass a ``mask`` to keep it out of ``mean_crps``."""
+
+    crps: np.ndarray
+    below: np.ndarray
+    equal: np.ndarray
+    observed_peak: np.ndarray
+    members: int
+    thresholds: np.ndarray
+    exceed_counts: np.ndarray
+    names: list = field(default_factory=list)
+
+    @property
+    def valid(self) -> np.ndarray:
+        return self.below >= 0
+
+    def _mask(self, mask) -> np.ndarray:
+        if mask is None:
+            return self.valid
+        m = np.asarray(mask, dtype=bool)
+        return self.valid & np.broadcast_to(m, self.below.shape)
+
+    def _weights(self, cell_areas, mask) -> np.ndarray:
+        a = np.ones(self.below.shape[1]) if cell_areas is None else np.asarray(cell_areas, dtype=np.float64)
+        if a.shape != (self.below.shape[1],):
+            raise ValueError(f"cell_areas must be ({self.below.shape[1]},)")
+        return np.where(self._mask(mask), a[None, :], 0.0)
+
+    def rank_histogram(self, mask=None) -> np.ndarray:
+        """``(E, S + 1)``: the Talagrand histogram of the observation's rank among the members.  A cell with ``(b, q) = (below, equal)`` puts
+        ``1 / (q + 1)`` into each of the bins ``b .. b + q`` (ties share the cell evenly).  The default mask is ``valid & (equal < S)``: it
+        drops the cells where the truth and every member coincide (dry everywhere).  A row sums to the number of counted cells."""
+        s = int(self.members)
+        m = self._mask(self.equal < s if mask is None else mask)
+        hist = np.zeros((self.below.shape[0], s + 1))
+        for e in range(hist.shape[0]):
+            b, q = self.below[e][m[e]].astype(np.int64), self.equal[e][m[e]].astype(np.int64)
+            for ties in np.unique(q).tolist():
+                start = np.bincount(b[q == ties], minlength=s + 1)  # cells whose run of bins starts here: integers
+                run = np.cumsum(start)
+                run[ties + 1:] -= run[: s - ties].copy()  # cells whose run covers the bin, still integers
+                hist[e] += run if ties == 0 else run / (ties + 1.0)
+        return hist
+
+    def mean_crps(self, cell_areas=None, mask=None) -> np.ndarray:
+        """``(E,)``: the (area-weighted) mean of the CRPS over the valid cells of ``mask``."""
+        w = self._weights(cell_areas, mask)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return (np.where(w > 0.0, self.crps, 0.0) * w).sum(axis=1) / w.sum(axis=1)
+
+    def brier(self, cell_areas=None, mask=None) -> np.ndarray:
+        """``(E, n_thr)``: the (area-weighted) mean of ``(p - o)^2`` with ``p = exceed_counts / S`` and ``o = observed_peak > threshold``
+        (strict, as the exceedance itself)."""
+        w = self._weights(cell_areas, mask)
+        p = self.exceed_counts / float(self.members)
+        o = (self.observed_peak[:, None, :] > np.asarray(self.thresholds, dtype=np.float64)[None, :, None]).astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return ((p - o) ** 2 * w[:, None, :]).sum(axis=2) / w.sum(axis=1)[:, None]
+
+    def reliability(self, bins: int = 10) -> np.ndarray:
+        """int64 ``(E, n_thr, bins, 2)`` over the valid cells: ``[..., 0]`` the forecasts whose exceedance count falls into the bin
+        ``min(bins - 1, count * bins // S)`` (integer arithmetic), ``[..., 1]`` those among them where the observed peak exceeded."""
+        bins = int(bins)
+        if bins < 1:
+            raise ValueError("bins must be positive")
+        ne, n_thr = self.exceed_counts.shape[:2]
+        out = np.zeros((ne, n_thr, bins, 2), dtype=np.int64)
+        idx = np.minimum(bins - 1, self.exceed_counts.astype(np.int64) * bins // int(self.members))
+        for e in range(ne):
+            v = self.valid[e]
+            for j in range(n_thr):
+                o = self.observed_peak[e][v] > self.thresholds[j]
+                out[e, j, :, 0] = np.bincount(idx[e, j][v], minlength=bins)
+                out[e, j, :, 1] = np.bincount(idx[e, j][v][o], minlength=bins)
+        return out
+
+    def coverage(self, lo_rank: int, hi_rank: int) -> np.ndarray:
+        """``(E,)``: the share of the valid cells whose observed peak lies in ``[x_(lo_rank), x_(hi_rank)]`` of the sorted members:
+        ``below + equal >= lo_rank + 1`` and ``below <= hi_rank``."""
+        lo_rank, hi_rank = int(lo_rank), int(hi_rank)
+        if not 0 <= lo_rank <= hi_rank < int(self.members):
+            raise ValueError("need 0 <= lo_rank <= hi_rank < members")
+        v = self.valid
+        inside = v & (self.below.astype(np.int64) + self.equal >= lo_rank + 1) & (self.below <= hi_rank)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return inside.sum(axis=1) / v.sum(axis=1).astype(np.float64)
 
 
 class PeakEnsemble:
@@ -153,6 +268,7 @@ class PeakEnsemble:
         self.device = projector.device
         self._lib = _lib.load()
         self.last_device_peaks_ms = 0.0  # device time of the last fused peak kernel (``gprx_pca_ensemble_ms``)
+        self.last_device_verify_ms = 0.0  # device time of the last verification kernel (``gprx_pca_member_verify_ms``)
 
     # ---- 1. joint prediction over one event -------------------------------------------------------------------------------------------
     def joint_dev(self, x_event, include_noise: bool = True):
@@ -355,14 +471,81 @@ class PeakEnsemble:
         return {"exceed": exceed, "mean": host[o_mean:o_std].copy(), "std": host[o_std:o_order].copy(),
                 "order": host[o_order:o_wet].reshape(n_rk, cells).copy(), "wet_area": host[o_wet:].reshape(members, n_thr).copy()}
 
+    # ---- 5. verification against the observed peak -----------------------------------------------------------------------------------------
+    def observed_peak_dev(self, truth, lo: int, hi: int) -> DeviceBuffer:
+        """The observed peak ``(cells,)`` of the event in rows ``[lo, hi)`` of ``truth (rows, cells)``, a host array or a device buffer already
+        in the peaks' units: ``gprx_pca_member_peaks_dev`` with one member, so the first-maximum rule (a NaN is the maximum) is the members'
+        own.  The caller frees the buffer."""
+        lo, hi = int(lo), int(hi)
+        cells, dev = self.projector.n_cells, self.device
+        if not 0 <= lo < hi:
+            raise ValueError("need 0 <= lo < hi")
+        owned = None
+        if isinstance(truth, DeviceBuffer):
+            if truth.nbytes < 8 * hi * cells:
+                raise ValueError(f"the truth buffer does not reach row {hi}")
+            src = truth.at(lo * cells)
+        else:
+            arr = np.asarray(truth)
+            if arr.ndim != 2 or arr.shape[1] != cells or arr.shape[0] < hi:
+                raise ValueError(f"truth must be (rows >= {hi}, {cells})")
+            owned = DeviceBuffer.from_array(arr[lo:hi], dev)
+            src = owned.ptr
+        out = DeviceBuffer(8 * cells, dev)
+        try:
+            check(self._lib.gprx_pca_member_peaks_dev(self.projector.handle, src, 1, hi - lo, out.ptr))
+            check(self._lib.gprx_pca_synchronize(self.projector.handle))
+        except Exception:
+            out.free()
+            raise
+        finally:
+            if owned is not None:
+                owned.free()
+        return out
+
+    def verify_peaks(self, peak_dev, obs_dev, members: int, ranks=()) -> dict:
+        """A ``(S, cells)`` peak block on the device against the observed peak ``(cells,)`` on the device, as host arrays
+        (``gprx_pca_member_verify_dev``, csrc/verify.h): ``crps (cells,)``, ``below`` and ``equal`` ``(cells,)`` int32 and
+        ``order (n_rank, cells)``, the sorted members at ``ranks``.  A cell whose observation or any member is NaN: ``crps`` NaN,
+        ``below = equal = -1``; infinities follow the formula (``|inf - inf|`` makes the CRPS a NaN, the counts stay counts)."""
+        rk = check_verify_args(members, ranks)
+        pr, dev = self.projector, self.device
+        cells, members, n_rk = pr.n_cells, int(members), int(rk.size)
+        # one block: crps | order | below, equal (int32)
+        o_order, o_int = cells, (1 + n_rk) * cells
+        out = DeviceBuffer(8 * (o_int + cells), dev)
+        try:
+            below_ptr = out.at(o_int)
+            equal_ptr = C.c_void_p(below_ptr.value + 4 * cells)
+            rc = self._lib.gprx_pca_member_verify_dev(pr.handle, peak_dev.ptr if hasattr(peak_dev, "ptr") else peak_dev,
+                                                      obs_dev.ptr if hasattr(obs_dev, "ptr") else obs_dev, members, n_rk, ptr(rk), out.ptr, below_ptr,
+                                                      equal_ptr, out.at(o_order) if n_rk else None)
+            if rc == _lib.GPRX_EINVAL:
+                raise ValueError((self._lib.gprx_pca_last_error(pr.handle) or b"").decode())
+            check(rc)
+            ms = C.c_double()
+            check(self._lib.gprx_pca_member_verify_ms(pr.handle, C.byref(ms)))
+            self.last_device_verify_ms = ms.value
+            host = out.to_array((o_int + cells,))
+        finally:
+            out.free()
+        counts = host[o_int:].view(np.int32)
+        return {"crps": host[:cells].copy(), "below": counts[:cells].copy(), "equal": counts[cells:].copy(),
+                "order": host[o_order:o_int].reshape(n_rk, cells).copy()}
+
     # ---- the whole chain ------------------------------------------------------------------------------------------------------------------
     def evaluate(self, x_test, ranges, members: int, thresholds=(0.5,), quantiles=(0.05, 0.5, 0.95), seed=0, normals=None, cell_areas=None,
-                 include_noise: bool = True, route: str | None = None, rng: str = DEFAULT_RNG, stream=0, antithetic: bool = False) -> EnsembleResult:
+                 include_noise: bool = True, route: str | None = None, rng: str = DEFAULT_RNG, stream=0, antithetic: bool = False,
+                 observed=None) -> EnsembleResult:
         """``x_test (rows, d)``; ``ranges``: the events' ``(lo, hi)`` row ranges, ascending and disjoint; ``members``: S.  ``normals``: one
         ``(K, S, rows_e)`` array per event instead of the generator seeded with ``seed``.  ``rng="host"``: ``np.random.default_rng(seed)``, one
         sequential stream over the events; ``rng="device"``: event ``e`` takes ``normals_dev(e, members, rows_e, seed, stream, antithetic)`` --
         every draw a function of ``(seed, stream, e, mode, member, row)`` alone, so the members of a smaller ensemble are the first members
-        of a larger one; ``antithetic`` (device only, ``members`` even): member ``s + S / 2`` draws the negation of member ``s``."""
+        of a larger one; ``antithetic`` (device only, ``members`` even): member ``s + S / 2`` draws the negation of member ``s``.
+        ``observed``: the truth ``(rows, cells)``, row-aligned with ``x_test`` and in the peaks' units, a host array (sent up event by event, every row once) or a
+        ``DeviceBuffer``: every event's peaks are then also scored against its observed peak (``observed_peak_dev``, ``verify_peaks``) in a
+        ``"verify"`` stage of the timer and the result carries a ``PeakVerification``; ``None`` launches nothing more and leaves
+        ``verification`` None."""
         route = DEFAULT_ROUTE if route is None else route
         if route not in ROUTES:
             raise ValueError(f"route must be one of {ROUTES}")
@@ -390,15 +573,21 @@ class PeakEnsemble:
             raise ValueError("one array of normals per event")
         k, cells, ne = self.projector.spatial_mode_count, self.projector.n_cells, int(lo.size)
         host_rng = np.random.default_rng(seed) if rng == "host" and normals is None else None
-        timer = StageTimer(STAGES)
+        verify = observed is not None
+        if verify:
+            observed = check_observed(observed, x.shape[0], cells)
+        timer = StageTimer(STAGES + ("verify",) if verify else STAGES)
         counts = np.zeros((ne, thr.size, cells), dtype=np.int32)
         mean, std = np.zeros((ne, cells)), np.zeros((ne, cells))
         order = np.zeros((ne, rk.size, cells))
         wet = np.zeros((ne, members, thr.size))
-        device_peaks = 0.0
+        device_peaks = device_verify = 0.0
+        if verify:
+            crps, obs_peak = np.zeros((ne, cells)), np.zeros((ne, cells))
+            below, equal = np.zeros((ne, cells), dtype=np.int32), np.zeros((ne, cells), dtype=np.int32)
         for e, (a, b) in enumerate(zip(lo.tolist(), hi.tolist())):
             rows = b - a
-            mean_dev = lc_dev = scores = peak = zn = None
+            mean_dev = lc_dev = scores = peak = zn = truth_peak = None
             try:
                 mean_dev, lc_dev, _ = self.joint_dev(x[a:b], include_noise=include_noise)
                 timer.lap("joint")
@@ -413,13 +602,26 @@ class PeakEnsemble:
                 device_peaks += self.last_device_peaks_ms if route == "fused" else 0.0
                 st = self.member_stats(peak, members, thr, rk, cell_areas)
                 timer.lap("stats")
+                if verify:
+                    # (a host truth goes up event by event, every row once: the events are disjoint)
+                    truth_peak = self.observed_peak_dev(observed, a, b)
+                    if not isinstance(observed, DeviceBuffer):
+                        timer.link_bytes += 8 * rows * cells
+                    vr = self.verify_peaks(peak, truth_peak, members)
+                    device_verify += self.last_device_verify_ms
+                    crps[e], below[e], equal[e], obs_peak[e] = vr["crps"], vr["below"], vr["equal"], truth_peak.to_array((cells,))
+                    timer.lap("verify")
             finally:
-                for buf in (mean_dev, lc_dev, scores, peak, zn if rng == "device" else None):
+                for buf in (mean_dev, lc_dev, scores, peak, zn if rng == "device" else None, truth_peak):
                     if buf is not None:
                         buf.free()
             counts[e], mean[e], std[e], order[e], wet[e] = st["exceed"], st["mean"], st["std"], st["order"], st["wet_area"]
         timings = timer.finish()
         if route == "fused":
             timings["device_peaks"] = device_peaks
+        verification = None
+        if verify:
+            timings["device_verify"] = device_verify
+            verification = PeakVerification(crps, below, equal, obs_peak, members, thr, counts)
         return EnsembleResult(counts / members, mean, std, order, wet, counts, thr, q, list(zip(lo.tolist(), hi.tolist())), members, route, timings,
-                              rng=rng)
+                              rng=rng, verification=verification)

@@ -227,11 +227,13 @@ class DevicePipeline:
                 if buf is not None:
                     buf.free()
 
-    def peak_ensemble(self, x_test, hf_test_data_df_or_index, members: int, **kwargs):
+    def peak_ensemble(self, x_test, hf_test_data_df_or_index, members: int, verify: bool = False, **kwargs):
         """Maps of every event's PEAK from ``members`` joint posterior draws (``gpras_amd.ensemble``): exceedance probabilities, mean, standard
         deviation and quantiles of the peak per cell and the wet area per member.  The events come from the two-level ``(event, timestep)``
         index of ``hf_test_data_df_or_index`` (a data frame or the index itself, one entry per row of ``x_test``); ``kwargs`` are those of
-        ``PeakEnsemble.evaluate``.  Returns its ``EnsembleResult`` with the events' labels in ``names``."""
+        ``PeakEnsemble.evaluate``.  Returns its ``EnsembleResult`` with the events' labels in ``names``.  ``verify=True`` (a data frame, not the
+        index alone): the truth goes up once through ``truth_depth_dev`` and the result carries the ``PeakVerification`` of the ensemble
+        against every event's observed peak."""
         from .diagnostics import event_ranges
         from .ensemble import PeakEnsemble
 
@@ -239,8 +241,20 @@ class DevicePipeline:
         if callable(index) or len(index) != np.shape(x_test)[0]:
             raise ValueError("x_test and the index must have one row per test timestep")
         names, ranges = event_ranges(index)
-        result = PeakEnsemble(self.gpr, self.projector).evaluate(x_test, ranges, members, **kwargs)
+        truth = None
+        if verify:
+            if index is hf_test_data_df_or_index or not hasattr(hf_test_data_df_or_index, "values"):
+                raise ValueError("verify=True needs the high-fidelity data frame, not its index alone")
+            truth = self.truth_depth_dev(hf_test_data_df_or_index.values)
+            kwargs["observed"] = truth
+        try:
+            result = PeakEnsemble(self.gpr, self.projector).evaluate(x_test, ranges, members, **kwargs)
+        finally:
+            if truth is not None:
+                truth.free()
         result.names = list(names)
+        if result.verification is not None:
+            result.verification.names = list(names)
         return result
 
     # ---- pipeline.py:90-210 (gen_plots) -----------------------------------------------------------------------------------------

@@ -604,6 +604,23 @@ int gprx_pca_member_peaks_dev(gprx_pca_handle p, const double* field_dev, int64_
  * exceed / wet_area may be NULL when n_thr = 0, order when n_rank = 0.  The call synchronises.  GPRX_EINVAL leaves the handle usable. */
 int gprx_pca_member_stats_dev(gprx_pca_handle p, const double* peak_dev, int64_t members, int n_thr, const double* thresholds, int n_rank, const int* ranks,
                               const double* area_dev, int* exceed_dev, double* mean_dev, double* std_dev, double* order_dev, double* wet_area_dev);
+/* The ensemble against the truth: peak_dev (members, n_cells) and the observed peak obs_dev (n_cells), 1 <= members = S <= 4096.  Per cell,
+ * with x_(0) <= ... <= x_(S-1) the members in np.sort's order (-0 before +0, every NaN last) and y the observation:
+ *   below, equal (n_cells) int32: the counts of x_s < y and of x_s == y (values compared: -0 == +0)
+ *   crps (n_cells): (2 acc) / ((double)S (double)S), acc = sum over i = 0, 1, ... of |x_(i) - y| w_i in that order, w_i = (S - i) - 0.5 where
+ *     x_(i) > y and i + 0.5 elsewhere, each term a rounded product followed by a rounded addition: the CRPS of the empirical distribution,
+ *     mean |x - y| - 1/2 mean |x - x'|, every term non-negative; the same bits for any permutation of the members
+ *   order (n_rank, n_cells): x_(ranks[j]) read out of the sorted column, n_rank <= 8 ranks in [0, members) (host array): bit for bit the
+ *     order of gprx_pca_member_stats_dev
+ * A cell whose observation or any member is NaN: crps = NaN, below = equal = -1, order still in the key order.  Infinite members or
+ * observation follow the formula as written: |inf - inf| is a NaN, so the CRPS of such a cell is NaN while below and equal stay counts.
+ * A cell's outputs depend on its own column and observation alone.  order_dev may be NULL when n_rank = 0.  The call synchronises;
+ * gprx_pca_member_verify_ms: device milliseconds of the last one; gprx_pca_member_verify_tile: the consecutive cells one workgroup sorts
+ * at this member count.  GPRX_EINVAL leaves the handle usable. */
+int gprx_pca_member_verify_dev(gprx_pca_handle p, const double* peak_dev, const double* obs_dev, int64_t members, int n_rank, const int* ranks,
+                               double* crps_dev, int* below_dev, int* equal_dev, double* order_dev);
+int gprx_pca_member_verify_ms(gprx_pca_handle p, double* ms);
+int gprx_pca_member_verify_tile(int64_t members, int* tile_cells);
 
 /* ---- fitting the EOF preprocessor: PreProcessor.fit (gpras/preprocess.py:947-1007) --------------------------------------- */
 /* The fitted state gprx_pca_create takes, computed on the device.  Single-batch IncrementalPCA (sklearn partial_fit, first

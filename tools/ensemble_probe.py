@@ -3,7 +3,7 @@ the existing kernels), alternating, by the stage timer of ``PeakEnsemble.evaluat
 synchronisation) and the device time of the fused launches.
 
     python tools/ensemble_probe.py [--events 35] [--event-rows 86] [--cells 100000] [--modes 50] [--members 256] [--repeats 3]
-                                   [--rng host|device|both] [--out profiles/ensemble_peaks.json]
+                                   [--rng host|device|both] [--verify] [--out profiles/ensemble_peaks.json]
 
 A ``GPRAS`` of ``--modes`` sparse models (M = 50, a few Adam steps: the probe times the prediction side) feeds ``PeakEnsemble.evaluate``.
 The first round warms both routes up and compares them (every output bit for bit), so that a faster number is a number for the same
@@ -14,7 +14,11 @@ time of generating the normals and sending them up over the whole call.
 ``--rng host`` (the default) and ``--rng device`` run that comparison of the routes with the one generator.  ``--rng both`` compares the
 generators instead (profiles/ensemble_rng.json): ``rng="host"`` -- ``np.random.default_rng`` and the upload, the route every earlier release
 took and the yardstick -- against ``rng="device"`` (``gprx_pca_normals_dev``), alternating in one run on the default route, by the same stage
-timer; ``draw_upload`` is the stage the generator is timed in."""
+timer; ``draw_upload`` is the stage the generator is timed in.
+
+``--verify`` (profiles/ensemble_verify.json) measures the verification against the truth instead: the ``"verify"`` stage of
+``evaluate(observed=...)`` with ``"stats"`` beside it, the device time of ``gprx_pca_member_verify_dev`` by HIP events, and the same scores formed
+on the host from a downloaded ``peak`` block (download, ``np.sort``, vectorised weights: the yardstick), alternating in one run."""
 
 from __future__ import annotations
 
@@ -70,6 +74,93 @@ def compare_generators(args, run, shape, draw_ms) -> None:
             f.write(text + "\n")
 
 
+def host_scores(peak_dev, obs, members, cells):
+    """The yardstick of ``--verify``: the scores of ``gprx_pca_member_verify_dev`` formed on the host from a downloaded ``peak`` -- the
+    download, ``np.sort`` over the members and the weights vectorised over ``(S, cells)``.  Returns the scores and the three times in ms."""
+    t0 = time.perf_counter()
+    peak = peak_dev.to_array((members, cells))
+    t1 = time.perf_counter()
+    xs = np.sort(peak, axis=0)
+    t2 = time.perf_counter()
+    i = np.arange(members, dtype=np.float64)[:, None]
+    gt = xs > obs[None, :]
+    acc = (np.abs(xs - obs[None, :]) * np.where(gt, (members - i) - 0.5, i + 0.5)).sum(axis=0)
+    crps = (2.0 * acc) / (float(members) * float(members))
+    below, equal = (xs < obs[None, :]).sum(axis=0), (xs == obs[None, :]).sum(axis=0)
+    t3 = time.perf_counter()
+    return (crps, below, equal), {"download": (t1 - t0) * 1e3, "sort": (t2 - t1) * 1e3, "weights": (t3 - t2) * 1e3, "total": (t3 - t0) * 1e3}
+
+
+def measure_verification(args, ens, xs, ranges, shape) -> None:
+    """``--verify``: ``evaluate(observed=...)`` by its stage timer (the ``"verify"`` stage, ``"stats"`` for context), the device time of the
+    verification kernel by HIP events, and per event the call ``verify_peaks`` against the host yardstick (``host_scores``) on the same
+    resident peak block, alternating; the first round warms both up and compares their answers."""
+    from gpras_amd._lib import DeviceBuffer
+    from gpras_amd.ensemble import DEFAULT_ROUTE
+
+    members, cells, rows = shape["members"], shape["cells"], shape["rows"]
+    rng = np.random.default_rng(2)
+    truth = DeviceBuffer.from_array(np.maximum(rng.normal(size=(rows, cells)) * 0.5 + 0.6, 0.0), ens.device)
+    lo, hi = ranges[0]
+    mean_dev, lc_dev, _ = ens.joint_dev(xs[lo:hi])
+    scores = ens.scores_dev(mean_dev, lc_dev, np.random.default_rng(3).standard_normal((shape["modes"], members, hi - lo)), members, hi - lo)
+    peak = ens.member_peaks_dev(scores, members, hi - lo)
+    obs_dev = ens.observed_peak_dev(truth, lo, hi)
+    obs = obs_dev.to_array((cells,))
+    for buf in (mean_dev, lc_dev, scores):
+        buf.free()
+    calls, host, kernel, stages = [], [], [], []
+    agree = None
+    for rep in range(args.repeats + 1):
+        for side in ("device", "host") if rep % 2 == 0 else ("host", "device"):
+            if side == "device":
+                t0 = time.perf_counter()
+                got = ens.verify_peaks(peak, obs_dev, members)
+                call_ms = (time.perf_counter() - t0) * 1e3
+                res = ens.evaluate(xs, ranges, members, thresholds=(0.5, 1.0), quantiles=(0.05, 0.5, 0.95), seed=1, route=DEFAULT_ROUTE, rng=args.rng,
+                                   observed=truth)
+                if rep:
+                    calls.append(call_ms)
+                    kernel.append(ens.last_device_verify_ms)
+                    stages.append(res.last_timings_ms)
+            else:
+                (crps, below, equal), ms = host_scores(peak, obs, members, cells)
+                if rep:
+                    host.append(ms)
+                else:
+                    want = (crps, below, equal)
+        if rep == 0:
+            agree = bool(np.array_equal(got["below"], want[1]) and np.array_equal(got["equal"], want[2])
+                         and np.allclose(got["crps"], want[0], rtol=1e-12, atol=0))
+    for buf in (peak, obs_dev, truth):
+        buf.free()
+
+    def med(rows_, key):
+        return statistics.median(t[key] for t in rows_)
+
+    events = shape["events"]
+    out = {
+        "shape": shape, "route": DEFAULT_ROUTE, "rng": args.rng, "repeats": args.repeats, "host_agrees": agree,
+        "evaluate_stage_ms_median": {key: med(stages, key) for key in ("joint", "draw_upload", "draws", "peaks", "stats", "verify", "total")},
+        "evaluate_device_verify_ms_median": med(stages, "device_verify"),
+        "per_event": {
+            "device_kernel_ms": {"median": statistics.median(kernel), "min": min(kernel), "max": max(kernel)},
+            "verify_peaks_call_ms": {"median": statistics.median(calls), "min": min(calls), "max": max(calls)},
+            "host_yardstick_ms": {key: {"median": med(host, key), "min": min(t[key] for t in host), "max": max(t[key] for t in host)}
+                                  for key in ("download", "sort", "weights", "total")},
+            "peak_bytes_downloaded_by_the_yardstick": 8 * members * cells,
+        },
+    }
+    out["host_yardstick_ms_per_call"] = med(host, "total") * events
+    out["speedup_host_yardstick_over_verify_peaks_call"] = med(host, "total") / statistics.median(calls)
+    out["speedup_host_yardstick_over_verify_stage"] = out["host_yardstick_ms_per_call"] / med(stages, "verify")
+    text = json.dumps(out, indent=1, sort_keys=True)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--events", type=int, default=35)
@@ -82,8 +173,11 @@ def main() -> None:
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--hydraulic-parameter", default="wse")
     ap.add_argument("--rng", choices=("host", "device", "both"), default="host")
+    ap.add_argument("--verify", action="store_true", help="measure the verification against the truth (profiles/ensemble_verify.json)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
+    if args.verify and args.rng == "both":
+        ap.error("--verify takes one generator: --rng host or --rng device")
 
     from gpras_amd.ensemble import PeakEnsemble
     from gpras_amd.gpr import GPRAS
@@ -118,6 +212,10 @@ def main() -> None:
              "train_rows": args.train_rows, "inducing": 50, "hydraulic_parameter": args.hydraulic_parameter}
     if args.rng == "both":
         compare_generators(args, run, shape, draw_ms)
+        proj.close()
+        return
+    if args.verify:
+        measure_verification(args, ens, xs, ranges, shape)
         proj.close()
         return
 
