@@ -226,7 +226,7 @@ PROTOTYPES = {
 
 # keys of gprx_set_tuning / gprx_set_handle_tuning (include/gprx.h)
 TUNING_KEYS = (
-    "outer_block", "update_tile", "no_lookahead", "split_panel", "dag", "rhs_vector", "cell_kernel", "poison_workspace", "predict_path",
+    "outer_block", "update_tile", "no_lookahead", "split_panel", "dag", "rhs_vector", "rows_pair", "cell_kernel", "poison_workspace", "predict_path",
     "sgpr_fused", "sgpr_resident", "wait_handover_us", "sgpr_groups_from", "loeo_blocked_potrf",
     "held_general",  # (gprx_set_handle_tuning only)
     "pcafit_rowsplit",  # (gprx_set_tuning only: read when gprx_pcafit_create_auto runs)

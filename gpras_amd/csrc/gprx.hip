@@ -728,6 +728,7 @@ int gprx_potrf_batched(int device, double* a_dev, int64_t lda, int64_t np, int64
     tune.outer_block = outer_block;
     tune.update_tile = update_tile;
     tune.split_panel = route == 1 ? 1 : -1;
+    tune.rows_pair = potrf_tuning().rows_pair;  // (the one process default the probe reads: both forms of the split panel's rows launches)
     HIPCHK(nullptr, hipSetDevice(device));
     hipStream_t st = util_stream();
     int* dinfo = nullptr;
@@ -901,6 +902,7 @@ bool apply_tuning(PotrfTuning& t, int& predict_path, int& fused, int& resident, 
   else if (k == "dag" && value >= -1 && value <= 1) t.dag = value;
   else if (k == "rhs_vector" && value >= -1 && value <= 1) t.rhs_vector = value;
   else if (k == "cell_kernel" && value >= -1 && value <= 1) t.cell_kernel = value;
+  else if (k == "rows_pair" && value >= 0 && value <= 1) t.rows_pair = value;
   else if (k == "poison_workspace" && value >= 0 && value <= 1) t.poison_workspace = value;
   else if (k == "predict_path" && value >= 0 && value <= 2) predict_path = value;
   else if (k == "sgpr_fused" && value >= 0 && value <= 1) fused = value;

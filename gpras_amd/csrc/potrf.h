@@ -221,7 +221,7 @@ __global__ __launch_bounds__(256, 2) void potrf_panel_kernel(double* __restrict_
                                                           double* __restrict__ inv_diag, int* __restrict__ info, int col0,
                                                           double* __restrict__ stage_out, const double* __restrict__ prev_stage,
                                                           double* __restrict__ prev_dst, int prev_pw, int64_t cs, int info_stride,
-                                                          double* __restrict__ yv) {
+                                                          double* __restrict__ yv, int y_left) {
   constexpr int PWG_ROWS = PANEL_WG_ROWS;
   constexpr int PANEL_ROWS = PANEL_OWN_ROWS;
   constexpr int WROWS = 16 * RT;
@@ -410,9 +410,23 @@ __global__ __launch_bounds__(256, 2) void potrf_panel_kernel(double* __restrict_
     double* sv = sIn;         // (the sub-panel buffers are free now)
     double* sred = sIn + NB;
     static_assert(PWG_ROWS * PSUB >= NB + 256, "the sub-panel buffer holds y_j and the partial sums");
-    if (c.tid < NB) sv[c.tid] = yv[c.tid];
-    __syncthreads();
     const int a = c.tid & 63, qq = c.tid >> 6;
+    if (FUSE_K64 && y_left) {
+      // Right panel of a rows pair (potrf_rows_pair_kernel): its 64 rows B = L(c .. c + 63, c - 64 .. c - 1) were solved by the chunk
+      // workgroup of the left panel's diagonal launch, which carries no y, so y_j -= B beta_{j-1} happens here, before beta_j is formed.
+      // Row a of B times beta_{j-1}: four partial sums of 16 terms (k ascending), added in order of k, then taken off y_j[a].
+      const double* brow = A + (int64_t)a * lda - NB + 16 * qq;
+      const double* bl = yv - NB + 16 * qq;
+      double sum = 0.0;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) sum = __builtin_fma(brow[i], bl[i], sum);
+      sred[c.tid] = sum;
+      __syncthreads();
+      if (c.tid < NB) sv[c.tid] = yv[c.tid] - (((sred[c.tid] + sred[64 + c.tid]) + sred[128 + c.tid]) + sred[192 + c.tid]);
+    } else {
+      if (c.tid < NB) sv[c.tid] = yv[c.tid];
+    }
+    __syncthreads();
     const double* row = inv_diag + a * NB + 16 * qq;
     double sum = 0.0;
 #pragma unroll
@@ -516,29 +530,55 @@ __device__ __forceinline__ void rows_step(d4 (&acc)[RT][4], double* __restrict__
 // of it -- beta_j = L11^-1 y_j, written by the diagonal workgroup at its end (a launch of its own for it: same sums, removed) -- followed by the
 // entries of the rows below, which this kernel updates: y_i -= sum_c L(i, c) beta_j[c], the 64 products of a row summed over the tile
 // columns in a lane (k t ascending) and then over the 16 lanes that hold the row (xor 1, 2, 4, 8): a fixed order.
-// (four workgroups per CU; two with the accumulators of the K = 64 update)
-template <bool FUSE_K64, bool YVEC>
-__global__ __launch_bounds__(256, FUSE_K64 ? 2 : 4) void potrf_rows_kernel(double* __restrict__ A21, int64_t lda, int rows_below,
-                                                                           const double* __restrict__ stage, int64_t cs, double* __restrict__ yv) {
-  constexpr int WG_ROWS = ROWS_WG, WROWS = 16 * RT;
-  __shared__ __attribute__((aligned(16))) double sIn[WG_ROWS * PSUB];
-  __shared__ __attribute__((aligned(16))) double sX[WG_ROWS * PSUB];
-  A21 += (int64_t)blockIdx.y * cs;
-  stage += (int64_t)blockIdx.y * cs;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, r = lane & 15;
-  const int row0 = blockIdx.x * WG_ROWS;
-  // own rows -> accumulator layout, every load unconditional (rows past the end re-read row 0 and are masked)
+//
+// rows_pass is the body: one workgroup's 128 rows (from row0 of A21 on) against one panel.  Of the cell's right-hand side yv + ycell, the
+// panel's beta_j starts at entry ybeta and the entries that belong to A21's rows at entry yrows.  potrf_rows_pair_kernel runs it twice on
+// the same rows, for the two panels of a pair:
+//   X_L2   the A operand of the K = 64 update (the left panel's solved rows) was stored by THIS wave a moment ago: 16-byte sc1 loads, served
+//          by the XCD's L2 past the CU's L1 (which may still hold the lines as they were before the solve);
+//   NT_IN  the rows' own columns are read once and NT_OUT their solved values are not read again in this launch: non-temporal accesses
+//          (measured: 348 -> 338 us per pair launch at 256 cells of N = 4096; the bytes fetched stay what they were);
+//   Y_OUT  the updated entries of y are not stored but kept for the second pass, in the padding word of the rows' sub-panel lines in LDS
+//          (column 8 of PSUB = 9, which no sub-panel step touches; a wave's own rows, so wave-scope fences do); Y_IN takes them from there.
+__device__ __forceinline__ d2 ld2_l2(__amdgpu_buffer_rsrc_t rs, unsigned voff, unsigned soff) {
+  typedef unsigned int u4v __attribute__((ext_vector_type(4)));
+  const u4v v = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 16);  // aux 16 = sc1
+  d2 out;
+  __builtin_memcpy(&out, &v, 16);
+  return out;
+}
+// v of lane (own index ^ M), M < 32: the exchange pattern is an immediate (ds_swizzle, bit mode), so no lane-address register lives
+// through the kernel as with __shfl_xor
+template <int M>
+__device__ __forceinline__ double lane_xor(double v) {
+  int w[2];
+  __builtin_memcpy(w, &v, 8);
+  w[0] = __builtin_amdgcn_ds_swizzle(w[0], (M << 10) | 0x1f);
+  w[1] = __builtin_amdgcn_ds_swizzle(w[1], (M << 10) | 0x1f);
+  __builtin_memcpy(&v, w, 8);
+  return v;
+}
+template <bool FUSE_K64, bool YVEC, bool X_L2, bool Y_IN, bool Y_OUT, bool NT_IN = false, bool NT_OUT = false>
+__device__ __forceinline__ void rows_pass(double* __restrict__ A21, int64_t lda, int rows_below, int row0, const double* __restrict__ stage,
+                                          double* __restrict__ yv, int64_t ycell, int ybeta, int yrows, double* __restrict__ sIn,
+                                          double* __restrict__ sX) {
+  constexpr int WROWS = 16 * RT;
+  // (the wave index as a scalar, the lane index from the execution mask: every wave-dependent address term lives in SGPRs)
+  const int lane = __lane_id(), wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), tid = 64 * wave + lane, g = lane >> 4, r = lane & 15;
+  // own rows -> accumulator layout, every load unconditional (rows past the end re-read the workgroup's first row and are masked)
   d4 acc[RT][4];
   {
-    const double* rowp[RT][4];
+    // (a row's address = the workgroup's first row, which exists -- a scalar -- plus a 32-bit byte offset: one register per row, not two)
+    const char* wg0 = reinterpret_cast<const char*>(A21 + (int64_t)row0 * lda);
+    unsigned rowp[RT][4];
     bool valid[RT][4];
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const int idx = row0 + WROWS * wave + 16 * rt + g + 4 * q;
-        valid[rt][q] = idx < rows_below;
-        rowp[rt][q] = A21 + (int64_t)(valid[rt][q] ? idx : 0) * lda + r;
+        const int lrow = WROWS * wave + 16 * rt + g + 4 * q;
+        valid[rt][q] = row0 + lrow < rows_below;
+        rowp[rt][q] = ((unsigned)(valid[rt][q] ? lrow : 0) * (unsigned)lda + r) * 8u;
       }
     d4 upd[FUSE_K64 ? RT : 1][4];
     if constexpr (FUSE_K64) {
@@ -547,10 +587,16 @@ __global__ __launch_bounds__(256, FUSE_K64 ? 2 : 4) void potrf_rows_kernel(doubl
 #pragma unroll
         for (int kt = 0; kt < 4; ++kt) upd[rt][kt] = d4{0.0, 0.0, 0.0, 0.0};
       const double* arow[RT];
+      // (X_L2: descriptor at the workgroup's first row, which exists; per-lane byte offsets within its 128 rows.  Rows past the end read
+      // that first row and are masked below, as the plain form reads row 0.)
+      [[maybe_unused]] __amdgpu_buffer_rsrc_t xrs;
+      [[maybe_unused]] unsigned xoff[RT];
+      if constexpr (X_L2) xrs = __builtin_amdgcn_make_buffer_rsrc(A21 + (int64_t)row0 * lda - NB, 0, 0xffffffff, 0x00020000);
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt) {
         const int idx = row0 + WROWS * wave + 16 * rt + r;  // A operand: lane (g, r) supplies row r of the tile, k = 4 g + j
         arow[rt] = A21 + (int64_t)(idx < rows_below ? idx : 0) * lda - NB + 4 * g;
+        if constexpr (X_L2) xoff[rt] = ((unsigned)(idx < rows_below ? idx - row0 : 0) * (unsigned)lda + 4u * g) * 8u;
       }
       const double* brow = A21 - (int64_t)NB * lda + (int64_t)r * lda - NB + 4 * g;  // B operand: the diagonal block's rows, previous 64 columns
 #pragma unroll
@@ -558,7 +604,14 @@ __global__ __launch_bounds__(256, FUSE_K64 ? 2 : 4) void potrf_rows_kernel(doubl
         double fa[RT][4], fb[4][4];
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) {
-          const d2 lo = *reinterpret_cast<const d2*>(arow[rt] + k0), hi = *reinterpret_cast<const d2*>(arow[rt] + k0 + 2);
+          d2 lo, hi;
+          if constexpr (X_L2) {
+            lo = ld2_l2(xrs, xoff[rt], 8u * k0);
+            hi = ld2_l2(xrs, xoff[rt], 8u * k0 + 16u);
+          } else {
+            lo = *reinterpret_cast<const d2*>(arow[rt] + k0);
+            hi = *reinterpret_cast<const d2*>(arow[rt] + k0 + 2);
+          }
           fa[rt][0] = lo.x; fa[rt][1] = lo.y; fa[rt][2] = hi.x; fa[rt][3] = hi.y;
         }
 #pragma unroll
@@ -580,7 +633,10 @@ __global__ __launch_bounds__(256, FUSE_K64 ? 2 : 4) void potrf_rows_kernel(doubl
 #pragma unroll
       for (int q = 0; q < 4; ++q)
 #pragma unroll
-        for (int kt = 0; kt < 4; ++kt) acc[rt][kt][q] = rowp[rt][q][kt * 16];
+        for (int kt = 0; kt < 4; ++kt) {
+          const double* src = reinterpret_cast<const double*>(wg0 + rowp[rt][q] + kt * 128);
+          acc[rt][kt][q] = NT_IN ? __builtin_nontemporal_load(src) : *src;
+        }
     if constexpr (FUSE_K64) {
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt)
@@ -608,16 +664,18 @@ __global__ __launch_bounds__(256, FUSE_K64 ? 2 : 4) void potrf_rows_kernel(doubl
   // (YVEC: beta_j and this lane group's entries of y are requested before the last two sub-panel steps -- their latency hides behind
   // those -- and only stored at the end; not earlier, the registers are needed)
   double ybj[YVEC ? 4 : 1], yold[YVEC ? RT : 1][4];
+  [[maybe_unused]] int yrow0 = row0;
   if constexpr (YVEC) {
-    yv += (int64_t)blockIdx.y * cs;
+    yv += ycell;
+    asm volatile("" : "+s"(yrow0));  // (the addresses of the y entries are formed here, not at the top beside the rows' own)
 #pragma unroll
-    for (int kt = 0; kt < 4; ++kt) ybj[kt] = yv[16 * kt + r];
+    for (int kt = 0; kt < 4; ++kt) ybj[kt] = yv[ybeta + 16 * kt + r];
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const int idx = row0 + WROWS * wave + 16 * rt + g + 4 * q;
-        yold[rt][q] = yv[NB + (idx < rows_below ? idx : 0)];
+        const int idx = yrow0 + WROWS * wave + 16 * rt + g + 4 * q;
+        yold[rt][q] = Y_IN ? sIn[(WROWS * wave + 16 * rt + g + 4 * q) * PSUB + 8] : yv[yrows + (idx < rows_below ? idx : 0)];
       }
   }
   rows_step<6>(acc, sIn, sX, tid, wave, g, r, stage);
@@ -630,7 +688,10 @@ __global__ __launch_bounds__(256, FUSE_K64 ? 2 : 4) void potrf_rows_kernel(doubl
       if (idx < rows_below) {
         double* dst = A21 + (int64_t)idx * lda + r;
 #pragma unroll
-        for (int kt = 0; kt < 4; ++kt) dst[kt * 16] = acc[rt][kt][q];
+        for (int kt = 0; kt < 4; ++kt) {
+          if constexpr (NT_OUT) __builtin_nontemporal_store(acc[rt][kt][q], dst + kt * 16);
+          else dst[kt * 16] = acc[rt][kt][q];
+        }
       }
     }
   if constexpr (YVEC) {
@@ -641,12 +702,54 @@ __global__ __launch_bounds__(256, FUSE_K64 ? 2 : 4) void potrf_rows_kernel(doubl
         double sum = acc[rt][0][q] * ybj[0];
 #pragma unroll
         for (int kt = 1; kt < 4; ++kt) sum = __builtin_fma(acc[rt][kt][q], ybj[kt], sum);
-#pragma unroll
-        for (int m = 1; m < 16; m <<= 1) sum += __shfl_xor(sum, m, 64);
-        const int idx = row0 + WROWS * wave + 16 * rt + g + 4 * q;
-        if (r == 0 && idx < rows_below) yv[NB + idx] = yold[rt][q] - sum;
+        sum += lane_xor<1>(sum);
+        sum += lane_xor<2>(sum);
+        sum += lane_xor<4>(sum);
+        sum += lane_xor<8>(sum);
+        const int idx = yrow0 + WROWS * wave + 16 * rt + g + 4 * q;
+        if constexpr (Y_OUT) {
+          if (r == 0) sIn[(WROWS * wave + 16 * rt + g + 4 * q) * PSUB + 8] = yold[rt][q] - sum;
+        } else {
+          if (r == 0 && idx < rows_below) yv[yrows + idx] = yold[rt][q] - sum;
+        }
       }
   }
+}
+
+// (four workgroups per CU; three with the accumulators of the K = 64 update: 168 registers)
+template <bool FUSE_K64, bool YVEC>
+__global__ __launch_bounds__(256, FUSE_K64 ? 3 : 4) void potrf_rows_kernel(double* __restrict__ A21, int64_t lda, int rows_below,
+                                                                           const double* __restrict__ stage, int64_t cs, double* __restrict__ yv) {
+  __shared__ __attribute__((aligned(16))) double sIn[ROWS_WG * PSUB];
+  __shared__ __attribute__((aligned(16))) double sX[ROWS_WG * PSUB];
+  const int64_t off = (int64_t)blockIdx.y * cs;
+  rows_pass<FUSE_K64, YVEC, false, false, false>(A21 + off, lda, rows_below, blockIdx.x * ROWS_WG, stage + off, yv, off, 0, NB, sIn, sX);
+}
+
+// The rows below a PAIR of panels (columns c .. c + 63 and c + 64 .. c + 127) in one launch: what potrf_rows_kernel<false> at c and
+// potrf_rows_kernel<true> at c + 64 do, back to back on the same 128 rows, every operation in the same order -- the same bits.  The fused
+// kernel's A operand is the left panel's solved rows X, which the same rows' workgroup stored one launch earlier; with 256 cells x ~2000
+// rows x 512 B gone past in between it came from HBM.  Here the wave reads it back right after storing it: plain stores leave the lines in
+// this XCD's L2, every wave waits for its own stores (a wave's A operand is its own 32 rows: nothing crosses waves, no workgroup barrier),
+// and the loads are sc1, past the L1.  X is NOT kept in registers or LDS: its accumulators are dead once stored, so the register peak is the
+// fused rows kernel's and three workgroups fit a CU.
+// A21: row c + 128, column c (rows_below rows); stage, stage2: the two panels' staged blocks; yv: the right-hand side from entry c on
+// (beta_c, beta_{c+64}, then the rows' entries, which stay in registers between the two updates).  grid = (ceil(rows_below / ROWS_WG), cells).
+template <bool YVEC>
+__global__ __launch_bounds__(256, 3) void potrf_rows_pair_kernel(double* __restrict__ A21, int64_t lda, int rows_below,
+                                                                 const double* __restrict__ stage, const double* __restrict__ stage2, int64_t cs,
+                                                                 double* __restrict__ yv) {
+  __shared__ __attribute__((aligned(16))) double sIn[ROWS_WG * PSUB];
+  __shared__ __attribute__((aligned(16))) double sX[ROWS_WG * PSUB];
+  const int64_t off = (int64_t)blockIdx.y * cs;
+  const int row0 = blockIdx.x * ROWS_WG;
+  rows_pass<false, YVEC, false, false, true, true, false>(A21 + off, lda, rows_below, row0, stage + off, yv, off, 0, 2 * NB, sIn, sX);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's stores of X have reached the L2
+  wave_sync_lds();                                   // (and its entries of y the padding words)
+  // (the second pass forms its addresses anew: shared with the first pass's they would stay live through it, which spills)
+  int row0b = row0;
+  asm volatile("" : "+s"(row0b));
+  rows_pass<true, YVEC, true, true, false, true, true>(A21 + off + NB, lda, rows_below, row0b, stage2 + off, yv, off, NB, 2 * NB, sIn, sX);
 }
 
 // staging area: STAGE_LD doubles per matrix column; the panel at column c stages its diagonal block (64 x 64, row-major) at
@@ -691,6 +794,7 @@ struct PotrfTuning {
   int cell_kernel = 0;   // batched cells: 1 = always one workgroup per cell (potrf_cell.h), -1 never, 0 = for np <= 1024 and >= 256 cells
   int rhs_vector = 0;    // batched cells, split panel: -1 = the right-hand side always rides as a 64-row tile; 0 / 1 = as a vector where the schedule knows it
   int dag = 0;           // lone matrices: 1 = the tile-DAG factorisation (potrf_dag.h); 0 / -1 = the launch-per-panel schedule (default)
+  int rows_pair = 1;     // batched cells, split panel: 1 = one rows launch per pair of panels (potrf_rows_pair_kernel, default); 0 = one per panel (A/B runs, tests)
 };
 inline PotrfTuning& potrf_tuning() {
   static PotrfTuning t = [] {
@@ -701,6 +805,7 @@ inline PotrfTuning& potrf_tuning() {
     if (const char* e = getenv("GPRX_DAG")) v.dag = atoi(e);
     if (const char* e = getenv("GPRX_RHS_VECTOR")) v.rhs_vector = atoi(e);
     if (const char* e = getenv("GPRX_CELL_KERNEL")) v.cell_kernel = atoi(e);
+    if (const char* e = getenv("GPRX_ROWS_PAIR")) v.rows_pair = atoi(e) != 0;
     return v;
   }();
   return t;
@@ -787,9 +892,15 @@ inline hipError_t potrf_lower(hipStream_t st, double* A, int64_t lda, int np, in
   hipError_t err = hipSuccess;
   const bool split_panel = potrf_split_panel(tune, batch);
   if (yvec && !split_panel) return hipErrorInvalidValue;  // only the split panel carries the right-hand side as a vector
+  const bool rows_pair = split_panel && batch > 1 && tune.rows_pair != 0;
   // one panel: factor the diagonal block at column c and solve every row below it.  fuse: the K = 64 update of these 64 columns by the
   // 64 columns left of them happens inside the panel kernel (one dependent launch less; same arithmetic as the general NT kernel)
-  auto panel = [&](int c, bool fuse = false) {
+  // pair (rows_pair): 1 = the left panel of a pair, 2 = its right panel.  The left panel's launch solves only the 64 rows B that the right
+  // diagonal block needs (one chunk workgroup in its fused-panel role beside the diagonal workgroup -- the launch is chip-idle anyway; the
+  // role repeats the rows kernel's substitution operand for operand, so B has the same bits); the right panel's diagonal launch is today's
+  // (with the right-hand side as a vector it first takes B beta_c off its 64 entries of y, which the chunk role does not carry), and ONE
+  // rows launch then solves the rows from c + 128 down for both panels (potrf_rows_pair_kernel).
+  auto panel = [&](int c, bool fuse = false, int pair = 0) {
     const int rows_below = total_rows - c - NB;
     double* Acc = A + (int64_t)c * lda + c;
     if (prof) {
@@ -801,13 +912,19 @@ inline hipError_t potrf_lower(hipStream_t st, double* A, int64_t lda, int np, in
     // fused: every workgroup factors the diagonal block and solves its 64 rows.  split: one workgroup per cell, the `last` role of the
     // panel kernel alone (L11 staged, L11^-1, pivots; right-hand side as a vector: beta_j = L11^-1 y_j at its end) ...
     double* yv = yvec ? yvec + c : nullptr;
-    const int own_rows = split_panel ? 0 : rows_below;
+    const int own_rows = split_panel ? (pair == 1 ? NB : 0) : rows_below;
     const int nchunks = (own_rows + PANEL_OWN_ROWS - 1) / PANEL_OWN_ROWS;
     const auto diag = fuse ? potrf_panel_kernel<true> : potrf_panel_kernel<false>;
     hipLaunchKernelGGL(diag, dim3(nchunks + 1, batch), dim3(256), 0, st, Acc, lda,
-                       own_rows, nchunks, invd, info, col_base + c, stage_out, prev_stage, prev_dst, NB, cs, info_stride, yv);
+                       own_rows, nchunks, invd, info, col_base + c, stage_out, prev_stage, prev_dst, NB, cs, info_stride, yv, (int)(pair == 2 && yv));
     // ... then the rows below it, 128 per workgroup (and L21 beta_j off the entries of y below)
-    if (split_panel && rows_below > 0) {
+    if (pair == 2) {
+      if (rows_below > 0) {
+        const auto rows = yv ? potrf_rows_pair_kernel<true> : potrf_rows_pair_kernel<false>;
+        hipLaunchKernelGGL(rows, dim3((rows_below + ROWS_WG - 1) / ROWS_WG, batch), dim3(256), 0, st, Acc + (int64_t)NB * lda - NB, lda, rows_below,
+                           (const double*)(stage_out - (int64_t)NB * STAGE_LD), (const double*)stage_out, cs, yv ? yv - NB : nullptr);
+      }
+    } else if (split_panel && rows_below > 0 && pair == 0) {
       const auto rows = fuse ? (yv ? potrf_rows_kernel<true, true> : potrf_rows_kernel<true, false>)
                              : (yv ? potrf_rows_kernel<false, true> : potrf_rows_kernel<false, false>);
       hipLaunchKernelGGL(rows, dim3((rows_below + ROWS_WG - 1) / ROWS_WG, batch), dim3(256), 0, st, Acc + (int64_t)NB * lda, lda, rows_below,
@@ -840,6 +957,11 @@ inline hipError_t potrf_lower(hipStream_t st, double* A, int64_t lda, int np, in
       return;
     }
     const int h = ((w / NB + 1) / 2) * NB;
+    if (h == NB && w - h == NB && rows_pair) {
+      panel(c0, false, 1);
+      panel(c0 + h, true, 2);
+      return;
+    }
     self(self, c0, h);
     if (h == NB && w - h == NB) {
       // the K = 64 update of the right panel rides in its own kernel (split panels too since round 3: the update is HBM-bound there; the

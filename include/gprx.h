@@ -989,6 +989,10 @@ int gprx_gather_rows(int device, const double* field_dev, int64_t rows, int64_t 
  * gprx_factorize_batch).
  * "rhs_vector" (-1: batched cells always carry their right-hand side as a 64-row tile below the matrix, as single calls do; default 0:
  * as a vector wherever the split panel runs -- potrf_rows_kernel<..., YVEC>; see gprx_factorize_batch).
+ * "rows_pair" (batched cells under the split panel; 1, the default: the rows below a pair of panels are solved by ONE launch,
+ * potrf_rows_pair_kernel, which reads the left panel's solved rows back through the L2; 0: one rows launch per panel.  The factor is the
+ * same bit for bit; with the right-hand side as a vector, 64 entries of y per pair are updated in another summation order).  The probe
+ * gprx_potrf_batched reads this key from the process defaults.
  * "dag" (1: ONE matrix is factored by the tile-DAG kernel -- a single persistent launch, the dependent chain of diagonal
  * blocks in one workgroup, every other tile task claimed from a queue and ordered by per-tile version counters in device memory;
  * deterministic, within rounding of the default; default 0 = the launch-per-panel schedule, which measured faster on MI355X:
