@@ -17,6 +17,7 @@
 #include "sweep.h"
 #include "ensemble.h"
 #include "verify.h"
+#include "timing.h"
 
 using namespace gprx;
 
@@ -34,6 +35,7 @@ struct gprx_pca_ctx {
   Buf ens_part;               // gprx_pca_member_stats_dev: per-workgroup wet areas
   double ens_ms = 0.0;        // device time of the last gprx_pca_ensemble_peaks_dev
   double ver_ms = 0.0;        // device time of the last gprx_pca_member_verify_dev
+  double tim_ms = 0.0;        // device time of the last gprx_pca_ensemble_timing_dev
   std::string err;
 };
 
@@ -354,21 +356,40 @@ int check_members(gprx_pca_handle p, int64_t members, int64_t rows_e) {
   if (rows_e >= ((int64_t)1 << 31) || members >= ((int64_t)1 << 31) / rows_e) return fail(p, GPRX_EINVAL, "members x rows must stay below 2^31");
   return GPRX_OK;
 }
+
+// the checks of a fused walk over the members' scores and its grid: *group members per workgroup, *ngroups of them
+int ensemble_walk(gprx_pca_handle p, const double* scores_dev, int64_t members, int64_t rows_e, int depth_mode, int member_group, int* group, int64_t* ngroups) {
+  if (!scores_dev) return fail(p, GPRX_EINVAL, "null argument");
+  int rc;
+  if ((rc = check_members(p, members, rows_e))) return rc;
+  if (depth_mode < 0 || depth_mode > 2) return fail(p, GPRX_EINVAL, "depth mode must be 0 (none), 1 (wse) or 2 (depth)");
+  if (depth_mode && !p->has_elev) return fail(p, GPRX_EINVAL, "the depth conversion needs the cell elevations (the projector was created without them)");
+  if (member_group < 0 || member_group > 64) return fail(p, GPRX_EINVAL, "member_group must be 0 (the launcher's choice) or between 1 and 64");
+  *group = member_group ? member_group : ensemble_group(p->cells, members);
+  *ngroups = (members + *group - 1) / *group;
+  if (*ngroups > 65535) return fail(p, GPRX_EINVAL, "too many member groups: raise member_group");
+  return GPRX_OK;
+}
+
+// n_thr thresholds as the timing kernels take them, copied into dst[ENS_TMAX]
+int check_thresholds(gprx_pca_handle p, int n_thr, const double* thr, double* dst) {
+  if (n_thr < 0 || n_thr > ENS_TMAX || (n_thr && !thr)) return fail(p, GPRX_EINVAL, "at most " + std::to_string(ENS_TMAX) + " thresholds");
+  for (int j = 0; j < n_thr; ++j) {
+    if (thr[j] != thr[j]) return fail(p, GPRX_EINVAL, "a threshold is NaN");
+    dst[j] = thr[j];
+  }
+  return GPRX_OK;
+}
 }  // namespace
 
 int gprx_pca_ensemble_peaks_dev(gprx_pca_handle p, const double* scores_dev, int64_t members, int64_t rows_e, int depth_mode, int member_group,
                                 double* peak_dev) {
   return guarded(p, [&]() -> int {
     if (!p) return fail(p, GPRX_EINVAL, "null handle");
-    if (!scores_dev || !peak_dev) return fail(p, GPRX_EINVAL, "null argument");
-    int rc;
-    if ((rc = check_members(p, members, rows_e))) return rc;
-    if (depth_mode < 0 || depth_mode > 2) return fail(p, GPRX_EINVAL, "depth mode must be 0 (none), 1 (wse) or 2 (depth)");
-    if (depth_mode && !p->has_elev) return fail(p, GPRX_EINVAL, "the depth conversion needs the cell elevations (the projector was created without them)");
-    if (member_group < 0 || member_group > 64) return fail(p, GPRX_EINVAL, "member_group must be 0 (the launcher's choice) or between 1 and 64");
-    const int group = member_group ? member_group : ensemble_group(p->cells, members);
-    const int64_t ngroups = (members + group - 1) / group;
-    if (ngroups > 65535) return fail(p, GPRX_EINVAL, "too many member groups: raise member_group");
+    if (!peak_dev) return fail(p, GPRX_EINVAL, "null argument");
+    int rc, group;
+    int64_t ngroups;
+    if ((rc = ensemble_walk(p, scores_dev, members, rows_e, depth_mode, member_group, &group, &ngroups))) return rc;
     HIPCHK(p, hipSetDevice(p->device));
     hipStream_t st = p->stream;
     EnsembleArgs a{scores_dev, members, rows_e, p->cells, p->k, p->E.p, p->cells_p, p->wrev.p, p->base.p, p->xm.p, p->xs.p, p->elev.p, depth_mode, group, peak_dev};
@@ -380,6 +401,91 @@ int gprx_pca_ensemble_peaks_dev(gprx_pca_handle p, const double* scores_dev, int
     HIPCHK(p, hipEventRecord(p->ev[1], st));
     HIPCHK(p, hipStreamSynchronize(st));
     p->ens_ms = elapsed_ms(p->ev[0], p->ev[1]);
+    return GPRX_OK;
+  });
+}
+
+int gprx_pca_ensemble_timing_dev(gprx_pca_handle p, const double* scores_dev, int64_t members, int64_t rows_e, int depth_mode, int member_group, int n_thr,
+                                 const double* thresholds, double* peak_dev, int* timing_dev) {
+  return guarded(p, [&]() -> int {
+    if (!p) return fail(p, GPRX_EINVAL, "null handle");
+    if (!peak_dev || !timing_dev) return fail(p, GPRX_EINVAL, "null argument");
+    int rc, group;
+    int64_t ngroups;
+    if ((rc = ensemble_walk(p, scores_dev, members, rows_e, depth_mode, member_group, &group, &ngroups))) return rc;
+    if (rows_e > 2147483646) return fail(p, GPRX_EINVAL, "the event's rows must not exceed 2^31 - 2");
+    TimingArgs a{};
+    if ((rc = check_thresholds(p, n_thr, thresholds, a.thr))) return rc;
+    HIPCHK(p, hipSetDevice(p->device));
+    hipStream_t st = p->stream;
+    a.e = EnsembleArgs{scores_dev, members, rows_e, p->cells, p->k, p->E.p, p->cells_p, p->wrev.p, p->base.p, p->xm.p, p->xs.p, p->elev.p, depth_mode, group, peak_dev};
+    a.n_thr = n_thr, a.timing = timing_dev;
+    const dim3 grid((unsigned)((p->cells + 255) / 256), (unsigned)ngroups);
+    HIPCHK(p, hipEventRecord(p->ev[0], st));
+    if (p->k <= 16) hipLaunchKernelGGL(pca_ensemble_timing_kernel<16>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(pca_ensemble_timing_kernel<64>, grid, dim3(256), 0, st, a);
+    HIPCHK(p, hipGetLastError());
+    HIPCHK(p, hipEventRecord(p->ev[1], st));
+    HIPCHK(p, hipStreamSynchronize(st));
+    p->tim_ms = elapsed_ms(p->ev[0], p->ev[1]);
+    return GPRX_OK;
+  });
+}
+
+int gprx_pca_ensemble_timing_ms(gprx_pca_handle p, double* ms) {
+  if (!p || !ms) return fail(p, GPRX_EINVAL, "null argument");
+  *ms = p->tim_ms;
+  return GPRX_OK;
+}
+
+int gprx_pca_member_timing_dev(gprx_pca_handle p, const double* field_dev, int64_t members, int64_t rows_e, int n_thr, const double* thresholds,
+                               double* peak_dev, int* timing_dev) {
+  return guarded(p, [&]() -> int {
+    if (!p) return fail(p, GPRX_EINVAL, "null handle");
+    if (!field_dev || !timing_dev) return fail(p, GPRX_EINVAL, "null argument");
+    int rc;
+    if ((rc = check_members(p, members, rows_e))) return rc;
+    if (rows_e > 2147483646) return fail(p, GPRX_EINVAL, "the event's rows must not exceed 2^31 - 2");
+    if (members > 65535) return fail(p, GPRX_EINVAL, "at most 65535 members per call");
+    FieldTimingArgs a{};
+    if ((rc = check_thresholds(p, n_thr, thresholds, a.thr))) return rc;
+    a.f = field_dev, a.rows_e = rows_e, a.cells = p->cells, a.n_thr = n_thr, a.peak = peak_dev, a.timing = timing_dev;
+    HIPCHK(p, hipSetDevice(p->device));
+    hipLaunchKernelGGL(field_member_timing_kernel, dim3((unsigned)((p->cells + 255) / 256), (unsigned)members), dim3(256), 0, p->stream, a);
+    HIPCHK(p, hipGetLastError());
+    return GPRX_OK;
+  });
+}
+
+int gprx_pca_timing_stats_dev(gprx_pca_handle p, const int* timing_dev, int64_t members, int n_maps, int map0, int n_sel, int64_t rows_e, int sentinel,
+                              int n_lev, const int* levels, int n_rank, const int* ranks, const int* obs_dev, int* cdf_dev, int* n_valid_dev,
+                              int64_t* sum_dev, int* order_dev, int* below_dev, int* equal_dev) {
+  return guarded(p, [&]() -> int {
+    if (!p) return fail(p, GPRX_EINVAL, "null handle");
+    if (!timing_dev || !n_valid_dev || !sum_dev) return fail(p, GPRX_EINVAL, "null argument");
+    if (members < 1 || members > ENS_SMAX) return fail(p, GPRX_EINVAL, "members must be between 1 and " + std::to_string(ENS_SMAX));
+    if (rows_e < 1 || rows_e > 2147483646) return fail(p, GPRX_EINVAL, "the event's rows must lie between 1 and 2^31 - 2");
+    if (n_maps < 1 || n_maps > 1 + 2 * ENS_TMAX || map0 < 0 || n_sel < 1 || n_sel > n_maps - map0)
+      return fail(p, GPRX_EINVAL, "the maps [map0, map0 + n_sel) must lie inside the block's n_maps <= " + std::to_string(1 + 2 * ENS_TMAX));
+    if (sentinel != -1 && (sentinel < 0 || sentinel > rows_e)) return fail(p, GPRX_EINVAL, "the sentinel must be -1 (none) or a value in [0, rows]");
+    if (n_lev < 0 || n_lev > TM_LMAX || (n_lev && (!levels || !cdf_dev)))
+      return fail(p, GPRX_EINVAL, "at most " + std::to_string(TM_LMAX) + " levels, with their output block");
+    if (n_rank < 0 || n_rank > ENS_RMAX || (n_rank && (!ranks || !order_dev)))
+      return fail(p, GPRX_EINVAL, "at most " + std::to_string(ENS_RMAX) + " ranks, with their output block");
+    for (int j = 0; j < n_rank; ++j)
+      if (ranks[j] < 0 || ranks[j] >= members) return fail(p, GPRX_EINVAL, "ranks must lie in [0, members)");
+    if (obs_dev && (!below_dev || !equal_dev)) return fail(p, GPRX_EINVAL, "the observed maps need the below and equal blocks");
+    HIPCHK(p, hipSetDevice(p->device));
+    hipStream_t st = p->stream;
+    TimingStatsArgs a{};
+    a.timing = timing_dev, a.members = members, a.cells = p->cells, a.n_maps = n_maps, a.map0 = map0, a.rows_e = (int)rows_e, a.sentinel = sentinel;
+    a.n_lev = n_lev, a.n_rank = n_rank;
+    for (int j = 0; j < n_lev; ++j) a.level[j] = levels[j];
+    for (int j = 0; j < n_rank; ++j) a.rank[j] = ranks[j];
+    a.obs = obs_dev, a.cdf = cdf_dev, a.n_valid = n_valid_dev, a.sum = reinterpret_cast<long long*>(sum_dev), a.order = order_dev, a.below = below_dev, a.equal = equal_dev;
+    hipLaunchKernelGGL(member_timing_stats_kernel, dim3((unsigned)((p->cells + 255) / 256), (unsigned)n_sel), dim3(256), 0, st, a);
+    HIPCHK(p, hipGetLastError());
+    HIPCHK(p, hipStreamSynchronize(st));
     return GPRX_OK;
   });
 }

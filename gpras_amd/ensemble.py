@@ -23,7 +23,12 @@ maximum over an event's rows does not follow from marginals: the GP's prediction
   event's observed peak -- the CRPS and the rank counts per cell --, and ``PeakVerification`` aggregates those maps on the host: rank
   histogram, mean CRPS, Brier score, reliability table, coverage of a quantile band.
 
-DESIGN.md section 3.23 has the mapping, the determinism argument and the measurement behind ``DEFAULT_ROUTE``; section 3.24 the verification.
+* with ``timing=True``: the same walk (``gprx_pca_ensemble_timing_dev``, csrc/timing.h, in place of the peaks kernel) also leaves per member
+  the row of the peak and per threshold the rows above it and the first of them; ``gprx_pca_timing_stats_dev`` reduces those integer maps over
+  the members and ``EventTiming`` holds the result: when the water arrives, how long it stays, when it peaks.
+
+DESIGN.md section 3.23 has the mapping, the determinism argument and the measurement behind ``DEFAULT_ROUTE``; section 3.24 the verification;
+section 3.25 the event timing.
 """
 
 from __future__ import annotations
@@ -49,7 +54,10 @@ DEFAULT_RNG = "host"
 DEPTH_MODES = {"velocity": 0, "wse": 1, "depth": 2}
 JOINT_MAX_M, JOINT_MAX_ROWS, JOINT_MAX_D = 320, 1024, 64
 MAX_MEMBERS, MAX_THRESHOLDS, MAX_RANKS = 4096, 8, 8
-STAGES = ("joint", "draw_upload", "draws", "peaks", "stats")  # (the statistics' stage includes their download; ``observed=`` adds "verify")
+MAX_LEVELS = 8  # levels of the distribution function per ``gprx_pca_timing_stats_dev``: ``durations`` and ``arrive_by`` of ``evaluate``
+MAX_EVENT_ROWS = 2**31 - 2  # the timing maps are int32 and the arrival's sentinel is the row count itself
+# (the statistics' stage includes their download; ``observed=`` adds "verify", ``timing=True`` adds "timing")
+STAGES = ("joint", "draw_upload", "draws", "peaks", "stats")
 
 
 def joint_applies(n_inducing, d: int, rows: int) -> str | None:
@@ -141,6 +149,57 @@ def check_event_ranges(ranges, rows: int):
     return lo, hi
 
 
+def timing_maps(n_thr: int) -> int:
+    """The maps of a timing block: ``t_peak``, then a duration and an arrival per threshold."""
+    return 1 + 2 * int(n_thr)
+
+
+def check_levels(values, name: str) -> np.ndarray:
+    """``values`` (``durations`` or ``arrive_by``) as int32: at most ``MAX_LEVELS`` non-negative integers, in rows."""
+    v = np.atleast_1d(np.asarray(values))
+    if v.size == 0:
+        return np.zeros(0, dtype=np.int32)
+    if v.dtype.kind not in "iu":
+        raise ValueError(f"{name} must be integers (rows)")
+    if v.ndim != 1 or v.size > MAX_LEVELS:
+        raise ValueError(f"at most {MAX_LEVELS} {name}")
+    if np.any(v < 0) or np.any(v > MAX_EVENT_ROWS):
+        raise ValueError(f"{name} must lie in [0, {MAX_EVENT_ROWS}]")
+    return np.ascontiguousarray(v, dtype=np.int32)
+
+
+def check_timing_args(timing: bool, thresholds, durations=(), arrive_by=()):
+    """``(durations, arrive_by)`` int32 as ``evaluate`` takes them: each at most ``MAX_LEVELS`` non-negative integers; ``timing=True`` needs a
+    threshold, and without it neither list may be given."""
+    dur, by = check_levels(durations, "durations"), check_levels(arrive_by, "arrive_by")
+    if not timing:
+        if dur.size or by.size:
+            raise ValueError("durations and arrive_by need timing=True")
+    elif np.atleast_1d(np.asarray(thresholds)).size == 0:
+        raise ValueError("timing=True needs at least one threshold")
+    return dur, by
+
+
+def check_timing_stats_args(members: int, n_maps: int, map0: int, n_sel: int, rows: int, sentinel: int = -1, levels=(), ranks=()):
+    """``(levels int32, ranks int32)`` as ``gprx_pca_timing_stats_dev`` takes them, the other arguments checked as it checks them."""
+    _, rk = check_stats_args(members, (), ranks)
+    n_maps, map0, n_sel, rows, sentinel = int(n_maps), int(map0), int(n_sel), int(rows), int(sentinel)
+    if not 1 <= rows <= MAX_EVENT_ROWS:
+        raise ValueError(f"an event has between 1 and {MAX_EVENT_ROWS} rows")
+    if not 1 <= n_maps <= timing_maps(MAX_THRESHOLDS) or map0 < 0 or n_sel < 1 or map0 + n_sel > n_maps:
+        raise ValueError(f"the maps [map0, map0 + n_sel) must lie inside the block's n_maps <= {timing_maps(MAX_THRESHOLDS)}")
+    if sentinel != -1 and not 0 <= sentinel <= rows:
+        raise ValueError("the sentinel must be -1 (none) or a value in [0, rows]")
+    lv = np.atleast_1d(np.asarray(levels))
+    if lv.size and lv.dtype.kind not in "iu":
+        raise ValueError("levels must be integers")
+    if lv.ndim != 1 or lv.size > MAX_LEVELS:
+        raise ValueError(f"at most {MAX_LEVELS} levels")
+    if lv.size and (np.any(lv < -(2**31)) or np.any(lv >= 2**31)):
+        raise ValueError("levels must be 32-bit integers")
+    return np.ascontiguousarray(lv, dtype=np.int32), rk
+
+
 @dataclass
 class EnsembleResult:
     """Per event ``e``: ``p_exceed (E, n_thr, cells)`` = exceedance counts / S; ``peak_mean``, ``peak_std`` ``(E, cells)`` (ddof = 0);
@@ -162,6 +221,7 @@ class EnsembleResult:
     names: list = field(default_factory=list)  # the events' labels (``DevicePipeline.peak_ensemble``)
     rng: str = DEFAULT_RNG  # where the normals were drawn ("host" also when the caller passed ``normals``)
     verification: "PeakVerification | None" = None  # the ensemble against the observed peaks (``evaluate(observed=...)``)
+    timing: "EventTiming | None" = None  # arrival, duration and time of the peak (``evaluate(timing=True)``)
 
 
 @dataclass
@@ -257,6 +317,74 @@ class PeakVerification:
             return inside.sum(axis=1) / v.sum(axis=1).astype(np.float64)
 
 
+@dataclass
+class EventTiming:
+    """When the water arrives, how long it stays and when it peaks, per event ``e`` and cell over the ``members`` of the ensemble, in ROWS
+    counted from the event's first (hours are the caller's ``dt``).  Per member: ``t_peak`` the row of the first maximum, ``duration[j]``
+    the rows with depth ``> thresholds[j]`` (strict), ``arrival[j]`` the first of them.  What is stored are the exact integers
+    ``gprx_pca_timing_stats_dev`` leaves; the probabilities and means are properties, one division each:
+
+    * ``t_peak_sum (E, cells)`` int64, ``t_peak_quantiles (E, n_q, cells)`` int32 (rank ``floor(q (S - 1))``, as the peak's quantiles);
+    * ``duration_sum (E, n_thr, cells)`` int64, ``duration_quantiles (E, n_thr, n_q, cells)``, ``duration_below_counts (E, n_thr, n_dur, cells)``:
+      the members with ``duration <= durations[i] - 1``;
+    * ``arrival_counts (E, n_thr, cells)``: the members that arrive at all (it equals the exceedance count of the peak), ``arrival_sum`` over those
+      members, ``arrival_quantiles (E, n_thr, n_q, cells)`` over ALL members -- the value ``rows[e]`` reads "not within the event" --,
+      ``arrival_by_counts (E, n_thr, n_by, cells)``: the members with ``arrival <= arrive_by[i]`` (a member that never arrives is in none);
+    * with ``observed=``: ``observed (E, n_maps, cells)`` the same maps of the truth (``n_maps = 1 + 2 n_thr``: ``t_peak``, the durations, the
+      arrivals) and ``below``, ``equal`` ``(E, n_maps, cells)``: the members below the observed value and equal to it."""
+
+    t_peak_sum: np.ndarray
+    t_peak_quantiles: np.ndarray
+    duration_sum: np.ndarray
+    duration_quantiles: np.ndarray
+    duration_below_counts: np.ndarray
+    arrival_counts: np.ndarray
+    arrival_sum: np.ndarray
+    arrival_quantiles: np.ndarray
+    arrival_by_counts: np.ndarray
+    rows: np.ndarray
+    members: int
+    thresholds: np.ndarray
+    quantiles: np.ndarray
+    durations: np.ndarray
+    arrive_by: np.ndarray
+    observed: np.ndarray | None = None
+    below: np.ndarray | None = None
+    equal: np.ndarray | None = None
+    names: list = field(default_factory=list)
+
+    @property
+    def t_peak_mean(self) -> np.ndarray:
+        """``(E, cells)``: the mean row of the peak."""
+        return self.t_peak_sum / float(self.members)
+
+    @property
+    def duration_mean(self) -> np.ndarray:
+        """``(E, n_thr, cells)``: the mean number of rows above the threshold (members that stay dry count with 0)."""
+        return self.duration_sum / float(self.members)
+
+    @property
+    def p_duration_at_least(self) -> np.ndarray:
+        """``(E, n_thr, n_dur, cells)``: ``P(duration >= durations[i]) = 1 - cdf(durations[i] - 1) / S``."""
+        return 1.0 - self.duration_below_counts / float(self.members)
+
+    @property
+    def p_arrival(self) -> np.ndarray:
+        """``(E, n_thr, cells)``: the share of the members in which the water arrives within the event."""
+        return self.arrival_counts / float(self.members)
+
+    @property
+    def arrival_mean(self) -> np.ndarray:
+        """``(E, n_thr, cells)``: the mean arrival row over the members that arrive; NaN where none does."""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(self.arrival_counts > 0, self.arrival_sum / self.arrival_counts.astype(np.float64), np.nan)
+
+    @property
+    def p_arrival_by(self) -> np.ndarray:
+        """``(E, n_thr, n_by, cells)``: ``P(arrival <= arrive_by[i])``."""
+        return self.arrival_by_counts / float(self.members)
+
+
 class PeakEnsemble:
     def __init__(self, gpr, projector):
         """``gpr``: a fitted (or loaded) ``gpras_amd.GPRAS`` of sparse models; ``projector``: the ``EOFProjector`` of its outputs."""
@@ -269,6 +397,13 @@ class PeakEnsemble:
         self._lib = _lib.load()
         self.last_device_peaks_ms = 0.0  # device time of the last fused peak kernel (``gprx_pca_ensemble_ms``)
         self.last_device_verify_ms = 0.0  # device time of the last verification kernel (``gprx_pca_member_verify_ms``)
+        self.last_device_timing_ms = 0.0  # device time of the last fused timing kernel (``gprx_pca_ensemble_timing_ms``)
+
+    def _check(self, rc: int) -> None:
+        """``check``, with the handle's reason as a ValueError where the library refused the arguments."""
+        if rc == _lib.GPRX_EINVAL:
+            raise ValueError((self._lib.gprx_pca_last_error(self.projector.handle) or b"").decode())
+        check(rc)
 
     # ---- 1. joint prediction over one event -------------------------------------------------------------------------------------------
     def joint_dev(self, x_event, include_noise: bool = True):
@@ -392,6 +527,19 @@ class PeakEnsemble:
     # ---- 3. peaks -----------------------------------------------------------------------------------------------------------------------
     def member_peaks_dev(self, scores, members: int, rows: int, route: str | None = None, member_group: int = 0) -> DeviceBuffer:
         """``peak (S, cells)`` on the device from the members' scores: a host array ``(S, rows, K)`` or a device buffer of that block."""
+        return self._member_walk(scores, members, rows, route, member_group, None)[0]
+
+    def member_timing_dev(self, scores, members: int, rows: int, thresholds, route: str | None = None, member_group: int = 0):
+        """``(peak, timing)`` on the device from the members' scores (as ``member_peaks_dev`` takes them): ``peak (S, cells)``, bit for bit
+        ``member_peaks_dev``'s, and the int32 block ``timing (S, n_maps, cells)``, ``n_maps = 1 + 2 n_thr``: map 0 the row of the peak
+        (``np.argmax`` over the member's rows), map ``1 + j`` the rows with depth ``> thresholds[j]`` (strict), map ``1 + n_thr + j`` the first
+        of them, ``rows`` where there is none.  ``route="fused"``: ``gprx_pca_ensemble_timing_dev``, one walk for both; ``route="refield"``:
+        reverse -> depth -> ``gprx_pca_member_timing_dev`` on slabs of whole members.  The caller frees both buffers."""
+        thr, _ = check_stats_args(1, thresholds, ())
+        return self._member_walk(scores, members, rows, route, member_group, thr)
+
+    def _member_walk(self, scores, members: int, rows: int, route, member_group: int, thr):
+        """``(peak, timing)`` of one walk over the members' rows; ``thr`` None: the peaks alone (``timing`` None)."""
         route = DEFAULT_ROUTE if route is None else route
         if route not in ROUTES:
             raise ValueError(f"route must be one of {ROUTES}")
@@ -410,14 +558,24 @@ class PeakEnsemble:
             scores = owned = DeviceBuffer.from_array(arr, dev)
         elif getattr(scores, "nbytes", 8 * members * rows * k) < 8 * members * rows * k:
             raise ValueError("the scores buffer is too small")
-        peak = DeviceBuffer(8 * members * cells, dev)
+        n_thr = 0 if thr is None else int(thr.size)
+        member_ints = timing_maps(n_thr) * cells  # int32 values of one member's maps
+        peak = timing = None
         try:
+            peak = DeviceBuffer(8 * members * cells, dev)
+            if thr is not None:
+                timing = DeviceBuffer((4 * members * member_ints + 7) // 8 * 8, dev)
             ph = pr.handle
-            if route == "fused":
+            ms = C.c_double()
+            if route == "fused" and thr is None:
                 check(lib.gprx_pca_ensemble_peaks_dev(ph, scores.ptr, members, rows, DEPTH_MODES[pr.hydraulic_parameter], int(member_group), peak.ptr))
-                ms = C.c_double()
                 check(lib.gprx_pca_ensemble_ms(ph, C.byref(ms)))
                 self.last_device_peaks_ms = ms.value
+            elif route == "fused":
+                self._check(lib.gprx_pca_ensemble_timing_dev(ph, scores.ptr, members, rows, DEPTH_MODES[pr.hydraulic_parameter], int(member_group), n_thr,
+                                                             ptr(thr), peak.ptr, timing.ptr))
+                check(lib.gprx_pca_ensemble_timing_ms(ph, C.byref(ms)))
+                self.last_device_timing_ms = ms.value
             else:
                 per_slab = max(1, min(members, 65535, slab_rows(pr) // rows))
                 fieldbuf = DeviceBuffer(8 * per_slab * rows * cells, dev)
@@ -427,17 +585,102 @@ class PeakEnsemble:
                         check(lib.gprx_pca_reverse_dev(ph, scores.at(s0 * rows * k), None, ns * rows, fieldbuf.ptr, None))
                         if pr.hydraulic_parameter != "velocity":
                             check(lib.gprx_pca_to_depth_dev(ph, fieldbuf.ptr, ns * rows, int(pr.hydraulic_parameter == "depth")))
-                        check(lib.gprx_pca_member_peaks_dev(ph, fieldbuf.ptr, ns, rows, peak.at(s0 * cells)))
+                        if thr is None:
+                            check(lib.gprx_pca_member_peaks_dev(ph, fieldbuf.ptr, ns, rows, peak.at(s0 * cells)))
+                        else:
+                            self._check(lib.gprx_pca_member_timing_dev(ph, fieldbuf.ptr, ns, rows, n_thr, ptr(thr), peak.at(s0 * cells),
+                                                                       C.c_void_p(timing.ptr.value + 4 * s0 * member_ints)))
                     check(lib.gprx_pca_synchronize(ph))
                 finally:
                     fieldbuf.free()
         except Exception:
-            peak.free()
+            for buf in (peak, timing):
+                if buf is not None:
+                    buf.free()
             raise
         finally:
             if owned is not None:
                 owned.free()
-        return peak
+        return peak, timing
+
+    # ---- 3b. event timing: the observed maps and the statistics over the members' maps ------------------------------------------------------
+    def observed_timing_dev(self, truth, lo: int, hi: int, thresholds) -> DeviceBuffer:
+        """The observed timing maps, int32 ``(n_maps, cells)`` on the device, of the event in rows ``[lo, hi)`` of ``truth (rows, cells)`` (as
+        ``observed_peak_dev`` takes it): ``gprx_pca_member_timing_dev`` with one member, so every rule is the members' own.  The caller frees it."""
+        thr, _ = check_stats_args(1, thresholds, ())
+        lo, hi = int(lo), int(hi)
+        cells, dev = self.projector.n_cells, self.device
+        if not 0 <= lo < hi:
+            raise ValueError("need 0 <= lo < hi")
+        owned = None
+        if isinstance(truth, DeviceBuffer):
+            if truth.nbytes < 8 * hi * cells:
+                raise ValueError(f"the truth buffer does not reach row {hi}")
+            src = truth.at(lo * cells)
+        else:
+            arr = np.asarray(truth)
+            if arr.ndim != 2 or arr.shape[1] != cells or arr.shape[0] < hi:
+                raise ValueError(f"truth must be (rows >= {hi}, {cells})")
+            owned = DeviceBuffer.from_array(arr[lo:hi], dev)
+            src = owned.ptr
+        out = DeviceBuffer((4 * timing_maps(thr.size) * cells + 7) // 8 * 8, dev)
+        try:
+            self._check(self._lib.gprx_pca_member_timing_dev(self.projector.handle, src, 1, hi - lo, int(thr.size), ptr(thr), None, out.ptr))
+            check(self._lib.gprx_pca_synchronize(self.projector.handle))
+        except Exception:
+            out.free()
+            raise
+        finally:
+            if owned is not None:
+                owned.free()
+        return out
+
+    def timing_to_array(self, timing_dev, members: int, n_maps: int) -> np.ndarray:
+        """A timing block on the device as the host array int32 ``(members, n_maps, cells)``."""
+        n = int(members) * int(n_maps) * self.projector.n_cells
+        return timing_dev.to_array(((n + 1) // 2,)).view(np.int32)[:n].reshape(int(members), int(n_maps), self.projector.n_cells).copy()
+
+    def timing_stats(self, timing_dev, members: int, n_maps: int, map0: int, n_sel: int, rows: int, sentinel: int = -1, levels=(), ranks=(),
+                     obs_dev=None) -> dict:
+        """The statistics over the members of the maps ``[map0, map0 + n_sel)`` of a timing block ``(S, n_maps, cells)`` on the device, as host
+        arrays (``gprx_pca_timing_stats_dev``, csrc/timing.h), all exact integers: ``cdf (n_sel, n_lev, cells)`` int32, the members with a value
+        ``<= levels[l]``; ``n_valid (n_sel, cells)`` int32 and ``sum (n_sel, cells)`` int64 over the members whose value is not ``sentinel`` (-1: every
+        member counts); ``order (n_sel, n_rank, cells)`` int32 = ``np.sort(v, axis=0)[ranks]`` over all members; and with ``obs_dev``, the observed value of
+        each selected map ``(n_sel, cells)`` int32 on the device (a pointer or a buffer), ``below`` and ``equal`` ``(n_sel, cells)`` int32."""
+        lv, rk = check_timing_stats_args(members, n_maps, map0, n_sel, rows, sentinel, levels, ranks)
+        pr, dev = self.projector, self.device
+        cells, members, n_sel = pr.n_cells, int(members), int(n_sel)
+        n_lev, n_rk = int(lv.size), int(rk.size)
+        with_obs = obs_dev is not None
+        # one block: sum (int64) | cdf | n_valid | order | below | equal (int32)
+        mc = n_sel * cells
+        o_cdf = 2 * mc
+        o_valid = o_cdf + n_lev * mc
+        o_order = o_valid + mc
+        o_below = o_order + n_rk * mc
+        n_int = o_below + (2 * mc if with_obs else 0)
+        out = DeviceBuffer((4 * n_int + 7) // 8 * 8, dev)
+
+        def at(off):
+            return C.c_void_p(out.ptr.value + 4 * off)
+
+        try:
+            self._check(self._lib.gprx_pca_timing_stats_dev(
+                pr.handle, timing_dev.ptr if hasattr(timing_dev, "ptr") else timing_dev, members, int(n_maps), int(map0), n_sel, int(rows), int(sentinel),
+                n_lev, ptr(lv), n_rk, ptr(rk), None if not with_obs else (obs_dev.ptr if hasattr(obs_dev, "ptr") else obs_dev),
+                at(o_cdf) if n_lev else None, at(o_valid), out.ptr, at(o_order) if n_rk else None, at(o_below) if with_obs else None,
+                at(o_below + mc) if with_obs else None))
+            host = out.to_array(((n_int + 1) // 2,))
+        finally:
+            out.free()
+        ints = host.view(np.int32)
+        res = {"sum": host[:mc].view(np.int64).reshape(n_sel, cells).copy(), "cdf": ints[o_cdf:o_valid].reshape(n_sel, n_lev, cells).copy(),
+               "n_valid": ints[o_valid:o_order].reshape(n_sel, cells).copy(), "order": ints[o_order:o_below].reshape(n_sel, n_rk, cells).copy(),
+               "below": None, "equal": None}
+        if with_obs:
+            res["below"] = ints[o_below:o_below + mc].reshape(n_sel, cells).copy()
+            res["equal"] = ints[o_below + mc:o_below + 2 * mc].reshape(n_sel, cells).copy()
+        return res
 
     # ---- 4. statistics ------------------------------------------------------------------------------------------------------------------
     def member_stats(self, peak_dev, members: int, thresholds=(), ranks=(), cell_areas=None) -> dict:
@@ -536,7 +779,7 @@ class PeakEnsemble:
     # ---- the whole chain ------------------------------------------------------------------------------------------------------------------
     def evaluate(self, x_test, ranges, members: int, thresholds=(0.5,), quantiles=(0.05, 0.5, 0.95), seed=0, normals=None, cell_areas=None,
                  include_noise: bool = True, route: str | None = None, rng: str = DEFAULT_RNG, stream=0, antithetic: bool = False,
-                 observed=None) -> EnsembleResult:
+                 observed=None, timing: bool = False, durations=(), arrive_by=()) -> EnsembleResult:
         """``x_test (rows, d)``; ``ranges``: the events' ``(lo, hi)`` row ranges, ascending and disjoint; ``members``: S.  ``normals``: one
         ``(K, S, rows_e)`` array per event instead of the generator seeded with ``seed``.  ``rng="host"``: ``np.random.default_rng(seed)``, one
         sequential stream over the events; ``rng="device"``: event ``e`` takes ``normals_dev(e, members, rows_e, seed, stream, antithetic)`` --
@@ -545,7 +788,12 @@ class PeakEnsemble:
         ``observed``: the truth ``(rows, cells)``, row-aligned with ``x_test`` and in the peaks' units, a host array (sent up event by event, every row once) or a
         ``DeviceBuffer``: every event's peaks are then also scored against its observed peak (``observed_peak_dev``, ``verify_peaks``) in a
         ``"verify"`` stage of the timer and the result carries a ``PeakVerification``; ``None`` launches nothing more and leaves
-        ``verification`` None."""
+        ``verification`` None.
+        ``timing=True`` (at least one threshold): the walk over the members' rows is ``member_timing_dev`` in place of ``member_peaks_dev`` -- one
+        walk, the same ``peak`` bit for bit, so every other field of the result keeps its bits -- and a ``"timing"`` stage reduces the members'
+        maps (``timing_stats``) to ``result.timing``, an ``EventTiming`` at ``thresholds`` and ``quantiles``: ``durations`` (rows, at most 8) are the
+        ``D`` of ``p_duration_at_least``, ``arrive_by`` (rows, at most 8) the ``t`` of ``p_arrival_by``; with ``observed=`` it carries the observed maps
+        (``observed_timing_dev``) and the members below and equal to them.  ``timing=False`` launches nothing more and leaves ``timing`` None."""
         route = DEFAULT_ROUTE if route is None else route
         if route not in ROUTES:
             raise ValueError(f"route must be one of {ROUTES}")
@@ -567,6 +815,7 @@ class PeakEnsemble:
         lo, hi = check_event_ranges(ranges, x.shape[0])
         members = int(members)
         thr, _ = check_stats_args(members, thresholds, ())
+        dur, by = check_timing_args(timing, thr, durations, arrive_by)
         q = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
         _, rk = check_stats_args(members, (), quantile_ranks(q, members))
         if normals is not None and len(normals) != lo.size:
@@ -576,7 +825,7 @@ class PeakEnsemble:
         verify = observed is not None
         if verify:
             observed = check_observed(observed, x.shape[0], cells)
-        timer = StageTimer(STAGES + ("verify",) if verify else STAGES)
+        timer = StageTimer(STAGES + (("verify",) if verify else ()) + (("timing",) if timing else ()))
         counts = np.zeros((ne, thr.size, cells), dtype=np.int32)
         mean, std = np.zeros((ne, cells)), np.zeros((ne, cells))
         order = np.zeros((ne, rk.size, cells))
@@ -585,9 +834,18 @@ class PeakEnsemble:
         if verify:
             crps, obs_peak = np.zeros((ne, cells)), np.zeros((ne, cells))
             below, equal = np.zeros((ne, cells), dtype=np.int32), np.zeros((ne, cells), dtype=np.int32)
+        if timing:
+            n_thr, n_q, n_maps = int(thr.size), int(rk.size), timing_maps(thr.size)
+            tm = EventTiming(np.zeros((ne, cells), dtype=np.int64), np.zeros((ne, n_q, cells), dtype=np.int32),
+                             np.zeros((ne, n_thr, cells), dtype=np.int64), np.zeros((ne, n_thr, n_q, cells), dtype=np.int32),
+                             np.zeros((ne, n_thr, dur.size, cells), dtype=np.int32), np.zeros((ne, n_thr, cells), dtype=np.int32),
+                             np.zeros((ne, n_thr, cells), dtype=np.int64), np.zeros((ne, n_thr, n_q, cells), dtype=np.int32),
+                             np.zeros((ne, n_thr, by.size, cells), dtype=np.int32), (hi - lo).astype(np.int64), members, thr, q, dur, by)
+            if verify:
+                tm.observed, tm.below, tm.equal = (np.zeros((ne, n_maps, cells), dtype=np.int32) for _ in range(3))
         for e, (a, b) in enumerate(zip(lo.tolist(), hi.tolist())):
             rows = b - a
-            mean_dev = lc_dev = scores = peak = zn = truth_peak = None
+            mean_dev = lc_dev = scores = peak = zn = truth_peak = maps_dev = truth_maps = None
             try:
                 mean_dev, lc_dev, _ = self.joint_dev(x[a:b], include_noise=include_noise)
                 timer.lap("joint")
@@ -597,9 +855,12 @@ class PeakEnsemble:
                 else:
                     zn = host_rng.standard_normal((k, members, rows)) if host_rng is not None else normals[e]
                 scores = self.scores_dev(mean_dev, lc_dev, zn, members, rows, timer=timer)
-                peak = self.member_peaks_dev(scores, members, rows, route=route)
+                if timing:
+                    peak, maps_dev = self.member_timing_dev(scores, members, rows, thr, route=route)
+                else:
+                    peak = self.member_peaks_dev(scores, members, rows, route=route)
                 timer.lap("peaks")
-                device_peaks += self.last_device_peaks_ms if route == "fused" else 0.0
+                device_peaks += (self.last_device_timing_ms if timing else self.last_device_peaks_ms) if route == "fused" else 0.0
                 st = self.member_stats(peak, members, thr, rk, cell_areas)
                 timer.lap("stats")
                 if verify:
@@ -611,8 +872,27 @@ class PeakEnsemble:
                     device_verify += self.last_device_verify_ms
                     crps[e], below[e], equal[e], obs_peak[e] = vr["crps"], vr["below"], vr["equal"], truth_peak.to_array((cells,))
                     timer.lap("verify")
+                if timing:
+                    if verify:
+                        truth_maps = self.observed_timing_dev(observed, a, b, thr)
+                        if not isinstance(observed, DeviceBuffer):
+                            timer.link_bytes += 8 * rows * cells
+                        tm.observed[e] = self.timing_to_array(truth_maps, 1, n_maps)[0]
+                    # the row of the peak | the durations | the arrivals (sentinel: the row count; a level at or past it would count it)
+                    parts = ((0, 1, -1, ()), (1, n_thr, -1, dur - 1), (1 + n_thr, n_thr, rows, np.minimum(by, rows - 1)))
+                    st_t, st_d, st_a = (self.timing_stats(maps_dev, members, n_maps, m0, n_sel, rows, sentinel, levels, rk,
+                                                          None if truth_maps is None else C.c_void_p(truth_maps.ptr.value + 4 * m0 * cells))
+                                        for m0, n_sel, sentinel, levels in parts)
+                    tm.t_peak_sum[e], tm.t_peak_quantiles[e] = st_t["sum"][0], st_t["order"][0]
+                    tm.duration_sum[e], tm.duration_quantiles[e], tm.duration_below_counts[e] = st_d["sum"], st_d["order"], st_d["cdf"]
+                    tm.arrival_counts[e], tm.arrival_sum[e], tm.arrival_quantiles[e] = st_a["n_valid"], st_a["sum"], st_a["order"]
+                    tm.arrival_by_counts[e] = st_a["cdf"]
+                    if verify:
+                        tm.below[e] = np.concatenate([st_t["below"], st_d["below"], st_a["below"]])
+                        tm.equal[e] = np.concatenate([st_t["equal"], st_d["equal"], st_a["equal"]])
+                    timer.lap("timing")
             finally:
-                for buf in (mean_dev, lc_dev, scores, peak, zn if rng == "device" else None, truth_peak):
+                for buf in (mean_dev, lc_dev, scores, peak, zn if rng == "device" else None, truth_peak, maps_dev, truth_maps):
                     if buf is not None:
                         buf.free()
             counts[e], mean[e], std[e], order[e], wet[e] = st["exceed"], st["mean"], st["std"], st["order"], st["wet_area"]
@@ -624,4 +904,4 @@ class PeakEnsemble:
             timings["device_verify"] = device_verify
             verification = PeakVerification(crps, below, equal, obs_peak, members, thr, counts)
         return EnsembleResult(counts / members, mean, std, order, wet, counts, thr, q, list(zip(lo.tolist(), hi.tolist())), members, route, timings,
-                              rng=rng, verification=verification)
+                              rng=rng, verification=verification, timing=tm if timing else None)

@@ -233,7 +233,8 @@ class DevicePipeline:
         index of ``hf_test_data_df_or_index`` (a data frame or the index itself, one entry per row of ``x_test``); ``kwargs`` are those of
         ``PeakEnsemble.evaluate``.  Returns its ``EnsembleResult`` with the events' labels in ``names``.  ``verify=True`` (a data frame, not the
         index alone): the truth goes up once through ``truth_depth_dev`` and the result carries the ``PeakVerification`` of the ensemble
-        against every event's observed peak."""
+        against every event's observed peak.  ``timing=True`` (a keyword of ``evaluate``) adds the ``EventTiming`` -- arrival, duration and time of
+        the peak --, with ``verify=True`` against the observed ones."""
         from .diagnostics import event_ranges
         from .ensemble import PeakEnsemble
 
@@ -255,6 +256,8 @@ class DevicePipeline:
         result.names = list(names)
         if result.verification is not None:
             result.verification.names = list(names)
+        if result.timing is not None:
+            result.timing.names = list(names)
         return result
 
     # ---- pipeline.py:90-210 (gen_plots) -----------------------------------------------------------------------------------------

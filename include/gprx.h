@@ -621,6 +621,36 @@ int gprx_pca_member_verify_dev(gprx_pca_handle p, const double* peak_dev, const 
                                double* crps_dev, int* below_dev, int* equal_dev, double* order_dev);
 int gprx_pca_member_verify_ms(gprx_pca_handle p, double* ms);
 int gprx_pca_member_verify_tile(int64_t members, int* tile_cells);
+/* Event timing of the same members (csrc/timing.h): with y[t] the value gprx_pca_ensemble_peaks_dev forms at row t of a member, thresholds
+ * thr[0 .. n_thr), n_thr <= 8 (host array, no NaN), per (member, cell) in rows counted from the event's first:
+ *   t_peak      = the row of the first maximum (a NaN is the maximum and sticks): np.argmax(y)
+ *   duration[j] = the number of rows with y[t] > thr[j] (strict; a NaN row is not counted)
+ *   arrival[j]  = the first such row, or the sentinel rows_e when there is none
+ * timing_dev: int32 (members, n_maps, n_cells), n_maps = 1 + 2 n_thr: map 0 t_peak, map 1 + j duration[j], map 1 + n_thr + j arrival[j].
+ * gprx_pca_ensemble_timing_dev: the walk of gprx_pca_ensemble_peaks_dev with the same arguments; it also writes peak_dev (members, n_cells),
+ * bit for bit that call's, so one walk serves both.  The maps do not depend on the grouping.  rows_e <= 2^31 - 2.  The call synchronises;
+ * gprx_pca_ensemble_timing_ms: device milliseconds of the last one.
+ * gprx_pca_member_timing_dev: the same maps from a resident field_dev (members * rows_e, n_cells) as gprx_pca_member_peaks_dev reads it (one
+ * member of the truth: the observed maps); peak_dev may be NULL.  At most 65535 members per call.  Asynchronous on the projector's stream.
+ * GPRX_EINVAL leaves the handle usable. */
+int gprx_pca_ensemble_timing_dev(gprx_pca_handle p, const double* scores_dev, int64_t members, int64_t rows_e, int depth_mode, int member_group, int n_thr,
+                                 const double* thresholds, double* peak_dev, int* timing_dev);
+int gprx_pca_ensemble_timing_ms(gprx_pca_handle p, double* ms);
+int gprx_pca_member_timing_dev(gprx_pca_handle p, const double* field_dev, int64_t members, int64_t rows_e, int n_thr, const double* thresholds,
+                               double* peak_dev, int* timing_dev);
+/* Statistics over the members of the maps [map0, map0 + n_sel) of a timing block (members, n_maps, n_cells), 1 <= members <= 4096, whose values
+ * v_s lie in [0, rows_e], 1 <= rows_e <= 2^31 - 2; every loop in member order and every result an exact integer.  Per (map, cell):
+ *   cdf (n_sel, n_lev, n_cells) int32: the count of v_s <= levels[l], n_lev <= 8 (host array)
+ *   n_valid (n_sel, n_cells) int32 and sum (n_sel, n_cells) int64: the members with v_s != sentinel and the sum of their values; sentinel
+ *     -1: every member counts, else a value in [0, rows_e] (the arrival maps: rows_e).  The mean is the caller's one division sum / n_valid.
+ *   order (n_sel, n_rank, n_cells) int32: np.sort(v, axis=0)[ranks[j]] over ALL members (the sentinel rows_e is the largest value and sorts
+ *     last), n_rank <= 8 ranks in [0, members) (host array): bisection on the values, ceil(log2(rows_e + 1)) passes over the members
+ *   below, equal (n_sel, n_cells) int32, with obs_dev (n_sel, n_cells) int32, the observed value of each selected map: the counts of
+ *     v_s < obs and of v_s == obs; obs_dev NULL: not written (below_dev, equal_dev may be NULL)
+ * cdf_dev may be NULL when n_lev = 0, order_dev when n_rank = 0.  The call synchronises.  GPRX_EINVAL leaves the handle usable. */
+int gprx_pca_timing_stats_dev(gprx_pca_handle p, const int* timing_dev, int64_t members, int n_maps, int map0, int n_sel, int64_t rows_e, int sentinel,
+                              int n_lev, const int* levels, int n_rank, const int* ranks, const int* obs_dev, int* cdf_dev, int* n_valid_dev,
+                              int64_t* sum_dev, int* order_dev, int* below_dev, int* equal_dev);
 
 /* ---- fitting the EOF preprocessor: PreProcessor.fit (gpras/preprocess.py:947-1007) --------------------------------------- */
 /* The fitted state gprx_pca_create takes, computed on the device.  Single-batch IncrementalPCA (sklearn partial_fit, first

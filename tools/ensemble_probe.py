@@ -3,7 +3,7 @@ the existing kernels), alternating, by the stage timer of ``PeakEnsemble.evaluat
 synchronisation) and the device time of the fused launches.
 
     python tools/ensemble_probe.py [--events 35] [--event-rows 86] [--cells 100000] [--modes 50] [--members 256] [--repeats 3]
-                                   [--rng host|device|both] [--verify] [--out profiles/ensemble_peaks.json]
+                                   [--rng host|device|both] [--verify] [--timing] [--out profiles/ensemble_peaks.json]
 
 A ``GPRAS`` of ``--modes`` sparse models (M = 50, a few Adam steps: the probe times the prediction side) feeds ``PeakEnsemble.evaluate``.
 The first round warms both routes up and compares them (every output bit for bit), so that a faster number is a number for the same
@@ -18,7 +18,13 @@ timer; ``draw_upload`` is the stage the generator is timed in.
 
 ``--verify`` (profiles/ensemble_verify.json) measures the verification against the truth instead: the ``"verify"`` stage of
 ``evaluate(observed=...)`` with ``"stats"`` beside it, the device time of ``gprx_pca_member_verify_dev`` by HIP events, and the same scores formed
-on the host from a downloaded ``peak`` block (download, ``np.sort``, vectorised weights: the yardstick), alternating in one run."""
+on the host from a downloaded ``peak`` block (download, ``np.sort``, vectorised weights: the yardstick), alternating in one run.
+
+``--timing`` (profiles/ensemble_timing.json) measures the event timing instead -- arrival, duration and time of the peak at three thresholds:
+``evaluate`` with the peaks kernel alone (``timing=False``, what the parent commit ran), with the timing kernel in its place (``timing=True``) and with
+``route="refield"`` for the same maps, alternating in one run after a warm-up round that compares the two routes bit for bit; the device times of
+the two fused kernels, the ``"peaks"``, ``"stats"`` and ``"timing"`` stages, and the same maps with numpy from downloaded fields of one event
+at ``--host-members`` members (the yardstick: what a caller without the kernel would do)."""
 
 from __future__ import annotations
 
@@ -161,6 +167,118 @@ def measure_verification(args, ens, xs, ranges, shape) -> None:
             f.write(text + "\n")
 
 
+TIMING_FIELDS = ("t_peak_sum", "t_peak_quantiles", "duration_sum", "duration_quantiles", "duration_below_counts", "arrival_counts", "arrival_sum",
+                 "arrival_quantiles", "arrival_by_counts")
+RESULT_FIELDS = ("exceed_counts", "peak_mean", "peak_std", "peak_quantiles", "wet_area")
+
+
+def host_timing(ens, scores, members, rows, thr):
+    """The yardstick of ``--timing``: the members' fields of one event formed on the device (reverse -> depth), downloaded, and reduced with
+    numpy to the maps of ``member_timing_dev``.  Returns the maps and the times in ms."""
+    from gpras_amd._lib import DeviceBuffer, check
+
+    pr, lib = ens.projector, ens._lib
+    cells, k = pr.n_cells, pr.spatial_mode_count
+    field = DeviceBuffer(8 * members * rows * cells, ens.device)
+    try:
+        t0 = time.perf_counter()
+        check(lib.gprx_pca_reverse_dev(pr.handle, scores.ptr, None, members * rows, field.ptr, None))
+        if pr.hydraulic_parameter != "velocity":
+            check(lib.gprx_pca_to_depth_dev(pr.handle, field.ptr, members * rows, int(pr.hydraulic_parameter == "depth")))
+        check(lib.gprx_pca_synchronize(pr.handle))
+        t1 = time.perf_counter()
+        y = field.to_array((members, rows, cells))
+        t2 = time.perf_counter()
+    finally:
+        field.free()
+    maps = [np.argmax(y, axis=1)]
+    above = [y > t for t in thr]
+    maps += [a.sum(axis=1) for a in above]
+    maps += [np.where(a.any(axis=1), np.argmax(a, axis=1), rows) for a in above]
+    out = np.stack(maps, axis=1).astype(np.int32)
+    t3 = time.perf_counter()
+    return out, {"fields_on_device": (t1 - t0) * 1e3, "download": (t2 - t1) * 1e3, "numpy": (t3 - t2) * 1e3, "total": (t3 - t0) * 1e3}
+
+
+def measure_timing(args, ens, xs, ranges, shape) -> None:
+    """``--timing``: see the module's docstring."""
+    members, k = shape["members"], shape["modes"]
+    thr, durations, arrive_by = (0.25, 0.5, 1.0), (1, 6, 24), (6, 24, 48)
+    kw = dict(thresholds=thr, quantiles=(0.05, 0.5, 0.95), seed=1, rng=args.rng)
+    variants = {"peaks_only": dict(route="fused"), "timing_fused": dict(route="fused", timing=True, durations=durations, arrive_by=arrive_by),
+                "timing_refield": dict(route="refield", timing=True, durations=durations, arrive_by=arrive_by)}
+    order = list(variants)
+    stages = {name: [] for name in variants}
+    agree = {}
+    for rep in range(args.repeats + 1):
+        keep = {}
+        for name in order if rep % 2 == 0 else order[::-1]:
+            res = ens.evaluate(xs, ranges, members, **kw, **variants[name])
+            if rep == 0:
+                keep[name] = res
+            else:
+                stages[name].append(res.last_timings_ms)
+        if rep == 0:
+            a, b, c = keep["timing_fused"], keep["timing_refield"], keep["peaks_only"]
+            agree["routes_agree_bit_for_bit"] = bool(all(np.array_equal(getattr(a.timing, n), getattr(b.timing, n)) for n in TIMING_FIELDS)
+                                                     and all(np.array_equal(getattr(a, n), getattr(b, n)) for n in RESULT_FIELDS))
+            agree["peaks_fields_keep_their_bits"] = bool(all(np.array_equal(getattr(a, n), getattr(c, n)) for n in RESULT_FIELDS))
+            agree["arrival_counts_equal_exceed_counts"] = bool(np.array_equal(a.timing.arrival_counts, a.exceed_counts))
+            agree["share_of_member_cells_never_arriving"] = [float(1.0 - a.timing.p_arrival[:, j].mean()) for j in range(len(thr))]
+            del keep, a, b, c
+    # the yardstick on one event at a member count whose fields fit the host
+    hm = max(1, min(args.host_members, members))
+    lo, hi = ranges[0]
+    rows = hi - lo
+    mean_dev, lc_dev, _ = ens.joint_dev(xs[lo:hi])
+    scores = ens.scores_dev(mean_dev, lc_dev, np.random.default_rng(3).standard_normal((k, hm, rows)), hm, rows)
+    host, host_same = [], None
+    for rep in range(args.repeats + 1):
+        maps, ms = host_timing(ens, scores, hm, rows, thr)
+        if rep == 0:
+            peak_dev, timing_dev = ens.member_timing_dev(scores, hm, rows, thr)
+            host_same = bool(np.array_equal(ens.timing_to_array(timing_dev, hm, 1 + 2 * len(thr)), maps))
+            peak_dev.free()
+            timing_dev.free()
+        else:
+            host.append(ms)
+    for buf in (mean_dev, lc_dev, scores):
+        buf.free()
+
+    def med(name, key):
+        return statistics.median(t[key] for t in stages[name])
+
+    def spread(name, key):
+        return {"median": med(name, key), "min": min(t[key] for t in stages[name]), "max": max(t[key] for t in stages[name])}
+
+    events = shape["events"]
+    out = {
+        "shape": shape, "rng": args.rng, "repeats": args.repeats, "thresholds": thr, "durations": durations, "arrive_by": arrive_by, **agree,
+        "stage_ms_median": {name: {key: med(name, key) for key in stages[name][0] if key != "host_link_bytes"} for name in stages},
+        "device_walk_ms": {name: spread(name, "device_peaks") for name in ("peaks_only", "timing_fused")},
+        "peaks_stage_ms": {name: spread(name, "peaks") for name in stages},
+        "timing_stage_ms": {name: spread(name, "timing") for name in ("timing_fused", "timing_refield")},
+        "total_ms": {name: spread(name, "total") for name in stages},
+        "host_yardstick": {
+            "members": hm, "events": 1, "maps_agree_bit_for_bit": host_same, "field_bytes_downloaded": 8 * hm * rows * shape["cells"],
+            "ms": {key: {"median": statistics.median(t[key] for t in host), "min": min(t[key] for t in host), "max": max(t[key] for t in host)}
+                   for key in ("fields_on_device", "download", "numpy", "total")},
+        },
+    }
+    out["timing_kernel_over_peaks_kernel"] = med("timing_fused", "device_peaks") / med("peaks_only", "device_peaks")
+    out["refield_over_fused_peaks_stage_with_timing"] = med("timing_refield", "peaks") / med("timing_fused", "peaks")
+    out["timing_call_over_peaks_call_total"] = med("timing_fused", "total") / med("peaks_only", "total")
+    per_member_event = out["host_yardstick"]["ms"]["total"]["median"] / hm
+    out["host_yardstick"]["ms_per_member_event"] = per_member_event
+    out["host_yardstick"]["extrapolated_ms_per_call"] = per_member_event * members * events  # (linear in members x events: every field is touched once)
+    out["device_walk_ms_per_member_event"] = med("timing_fused", "device_peaks") / (members * events)
+    text = json.dumps(out, indent=1, sort_keys=True)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--events", type=int, default=35)
@@ -174,8 +292,12 @@ def main() -> None:
     ap.add_argument("--hydraulic-parameter", default="wse")
     ap.add_argument("--rng", choices=("host", "device", "both"), default="host")
     ap.add_argument("--verify", action="store_true", help="measure the verification against the truth (profiles/ensemble_verify.json)")
+    ap.add_argument("--timing", action="store_true", help="measure the event timing (profiles/ensemble_timing.json)")
+    ap.add_argument("--host-members", type=int, default=8, help="--timing: members whose fields the numpy yardstick downloads")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
+    if args.timing and (args.verify or args.rng == "both"):
+        ap.error("--timing is a mode of its own: not with --verify or --rng both")
     if args.verify and args.rng == "both":
         ap.error("--verify takes one generator: --rng host or --rng device")
 
@@ -216,6 +338,10 @@ def main() -> None:
         return
     if args.verify:
         measure_verification(args, ens, xs, ranges, shape)
+        proj.close()
+        return
+    if args.timing:
+        measure_timing(args, ens, xs, ranges, shape)
         proj.close()
         return
 
