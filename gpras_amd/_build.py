@@ -2,7 +2,7 @@
 
 The library is several translation units (one object each, compiled in parallel, then linked): the C ABI by subsystem -- `gprx.hip`
 (the C boundary of the GP path and the raw kernel entry points; the GP path's host code is `gp_ctx.h`, `gp_exact.h`, `gp_sparse.h`,
-`gp_resident.h`, `gp_objective.h`, `gp_predict.h`, `gp_loeo.h`, `gp_loeo_blocked.h`, `gp_joint.h` (the joint prediction of the peak ensemble), included into that one unit so that its kernels are instantiated once), `abi_eof.hip` (EOF projection, its fit, HmsPreProcessor, the mode-count sweep and the peak ensemble's kernels of `ensemble.h`, `verify.h` and `timing.h`), `abi_pseudo.hip`, `abi_resample.hip` (LF-to-HF mesh resampling), `abi_align.hip` (per-event temporal clipping), `abi_diag.hip` (sort, scatter summary and detection codes of the diagnostic plots), `abi_events.hip` (storm-event selection),
+`gp_resident.h`, `gp_objective.h`, `gp_predict.h`, `gp_loeo.h`, `gp_loeo_blocked.h`, `gp_joint.h` (the joint prediction of the peak ensemble), included into that one unit so that its kernels are instantiated once), `abi_eof.hip` (EOF projection, its fit, HmsPreProcessor, the mode-count sweep and the peak ensemble's kernels of `ensemble.h`, `verify.h` and `timing.h`, and the depth-frequency maps of `frequency.h`), `abi_pseudo.hip`, `abi_resample.hip` (LF-to-HF mesh resampling), `abi_align.hip` (per-event temporal clipping), `abi_diag.hip` (sort, scatter summary and detection codes of the diagnostic plots), `abi_events.hip` (storm-event selection),
 `abi_fields.hip` (metrics, k-means, row gather), `abi_comm.hip` (RCCL), `abi_eig.hip` (symmetric eigensolver), all over the host toolkit of `abi_common.h` -- and the fused
 sparse evaluation, whose pass kernels are compiled once per kernel id (`-DSF_KID=k`) and whose resident-loop launch once per optimiser
 (`sf_adam.hip`, `sf_adadelta.hip` over `sf_adam_prep.h`), the leave-one-event-out downdate (`sf_loeo.hip`; `sf_loeo_blocked.hip` for 64 < M <= 320, driven by `gp_loeo_blocked.h`), beside the step kernel of the resident loop of the general sparse launch

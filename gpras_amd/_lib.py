@@ -123,6 +123,9 @@ PROTOTYPES = {
     "gprx_pca_member_timing_dev": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, _vp, _vp, _vp]),
     "gprx_pca_timing_stats_dev": (C.c_int, [_vp, _vp, _i64, C.c_int, C.c_int, C.c_int, _i64, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
                                             _vp, _vp]),
+    "gprx_pca_freq_accumulate_dev": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp, C.c_double, _vp, _vp]),
+    "gprx_pca_freq_invert_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, _vp]),
+    "gprx_pca_freq_ms": (C.c_int, [_vp, _dp]),
     "gprx_pcafit_create": (C.c_int, [C.c_int, _vp, _i64, _i64, _vp, _vp, C.c_int, C.c_double, C.POINTER(_vp)]),
     "gprx_pcafit_gram": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_i64)]),
     "gprx_pcafit_components": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),

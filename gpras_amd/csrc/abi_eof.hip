@@ -18,6 +18,7 @@
 #include "ensemble.h"
 #include "verify.h"
 #include "timing.h"
+#include "frequency.h"
 
 using namespace gprx;
 
@@ -36,6 +37,9 @@ struct gprx_pca_ctx {
   double ens_ms = 0.0;        // device time of the last gprx_pca_ensemble_peaks_dev
   double ver_ms = 0.0;        // device time of the last gprx_pca_member_verify_dev
   double tim_ms = 0.0;        // device time of the last gprx_pca_ensemble_timing_dev
+  Buf freq_lev;               // gprx_pca_freq_*_dev: the levels staged on the device, freq_lev_host what it holds
+  std::vector<double> freq_lev_host;
+  double freq_ms = 0.0;       // device time of the last gprx_pca_freq_accumulate_dev
   std::string err;
 };
 
@@ -165,7 +169,7 @@ int gprx_pca_create(int device, int64_t n_cells, int k, const unsigned char* dry
 int gprx_pca_destroy(gprx_pca_handle p) {
   if (!p) return GPRX_OK;
   release_handle(p->device, p->stream, {p->mu.p, p->wfwd.p, p->wrev.p, p->elev.p, p->E.p, p->base.p, p->xm.p, p->xs.p, p->dX.p, p->dZ.p, p->ws.p, p->dMean.p, p->dVar.p,
-                                           p->dFull.p, p->dVfull.p, p->sweep_part.p, p->sweep_aux.p, p->ens_part.p}, p->ev, 2);
+                                           p->dFull.p, p->dVfull.p, p->sweep_part.p, p->sweep_aux.p, p->ens_part.p, p->freq_lev.p}, p->ev, 2);
   delete p;
   return GPRX_OK;
 }
@@ -653,6 +657,88 @@ int gprx_pca_member_verify_ms(gprx_pca_handle p, double* ms) {
 int gprx_pca_member_verify_tile(int64_t members, int* tile_cells) {
   if (!tile_cells || members < 1 || members > ENS_SMAX) return fail(nullptr, GPRX_EINVAL, "members must be between 1 and " + std::to_string(ENS_SMAX));
   *tile_cells = verify_tile_keys(verify_log_sp(members)) >> verify_log_sp(members);
+  return GPRX_OK;
+}
+
+// ---- depth-frequency maps (frequency.h) -------------------------------------------------------------------------------------------
+namespace {
+int check_freq_levels(gprx_pca_handle p, int n_levels, const double* levels) {
+  if (n_levels < 1 || n_levels > FREQ_LMAX) return fail(p, GPRX_EINVAL, "n_levels must be between 1 and " + std::to_string(FREQ_LMAX));
+  if (!levels) return fail(p, GPRX_EINVAL, "null argument: levels");
+  for (int l = 0; l < n_levels; ++l) {
+    if (!std::isfinite(levels[l])) return fail(p, GPRX_EINVAL, "the levels must be finite");
+    if (l && !(levels[l] > levels[l - 1])) return fail(p, GPRX_EINVAL, "the levels must be strictly increasing");
+  }
+  return GPRX_OK;
+}
+
+// the levels on the device; uploaded when they are not the ones staged last (freq_lev_host outlives the copy: the calls synchronise)
+int stage_freq_levels(gprx_pca_handle p, int n_levels, const double* levels) {
+  const size_t bytes = sizeof(double) * (size_t)n_levels;
+  if (p->freq_lev.p && p->freq_lev_host.size() == (size_t)n_levels && !std::memcmp(p->freq_lev_host.data(), levels, bytes)) return GPRX_OK;
+  int rc;
+  if ((rc = ensure(p, p->freq_lev, sizeof(double) * FREQ_LMAX))) return rc;
+  p->freq_lev_host.assign(levels, levels + n_levels);
+  const hipError_t e = hipMemcpyAsync(p->freq_lev.p, p->freq_lev_host.data(), bytes, hipMemcpyHostToDevice, p->stream);
+  if (e != hipSuccess) p->freq_lev_host.clear();
+  HIPCHK(p, e);
+  return GPRX_OK;
+}
+}  // namespace
+
+int gprx_pca_freq_accumulate_dev(gprx_pca_handle p, const double* peak_dev, int64_t members, int n_levels, const double* levels, double weight,
+                                 double* rate_dev, int* nan_dev) {
+  return guarded(p, [&]() -> int {
+    if (!p) return fail(p, GPRX_EINVAL, "null handle");
+    if (!peak_dev || !rate_dev || !nan_dev) return fail(p, GPRX_EINVAL, "null argument");
+    if (members < 1 || members > FREQ_SMAX) return fail(p, GPRX_EINVAL, "members must be between 1 and " + std::to_string(FREQ_SMAX));
+    int rc;
+    if ((rc = check_freq_levels(p, n_levels, levels))) return rc;
+    if (!std::isfinite(weight) || weight < 0.0) return fail(p, GPRX_EINVAL, "the weight must be finite and not negative");
+    HIPCHK(p, hipSetDevice(p->device));
+    hipStream_t st = p->stream;
+    if ((rc = stage_freq_levels(p, n_levels, levels))) return rc;
+    FreqAccumulateArgs a{peak_dev, p->freq_lev.p, members, p->cells, n_levels, weight, rate_dev, nan_dev};
+    const dim3 grid((unsigned)((p->cells + FREQ_TILE - 1) / FREQ_TILE));
+    HIPCHK(p, hipEventRecord(p->ev[0], st));
+    if (n_levels <= 64) hipLaunchKernelGGL(freq_accumulate_kernel<64>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(freq_accumulate_kernel<FREQ_LMAX>, grid, dim3(256), 0, st, a);
+    HIPCHK(p, hipGetLastError());
+    HIPCHK(p, hipEventRecord(p->ev[1], st));
+    HIPCHK(p, hipStreamSynchronize(st));
+    p->freq_ms = elapsed_ms(p->ev[0], p->ev[1]);
+    return GPRX_OK;
+  });
+}
+
+int gprx_pca_freq_invert_dev(gprx_pca_handle p, const double* rate_dev, const int* nan_dev, int n_levels, const double* levels, int n_aep, const double* aep,
+                             int interp, double* depth_dev, int* bracket_dev) {
+  return guarded(p, [&]() -> int {
+    if (!p) return fail(p, GPRX_EINVAL, "null handle");
+    if (!rate_dev || !nan_dev || !depth_dev || !bracket_dev) return fail(p, GPRX_EINVAL, "null argument");
+    int rc;
+    if ((rc = check_freq_levels(p, n_levels, levels))) return rc;
+    if (n_aep < 1 || n_aep > FREQ_PMAX || !aep) return fail(p, GPRX_EINVAL, "need between 1 and " + std::to_string(FREQ_PMAX) + " targets");
+    for (int j = 0; j < n_aep; ++j)
+      if (!std::isfinite(aep[j]) || !(aep[j] > 0.0)) return fail(p, GPRX_EINVAL, "the targets must be finite and positive");
+    if (interp != 0 && interp != 1) return fail(p, GPRX_EINVAL, "interp must be 0 (linear) or 1 (step)");
+    HIPCHK(p, hipSetDevice(p->device));
+    hipStream_t st = p->stream;
+    if ((rc = stage_freq_levels(p, n_levels, levels))) return rc;
+    FreqInvertArgs a{};
+    a.rate = rate_dev, a.nan_members = nan_dev, a.levels = p->freq_lev.p, a.cells = p->cells, a.n_levels = n_levels, a.n_aep = n_aep, a.interp = interp;
+    for (int j = 0; j < n_aep; ++j) a.aep[j] = aep[j];
+    a.depth = depth_dev, a.bracket = bracket_dev;
+    hipLaunchKernelGGL(freq_invert_kernel, dim3((unsigned)((p->cells + 255) / 256)), dim3(256), 0, st, a);
+    HIPCHK(p, hipGetLastError());
+    HIPCHK(p, hipStreamSynchronize(st));
+    return GPRX_OK;
+  });
+}
+
+int gprx_pca_freq_ms(gprx_pca_handle p, double* ms) {
+  if (!p || !ms) return fail(p, GPRX_EINVAL, "null argument");
+  *ms = p->freq_ms;
   return GPRX_OK;
 }
 

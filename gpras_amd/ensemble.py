@@ -56,7 +56,7 @@ JOINT_MAX_M, JOINT_MAX_ROWS, JOINT_MAX_D = 320, 1024, 64
 MAX_MEMBERS, MAX_THRESHOLDS, MAX_RANKS = 4096, 8, 8
 MAX_LEVELS = 8  # levels of the distribution function per ``gprx_pca_timing_stats_dev``: ``durations`` and ``arrive_by`` of ``evaluate``
 MAX_EVENT_ROWS = 2**31 - 2  # the timing maps are int32 and the arrival's sentinel is the row count itself
-# (the statistics' stage includes their download; ``observed=`` adds "verify", ``timing=True`` adds "timing")
+# (the statistics' stage includes their download; ``observed=`` adds "verify", ``timing=True`` adds "timing", ``frequency=`` adds "frequency")
 STAGES = ("joint", "draw_upload", "draws", "peaks", "stats")
 
 
@@ -779,7 +779,7 @@ class PeakEnsemble:
     # ---- the whole chain ------------------------------------------------------------------------------------------------------------------
     def evaluate(self, x_test, ranges, members: int, thresholds=(0.5,), quantiles=(0.05, 0.5, 0.95), seed=0, normals=None, cell_areas=None,
                  include_noise: bool = True, route: str | None = None, rng: str = DEFAULT_RNG, stream=0, antithetic: bool = False,
-                 observed=None, timing: bool = False, durations=(), arrive_by=()) -> EnsembleResult:
+                 observed=None, timing: bool = False, durations=(), arrive_by=(), frequency=None, weights=None) -> EnsembleResult:
         """``x_test (rows, d)``; ``ranges``: the events' ``(lo, hi)`` row ranges, ascending and disjoint; ``members``: S.  ``normals``: one
         ``(K, S, rows_e)`` array per event instead of the generator seeded with ``seed``.  ``rng="host"``: ``np.random.default_rng(seed)``, one
         sequential stream over the events; ``rng="device"``: event ``e`` takes ``normals_dev(e, members, rows_e, seed, stream, antithetic)`` --
@@ -793,7 +793,11 @@ class PeakEnsemble:
         walk, the same ``peak`` bit for bit, so every other field of the result keeps its bits -- and a ``"timing"`` stage reduces the members'
         maps (``timing_stats``) to ``result.timing``, an ``EventTiming`` at ``thresholds`` and ``quantiles``: ``durations`` (rows, at most 8) are the
         ``D`` of ``p_duration_at_least``, ``arrive_by`` (rows, at most 8) the ``t`` of ``p_arrival_by``; with ``observed=`` it carries the observed maps
-        (``observed_timing_dev``) and the members below and equal to them.  ``timing=False`` launches nothing more and leaves ``timing`` None."""
+        (``observed_timing_dev``) and the members below and equal to them.  ``timing=False`` launches nothing more and leaves ``timing`` None.
+        ``frequency``: a ``gpras_amd.frequency.FrequencyMaps`` over the same projector, with ``weights`` one per event (finite, not negative: the
+        annual rate of the stratum the event stands for): after an event's peaks ``frequency.add_peaks(peak, members, weights[e])`` runs in a
+        ``"frequency"`` stage of the timer and ``last_timings_ms["device_frequency"]`` sums its device time; every other field of the result keeps
+        its bits.  ``frequency=None`` launches nothing more (``weights`` must then be None too)."""
         route = DEFAULT_ROUTE if route is None else route
         if route not in ROUTES:
             raise ValueError(f"route must be one of {ROUTES}")
@@ -822,15 +826,23 @@ class PeakEnsemble:
             raise ValueError("one array of normals per event")
         k, cells, ne = self.projector.spatial_mode_count, self.projector.n_cells, int(lo.size)
         host_rng = np.random.default_rng(seed) if rng == "host" and normals is None else None
+        if frequency is not None:
+            from .frequency import check_weights
+
+            weights = check_weights(weights, ne)
+            if frequency.cells != cells:
+                raise ValueError(f"the frequency maps are over {frequency.cells} cells, the projector over {cells}")
+        elif weights is not None:
+            raise ValueError("weights were given without frequency maps to add to")
         verify = observed is not None
         if verify:
             observed = check_observed(observed, x.shape[0], cells)
-        timer = StageTimer(STAGES + (("verify",) if verify else ()) + (("timing",) if timing else ()))
+        timer = StageTimer(STAGES + (("verify",) if verify else ()) + (("timing",) if timing else ()) + (("frequency",) if frequency is not None else ()))
         counts = np.zeros((ne, thr.size, cells), dtype=np.int32)
         mean, std = np.zeros((ne, cells)), np.zeros((ne, cells))
         order = np.zeros((ne, rk.size, cells))
         wet = np.zeros((ne, members, thr.size))
-        device_peaks = device_verify = 0.0
+        device_peaks = device_verify = device_frequency = 0.0
         if verify:
             crps, obs_peak = np.zeros((ne, cells)), np.zeros((ne, cells))
             below, equal = np.zeros((ne, cells), dtype=np.int32), np.zeros((ne, cells), dtype=np.int32)
@@ -891,6 +903,10 @@ class PeakEnsemble:
                         tm.below[e] = np.concatenate([st_t["below"], st_d["below"], st_a["below"]])
                         tm.equal[e] = np.concatenate([st_t["equal"], st_d["equal"], st_a["equal"]])
                     timer.lap("timing")
+                if frequency is not None:
+                    frequency.add_peaks(peak, members, weights[e])
+                    device_frequency += frequency.last_device_ms
+                    timer.lap("frequency")
             finally:
                 for buf in (mean_dev, lc_dev, scores, peak, zn if rng == "device" else None, truth_peak, maps_dev, truth_maps):
                     if buf is not None:
@@ -899,6 +915,8 @@ class PeakEnsemble:
         timings = timer.finish()
         if route == "fused":
             timings["device_peaks"] = device_peaks
+        if frequency is not None:
+            timings["device_frequency"] = device_frequency
         verification = None
         if verify:
             timings["device_verify"] = device_verify

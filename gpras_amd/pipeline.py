@@ -234,7 +234,8 @@ class DevicePipeline:
         ``PeakEnsemble.evaluate``.  Returns its ``EnsembleResult`` with the events' labels in ``names``.  ``verify=True`` (a data frame, not the
         index alone): the truth goes up once through ``truth_depth_dev`` and the result carries the ``PeakVerification`` of the ensemble
         against every event's observed peak.  ``timing=True`` (a keyword of ``evaluate``) adds the ``EventTiming`` -- arrival, duration and time of
-        the peak --, with ``verify=True`` against the observed ones."""
+        the peak --, with ``verify=True`` against the observed ones.  ``frequency=`` a ``gpras_amd.frequency.FrequencyMaps`` over this projector and
+        ``weights=`` one annual rate per event (keywords of ``evaluate``): every event's peaks are also added to the depth-frequency maps."""
         from .diagnostics import event_ranges
         from .ensemble import PeakEnsemble
 

@@ -651,6 +651,26 @@ int gprx_pca_member_timing_dev(gprx_pca_handle p, const double* field_dev, int64
 int gprx_pca_timing_stats_dev(gprx_pca_handle p, const int* timing_dev, int64_t members, int n_maps, int map0, int n_sel, int64_t rows_e, int sentinel,
                               int n_lev, const int* levels, int n_rank, const int* ranks, const int* obs_dev, int* cdf_dev, int* n_valid_dev,
                               int64_t* sum_dev, int* order_dev, int* below_dev, int* equal_dev);
+/* Depth-frequency maps of a weighted storm catalogue (csrc/frequency.h).  The state is the caller's device block:
+ * rate_dev (n_levels, n_cells) doubles and nan_dev (n_cells) int32, both zero before the first event.  levels: host array, 1 <= n_levels <=
+ * 256, finite and strictly increasing (d_0 < d_1 < ...).
+ * gprx_pca_freq_accumulate_dev adds one event: peak_dev (members, n_cells), 1 <= members = S <= 4096, weight finite and >= 0.  Per cell c
+ * and level l, with n = #{ s : peak[s, c] > d_l } (strict; a NaN member exceeds nothing; -0 and +0 both fail > 0.0):
+ *   t = (double)n / (double)S,  u = weight * t,  rate[l, c] = rate[l, c] + u     (three rounded operations, no fma)
+ *   nan[c] += #{ s : peak[s, c] is NaN }
+ * rate[:, c] is non-increasing in l exactly; a permutation of the members or an event of weight 0 changes no bit; a cell's state depends
+ * on its own column alone; the order of the events is the caller's.  One pass over peak, counting in integers; no atomics on global
+ * memory.  The call synchronises; gprx_pca_freq_ms: device milliseconds of the last accumulate.
+ * gprx_pca_freq_invert_dev: aep: host array of 1 <= n_aep <= 16 targets, finite and > 0; interp 0 (linear) or 1 (step).  Per cell and target p,
+ * k = #{ l : rate[l, c] >= p }:  bracket (n_aep, n_cells) int32 = k;  depth (n_aep, n_cells) = -inf where k = 0, +inf where k = n_levels, else
+ * step: d_{k-1};  linear: a = r_{k-1} - p, b = r_{k-1} - r_k, f = a / b, g = d_k - d_{k-1}, depth = d_{k-1} + g * f (each operation rounded).
+ * A cell with nan[c] > 0: depth NaN, bracket -1.  The call synchronises.
+ * Every refusal is GPRX_EINVAL with its reason in gprx_pca_last_error; a refused call writes nothing and leaves the handle usable. */
+int gprx_pca_freq_accumulate_dev(gprx_pca_handle p, const double* peak_dev, int64_t members, int n_levels, const double* levels, double weight,
+                                 double* rate_dev, int* nan_dev);
+int gprx_pca_freq_invert_dev(gprx_pca_handle p, const double* rate_dev, const int* nan_dev, int n_levels, const double* levels, int n_aep, const double* aep,
+                             int interp, double* depth_dev, int* bracket_dev);
+int gprx_pca_freq_ms(gprx_pca_handle p, double* ms);
 
 /* ---- fitting the EOF preprocessor: PreProcessor.fit (gpras/preprocess.py:947-1007) --------------------------------------- */
 /* The fitted state gprx_pca_create takes, computed on the device.  Single-batch IncrementalPCA (sklearn partial_fit, first
